@@ -156,7 +156,57 @@ def parse():
     ap.add_argument("--ba-cams", type=int, default=500)
     ap.add_argument("--ba-points", type=int, default=50000)
     ap.add_argument("--ba-iters", type=int, default=12)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: keypoints, descriptors, counts, "
+                         "match rows of a fixed seeded sample of frames / pairs) as DIR/<name>.npy, float32 / float64, <= 64 MB")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0x5EED0D0D
+DUMP_MAX_FRAMES = 64
+
+
+def dump_outputs(out_dir, outs, matches, counts_all, pq, pt):
+    """What a caller of the timed step receives, for output-for-output comparison of two builds.  `outs` = (kps, desc, counts)
+    of the last timed step, `matches` = its (idx, d1, d2) rows, one per pair (pq[p], pt[p]) of global frame indices into
+    `counts_all`.  A fixed seeded sample of frames and pairs keeps the files under DUMP_MAX_BYTES; entries past a frame's
+    keypoint count are not part of the result and are written as 0 (keypoints, descriptors) / -1, 0, 0 (match rows)."""
+    kps, desc, counts = outs
+    idx, d1, d2 = matches
+    F, K = desc.shape[0], desc.shape[1]
+    P = idx.shape[0]
+    # per sampled frame: keypoints 7 x f64, descriptor 32 x f32; per sampled pair: idx, d1, d2 x f32 (all values < 2^24)
+    per_frame = K * (7 * 8 + 32 * 4) + 8
+    per_pair = K * 3 * 4 + 16
+    n = max(1, min(F, DUMP_MAX_FRAMES, (DUMP_MAX_BYTES - 8 * F) // (per_frame + per_pair)))
+    rng = np.random.default_rng(DUMP_SEED)
+    fs = np.sort(rng.choice(F, size=n, replace=False))
+    ps = np.sort(rng.choice(P, size=min(n, P), replace=False)) if P > 0 else np.zeros(0, np.int64)
+    dev = desc.device
+    fi = torch.from_numpy(fs).to(dev)
+    pi = torch.from_numpy(ps).to(dev)
+    cnt = counts.cpu().numpy().astype(np.int64)
+    valid = np.arange(K)[None, :] < cnt[fs][:, None]
+    kp = kps.index_select(0, fi).cpu().numpy()
+    kp_rec = np.concatenate([kp[..., :5].astype(np.float64), kp[..., 5:].view(np.int32).astype(np.float64)], axis=-1)
+    kp_rec[~valid] = 0.0
+    de = desc.index_select(0, fi).cpu().numpy().astype(np.float32)
+    de[~valid] = 0.0
+    pqs, pts = pq.cpu().numpy()[ps].astype(np.int64), pt.cpu().numpy()[ps].astype(np.int64)
+    pvalid = np.arange(K)[None, :] < counts_all.cpu().numpy().astype(np.int64)[pqs][:, None]
+    mi = idx.index_select(0, pi).cpu().numpy().astype(np.float32)
+    md1 = (d1.index_select(0, pi).cpu().numpy().view(np.uint16)).astype(np.float32)
+    md2 = (d2.index_select(0, pi).cpu().numpy().view(np.uint16)).astype(np.float32)
+    mi[~pvalid], md1[~pvalid], md2[~pvalid] = -1.0, 0.0, 0.0
+    arrays = {"counts": cnt.astype(np.float64), "sample_frames": fs.astype(np.float64), "keypoints": kp_rec, "descriptors": de,
+              "sample_pairs": np.stack([pqs, pts], axis=1).astype(np.float64), "match_idx": mi, "match_d1": md1, "match_d2": md2}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    log("dumped %d arrays (%.1f MB; %d of %d frames, %d of %d pairs) to %s" % (len(arrays), total / 1e6, n, F, len(ps), P, out_dir))
 
 
 def main():
@@ -333,6 +383,8 @@ def main():
         prof.update(ctx_side.prof_collect())
         ctx_side.prof_enable(False)
     last_out = bufs[(step_no[0] - 1) & 1] if overlap else bufs[0]  # the output set of the last timed step (in-run parity)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_out, (m_idx, m_d1, m_d2), g_counts, pq, pt)
     match_overlap = None
     if overlap:
         # what a side stream would hide: the same steps with the matcher on the launch stream after the extraction and with
@@ -1200,7 +1252,7 @@ def main():
     # ---- latency of the deployed per-frame path (GSLAM/plugins/play/main.cpp:99-155 hands frames over one at a time;
     #      evaluation/metric_time/main.cpp:4-34 measures exactly this).  (a) C ABI: one frame through gh_orb_stream
     #      (chunk 1, nothing else in flight), host clock around submit + collect; (b) through the GSLAM plugins in a C++
-    #      host process (build/plugin_host lat): detectAndCompute + match + optimizePnP per frame, p50 / p99.
+    #      host process (oracle/_ref/bin/plugin_host lat): detectAndCompute + match + optimizePnP per frame, p50 / p99.
     def _leg_latency():
         import subprocess
         from gslam_amd.orb import OrbStream
@@ -1226,9 +1278,10 @@ def main():
                         "extract_link_to_link_p50_ms": round(float(gpu_ms[len(gpu_ms) // 2]), 3),
                         "keypoints": n_kp,
                         "what": "gh_orb_stream chunk 1: memcpy into pinned staging + H2D + extraction + packed D2H"}
-        hostbin = os.path.join(ROOT, "build", "plugin_host")
+        hostbin = os.path.join(ROOT, "oracle", "_ref", "bin", "plugin_host")
         libdir = os.path.join(ROOT, "gslam_amd", "lib")
-        if os.path.exists(hostbin) and os.path.exists(os.path.join(libdir, "libgslam_featuredetector.so")):
+        plugdir = os.path.join(ROOT, "oracle", "_ref", "plugins")
+        if os.path.exists(hostbin) and os.path.exists(os.path.join(plugdir, "libgslam_featuredetector.so")):
             env = dict(os.environ)
             env["LD_LIBRARY_PATH"] = libdir + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
             for (w, h, k, tag) in ((640, 480, 1000, "c1_640x480_k1000"), (W, H, K, "c2_%dx%d_k%d" % (W, H, K))):
@@ -1237,13 +1290,13 @@ def main():
                 raw = os.path.join("/tmp", "gslam_bench_lat_%d.raw" % os.getpid())
                 frames[:8, :h, :w].contiguous().cpu().numpy().tofile(raw)
                 try:
-                    r = subprocess.run([hostbin, "lat", libdir, str(w), str(h), "8", raw, str(k), "200"], capture_output=True,
+                    r = subprocess.run([hostbin, "lat", plugdir, str(w), str(h), "8", raw, str(k), "200"], capture_output=True,
                                        text=True, timeout=300, env=env)
                     kv = dict(tok.split("=", 1) for ln in r.stdout.splitlines() if ln.startswith("lat ")
                               for tok in ln.split()[1:])
                     if r.returncode == 0 and kv:
                         lat.setdefault(tag, {})["plugins"] = {
-                            "what": "C++ GSLAM host (build/plugin_host): FeatureDetector::detectAndCompute + match against the "
+                            "what": "C++ GSLAM host (oracle/_ref/bin/plugin_host): FeatureDetector::detectAndCompute + match against the "
                                     "previous frame + Optimizer::optimizePnP (300 points) per frame, 200 frames",
                             **{kk: round(float(kv[kk]), 3) for kk in kv if kk.endswith("_ms")},
                             "async_submit_collect_frames_per_s": round(float(kv.get("async_frames_per_s", 0.0)), 1)}
@@ -1253,7 +1306,7 @@ def main():
                     if os.path.exists(raw):
                         os.remove(raw)
         else:
-            lat["plugins"] = "build/plugin_host missing (built only where the GSLAM headers are)"
+            lat["plugins"] = "oracle/_ref/bin/plugin_host missing (built only where the GSLAM headers are)"
         extra["latency"] = lat
 
     # ---- the ends of north_star's frame range (SURVEY.md 8d byte figures): 640x480 K=1000 (5.44 MB / frame) and

@@ -194,14 +194,16 @@ ai, aj = all_pairs_block(0, 1, F, "cuda")
 out = m.match_pairs(desc, counts, ai, aj)
 torch.cuda.synchronize()
 if mode == "overlap":
-    # how long the queued work takes on the GPU
+    # how long the queued work takes on the GPU (enough of it that the host's fixed cost of issuing an exchange, ~0.5 ms,
+    # cannot decide the comparison below)
+    reps = 16
     t0 = time.perf_counter()
-    for _ in range(4):
+    for _ in range(reps):
         m.match_pairs(desc, counts, ai, aj, out=out)
     torch.cuda.synchronize()
     busy = time.perf_counter() - t0
     # the same work queued again, then an exchange behind it: the host must come back long before the GPU is done
-    for _ in range(4):
+    for _ in range(reps):
         m.match_pairs(desc, counts, ai, aj, out=out)
     t0 = time.perf_counter()
     comm.allgather_features(desc, counts, g_desc, g_counts)

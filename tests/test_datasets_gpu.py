@@ -9,7 +9,7 @@
     sequence: keypoints / descriptors / matches bit for bit, PnP and BA results to 1e-8;
   * `-orbhip.save_map map.gmap`: the application writes its map in the reference's `.gmap` format (OrbhipMap::save,
     field for field what GSLAM/plugins/gmap/MapHash.cpp:278-360 writes); the file is read back by the reference's own
-    MapHash::load (build/gmap_check, the reference's gmap sources compiled from where they lie) and must hold the frames,
+    MapHash::load (oracle/_ref/bin/gmap_check, the reference's gmap sources compiled from where they lie) and must hold the frames,
     poses, keypoints, descriptors, map points and observations of the run."""
 import os
 import subprocess
@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
-from test_launcher_gpu import LIBDIR, REFDIR, ROOT, _read_dump, _read_log
+from test_launcher_gpu import LIBDIR, PLUGDIR, REFDIR, ROOT, _read_dump, _read_log
 
 pytestmark = pytest.mark.gpu
 
@@ -26,12 +26,12 @@ W, H, K, N = 640, 480, 800, 25
 
 
 def _need():
-    for p in (os.path.join(REFDIR, "gslam"), os.path.join(REFDIR, "libgslam_play.so"), os.path.join(LIBDIR, "libgslamDB_kitti.so"),
-              os.path.join(REFDIR, "libgslam_gmap.so"), os.path.join(LIBDIR, "libgslam_orbhip.so"),
-              os.path.join(LIBDIR, "libgslamDB_synthplane.so"), os.path.join(LIBDIR, "libgslamDB_tumrgbd.so"),
-              os.path.join(ROOT, "build", "gmap_check")):
+    for p in (os.path.join(REFDIR, "gslam"), os.path.join(REFDIR, "libgslam_play.so"), os.path.join(PLUGDIR, "libgslamDB_kitti.so"),
+              os.path.join(REFDIR, "libgslam_gmap.so"), os.path.join(PLUGDIR, "libgslam_orbhip.so"),
+              os.path.join(PLUGDIR, "libgslamDB_synthplane.so"), os.path.join(PLUGDIR, "libgslamDB_tumrgbd.so"),
+              os.path.join(ROOT, "oracle", "_ref", "bin", "gmap_check")):
         if not os.path.exists(p):
-            pytest.skip(f"{p} missing: run `make plugins` in the authoring container (needs /root/reference at build time)")
+            pytest.skip(f"{p} missing: `make plugins` builds it where the GSLAM headers are")
 
 
 def _launch(cwd, dataset, apps=("orbhip", "play"), extra=()):
@@ -39,9 +39,9 @@ def _launch(cwd, dataset, apps=("orbhip", "play"), extra=()):
         "-dataset", str(dataset), "-slam", "orbhip", "-playspeed", "1", "-orbhip.nFeatures", str(K),
         "-orbhip.log", str(cwd / "orbhip.bin"), "-orbhip.stop_on_finish", "1", "-orbhip.start_dataset", "1",
         "-orbhip.ba_every", "10", "-orbhip.ba_window", "8",
-        "-FeatureDetectorPlugin", os.path.join(LIBDIR, "libgslam_featuredetector.so"),
-        "-OptimizerPlugin", os.path.join(LIBDIR, "libgslam_optimizer.so"),
-        "-GSLAM_LIBRARY_PATH", LIBDIR + ":" + REFDIR] + list(extra)
+        "-FeatureDetectorPlugin", os.path.join(PLUGDIR, "libgslam_featuredetector.so"),
+        "-OptimizerPlugin", os.path.join(PLUGDIR, "libgslam_optimizer.so"),
+        "-GSLAM_LIBRARY_PATH", PLUGDIR + ":" + LIBDIR + ":" + REFDIR] + list(extra)
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     r = None
@@ -78,7 +78,7 @@ def generated(tmp_path_factory):
     d = tmp_path_factory.mktemp("gen")
     seq = d / "seq.synthplane"
     seq.write_text(f"width {W}\nheight {H}\nframes {N}\nfps 100\ntexture 2048\nseed 1592590336\ndump {d / 'frames.bin'}\n")
-    os.symlink(os.path.join(LIBDIR, "libgslamDB_synthplane.so"), d / "libgslamDB_synthplane.so")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_synthplane.so"), d / "libgslamDB_synthplane.so")
     # (the reference's gmap APPLICATION is not used to trigger the save: loaded beside `play` it makes play's "qviz/open"
     # handler and frame delivery fire two and three times in this snapshot, or never when listed first -- reproduced with
     # reference plugins only; the application calls Map::save itself, the FILE is checked with the reference's loader)
@@ -89,7 +89,7 @@ def generated(tmp_path_factory):
 def test_gmap_file_is_read_by_the_reference_maphash(generated):
     d, log, frames = generated
     assert (d / "map.gmap").exists()
-    r = subprocess.run([os.path.join(ROOT, "build", "gmap_check"), str(d / "map.gmap")], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "bin", "gmap_check"), str(d / "map.gmap")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln.split() for ln in r.stdout.splitlines()]
     head = [ln for ln in lines if ln[0] == "map"][0]
@@ -157,7 +157,7 @@ def test_kitti_layout_through_the_stb_reader(generated, tmp_path):
         for i in range(4):
             fc.write(f"P{i}: 525 0 319.5 0 0 525 239.5 0 0 0 1 0\n")
     (tmp_path / "mono.kitti").write_text("VideoType mono\n")
-    os.symlink(os.path.join(LIBDIR, "libgslamDB_kitti.so"), tmp_path / "libgslamDB_kitti.so")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_kitti.so"), tmp_path / "libgslamDB_kitti.so")
     log_k = _launch(tmp_path, tmp_path / "mono.kitti")
     _same_run(log, log_k, "KITTI layout through libgslamDB_kitti.so")
 
@@ -177,6 +177,6 @@ def test_tum_rgbd_layout_through_the_stb_reader(generated, tmp_path):
             fa.write(f"{stamp:.6f} " + " ".join(repr(float(v)) for v in np.r_[pose[4:], pose[:4]]) +
                      f" {stamp:.6f} depth/{stamp:.6f}.png {stamp:.6f} rgb/{stamp:.6f}.png\n")
     (tmp_path / "rgbd.tumrgbd").write_text("UseRosCamera 1\n")
-    os.symlink(os.path.join(LIBDIR, "libgslamDB_tumrgbd.so"), tmp_path / "libgslamDB_tumrgbd.so")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_tumrgbd.so"), tmp_path / "libgslamDB_tumrgbd.so")
     log_t = _launch(tmp_path, tmp_path / "rgbd.tumrgbd")
     _same_run(log, log_t, "TUM-RGBD layout through libgslamDB_tumrgbd.so")

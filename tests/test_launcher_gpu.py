@@ -23,17 +23,18 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "gslam_amd", "lib")
-REFDIR = os.path.join(ROOT, "build", "ref")
+PLUGDIR = os.path.join(ROOT, "oracle", "_ref", "plugins")
+REFDIR = os.path.join(ROOT, "oracle", "_ref", "apps")
 W, H, K = 640, 480, 1000
 
 
 def _need():
     for p in (os.path.join(REFDIR, "gslam"), os.path.join(REFDIR, "libgslam_play.so"),
               os.path.join(REFDIR, "libgslam_metric_time.so"), os.path.join(REFDIR, "libgslam_metric_traj.so"),
-              os.path.join(LIBDIR, "libgslam_orbhip.so"),
-              os.path.join(LIBDIR, "libgslamDB_synthplane.so")):
+              os.path.join(PLUGDIR, "libgslam_orbhip.so"),
+              os.path.join(PLUGDIR, "libgslamDB_synthplane.so")):
         if not os.path.exists(p):
-            pytest.skip(f"{p} missing: run `make plugins` in the authoring container (needs /root/reference at build time)")
+            pytest.skip(f"{p} missing: `make plugins` builds it where the GSLAM headers are")
 
 
 def _read_dump(path):
@@ -144,7 +145,7 @@ def test_reference_launcher_runs_orbhip_on_the_synthetic_sequence(tmp_path, orac
     # Dataset::open -> Registry::load("gslamDB_synthplane") runs inside libgslam_play.so with THAT plugin's own svar
     # instance, whose search path is ".", /usr/lib ... (GSLAM/core/Registry.h:178-232): an installed GSLAM finds dataset
     # plugins in /usr/local/lib, here the plugin is linked into the working directory.
-    os.symlink(os.path.join(LIBDIR, "libgslamDB_synthplane.so"), tmp_path / "libgslamDB_synthplane.so")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_synthplane.so"), tmp_path / "libgslamDB_synthplane.so")
     # Application order: the launcher starts each application's thread as soon as its plugin is loaded and keeps writing
     # svar["gslam"]["apps"] for the next one from the main thread (GSLAM/gslam/main.cpp:17-45) -- svar is not thread safe
     # (Svar.h:783), so `play`, which touches svar for its whole life, goes last.
@@ -152,9 +153,9 @@ def test_reference_launcher_runs_orbhip_on_the_synthetic_sequence(tmp_path, orac
            "-dataset", str(seq), "-slam", "orbhip", "-playspeed", "1",
            "-orbhip.nFeatures", str(K), "-orbhip.log", str(tmp_path / "orbhip.bin"), "-orbhip.stop_on_finish", "1",
            "-orbhip.start_dataset", "1", "-orbhip.ba_every", "10", "-orbhip.ba_window", "8",
-           "-FeatureDetectorPlugin", os.path.join(LIBDIR, "libgslam_featuredetector.so"),
-           "-OptimizerPlugin", os.path.join(LIBDIR, "libgslam_optimizer.so"),
-           "-GSLAM_LIBRARY_PATH", LIBDIR + ":" + REFDIR]
+           "-FeatureDetectorPlugin", os.path.join(PLUGDIR, "libgslam_featuredetector.so"),
+           "-OptimizerPlugin", os.path.join(PLUGDIR, "libgslam_optimizer.so"),
+           "-GSLAM_LIBRARY_PATH", PLUGDIR + ":" + LIBDIR + ":" + REFDIR]
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     # The reference launcher races on its global svar while applications start (see above); a crash in that window is the
@@ -240,7 +241,7 @@ def test_launcher_bow_vectors_loop_candidates_and_connections(tmp_path, oracle):
     frames must find the first ones and verify them with node-consistent matches (a FrameConnection, "orbhip/loop")."""
     _need()
     from gslam_amd import bow_synth
-    voc_lib = os.path.join(LIBDIR, "libgslam_vocabulary.so")
+    voc_lib = os.path.join(PLUGDIR, "libgslam_vocabulary.so")
     if not os.path.exists(voc_lib):
         pytest.skip("libgslam_vocabulary.so missing")
     n_frames, gap, levels_up = 45, 20, 2
@@ -248,7 +249,7 @@ def test_launcher_bow_vectors_loop_candidates_and_connections(tmp_path, oracle):
     (tmp_path / "voc.gbow").write_bytes(bow_synth.to_gbow_bytes(voc))
     seq = tmp_path / "seq.synthplane"
     seq.write_text(f"width {W}\nheight {H}\nframes {n_frames}\nfps 200\ntexture 2048\nseed 1592590336\n")
-    os.symlink(os.path.join(LIBDIR, "libgslamDB_synthplane.so"), tmp_path / "libgslamDB_synthplane.so")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_synthplane.so"), tmp_path / "libgslamDB_synthplane.so")
     cmd = [os.path.join(REFDIR, "gslam"), "orbhip", "metric_time", "play",
            "-dataset", str(seq), "-slam", "orbhip", "-playspeed", "1",
            "-orbhip.nFeatures", str(K), "-orbhip.log", str(tmp_path / "orbhip.bin"), "-orbhip.stop_on_finish", "1",
@@ -256,9 +257,9 @@ def test_launcher_bow_vectors_loop_candidates_and_connections(tmp_path, oracle):
            "-orbhip.vocabulary", str(tmp_path / "voc.gbow"), "-orbhip.loop_gap", str(gap), "-orbhip.levels_up", str(levels_up),
            "-orbhip.loop_score", "0.0", "-orbhip.loop_matches", "30",
            "-VocabularyPlugin", voc_lib,
-           "-FeatureDetectorPlugin", os.path.join(LIBDIR, "libgslam_featuredetector.so"),
-           "-OptimizerPlugin", os.path.join(LIBDIR, "libgslam_optimizer.so"),
-           "-GSLAM_LIBRARY_PATH", LIBDIR + ":" + REFDIR]
+           "-FeatureDetectorPlugin", os.path.join(PLUGDIR, "libgslam_featuredetector.so"),
+           "-OptimizerPlugin", os.path.join(PLUGDIR, "libgslam_optimizer.so"),
+           "-GSLAM_LIBRARY_PATH", PLUGDIR + ":" + LIBDIR + ":" + REFDIR]
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     for attempt in range(3):

@@ -169,21 +169,22 @@ def test_fuzz_small_frames(ctx, oracle, w, h, pad, K, nlevels, min_th, ini_extra
 
 # ------------------------------------------------------------------------------------------------------------
 # the same images through the FeatureDetector plugin inside a real GSLAM host process
-HOST = os.path.join(ROOT, "build", "plugin_host")
+HOST = os.path.join(ROOT, "oracle", "_ref", "bin", "plugin_host")
 LIBDIR = os.path.join(ROOT, "gslam_amd", "lib")
+PLUGDIR = os.path.join(ROOT, "oracle", "_ref", "plugins")
 
 
 @pytest.mark.parametrize("name", ["noise", "binary_noise", "checker2", "dots8", "step_edges", "few_corners", "black"])
 def test_adversarial_through_featuredetector_plugin(tmp_path, oracle, name):
-    if not (os.path.exists(HOST) and os.path.exists(os.path.join(LIBDIR, "libgslam_featuredetector.so"))):
-        pytest.skip("build/plugin_host or libgslam_featuredetector.so missing (run `make plugins` where the GSLAM headers are)")
+    if not (os.path.exists(HOST) and os.path.exists(os.path.join(PLUGDIR, "libgslam_featuredetector.so"))):
+        pytest.skip("oracle/_ref/bin/plugin_host or libgslam_featuredetector.so missing (run `make plugins` where the GSLAM headers are)")
     w, h, K = 640, 480, 1500
     img = CLASSES[name](w, h, 77)
     inp, out = tmp_path / "img.raw", tmp_path / "out.bin"
     img.tofile(inp)
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([HOST, "orb", LIBDIR, str(w), str(h), "1", str(inp), str(out), str(K)], capture_output=True,
+    r = subprocess.run([HOST, "orb", PLUGDIR, str(w), str(h), "1", str(inp), str(out), str(K)], capture_output=True,
                        text=True, timeout=300, env=env)
     ek, ed = oracle.orb_extract(img, K)
     raw = open(out, "rb").read()

@@ -173,9 +173,10 @@ def test_featuredetector_batch_and_async_entries(tmp_path, oracle):
     import subprocess
     import oracle_lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    host, libdir = os.path.join(root, "build", "plugin_host"), os.path.join(root, "gslam_amd", "lib")
-    if not (os.path.exists(host) and os.path.exists(os.path.join(libdir, "libgslam_featuredetector.so"))):
-        pytest.skip("build/plugin_host or libgslam_featuredetector.so missing (run `make plugins` where the GSLAM headers are)")
+    host, libdir = os.path.join(root, "oracle", "_ref", "bin", "plugin_host"), os.path.join(root, "gslam_amd", "lib")
+    plugdir = os.path.join(root, "oracle", "_ref", "plugins")
+    if not (os.path.exists(host) and os.path.exists(os.path.join(plugdir, "libgslam_featuredetector.so"))):
+        pytest.skip("oracle/_ref/bin/plugin_host or libgslam_featuredetector.so missing (run `make plugins` where the GSLAM headers are)")
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = libdir + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     for ch in (1, 3):
@@ -190,7 +191,7 @@ def test_featuredetector_batch_and_async_entries(tmp_path, oracle):
             expect_gray = [oracle.bgr_to_gray(im) for im in imgs]
         inp, out = tmp_path / f"frames{ch}.raw", tmp_path / f"out{ch}.bin"
         imgs.tofile(inp)
-        r = subprocess.run([host, "orbbatch", libdir, str(w), str(h), str(ch), str(n), str(inp), str(out), str(K)],
+        r = subprocess.run([host, "orbbatch", plugdir, str(w), str(h), str(ch), str(n), str(inp), str(out), str(K)],
                            capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stdout + r.stderr
         assert "matchBatch=1" in r.stdout  # FeatureDetector::matchBatch (all ordered frame pairs, one device batch) == match() per pair

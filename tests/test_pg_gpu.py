@@ -159,13 +159,14 @@ import struct
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "build", "plugin_host")
+HOST = os.path.join(ROOT, "oracle", "_ref", "bin", "plugin_host")
 LIBDIR = os.path.join(ROOT, "gslam_amd", "lib")
+PLUGDIR = os.path.join(ROOT, "oracle", "_ref", "plugins")
 
 
 def _host(args):
-    if not (os.path.exists(HOST) and os.path.exists(os.path.join(LIBDIR, "libgslam_optimizer.so"))):
-        pytest.skip("build/plugin_host or libgslam_optimizer.so missing (run `make plugins` where the GSLAM headers are)")
+    if not (os.path.exists(HOST) and os.path.exists(os.path.join(PLUGDIR, "libgslam_optimizer.so"))):
+        pytest.skip("oracle/_ref/bin/plugin_host or libgslam_optimizer.so missing (run `make plugins` where the GSLAM headers are)")
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
     return subprocess.run([HOST] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=env)
@@ -189,7 +190,7 @@ def test_optimizer_plugin_pose_graph(tmp_path, oracle, kind, gps, info):
         f.write(np.asarray(gp[0], np.int32).tobytes() + np.asarray(gp[1], np.float64).tobytes())
         if info:
             f.write((np.asarray(gp[2], np.float64) if gp[2] is not None else np.tile(np.eye(6).reshape(-1), (len(gp[0]), 1))).tobytes())
-    r = _host(["pg", LIBDIR, inp, out])
+    r = _host(["pg", PLUGDIR, inp, out])
     assert r.returncode == 0 and "pose_graph_optimize=1" in r.stdout, r.stdout + r.stderr
     raw = open(out, "rb").read()
     S = np.frombuffer(raw, np.float64, len(start) * 8, 4).reshape(-1, 8)
@@ -225,7 +226,7 @@ def test_optimizer_plugin_icp_fitsim3_optimizepose(tmp_path, oracle):
     with open(inp, "wb") as f:
         f.write(np.array([n, 127], np.int32).tobytes() + src.tobytes() + dst.tobytes())
         f.write(np.array([m], np.int32).tobytes() + a1.tobytes() + a2.tobytes() + idp.tobytes() + start.tobytes())
-    r = _host(["align", LIBDIR, inp, out])
+    r = _host(["align", PLUGDIR, inp, out])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     assert struct.unpack("3i", raw[:12]) == (1, 1, 1)
@@ -283,7 +284,7 @@ def test_optimizer_plugin_general_graph_inverse_depth_and_mixed(tmp_path, oracle
             f.write((m3 * zm[:, None]).astype(np.float64).tobytes())
             if info:
                 f.write(oinfo[m].astype(np.float64).tobytes())
-    r = _host(["pg", LIBDIR, inp, out])
+    r = _host(["pg", PLUGDIR, inp, out])
     assert r.returncode == 0 and "pose_graph_optimize=1" in r.stdout, r.stdout + r.stderr
     raw = open(out, "rb").read()
     nf, nx, ni = len(start), len(xyz), len(rho)

@@ -1,5 +1,5 @@
-"""Drop-in boundary on the GPU box: a real GSLAM host (build/plugin_host, compiled against the GSLAM
-headers in the authoring container) loads libgslam_optimizer.so / libgslam_featuredetector.so through
+"""Drop-in boundary on the GPU box: a real GSLAM host (oracle/_ref/bin/plugin_host, compiled against the GSLAM
+headers where the reference is) loads libgslam_optimizer.so / libgslam_featuredetector.so through
 GSLAM::Optimizer::create() / Registry / dlopen and drives them with GSLAM's own containers.  Results
 must equal the C-ABI path (bit-exact for ORB/BF, tolerance for BA)."""
 import os
@@ -15,15 +15,16 @@ from gslam_amd.ba_synth import make_graph
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "build", "plugin_host")
+HOST = os.path.join(ROOT, "oracle", "_ref", "bin", "plugin_host")
 LIBDIR = os.path.join(ROOT, "gslam_amd", "lib")
+PLUGDIR = os.path.join(ROOT, "oracle", "_ref", "plugins")
 
 
 def _need_host():
-    if not (os.path.exists(HOST) and os.path.exists(os.path.join(LIBDIR, "libgslam_optimizer.so"))):
+    if not (os.path.exists(HOST) and os.path.exists(os.path.join(PLUGDIR, "libgslam_optimizer.so"))):
         # the plugins need the GSLAM headers at build time; a tree built where /root/reference is absent cannot have them
-        pytest.skip("build/plugin_host or the plugin .so files are missing: run `make plugins` in the authoring "
-                    "container (they travel to the GPU box as built artefacts)")
+        pytest.skip("oracle/_ref/bin/plugin_host or the plugin .so files are missing: `make plugins` builds them where the "
+                    "GSLAM headers are")
 
 
 def _run(args, extra_env=None):
@@ -48,7 +49,7 @@ def test_optimizer_plugin_optimize_matches_oracle(tmp_path, oracle):
                       ("point_free", np.uint8), ("obs_cam", np.int32), ("obs_point", np.int32),
                       ("obs_xy", np.float64)):
             f.write(np.ascontiguousarray(g[k], dtype=dt).tobytes())
-    r = _run(["ba", LIBDIR, inp, out])
+    r = _run(["ba", PLUGDIR, inp, out])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "optimize=1 optimizePose(unsupported)=0" in r.stdout
     raw = open(out, "rb").read()
@@ -74,7 +75,7 @@ def test_optimizer_plugin_magin(tmp_path, oracle):
         for k, dt in (("cam_pose", np.float64), ("cam_dof", np.int32), ("point_xyz", np.float64),
                       ("obs_cam", np.int32), ("obs_point", np.int32), ("obs_xy", np.float64)):
             f.write(np.ascontiguousarray(g[k], dtype=dt).tobytes())
-    r = _run(["magin", LIBDIR, inp, out])
+    r = _run(["magin", PLUGDIR, inp, out])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "magin=1" in r.stdout and "observations_left=0" in r.stdout and "posegraph_optimize=1" in r.stdout, r.stdout
     worst = float(r.stdout.split("worst_rotation_residual=")[1].split()[0])
@@ -140,7 +141,7 @@ def test_optimizer_plugin_self_calibration(tmp_path, ctx, model, dof_flags):
         f.write(np.ascontiguousarray(frame, np.int32).tobytes())
         f.write(np.ascontiguousarray(point, np.int32).tobytes())
         f.write(np.ascontiguousarray(px).tobytes())
-    r = _run(["calib", LIBDIR, inp, out])
+    r = _run(["calib", PLUGDIR, inp, out])
     assert r.returncode == 0 and "calib=1" in r.stdout, r.stdout + r.stderr
     raw = open(out, "rb").read()
     ok, n = struct.unpack("ii", raw[:8])
@@ -171,7 +172,7 @@ def test_optimizer_plugin_resident_graph_update_path(tmp_path, oracle):
     res = []
     for warm in (False, True):
         out = tmp_path / f"out_{int(warm)}.bin"
-        r = _run(["ba", LIBDIR, inp, out], {"GSLAM_HOST_WARM_GRAPH": "1"} if warm else None)
+        r = _run(["ba", PLUGDIR, inp, out], {"GSLAM_HOST_WARM_GRAPH": "1"} if warm else None)
         assert r.returncode == 0, r.stdout + r.stderr
         assert ("warm_optimize=1" in r.stdout) == warm
         raw = open(out, "rb").read()
@@ -204,7 +205,7 @@ def test_optimizer_plugin_sim3_scale_and_bad_anchor(tmp_path, oracle):
     res = {}
     for scale in (1.0, 2.5):
         out = tmp_path / f"out_{scale}.bin"
-        r = _run(["ba", LIBDIR, inp, out, scale])
+        r = _run(["ba", PLUGDIR, inp, out, scale])
         assert r.returncode == 0, r.stdout + r.stderr
         raw = open(out, "rb").read()
         poses = np.frombuffer(raw, np.float64, nc * 7, 4).reshape(nc, 7)
@@ -217,9 +218,9 @@ def test_optimizer_plugin_sim3_scale_and_bad_anchor(tmp_path, oracle):
     assert np.abs(res[2.5][0] - po).max() < 1e-7 and np.abs(res[2.5][1] - xo).max() < 1e-7
     for scale in (1.0, 2.5):
         assert abs(0.5 * res[scale][2] - so.final_cost) <= 1e-7 * so.final_cost
-    r = _run(["ba", LIBDIR, inp, tmp_path / "bad.bin", 1.0, 17])
+    r = _run(["ba", PLUGDIR, inp, tmp_path / "bad.bin", 1.0, 17])
     assert r.returncode == 3 and "optimize=0" in r.stdout
-    r = _run(["ba", LIBDIR, inp, tmp_path / "bad2.bin", -1.0])
+    r = _run(["ba", PLUGDIR, inp, tmp_path / "bad2.bin", -1.0])
     assert r.returncode == 3 and "optimize=0" in r.stdout
 
 
@@ -235,7 +236,7 @@ def test_optimizer_plugin_pnp(tmp_path, oracle):
     with open(inp, "wb") as f:
         f.write(struct.pack("i", len(X)))
         f.write(X.astype(np.float64).tobytes() + m.astype(np.float64).tobytes() + start.tobytes())
-    r = _run(["pnp", LIBDIR, inp, out])
+    r = _run(["pnp", PLUGDIR, inp, out])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     pose = np.frombuffer(raw, np.float64, 7, 4)
@@ -270,7 +271,7 @@ def test_optimizer_plugin_pnp_under_sphere_projection(tmp_path, oracle):
     with open(inp, "wb") as f:
         f.write(struct.pack("i", n))
         f.write(X.astype(np.float64).tobytes() + m.astype(np.float64).tobytes() + start.tobytes())
-    r = _run(["pnp", LIBDIR, inp, out, 1])
+    r = _run(["pnp", PLUGDIR, inp, out, 1])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     pose = np.frombuffer(raw, np.float64, 7, 4)
@@ -312,7 +313,7 @@ def test_featuredetector_plugin_matches_oracle(tmp_path, oracle, channels):
         expect_gray = oracle.bgr_to_gray(img)
     inp, out = tmp_path / "img.raw", tmp_path / "out.bin"
     img.tofile(inp)
-    r = _run(["orb", LIBDIR, w, h, channels, inp, out, K])
+    r = _run(["orb", PLUGDIR, w, h, channels, inp, out, K])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     ok, n, okm, nm = struct.unpack("4i", raw[:16])
@@ -337,7 +338,7 @@ def test_featuredetector_plugin_orbslam_mode(tmp_path, oracle):
     gray = oracle.synth_frame(w, h, 777)
     inp, out = tmp_path / "img.raw", tmp_path / "out.bin"
     gray.tofile(inp)
-    r = _run(["orb", LIBDIR, w, h, 1, inp, out, K],
+    r = _run(["orb", PLUGDIR, w, h, 1, inp, out, K],
              {"GSLAM_HOST_SVAR": "FeatureDetectorHIP.Steering=1;FeatureDetectorHIP.Distribution=1"})
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
@@ -372,7 +373,7 @@ def test_vocabulary_plugin_equals_reference_base_class(tmp_path, oracle, desc_by
     gb, df, out = tmp_path / "voc.gbow", tmp_path / "desc.raw", tmp_path / "out.bin"
     open(gb, "wb").write(bow_synth.to_gbow_bytes(voc))
     desc.tofile(df)
-    r = _run(["bow", LIBDIR, gb, df, 1500, 2, out])
+    r = _run(["bow", PLUGDIR, gb, df, 1500, 2, out])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "bow gpu==reference:1" in r.stdout
     assert "database vectors, mismatches=0" in r.stdout  # scoreVocabularyBatch == the reference's own score()
@@ -397,7 +398,7 @@ def test_vocabulary_plugin_overloads_and_large_images(tmp_path, oracle):
         df, out = tmp_path / f"desc{n}.raw", tmp_path / f"out{n}.bin"
         desc = np.concatenate([bow_synth.features_near_words(voc, n - n // 5, seed=n), oracle_lib.random_descriptors(n // 5, 0xAB + n)])
         desc.tofile(df)
-        r = _run(["bow", LIBDIR, gb, df, n, 1, out])
+        r = _run(["bow", PLUGDIR, gb, df, n, 1, out])
         assert r.returncode == 0, r.stdout + r.stderr
         assert "bow gpu==reference:1" in r.stdout and "list overload equal=1 single-feature word mismatches=0 failures=0" in r.stdout
 
@@ -410,7 +411,7 @@ def test_undistorter_hip_equals_reference_class(tmp_path, channels):
     img = rng.integers(0, 256, (240, 320, channels), dtype=np.uint8)
     f = tmp_path / "img.raw"
     img.tofile(f)
-    r = _run(["undist", LIBDIR, channels, f])
+    r = _run(["undist", PLUGDIR, channels, f])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "mismatches=0" in r.stdout
 
@@ -420,7 +421,7 @@ def test_application_plugin_on_the_message_bus(tmp_path, oracle):
     (Registry::load -> gslam.apps.orbhip, shared Messenger), receives "dataset/frame", publishes "orbhip/curframe"
     with keypoints + descriptors deposited through MapFrame::setKeyPoints.  Outputs equal the oracle bit for bit."""
     _need_host()
-    if not os.path.exists(os.path.join(LIBDIR, "libgslam_orbhip.so")):
+    if not os.path.exists(os.path.join(PLUGDIR, "libgslam_orbhip.so")):
         pytest.skip("libgslam_orbhip.so not built")
     w, h, n, K = 640, 480, 5, 1000
     frames = np.stack([oracle.synth_frame(w, h, 0x5EED0000 + i) for i in range(n)])
@@ -429,7 +430,7 @@ def test_application_plugin_on_the_message_bus(tmp_path, oracle):
     frames = np.stack([pano[:, 32 * i:32 * i + w] for i in range(n)])
     fin, out = tmp_path / "frames.raw", tmp_path / "out.bin"
     frames.tofile(fin)
-    r = _run(["app", LIBDIR, w, h, n, fin, out, K])
+    r = _run(["app", PLUGDIR, w, h, n, fin, out, K])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     n_out, n_msgs = struct.unpack("2i", raw[:8])
@@ -461,14 +462,14 @@ def test_estimator_plugin_through_estimator_create(tmp_path, oracle, model):
     """GSLAM::Estimator::create() loads libgslam_estimator.so (createEstimatorInstance, Estimator.h:42-53,175-191);
     findHomography / findAffine2D / findFundamental return the oracle's model and inlier mask bit for bit."""
     _need_host()
-    if not os.path.exists(os.path.join(LIBDIR, "libgslam_estimator.so")):
+    if not os.path.exists(os.path.join(PLUGDIR, "libgslam_estimator.so")):
         pytest.skip("libgslam_estimator.so not built")
     from test_ransac_oracle import _corr
     n, thr = 900, 2.0 if model < 2 else 1.0
     P, Q, inl, _ = _corr(model, n, 0.3, 40 + model, 0.3)
     fin, out = tmp_path / "pts.raw", tmp_path / "out.bin"
     np.ascontiguousarray(np.c_[P, Q], dtype=np.float64).tofile(fin)
-    r = _run(["est", LIBDIR, model, n, fin, thr, out])
+    r = _run(["est", PLUGDIR, model, n, fin, thr, out])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "EstimatorHIP ok=1 unsupported_paths=0" in r.stdout
     raw = open(out, "rb").read()
@@ -508,7 +509,7 @@ def test_estimator_plugin_remaining_solvers(tmp_path, oracle, model):
         P, Q, thr = _cases()[4]
         n = len(P)
         np.ascontiguousarray(np.c_[P, Q], dtype=np.float64).tofile(fin)
-        r = _run(["est", LIBDIR, 4, n, fin, thr, out])
+        r = _run(["est", PLUGDIR, 4, n, fin, thr, out])
         assert r.returncode == 0, r.stdout + r.stderr
         raw = open(out, "rb").read()
         ok, nm = struct.unpack("2i", raw[:8])
@@ -528,7 +529,7 @@ def test_estimator_plugin_remaining_solvers(tmp_path, oracle, model):
         d2[7] = R @ d1[7]
         with open(fin, "wb") as f:
             f.write(pose.tobytes() + np.ascontiguousarray(np.c_[d1, d2]).tobytes())
-        r = _run(["est3", LIBDIR, 8, 40, fin, 0.0, out])
+        r = _run(["est3", PLUGDIR, 8, 40, fin, 0.0, out])
         assert r.returncode == 0, r.stdout + r.stderr
         raw = open(out, "rb").read()
         ok, nm, nv = struct.unpack("3i", raw[:12])
@@ -545,7 +546,7 @@ def test_estimator_plugin_remaining_solvers(tmp_path, oracle, model):
     rows[:, :3] = P
     rows[:, 3:3 + Q.shape[1]] = Q
     rows.tofile(fin)
-    r = _run(["est3", LIBDIR, model, n, fin, thr, out])
+    r = _run(["est3", PLUGDIR, model, n, fin, thr, out])
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(out, "rb").read()
     ok, nm, nv = struct.unpack("3i", raw[:12])
