@@ -210,7 +210,18 @@ def arrow_solve_compact(ctx: hip.Context, A, b, n_band, half_bandwidth):
     import torch
     n = A.shape[0]
     lda, m, brow = compact_layout(n_band, half_bandwidth, n - n_band)
-    dA = torch.from_numpy(to_compact(A, n_band, lda, m, brow)).cuda()
+    return arrow_solve_compact_columns(ctx, to_compact(A, n_band, lda, m, brow), b, n_band, half_bandwidth)
+
+
+def arrow_solve_compact_columns(ctx: hip.Context, cols, b, n_band, half_bandwidth):
+    """gh_arrow_solve_compact_dev on prebuilt compact columns: cols (n x lda, row c = column c of the device matrix, laid out as
+    compact_layout(n_band, half_bandwidth, n - n_band) says, fill slots zero) -- no dense n x n on the way.  Returns (x, info)."""
+    import torch
+    n, lda = cols.shape
+    lay = compact_layout(n_band, half_bandwidth, n - n_band)
+    if lay is None or lay[0] != lda:
+        raise ValueError("compact columns of %d doubles, the layout wants %s" % (lda, lay and lay[0]))
+    dA = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.float64)).cuda()
     db = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float64)).cuda()
     info = C.c_int()
     ctx.check(hip.lib.gh_arrow_solve_compact_dev(ctx.h, C.c_void_p(dA.data_ptr()), n, lda, int(n_band), int(half_bandwidth),

@@ -60,10 +60,10 @@ def _quat_mul(a, b):
 COVIS_HALF_WINDOW = 12  # cameras either side of a point's home position that may observe it
 
 
-def _pick_observers(rng, n_cams, n_points, k):
-    """(n_points, k) camera ids: k distinct cameras out of the window of 2 * COVIS_HALF_WINDOW + 1 consecutive cameras
-    around a home position drawn uniformly along the trajectory (the whole trajectory when it is shorter than that)."""
-    win = min(n_cams, 2 * COVIS_HALF_WINDOW + 1)
+def _pick_observers(rng, n_cams, n_points, k, window):
+    """(n_points, k) camera ids: k distinct cameras out of the window of `window` consecutive cameras around a home position
+    drawn uniformly along the trajectory (the whole trajectory when it is shorter than that)."""
+    win = min(n_cams, window)
     home = rng.integers(0, n_cams, size=n_points)
     lo = np.clip(home - win // 2, 0, n_cams - win)
     nn = np.empty((n_points, k), np.int64)
@@ -102,8 +102,10 @@ def graph_census(g):
 
 
 def make_graph(n_cams, n_points, n_obs_per_point=6, seed=1, noise=0.002, outlier_frac=0.05, perturb=True, loop_closures=0,
-               closure_span=None):
-    """loop_closures: that many points (drawn by a generator of their own: the rest of the graph is the graph without them) keep
+               closure_span=None, covis_window=None):
+    """covis_window: the full width in cameras of a point's co-visibility window (default 2 * COVIS_HALF_WINDOW + 1; a wider one
+    widens the band of the reduced camera system: span window - 1 in order).
+    loop_closures: that many points (drawn by a generator of their own: the rest of the graph is the graph without them) keep
     the first half of their observers and take the other half from a window of cameras at least `closure_span` indices further
     along the trajectory (default: half of it) -- the revisits global BA exists for (GSLAM/core/Optimizer.h:127-148,162-167).
     g["closure_points"] lists them."""
@@ -121,11 +123,13 @@ def make_graph(n_cams, n_points, n_obs_per_point=6, seed=1, noise=0.002, outlier
     q_gt = _quat_from_R(R)
     pts_gt = rng.uniform(-3, 3, size=(n_points, 3))
     k = min(n_obs_per_point, n_cams)
-    nn = _pick_observers(rng, n_cams, n_points, k)
+    window = 2 * COVIS_HALF_WINDOW + 1 if covis_window is None else int(covis_window)
+    assert window >= 1, window
+    nn = _pick_observers(rng, n_cams, n_points, k, window)
     closure_points = np.zeros(0, np.int64)
     if loop_closures > 0 and k >= 2:
         lrng = np.random.default_rng(seed + 7919)
-        win = min(n_cams, 2 * COVIS_HALF_WINDOW + 1)
+        win = min(n_cams, window)
         span = int(closure_span) if closure_span else n_cams // 2
         assert win < span <= n_cams - win, (span, n_cams)
         fits = (nn[:, 0] + span <= n_cams - win) | (nn[:, 0] - span - win + 1 >= 0)  # a window `span` away exists

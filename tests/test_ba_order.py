@@ -139,3 +139,36 @@ def test_bad_indices_are_refused():
     g["obs_cam"][7] = 200
     with pytest.raises(ValueError):
         ba.camera_order(g)
+
+
+@pytest.mark.parametrize("shuffled", [False, True])
+@pytest.mark.parametrize("window", [31, 32, 33])
+def test_wide_covisibility_windows_around_the_band_limit(window, shuffled):
+    """Co-visibility windows of 31 / 32 / 33 cameras (in-order span 30 / 31 / 32): the widest band the solver takes (window 32,
+    span 31: half-bandwidth 6 * 31 + 5 = 191), and one past it.  What the ordering returns today; the border it finds for the
+    shuffled graphs (printed) decides speed, not correctness, so it carries no bound here."""
+    from gslam_amd import ba
+    g = make_graph(500, 50000, n_obs_per_point=6, seed=1, covis_window=window)
+    h = _shuffle(g, 1)[0] if shuffled else g
+    perm, nb, span, re = ba.camera_order(h)
+    print("window %d %s: border cameras %d, span %d, reordered %s" % (window, "shuffled" if shuffled else "in order", nb, span, re))
+    assert np.array_equal(np.sort(perm), np.arange(500))
+    assert span == _span(h, perm, nb)
+    if nb > 0 or re:
+        assert span <= BAND_SPAN
+    if window == 32 and not shuffled:
+        assert nb == 0 and span == BAND_SPAN and not re and np.array_equal(perm, np.arange(500))
+    if window == 33:
+        assert nb == 0 and not re and span > BAND_SPAN
+
+
+@pytest.mark.parametrize("cams,points", [(60, 3000), (500, 50000), (10000, 1000000)])
+@pytest.mark.parametrize("seed", [1, 2])
+def test_covis_window_default_draws_the_same_graph(cams, points, seed):
+    """make_graph(covis_window=25) is the default window: every existing graph byte for byte (the 1 M-point C5 graph crosses the
+    2^18-point chunk of _pick_observers)."""
+    a = make_graph(cams, points, n_obs_per_point=6, seed=seed)
+    b = make_graph(cams, points, n_obs_per_point=6, seed=seed, covis_window=25)
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k

@@ -81,7 +81,7 @@ def test_reorder_can_be_switched_off(ctx, monkeypatch):
     assert used[0] == "dense" and order == (0, False)
 
 
-def test_20k_cameras_2m_points_run_through_the_band_solver(ctx):
+def test_20k_cameras_2m_points_run_through_the_band_solver(ctx, oracle):
     """n = 120 000 unknowns: beyond the n < 65536 limit of rounds 1-5 (a 16-bit grid dimension of the seeding launch), and in
     COMPACT columns (cr_map.h): 2.0 GB for the reduced system where the dense lower triangle would take 115 GB."""
     import torch
@@ -100,3 +100,6 @@ def test_20k_cameras_2m_points_run_through_the_band_solver(ctx):
     assert s.iterations == 4 and s.accepted >= 3 and s.final_cost < 0.7 * s.initial_cost
     # the same graph at a tenth of the size goes through the same code with n < 65536: the per-observation cost agrees roughly
     assert np.isfinite(poses).all() and np.isfinite(pts).all()
+    # the reported costs are the oracle's at the start and at the returned state (the poses cross n = 65536 on their way back)
+    assert abs(oracle.ba_cost(g) - s.initial_cost) <= 1e-12 * s.initial_cost
+    assert abs(oracle.ba_cost(g, poses, pts) - s.final_cost) <= 1e-12 * s.final_cost
