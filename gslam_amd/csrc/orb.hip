@@ -15,7 +15,7 @@
 //   select      one workgroup per (level, frame): LDS histogram over (rank, score) finds the quota
 //               cut-off, block scans give the output slots - no sort, no float
 //   describe    one wave per keypoint: 33x33 patch in LDS, wave-reduced integer moments, separable
-//               integer blur in LDS, 4 x __ballot packs the 256 test bits
+//               integer blur (h-pass on MFMA), 4 x __ballot packs the 256 test bits
 #include <stdlib.h>
 
 #include "common.h"
@@ -344,34 +344,13 @@ __device__ __forceinline__ int wave_incl_scan_i32(int v) {
 __device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
 
-// r[] = the 16 ring intensities, c = the centre.  min/max commute with the subtraction of c, so the arcs are
-// evaluated on the raw intensities (no 16 differences) and the running best takes two arcs per v_max3 / v_min3:
-//   score = max(0, max_i min(arc_i) - c, c - min_i max(arc_i))
-__device__ __forceinline__ int fast_score16(const int (&r)[16], int c) {
-  int lo3[16], hi3[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    lo3[i] = min3i(r[i], r[(i + 1) & 15], r[(i + 2) & 15]);
-    hi3[i] = max3i(r[i], r[(i + 1) & 15], r[(i + 2) & 15]);
-  }
-  int best_lo = 0, best_hi = 255;
-#pragma unroll
-  for (int i = 0; i < 16; i += 2) {
-    const int lo9a = min3i(lo3[i], lo3[(i + 3) & 15], lo3[(i + 6) & 15]);
-    const int lo9b = min3i(lo3[i + 1], lo3[(i + 4) & 15], lo3[(i + 7) & 15]);
-    const int hi9a = max3i(hi3[i], hi3[(i + 3) & 15], hi3[(i + 6) & 15]);
-    const int hi9b = max3i(hi3[i + 1], hi3[(i + 4) & 15], hi3[(i + 7) & 15]);
-    best_lo = max3i(best_lo, lo9a, lo9b);
-    best_hi = min3i(best_hi, hi9a, hi9b);
-  }
-  return max3i(0, best_lo - c, c - best_hi);
-}
-
-// The same score with BOTH polarities in one register: v = r | (255 - r) << 16, two 16-bit lanes whose bit patterns are
-// fp16 DENORMALS (0 .. 255 -> exponent field 0), which order exactly as the integers do; the kernels run with fp16
-// denormals preserved (amdhsa_float_denorm_mode_16_64 = 3).  min over an arc of the high lane is 255 - max over the arc of
-// r, so ONE gfx950 v_pk_minimum3_f16 does the work of a v_min3_u32 and a v_max3_u32, and the running best of both
-// polarities is a maximum: 16 packs + 16 + 16 + 8 three-input packed ops + 5 instead of 32 + 32 + 16 + 3 (bit-identical:
+// r[] = the 16 ring intensities, c = the centre.  min/max commute with the subtraction of c, so the arcs are evaluated on the
+// raw intensities (no 16 differences):  score = max(0, max_i min(arc_i) - c, c - min_i max(arc_i)).
+// BOTH polarities live in one register: v = r | (255 - r) << 16, two 16-bit lanes whose bit patterns are fp16 DENORMALS
+// (0 .. 255 -> exponent field 0), which order exactly as the integers do; the kernels run with fp16 denormals preserved
+// (amdhsa_float_denorm_mode_16_64 = 3).  min over an arc of the high lane is 255 - max over the arc of r, so ONE gfx950
+// v_pk_minimum3_f16 does the work of a v_min3_u32 and a v_max3_u32, and the running best of both polarities is a maximum:
+// 16 packs + 16 + 16 + 8 three-input packed ops + 5 instead of 32 + 32 + 16 + 3 with 32-bit v_min3 / v_max3 (bit-identical:
 // every value is an exact small integer, no rounding anywhere).
 __device__ __forceinline__ uint32_t pk_min3_f16(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t d;
@@ -419,22 +398,11 @@ __shared__ unsigned int ph_slot;
 #define GH_PHASE_START()
 #define GH_PHASE(k)
 #endif
-// timing experiments only (docs/notes_r06.md: what each stage of orb_fast_cells costs; wrong results): bit 0 no pass 2, bit 1 no pass 1,
-// bit 2 no cell stage, bit 3 no next pyramid level
-#ifndef GH_ORB_WHATIF
-#define GH_ORB_WHATIF 0
-#endif
 constexpr int kTileW = 96;   // bytes per LDS tile row (6 x 16 B: 16-byte aligned window that covers x0-4 .. x0+67), 72 rows
 constexpr int kTileH = 72;
 constexpr int kScoreH = 66;   // score window: 64x64 region + 1 px NMS halo
 constexpr int kScoreOff = 3;  // window col sx is stored at byte sx + 3 so that both cells of a row start dword aligned
-constexpr int kScoreWPk = 72;  // row pitch (bytes) of the packed-16-bit pass 1; the SWAR pass 1 uses 68 (see fast_cells_tile)
 
-// One 64 x 64 tile (2 x 2 cells) of one level of one frame, by one 256-thread workgroup; tile_id in [0, nbx nby n_frames).
-// PK: arc scores through fast_score16_pk (GSLAM_HIP_ORB_PKSCORE, decided per plan).
-// P1: formulation of pass 1 (GSLAM_HIP_ORB_PASS1, decided per plan) -- 0 = packed 16-bit min / max (rounds 2-3),
-//     1 = SWAR on 16-bit fields (full-rate and / or / sub / v_bitop3), fields split in registers.  (A variant that read the
-//     fields pre-split from LDS planes lost 22 %: 38 KB of LDS leave 4 workgroups per CU; profiles/orb_pass1_ab_r04.txt.)
 // tile id -> (frame, tile row, tile column)
 __device__ __forceinline__ void fast_tile_coords(const NextLevel& nx, int nbx, int nby, int tile_id, int& frame, int& bx, int& by) {
   if (nx.tiles_inv != 0u && nx.nbx_inv != 0u) {  // (two integer divisions were ~40 VALU per wave: 4 % of the kernel)
@@ -462,27 +430,30 @@ __device__ __forceinline__ const uint4* fast_tile_src(const LevelView& lv, int f
   return reinterpret_cast<const uint4*>(lv.base + (size_t)frame * lv.frame_stride + (__umul24((uint32_t)gy, (uint32_t)lv.pitch) + (uint32_t)gx));
 }
 
-template <bool PK, int P1, bool PLANE = false>
+// One 64 x 64 tile (2 x 2 cells) of one level of one frame, by one 256-thread workgroup; tile_id in [0, nbx nby n_frames).
+// Pass 1 is SWAR on 16-bit fields (full-rate and / or / sub / v_bitop3), fields split in registers.  (A variant that read the
+// fields pre-split from LDS planes lost 22 %: 38 KB of LDS leave 4 workgroups per CU; profiles/orb_pass1_ab_r04.txt.)
+// PLANE: no cell stage; the tile's scores go to the level's score plane instead (the quadtree mode).
+template <bool PLANE>
 __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th,
                                                 uint32_t* __restrict__ cell_cnt, uint32_t* __restrict__ cell_ent,
                                                 int cells_per_frame, int cell_off, int n_frames, const NextLevel& nx,
                                                 uint32_t* __restrict__ dbg, int tile_id) {
-  // SWAR pass 1 covers a window row with 17 aligned dwords (window cols -2 .. 65) and the score tile is FLAT with 68 bytes
+  // Pass 1 covers a window row with 17 aligned dwords (window cols -2 .. 65) and the score tile is FLAT with 68 bytes
   // per row: byte 68 sy + 3 + sx, so (item, pixel k) lands at 4 item + 1 + k.  Cols -2 / -1 of a row share their bytes with
   // cols 66 / 67 of the row above; nothing ever reads them (NMS looks at cols 0 .. 65 only).
-  constexpr int kScoreW = P1 != 0 ? 68 : kScoreWPk;
-  constexpr int kScoreBytes = P1 != 0 ? kScoreH * 68 + 8 : kScoreH * kScoreWPk;
-  constexpr int kQueueLen = P1 != 0 ? kScoreH * 68 : kScoreH * kScoreH;
+  constexpr int kScoreW = 68;
+  constexpr int kScoreBytes = kScoreH * kScoreW + 8;
+  constexpr int kQueueLen = kScoreH * kScoreW;
   __shared__ __attribute__((aligned(16))) uint8_t tile[kTileH * kTileW];
   __shared__ __attribute__((aligned(16))) uint8_t score[kScoreBytes];
-  // the dense-cell lists of the NMS stage live in the image tile, which is dead after pass 2 (P1 != 0: 20.4 KB of LDS per
-  // workgroup -> 7-8 workgroups per CU instead of 6; the kernel is latency sensitive: profiles/orb_pass1_ab_r04.txt)
-  __shared__ uint32_t lists_own[P1 == 0 ? 4 * 256 : 1];
-  uint32_t(*lists)[256] = reinterpret_cast<uint32_t(*)[256]>(P1 == 0 ? reinterpret_cast<uint8_t*>(lists_own) : tile);
+  // the dense-cell lists of the NMS stage live in the image tile, which is dead after pass 2 (20.4 KB of LDS per workgroup
+  // -> 7-8 workgroups per CU instead of 6; the kernel is latency sensitive: profiles/orb_pass1_ab_r04.txt)
+  uint32_t(*lists)[256] = reinterpret_cast<uint32_t(*)[256]>(tile);
   static_assert(sizeof(tile) >= 4 * 256 * sizeof(uint32_t), "four 1 KB lists fit the tile");
   __shared__ uint16_t queue[kQueueLen];
   __shared__ int q_count;
-  __shared__ uint16_t bit_pos[32];  // P1 != 0: score-tile offset of candidate bit b of a thread, relative to 4 tid
+  __shared__ uint16_t bit_pos[32];  // score-tile offset of candidate bit b of a thread, relative to 4 tid
   GH_PHASE_START();
 
   const int tid = threadIdx.x;
@@ -509,219 +480,119 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   bool resized = false;
   ResizeOps rops;
   int rg0 = 0, rng = 0, rr0 = 0, rr1 = 0;
-  if constexpr (P1 != 0) {
-    if (!(GH_ORB_WHATIF & 8) && nx.dst_base != nullptr && nx.tb.mtab != nullptr && by > 0 && by < nby - 1 && bx < nbx - 1) {
-      rg0 = nx.gx0[bx];
-      rng = nx.gx0[bx + 1] - rg0;
-      if (rng <= 8) {
-        rr0 = nx.gy0[by];
-        rr1 = nx.gy0[by + 1];
-        rops = resize_tile_mfma_load(ax, nx.tb, rg0, rng, rr0, rr1);
-        resized = true;
-      }
+  if (nx.dst_base != nullptr && nx.tb.mtab != nullptr && by > 0 && by < nby - 1 && bx < nbx - 1) {
+    rg0 = nx.gx0[bx];
+    rng = nx.gx0[bx + 1] - rg0;
+    if (rng <= 8) {
+      rr0 = nx.gy0[by];
+      rr1 = nx.gy0[by + 1];
+      rops = resize_tile_mfma_load(ax, nx.tb, rg0, rng, rr0, rr1);
+      resized = true;
     }
   }
   // 16 B per lane: rows of the level are 16-byte aligned (pitch % 16 == 0, checked by the launcher)
   for (int i = tid; i < kTileH * (kTileW / 16); i += 256) *reinterpret_cast<uint4*>(&tile[16 * i]) = *fast_tile_src(lv, frame, bx, by, i);
-  if constexpr (P1 != 0) {
-    // candidate bit b of a thread (see pass 1): b ^ 15 = 16 (k >> 1) + 2 trip + (k & 1) -> score offset 1024 trip + 1 + k
-    if (tid < 32) {
-      const int ix = tid ^ 15, k = (ix & 1) + 2 * (ix >> 4), trip = (ix >> 1) & 7;
-      bit_pos[tid] = (uint16_t)(1024 * trip + 1 + k);
-    }
+  // candidate bit b of a thread (see pass 1): b ^ 15 = 16 (k >> 1) + 2 trip + (k & 1) -> score offset 1024 trip + 1 + k
+  if (tid < 32) {
+    const int ix = tid ^ 15, k = (ix & 1) + 2 * (ix >> 4), trip = (ix >> 1) & 7;
+    bit_pos[tid] = (uint16_t)(1024 * trip + 1 + k);
   }
   __syncthreads();
   GH_PHASE(0);
   // The next pyramid level of an INTERIOR tile, now, out of the image tile (which the NMS lists overwrite after pass 2): h-taps
-  // on MFMA.  Edge tiles (first / last tile row, last tile column: they also own what lies outside every tile) keep the VALU
-  // path at the end of the kernel, which reads global memory.
-  if constexpr (P1 != 0) {
-    if (resized) resize_tile_mfma(tile, kTileW, oy, nx.dst_base + (size_t)frame * nx.dst_frame_stride, nx.dst_pitch, rops, rg0, rng, rr0, rr1, dbg);
-  }
+  // on MFMA.  Edge tiles (first / last tile row, last tile column: they also own what lies outside every tile) and levels
+  // without MFMA tables keep the VALU path at the end of the kernel, which reads global memory.
+  if (resized) resize_tile_mfma(tile, kTileW, oy, nx.dst_base + (size_t)frame * nx.dst_frame_stride, nx.dst_pitch, rops, rg0, rng, rr0, rr1, dbg);
 
   // Scores for the 66x66 window (region + 1 px NMS halo); tile col of window col sx is sx + 18, row sy + 3.
   // Pass 1: cheap necessary condition on the 4 compass pixels (any 9-arc holds two ADJACENT compass
   // pixels) for every pixel; survivors are appended to an LDS queue so that pass 2 (the ~100-op arc
   // score) runs with all lanes busy instead of paying full price in every partially-hit wave.
   // The queue order is irrelevant: results land in score[] by position.
-  // score tile cleared (incl. pad cols): 16 bytes per store where the size allows (two trips instead of five)
-  if constexpr (kScoreBytes % 16 == 0) {
-    for (int i = tid; i < kScoreBytes / 16; i += 256) reinterpret_cast<uint4*>(score)[i] = make_uint4(0u, 0u, 0u, 0u);
-  } else {
-    for (int i = tid; i < kScoreBytes / 4; i += 256) reinterpret_cast<uint32_t*>(score)[i] = 0u;
-  }
-  // One work item = one aligned tile dword = 4 horizontally adjacent pixels (tile cols 4m .. 4m+3, m = 4..21,
-  // i.e. window cols -2 .. 69), evaluated with packed 16-bit math: 5 LDS dword reads and ~56 VALU per 4 px.
-  // bright test: some adjacent compass pair both > c + t; dark: both < c - t.
+  // score tile cleared (incl. pad cols): 16 bytes per store (two trips instead of five)
+  static_assert(kScoreBytes % 16 == 0, "the score tile is cleared by 16-byte stores");
+  for (int i = tid; i < kScoreBytes / 16; i += 256) reinterpret_cast<uint4*>(score)[i] = make_uint4(0u, 0u, 0u, 0u);
   const int sx_lo = max(0, kEdge - (x0 - 1)), sx_hi = min(kScoreH, lv.w - kEdge - (x0 - 1));
   // tile-uniform: every window pixel lies in the valid region [kEdge, dim - kEdge) -> constant trim masks
   const bool interior = sx_lo == 0 && sx_hi == kScoreH && y0 - 1 >= kEdge && y0 - 1 + kScoreH <= lv.h - kEdge;
-  if constexpr (P1 != 0) {
-    // SWAR pass 1.  Every byte sits zero-extended in a 16-bit field: E(w) = {b0, b2}, O(w) = {b1, b3} of a tile dword.
-    // With A = c + t + BIAS per field, A - x keeps its BIAS bit iff x <= c + t (x is NOT brighter), and with
-    // D = c - t - 1 + BIAS, D - x keeps it iff x < c - t (x IS darker); fields never borrow from each other (|c +- t - x| < 2^10).
-    // bright = (b_u | b_d) & (b_l | b_r), dark likewise, folded with and / or / v_bitop3: 4 px per instruction instead of 2,
-    // and the compare / fold instructions are in the full-rate ALU class (profiles/issue_probe_r03.txt).  BIAS = 2^15 for the even pixels of the
-    // dword and 2^14 for the odd ones, so that the four flags come out at bits 15, 14, 31, 30 (pixels 0, 1, 2, 3)
-    // without any shifting; trip t parks them 2 t bits lower.  No trimming here: the two extra pixels of a row (window
-    // cols -2, -1) and, in border tiles, pixels outside the valid region are dropped (or harmlessly scored) in pass 2.
-    constexpr int kItemsPerRow = 17, kItems = kScoreH * kItemsPerRow;
-    constexpr int kTrips = (kItems + 255) / 256;  // 5
-    static_assert(2 * kTrips <= 14 && kScoreW == 4 * kItemsPerRow, "candidate bits of all trips share one dword");
-    constexpr uint32_t kF = 0x00FF00FFu;
-    const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(min_th, 0), 255));  // (scalar: the constants below are s_mul)
-    const uint32_t kAe = (0x8000u + t) * 0x10001u, kDe = (0x8000u - t - 1u) * 0x10001u;
-    const uint32_t kAo = (0x4000u + t) * 0x10001u, kDo = (0x4000u - t - 1u) * 0x10001u;
-    const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-    const uint32_t tid3856 = (uint32_t)tid * 3856u;  // (item * 3856) >> 16 == item / 17 for item < 3855
-    uint32_t allbits = 0;
+  // SWAR pass 1 (bright: some adjacent compass pair both > c + t; dark: both < c - t).  Every byte sits zero-extended in a 16-bit field: E(w) = {b0, b2}, O(w) = {b1, b3} of a tile dword.
+  // With A = c + t + BIAS per field, A - x keeps its BIAS bit iff x <= c + t (x is NOT brighter), and with
+  // D = c - t - 1 + BIAS, D - x keeps it iff x < c - t (x IS darker); fields never borrow from each other (|c +- t - x| < 2^10).
+  // bright = (b_u | b_d) & (b_l | b_r), dark likewise, folded with and / or / v_bitop3: 4 px per instruction instead of 2,
+  // and the compare / fold instructions are in the full-rate ALU class (profiles/issue_probe_r03.txt).  BIAS = 2^15 for the even pixels of the
+  // dword and 2^14 for the odd ones, so that the four flags come out at bits 15, 14, 31, 30 (pixels 0, 1, 2, 3)
+  // without any shifting; trip t parks them 2 t bits lower.  No trimming here: the two extra pixels of a row (window
+  // cols -2, -1) and, in border tiles, pixels outside the valid region are dropped (or harmlessly scored) in pass 2.
+  constexpr int kItemsPerRow = 17, kItems = kScoreH * kItemsPerRow;
+  constexpr int kTrips = (kItems + 255) / 256;  // 5
+  static_assert(2 * kTrips <= 14 && kScoreW == 4 * kItemsPerRow, "candidate bits of all trips share one dword");
+  constexpr uint32_t kF = 0x00FF00FFu;
+  const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(min_th, 0), 255));  // (scalar: the constants below are s_mul)
+  const uint32_t kAe = (0x8000u + t) * 0x10001u, kDe = (0x8000u - t - 1u) * 0x10001u;
+  const uint32_t kAo = (0x4000u + t) * 0x10001u, kDo = (0x4000u - t - 1u) * 0x10001u;
+  const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
+  const uint32_t tid3856 = (uint32_t)tid * 3856u;  // (item * 3856) >> 16 == item / 17 for item < 3855
+  uint32_t allbits = 0;
 #pragma unroll
-    for (int trip = 0; trip < ((GH_ORB_WHATIF & 2) ? 0 : kTrips); ++trip) {
-      const int item = 256 * trip + tid;
-      if (item < kItems) {
-        const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
-        const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
-        const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
-        const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
-        // E(w) by one v_and, O(w) by one v_perm (bytes 1, 3 -> the two fields)
-        constexpr uint32_t kOdd = 0x0c030c01u;
-        const uint2 C{wc & kF, __builtin_amdgcn_perm(0u, wc, kOdd)}, U{wu & kF, __builtin_amdgcn_perm(0u, wu, kOdd)},
-            D{wd & kF, __builtin_amdgcn_perm(0u, wd, kOdd)};
-        // even pixels (cols 4m, 4m+2): left = cols 4m-3, 4m-1 = O(wl); right = cols 4m+3, 4m+5 = {wc.b3, wr.b1}
-        // odd pixels (cols 4m+1, 4m+3): left = cols 4m-2, 4m = {wl.b2, wc.b0}; right = cols 4m+4, 4m+6 = E(wr)
-        // (v_perm_b32 D, S0, S1: selector bytes 0-3 address S1, 4-7 address S0, 0x0c = zero)
-        const uint32_t le = __builtin_amdgcn_perm(0u, wl, kOdd), re = __builtin_amdgcn_perm(wr, wc, 0x0c050c03u);
-        const uint32_t lo = __builtin_amdgcn_perm(wc, wl, 0x0c040c02u), ro = wr & kF;
-        auto half = [](uint32_t A, uint32_t Dk, uint32_t u, uint32_t d, uint32_t l, uint32_t r) {
-          const uint32_t not_bright_lr = (A - l) & (A - r);
-          const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
-          const uint32_t dark_lr = (Dk - l) | (Dk - r);
-          const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
-          return bright | dark;
-        };
-        const uint32_t ye = half(C.x + kAe, C.x + kDe, U.x, D.x, le, re);
-        const uint32_t yo = half(C.y + kAo, C.y + kDo, U.y, D.y, lo, ro);
-        const uint32_t w = __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
-        allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * trip), 0xC000C000u >> (2 * trip), 0xF8);  // a | (b & c)
-      }
+  for (int trip = 0; trip < kTrips; ++trip) {
+    const int item = 256 * trip + tid;
+    if (item < kItems) {
+      const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
+      const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
+      const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
+      const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
+      // E(w) by one v_and, O(w) by one v_perm (bytes 1, 3 -> the two fields)
+      constexpr uint32_t kOdd = 0x0c030c01u;
+      const uint2 C{wc & kF, __builtin_amdgcn_perm(0u, wc, kOdd)}, U{wu & kF, __builtin_amdgcn_perm(0u, wu, kOdd)},
+          D{wd & kF, __builtin_amdgcn_perm(0u, wd, kOdd)};
+      // even pixels (cols 4m, 4m+2): left = cols 4m-3, 4m-1 = O(wl); right = cols 4m+3, 4m+5 = {wc.b3, wr.b1}
+      // odd pixels (cols 4m+1, 4m+3): left = cols 4m-2, 4m = {wl.b2, wc.b0}; right = cols 4m+4, 4m+6 = E(wr)
+      // (v_perm_b32 D, S0, S1: selector bytes 0-3 address S1, 4-7 address S0, 0x0c = zero)
+      const uint32_t le = __builtin_amdgcn_perm(0u, wl, kOdd), re = __builtin_amdgcn_perm(wr, wc, 0x0c050c03u);
+      const uint32_t lo = __builtin_amdgcn_perm(wc, wl, 0x0c040c02u), ro = wr & kF;
+      auto half = [](uint32_t A, uint32_t Dk, uint32_t u, uint32_t d, uint32_t l, uint32_t r) {
+        const uint32_t not_bright_lr = (A - l) & (A - r);
+        const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
+        const uint32_t dark_lr = (Dk - l) | (Dk - r);
+        const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
+        return bright | dark;
+      };
+      const uint32_t ye = half(C.x + kAe, C.x + kDe, U.x, D.x, le, re);
+      const uint32_t yo = half(C.y + kAo, C.y + kDo, U.y, D.y, lo, ro);
+      const uint32_t w = __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
+      allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * trip), 0xC000C000u >> (2 * trip), 0xF8);  // a | (b & c)
     }
-    // ONE queue reservation per wave for all trips; an entry is (bit << 8 | tid), decoded in pass 2 where every lane is busy
-    {
-      const int cnt = __popc(allbits);
-      const int incl = wave_incl_scan_i32(cnt);
-      const int wave_total = __builtin_amdgcn_readlane(incl, 63);
-      if (wave_total != 0) {
-        int base = 0;
-        if ((tid & 63) == 0) base = atomicAdd(&q_count, wave_total);
-        base = __builtin_amdgcn_readfirstlane(base) + incl - cnt;
-        while (allbits) {
-          const int b = __ffs((int)allbits) - 1;
-          queue[base++] = (uint16_t)((b << 8) | tid);
-          allbits &= allbits - 1u;
-        }
-      }
-    }
-  } else {
-    typedef short s16x2 __attribute__((ext_vector_type(2)));
-    const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-    constexpr int kRowDw = kTileW / 4, kItemsPerRow = 18;
-    const s16x2 T = {(short)min_th, (short)min_th};
-    constexpr int kTrips = (kScoreH * kItemsPerRow + 255) / 256;  // 5
-    static_assert(4 * kTrips <= 32 && kScoreW == 4 * kItemsPerRow, "candidate bits of all trips share one dword");
-    uint32_t allbits = 0;  // bit 4 t + k: pixel k of this thread's dword in trip t is a candidate
-#pragma unroll
-    for (int trip = 0; trip < kTrips; ++trip) {
-      const int item = 256 * trip + tid;
-      uint32_t bits = 0;  // bit k: pixel k of the dword is a candidate
-      int sy = 0, m = 4;
-      if (item < kScoreH * kItemsPerRow) {
-        sy = item / kItemsPerRow;
-        m = item - sy * kItemsPerRow + 4;
-        const int trow = (sy + 3) * kRowDw;
-        const uint32_t wc = tile32[trow + m], wl = tile32[trow + m - 1], wr = tile32[trow + m + 1];
-        const uint32_t wu = tile32[trow - 3 * kRowDw + m], wd = tile32[trow + 3 * kRowDw + m];
-        const uint32_t left4 = __builtin_amdgcn_alignbyte(wc, wl, 1);   // cols 4m-3 .. 4m
-        const uint32_t right4 = __builtin_amdgcn_alignbyte(wr, wc, 3);  // cols 4m+3 .. 4m+6
-        uint32_t eh[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          // bytes (2h, 2h+1) -> two zero-extended 16-bit lanes
-          const uint32_t sel = h == 0 ? 0x0c010c00u : 0x0c030c02u;
-          const s16x2 c = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, wc, sel));
-          const s16x2 pu = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, wu, sel));
-          const s16x2 pd = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, wd, sel));
-          const s16x2 pl = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, left4, sel));
-          const s16x2 pr = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, right4, sel));
-          // every adjacent compass pair holds one vertical (up/down) and one horizontal (left/right) pixel, so
-          // "some adjacent pair both brighter than c + t" == min(max(up, down), max(left, right)) > c + t, evaluated on
-          // the raw intensities (min / max commute with subtracting c: no per-pixel differences); likewise for darker
-          const s16x2 bright = __builtin_elementwise_min(__builtin_elementwise_max(pu, pd), __builtin_elementwise_max(pl, pr));
-          const s16x2 dark = __builtin_elementwise_max(__builtin_elementwise_min(pu, pd), __builtin_elementwise_min(pl, pr));
-          // sign bits: (c + t) - bright < 0  <=>  bright > c + t ;  dark - (c - t) < 0  <=>  dark < c - t
-          const uint32_t e = __builtin_bit_cast(uint32_t, (c + T) - bright) | __builtin_bit_cast(uint32_t, dark - (c - T));
-          eh[h] = e;
-        }
-        // the four sign bits (bit 15 / 31 of eh[0], eh[1]) -> a nibble: high bytes picked by one v_perm, flags gathered
-        // by one v_dot4_u32_u8 with weights 1, 2, 4, 8
-        const uint32_t mask = __builtin_amdgcn_udot4((__builtin_amdgcn_perm(eh[1], eh[0], 0x07050301u) >> 7) & 0x01010101u,
-                                                     0x08040201u, 0u, false);
-        // keep only pixels inside the 66-wide window and the valid image region: window cols [sx_lo, sx_hi)
-        if (interior) {
-          // whole window valid: only the dwords that stick out of it are trimmed (m = 4: window cols -2, -1; m = 21: 66 .. 69)
-          const uint32_t vm = m == 4 ? 0xCu : (m == 21 ? 0u : 0xFu);
-          bits = mask & vm;
-        } else {
-          const int py = y0 - 1 + sy;
-          const int first = 4 * m - 18;  // window col of pixel 0 of this dword
-          uint32_t vm = 0xFu;
-          if (first < sx_lo) vm = (0xFu << min(sx_lo - first, 4)) & 0xFu;
-          if (first + 4 > sx_hi) vm &= 0xFu >> min(first + 4 - sx_hi, 4);
-          if (py >= kEdge && py < lv.h - kEdge) bits = mask & vm;
-        }
-      }
-      allbits |= bits << (4 * trip);
-    }
-    // ONE queue reservation per wave for all trips: per-lane count (0..20), wave prefix sum (DPP scan), then
-    // each lane unpacks its bits.  Score position of (item, k) = kScoreW sy + kScoreOff + 4 m - 18 + k with
-    // m = item - 18 sy + 4, which is 4 item + 1 + k: no division needed.
-    {
-      const int cnt = __popc(allbits);
-      const int incl = wave_incl_scan_i32(cnt);
-      const int wave_total = __builtin_amdgcn_readlane(incl, 63);
-      if (wave_total != 0) {
-        int base = 0;
-        if ((tid & 63) == 0) base = atomicAdd(&q_count, wave_total);
-        base = __builtin_amdgcn_readfirstlane(base) + incl - cnt;
-        const int p0 = 4 * tid + 1;
-        while (allbits) {
-          const int b = __ffs((int)allbits) - 1;
-          queue[base++] = (uint16_t)(p0 + ((b >> 2) << 10) + (b & 3));
-          allbits &= allbits - 1u;
-        }
+  }
+  // ONE queue reservation per wave for all trips; an entry is (bit << 8 | tid), decoded in pass 2 where every lane is busy
+  {
+    const int cnt = __popc(allbits);
+    const int incl = wave_incl_scan_i32(cnt);
+    const int wave_total = __builtin_amdgcn_readlane(incl, 63);
+    if (wave_total != 0) {
+      int base = 0;
+      if ((tid & 63) == 0) base = atomicAdd(&q_count, wave_total);
+      base = __builtin_amdgcn_readfirstlane(base) + incl - cnt;
+      while (allbits) {
+        const int b = __ffs((int)allbits) - 1;
+        queue[base++] = (uint16_t)((b << 8) | tid);
+        allbits &= allbits - 1u;
       }
     }
   }
   __syncthreads();
   GH_PHASE(1);
-  const int nq = (GH_ORB_WHATIF & 1) ? 0 : q_count;
+  const int nq = q_count;
   for (int i = tid; i < nq; i += 256) {
-    int pos = queue[i];
-    if constexpr (P1 != 0) pos = 4 * (pos & 255) + bit_pos[pos >> 8];
+    const int e = queue[i];
+    const int pos = 4 * (e & 255) + bit_pos[e >> 8];
     // (flat 68-byte rows: position 68 sy + 1 + j holds window col j - 2, j = 0 .. 67)
-    // P1: n / 68 on the full-rate 24-bit multiplier (exact for n < 68 * 72: 15421 / 2^20 - 1 / 68 = 7.6e-7; a signed division by
+    // n / 68 on the full-rate 24-bit multiplier (exact for n < 68 * 72: 15421 / 2^20 - 1 / 68 = 7.6e-7; a signed division by
     // a constant is a quarter-rate v_mul_hi_i32 and three fix-up instructions)
-    int sy;
-    if constexpr (P1 != 0) {
-      static_assert(kScoreW == 68, "the constant below divides by 68");
-      sy = (int)(__umul24((uint32_t)(pos - 1), 15421u) >> 20);
-    } else {
-      sy = pos / kScoreW;
-    }
+    static_assert(kScoreW == 68, "the constant below divides by 68");
+    const int sy = (int)(__umul24((uint32_t)(pos - 1), 15421u) >> 20);
     const int sx = pos - sy * kScoreW - kScoreOff;
-    if constexpr (P1 != 0) {
-      // border tiles: pass 1 did not trim -- pixels outside the valid region [kEdge, dim - kEdge) keep S = 0 (oracle step 2)
-      if (!interior && (sx < sx_lo || sx >= sx_hi || y0 - 1 + sy < kEdge || y0 - 1 + sy >= lv.h - kEdge)) continue;
-    }
+    // border tiles: pass 1 did not trim -- pixels outside the valid region [kEdge, dim - kEdge) keep S = 0 (oracle step 2)
+    if (!interior && (sx < sx_lo || sx >= sx_hi || y0 - 1 + sy < kEdge || y0 - 1 + sy >= lv.h - kEdge)) continue;
     const uint8_t* p = &tile[(sy + 3) * kTileW + sx + 18];
     const int c = p[0];
     int r[16];
@@ -741,7 +612,7 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
     r[13] = p[-1 * kTileW - 3];
     r[14] = p[-2 * kTileW - 2];
     r[15] = p[-3 * kTileW - 1];
-    const int s = PK ? fast_score16_pk(r, c) : fast_score16(r, c);
+    const int s = fast_score16_pk(r, c);
     if (s > min_th) score[pos] = (uint8_t)s;
   }
   __syncthreads();
@@ -752,7 +623,7 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   // pulled through its L1 / the XCD's L2 for the tile (edge tiles also take the image border).  The pipeline is VALU-issue
   // bound and a stand-alone resize pass is memory-instruction bound, so the bilinear arithmetic rides in this kernel's idle
   // memory slots and the level is read from HBM once instead of twice.  Same arithmetic as resize_kernel (resize_item).
-  if (!(GH_ORB_WHATIF & 8) && nx.dst_base != nullptr && !resized) {
+  if (nx.dst_base != nullptr && !resized) {
     const int g0 = nx.gx0[bx], ng = nx.gx0[bx + 1] - g0;
     const int r0 = nx.gy0[by], r1 = nx.gy0[by + 1];
     const int nq = (r1 - r0 + kResizeRows - 1) / kResizeRows;
@@ -775,7 +646,6 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
     // the quadtree mode wants S itself: the tile's 64 x 64 scores (zero outside the valid region) to the level's score plane,
     // 16 dwords per row (score byte 68 (r + 1) + 4 + c is dword aligned at c % 4 == 0; plane column x0 + kQtPlaneX + c starts a 64-byte
     // segment: a tile row is ONE aligned 64-byte write -- at x + 1 it straddled two, and the kernel was store bound)
-    static_assert(P1 != 0, "the plane variant is written for the flat 68-byte score rows");
     uint8_t* pl = nx.plane + (size_t)frame * nx.plane_frame_stride;
     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(score);
 #pragma unroll
@@ -831,10 +701,6 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   // 32-byte record per cell instead of a count plus a 128-byte slot); entries 7.. go to the cell's slot in cell_ent
   uint32_t* rec = cell_cnt + cell * kCellRec;
   uint32_t* ovf = cell_ent + cell * kCap;
-  if (GH_ORB_WHATIF & 4) {
-    if (lane == 0) rec[0] = 0u;
-    return;
-  }
   auto put_entry = [&](int idx, uint32_t v) {
     if (idx < kCellRec - 1) rec[1 + idx] = v;
     else ovf[idx] = v;
@@ -862,12 +728,10 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
     // comparison (lane order is raster order, rc is unique): v_readlane + v_cmp + v_addc per candidate instead of three compares
     const uint32_t key = e ^ 0x3FFu;
     int rank = 0;
-#ifndef GH_ORB_WHATIF_NORANK  // (timing experiment only: what the in-cell ranking costs -- docs/notes_r06.md)
     for (uint64_t mm = cand; mm != 0ull; mm &= mm - 1ull) {
       const int j = __ffsll((unsigned long long)mm) - 1;
       rank += (uint32_t)__builtin_amdgcn_readlane((int)key, j) > key ? 1 : 0;
     }
-#endif
     const bool keep = ((cand >> lane) & 1ull) != 0ull && rank < kCap;
     const uint64_t m = __ballot(keep);
     if (keep) put_entry(__popcll(m & lt_mask), ((uint32_t)rank << 18) | e);
@@ -944,9 +808,9 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   }
 }
 
-// (SWAR variant: 8 waves per SIMD -- at most 64 VGPRs -- and 20.4 KB of LDS let 8 workgroups share a CU)
-template <bool PK, int P1, bool PLANE = false>
-__global__ __launch_bounds__(256, P1 != 0 ? GH_FAST_WAVES : 1) void fast_cells_kernel(LevelView lv, int ncx, int ncy, int min_th, int ini_th,
+// (8 waves per SIMD -- at most 64 VGPRs -- and 20.4 KB of LDS let 8 workgroups share a CU)
+template <bool PLANE>
+__global__ __launch_bounds__(256, GH_FAST_WAVES) void fast_cells_kernel(LevelView lv, int ncx, int ncy, int min_th, int ini_th,
                                                          uint32_t* __restrict__ cell_cnt,
                                                          uint32_t* __restrict__ cell_ent, int cells_per_frame,
                                                          int cell_off, int n_frames, NextLevel nx,
@@ -954,237 +818,7 @@ __global__ __launch_bounds__(256, P1 != 0 ? GH_FAST_WAVES : 1) void fast_cells_k
   const int total = ((ncx + 1) >> 1) * ((ncy + 1) >> 1) * n_frames;
   const int tile_id = xcd_strip_tile(blockIdx.x, total);
   if (tile_id >= total) return;
-  fast_cells_tile<PK, P1, PLANE>(lv, ncx, ncy, min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, cell_off, n_frames, nx, dbg, tile_id);
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXPERIMENT, round 6: the score plane by WAVE-AUTONOMOUS SLIDING WINDOWS -- no block-wide barrier, no shared tile.
-// fast_cells_tile stages a 64 x 64 tile for 256 threads and crosses three __syncthreads; its tile stages reach ~60 % of the issue
-// rate between them (docs/notes_r05.md).  Here a WAVE owns a strip of 256 pixel columns (one dword per lane; 248 of them are its
-// own, the rest is the +-3 px halo) and marches down kSwRows rows of one frame:
-//   * the image rows it needs live in a wave-private LDS ring of 16 rows x 256 B, fed from registers that were loaded two row
-//     groups (8 rows) ahead -- the HBM latency is covered by the wave's own work, not by occupancy;
-//   * pass 1 (the SWAR compass test of fast_cells_tile, same arithmetic) runs on 4 rows at a time, its survivors are appended to a
-//     wave-private queue with ONE wave scan per group;
-//   * pass 2 (exact arc score) pops 64 survivors at a time, so every lane is busy whatever the candidate density, reads its 17
-//     pixels from the ring and drops the score byte into a wave-private score ring (8 rows);
-//   * a row of the score ring leaves as 62 aligned dwords (one 248-byte run of the plane) once the survivors of its group are
-//     done -- at most one group later -- and is cleared for the row eight below.
-// Only wave-level ordering is needed (LDS operations of a wave execute in order; the fences below are compiler fences).
-// Output = the plane fast_cells_kernel<.., PLANE> writes (S of oracle step 2 / 3; pixel (y, x) at plane[y * pitch + x + kQtPlaneX]),
-// rows kEdge .. h - 1, bit for bit.  GSLAM_HIP_ORB_PLANE_SW=1 selects it for the quadtree mode (the pyramid then comes from the
-// stand-alone resize launches).  Result of the experiment: profiles/orb_sliding_window_r06.txt, DESIGN.md 6a.
-constexpr int kSwOwn = 248;    // pixels a strip owns: columns xs + 3 .. xs + 250 of its 256 (plane dwords are aligned at x = 3 mod 4)
-constexpr int kSwRows = 64;    // rows per wave (128: 1.49 ms per 100 x 1080p against 1.38 -- fewer, longer waves fill the chip worse)
-constexpr int kSwGroup = 4;    // rows per pass-1 group (their candidate flags share one register: bits 15 - 2 t, 14 - 2 t, 31 - 2 t, 30 - 2 t)
-constexpr int kSwRing = 16;    // image ring: rows y - 3 .. y + 6 of the current group + the 4 rows of the group before it (their leftover survivors)
-constexpr int kSwSRing = 8;    // score ring: two groups
-constexpr int kSwQueue = 4 * kSwOwn + 64 + 32;  // a whole group of candidates + the leftover of the one before
-struct SwLds {
-  uint32_t img[kSwRing * 64];
-  uint32_t sc[kSwSRing * 64];
-  uint16_t q[kSwQueue];
-};
-__device__ __forceinline__ void sw_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ __launch_bounds__(256) void fast_plane_sw_kernel(LevelView lv, int min_th, int nstrips, int nchunks, int n_frames,
-                                                            uint8_t* __restrict__ plane, size_t plane_frame_stride, int plane_pitch,
-                                                            int variant) {
-  __shared__ __attribute__((aligned(16))) SwLds lds_all[4];
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  SwLds& L = lds_all[wv];
-  const int total = nstrips * nchunks * n_frames;
-  const int wid = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wv);
-  if (wid >= total) return;
-  const int frame = wid / (nstrips * nchunks), rem = wid - frame * (nstrips * nchunks);
-  const int chunk = rem / nstrips, strip = rem - chunk * nstrips;
-  const int xs = kSwOwn * strip;                                        // first image column of the strip (a multiple of 4)
-  const int y_begin = kEdge + kSwRows * chunk;
-  const int y_out_end = min(y_begin + kSwRows, lv.h);                   // rows written (zeros below the valid region)
-  const int y_valid_end = min(y_out_end, lv.h - kEdge);                 // rows scored
-  const int ngroups = (y_out_end - y_begin + kSwGroup - 1) / kSwGroup;
-  const uint8_t* img = lv.base + (size_t)frame * lv.frame_stride;
-  uint8_t* pl = plane + (size_t)frame * plane_frame_stride;
-  const uint32_t gx = (uint32_t)min(xs + 4 * lane, lv.pitch - 4);
-  auto load_row = [&](int y) -> uint32_t {
-    const int yc = y < 0 ? 0 : (y > lv.h - 1 ? lv.h - 1 : y);
-    return *reinterpret_cast<const uint32_t*>(img + (__umul24((uint32_t)yc, (uint32_t)lv.pitch) + gx));
-  };
-  // The PREFETCHED rows are loaded by inline asm and waited for by hand.  The compiler's s_waitcnt insertion treats a counter with
-  // loads AND stores pending as out of order and drains it (vmcnt(0)) at the top of every other group -- the plane stores of the
-  // flush are always pending -- which cut the prefetch distance from two groups to none.  Loads return in order among themselves,
-  // so "at most 4 operations outstanding" implies that everything older than the 4 youngest loads has landed, whatever the stores
-  // do (a pending store can only make the wait longer).  The registers must not be copied between the two asm statements (the
-  // compiler believes they are valid at once): 48 of 128 registers are in use, and tests/test_build_isa.py looks at the code.
-  auto load_row_async = [&](int y, uint32_t& dst) {
-    const int yc = y < 0 ? 0 : (y > lv.h - 1 ? lv.h - 1 : y);
-    const uint32_t off = __umul24((uint32_t)yc, (uint32_t)lv.pitch) + gx;
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(off), "s"(img) : "memory");
-  };
-  auto ring_row = [&](int y) { return (uint32_t)(y - y_begin + 3) & (kSwRing - 1); };
-  // rows y_begin - 3 .. y_begin + 2 now, the new rows of groups 0 and 1 in flight
-  {
-    uint32_t v[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) v[r] = load_row(y_begin - 3 + r);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) L.img[r * 64 + lane] = v[r];
-  }
-  uint32_t pfA[kSwGroup], pfB[kSwGroup];
-#pragma unroll
-  for (int r = 0; r < kSwGroup; ++r) load_row_async(y_begin + 3 + r, pfA[r]);
-#pragma unroll
-  for (int r = 0; r < kSwGroup; ++r) load_row_async(y_begin + 3 + kSwGroup + r, pfB[r]);
-#pragma unroll
-  for (int r = 0; r < kSwSRing; ++r) L.sc[r * 64 + lane] = 0u;
-  // which of its four pixels a lane owns: lane 0 only pixel 3, lane 62 pixels 0 .. 2, lane 63 none
-  const uint32_t own = lane == 0 ? 0x55000000u : (lane == 62 ? 0xAA00FF00u : (lane == 63 ? 0u : 0xFF00FF00u));
-  constexpr uint32_t kF = 0x00FF00FFu;
-  const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(min_th, 0), 255));
-  const uint32_t kAe = (0x8000u + t) * 0x10001u, kDe = (0x8000u - t - 1u) * 0x10001u;
-  const uint32_t kAo = (0x4000u + t) * 0x10001u, kDo = (0x4000u - t - 1u) * 0x10001u;
-  const int lm = lane > 0 ? lane - 1 : 0, lp = lane < 63 ? lane + 1 : 63;
-  int q_n = 0, q_old = 0;  // entries in the queue; how many of them are left over from the group before (wave-uniform)
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  (void)lt_mask;
-
-  // pass 2 on the queue entries [head, head + cnt), cnt <= 64
-  auto pass2 = [&](int head, int cnt) {
-    if (lane < cnt) {
-      const uint32_t e = L.q[head + lane];
-      const uint32_t rr = e >> 8, col = e & 255u;
-      const uint8_t* ib = reinterpret_cast<const uint8_t*>(L.img);
-      auto px = [&](int dy, int dx) -> int { return ib[((rr + (uint32_t)(dy + kSwRing)) & (kSwRing - 1)) * 256u + col + dx]; };
-      const int c = px(0, 0);
-      int r[16];
-      r[0] = px(-3, 0);  r[1] = px(-3, 1);  r[2] = px(-2, 2);   r[3] = px(-1, 3);
-      r[4] = px(0, 3);   r[5] = px(1, 3);   r[6] = px(2, 2);    r[7] = px(3, 1);
-      r[8] = px(3, 0);   r[9] = px(3, -1);  r[10] = px(2, -2);  r[11] = px(1, -3);
-      r[12] = px(0, -3); r[13] = px(-1, -3); r[14] = px(-2, -2); r[15] = px(-3, -1);
-      const int s = fast_score16_pk(r, c);
-      const int x = xs + (int)col;
-      if (s > min_th && x >= kEdge && x < lv.w - kEdge)
-        reinterpret_cast<uint8_t*>(L.sc)[((rr - 3u) & (kSwSRing - 1)) * 256u + col - 3u] = (uint8_t)s;
-    }
-  };
-  // rows [y0, y0 + 4) of the score ring to the plane, then cleared
-  auto flush = [&](int y0) {
-#pragma unroll
-    for (int r = 0; r < kSwGroup; ++r) {
-      const int y = y0 + r;
-      const uint32_t idx = ((uint32_t)(y - y_begin) & (kSwSRing - 1)) * 64u + (uint32_t)lane;
-      const uint32_t v = L.sc[idx];
-      L.sc[idx] = 0u;
-      // UNCONDITIONAL store: a lane without a dword of its own writes to the row's left margin (plane columns 0 .. 3: pixel x sits
-      // at column x + kQtPlaneX, nobody reads the margin).  A branch around the store costs the compiler its count of the memory
-      // operations in flight: it then drains the prefetched rows (s_waitcnt vmcnt(0)) at the top of every other group.
-      const int pc = xs + 3 + kQtPlaneX + 4 * lane;  // plane column of the lane's first owned pixel (a multiple of 4)
-      const bool mine = lane < 62 && y < y_out_end && xs + 3 + 4 * lane < lv.w && pc + 3 < plane_pitch;
-      const int yy = y < lv.h ? y : lv.h - 1;
-      if (variant & 2) {  // (A/B: the conditional store of the first version)
-        if (mine) *reinterpret_cast<uint32_t*>(pl + (__umul24((uint32_t)yy, (uint32_t)plane_pitch) + (uint32_t)pc)) = v;
-      } else {
-        *reinterpret_cast<uint32_t*>(pl + (__umul24((uint32_t)yy, (uint32_t)plane_pitch) + (uint32_t)(mine ? pc : 0))) = v;
-      }
-    }
-  };
-  auto group = [&](int g, uint32_t (&pf)[kSwGroup]) {
-    const int y = y_begin + kSwGroup * g;
-    // the group's new rows y + 3 .. y + 6 (asked for two groups ago; the 4 loads of the group in between may still be in
-    // flight) into the ring; their registers go back out for the rows two groups on
-    static_assert(kSwGroup == 4, "the wait below names four registers and leaves four loads in flight");
-    asm volatile("s_waitcnt vmcnt(4)" : "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3])::"memory");
-#pragma unroll
-    for (int r = 0; r < kSwGroup; ++r) L.img[ring_row(y + 3 + r) * 64u + (uint32_t)lane] = pf[r];
-    if (variant & 8) {  // (A/B: compiler-tracked loads)
-#pragma unroll
-      for (int r = 0; r < kSwGroup; ++r) pf[r] = load_row(y + 3 + 2 * kSwGroup + r);
-    } else {
-#pragma unroll
-      for (int r = 0; r < kSwGroup; ++r) load_row_async(y + 3 + 2 * kSwGroup + r, pf[r]);
-    }
-    sw_fence();
-    // ---- pass 1: SWAR compass test (fast_cells_tile, P1 = 1) on the rows y .. y + 3
-    uint32_t allbits = 0;
-#pragma unroll
-    for (int tr = 0; tr < kSwGroup; ++tr) {
-      const uint32_t rc = ring_row(y + tr) * 64u, ru = ring_row(y + tr - 3) * 64u, rd = ring_row(y + tr + 3) * 64u;
-      const uint32_t wc = L.img[rc + lane], wl = L.img[rc + lm], wr = L.img[rc + lp], wu = L.img[ru + lane], wd = L.img[rd + lane];
-      constexpr uint32_t kOdd = 0x0c030c01u;
-      const uint2 C{wc & kF, __builtin_amdgcn_perm(0u, wc, kOdd)}, U{wu & kF, __builtin_amdgcn_perm(0u, wu, kOdd)},
-          D{wd & kF, __builtin_amdgcn_perm(0u, wd, kOdd)};
-      const uint32_t le = __builtin_amdgcn_perm(0u, wl, kOdd), re = __builtin_amdgcn_perm(wr, wc, 0x0c050c03u);
-      const uint32_t lo = __builtin_amdgcn_perm(wc, wl, 0x0c040c02u), ro = wr & kF;
-      auto half = [](uint32_t A, uint32_t Dk, uint32_t u, uint32_t d, uint32_t l, uint32_t r) {
-        const uint32_t not_bright_lr = (A - l) & (A - r);
-        const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
-        const uint32_t dark_lr = (Dk - l) | (Dk - r);
-        const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
-        return bright | dark;
-      };
-      const uint32_t ye = half(C.x + kAe, C.x + kDe, U.x, D.x, le, re);
-      const uint32_t yo = half(C.y + kAo, C.y + kDo, U.y, D.y, lo, ro);
-      const uint32_t w = __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
-      const uint32_t rowmask = y + tr < y_valid_end ? 0xC000C000u >> (2 * tr) : 0u;
-      allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * tr), rowmask, 0xF8);  // a | (b & c)
-    }
-    allbits &= own;
-    // ---- the survivors join the queue: one wave scan per group
-    {
-      const int cnt = __popc(allbits);
-      const int incl = wave_incl_scan_i32(cnt);
-      const int wave_total = __builtin_amdgcn_readlane(incl, 63);
-      int base = q_n + incl - cnt;
-      const uint32_t rr0 = ring_row(y);
-      while (allbits) {
-        const int b = __ffs((int)allbits) - 1;
-        const uint32_t bb = 15u - ((uint32_t)b & 15u), tr = bb >> 1, k = 2u * ((uint32_t)b >> 4) + (bb & 1u);
-        L.q[base++] = (uint16_t)((((rr0 + tr) & (kSwRing - 1)) << 8) | (4u * (uint32_t)lane + k));
-        allbits &= allbits - 1u;
-      }
-      q_n += wave_total;
-    }
-    sw_fence();
-    // ---- pass 2: full chunks, then whatever is still left of the group before (its rows leave the ring next group)
-    // (the leftover of the group before first, then ITS rows go out -- half a group ahead of the next wait for prefetched rows,
-    //  which would otherwise sit behind plane stores issued a moment ago -- then the rest of the full chunks)
-    int head = 0;
-    while (head < q_old) {
-      const int cnt = min(64, q_n - head);
-      pass2(head, cnt);
-      head += cnt;
-    }
-    sw_fence();
-    if (g > 0 && !(variant & 4)) flush(y - kSwGroup);
-    while (q_n - head >= 64) {
-      pass2(head, 64);
-      head += 64;
-    }
-    sw_fence();
-    // the leftover (< 64 entries, all of this group) to the front
-    const int left = q_n - head;
-    if (head > 0 && left > 0) {
-      const uint16_t e = lane < left ? L.q[head + lane] : (uint16_t)0;
-      sw_fence();
-      if (lane < left) L.q[lane] = e;
-    }
-    q_n = q_old = left;
-    sw_fence();
-    if (g > 0 && (variant & 4)) flush(y - kSwGroup);  // (A/B: the first version's place)
-  };
-  for (int g = 0; g < ngroups; g += 2) {
-    group(g, pfA);
-    if (g + 1 < ngroups) group(g + 1, pfB);
-  }
-  // the last group's leftover, then its rows
-  sw_fence();
-  if (q_n > 0) pass2(0, q_n);
-  sw_fence();
-  flush(y_begin + kSwGroup * (ngroups - 1));
+  fast_cells_tile<PLANE>(lv, ncx, ncy, min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, cell_off, n_frames, nx, dbg, tile_id);
 }
 
 // Every level in ONE launch, over a pyramid that exists already (stand-alone resize launches): what a small call wants --
@@ -1195,7 +829,6 @@ struct AllLevels {
   int ncx[kMaxL], ncy[kMaxL], cell_off[kMaxL], tile_start[kMaxL + 1];
   int n_levels;
 };
-template <bool PK, int P1>
 __global__ __launch_bounds__(256) void fast_cells_all_kernel(AllLevels A, int min_th, int ini_th,
                                                              uint32_t* __restrict__ cell_cnt,
                                                              uint32_t* __restrict__ cell_ent, int cells_per_frame,
@@ -1204,8 +837,8 @@ __global__ __launch_bounds__(256) void fast_cells_all_kernel(AllLevels A, int mi
   for (int k = 1; k < A.n_levels; ++k)
     if ((int)blockIdx.x >= A.tile_start[k]) l = k;
   const NextLevel none{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-  fast_cells_tile<PK, P1>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l], n_frames, none,
-                      dbg, (int)blockIdx.x - A.tile_start[l]);
+  fast_cells_tile<false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l], n_frames, none,
+                         dbg, (int)blockIdx.x - A.tile_start[l]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1452,11 +1085,7 @@ struct DescGeom {
   static constexpr int kPatch = 2 * kC + 1;                  // 33 / 45
   static constexpr int kPatchPitch = (kPatch + 6) & ~3;      // 36 / 48: whole dwords that cover any kPatch-byte run
   static constexpr int kRowDw = kPatchPitch / 4;
-  static constexpr int kBlur = 2 * BR + 1;                   // 27 / 39
-  static constexpr int kBlurPitch = (kBlur + 3) & ~3;        // 28 / 40
-  static constexpr int kGroups = kBlurPitch / 4;             // 4-column groups per blur row
 };
-constexpr int kBlurPitch = DescGeom<13>::kBlurPitch;  // (the table mode's pitch: upload_pattern bakes it into the offsets)
 
 // Continuous steering (gh_orb_plan_set_steering, oracle/orb_oracle.c steps 6' and 8'): the orientation is the fp32
 // polynomial arctangent OpenCV's fastAtan2 uses (ORB-SLAM's IC_Angle calls it), and every test point is rotated by it.
@@ -1492,7 +1121,7 @@ __host__ __device__ inline void orb_sincos_deg(float a, float* cs, float* sn) {
 }
 __host__ __device__ inline int orb_reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-// The h-pass of the 7x7 blur as a banded matrix product on the (otherwise idle) matrix cores -- describe_kernel<13, false, true>.
+// The h-pass of the 7x7 blur as a banded matrix product on the (otherwise idle) matrix cores -- describe_pipe_kernel, describe_kernel.
 // B operand of v_mfma_f32_16x16x32_f16 for the horizontal taps: B[k][n] = g[k - n] (0 <= k - n <= 6), the same for both
 // 16-column blocks because each block has its own K window (patch columns 16 nb .. 16 nb + 31).  Lane l supplies column
 // n = l & 15, k = 8 (l >> 4) + e, e = 0..7 as eight f16 (the taps 144 / 268 / 391 / 442 are exact in f16).
@@ -1517,9 +1146,9 @@ constexpr BlurBTable make_blur_b() {
 }
 __device__ const BlurBTable kBlurB = make_blur_b();
 
-// Layout of the blurred patch the MFMA variant leaves in LDS: column-major, one 32-byte line per blur column, row r at byte
+// Layout of the blurred 33 x 33 patch in LDS: column-major, one 32-byte line per blur column, row r at byte
 // 8 (r / 7) + r % 7 of the line (each lane of the v-pass owns 7 consecutive rows of one column and stores them as one
-// 8-byte write).  upload_pattern bakes either layout into the per-bin offset table.
+// 8-byte write).  upload_pattern bakes it into the per-bin offset table.
 __host__ __device__ constexpr int blur_offset_mfma(int row, int col) { return col * 32 + 8 * (row / 7) + row % 7; }
 
 // Intensity-centroid moments of a patch in LDS (oracle step 6): rows of kRowDw dwords, patch column 0 at byte xoff of a row,
@@ -1561,10 +1190,6 @@ __device__ __forceinline__ void desc_moments(const uint8_t* patch, uint32_t xoff
 
 // Orientation bin of the 30-bin table mode from the moments: the first bin whose direction has the centroid to its right
 // while the previous one has it to its left (integer cross products, oracle step 6).
-__device__ __forceinline__ int desc_bin(int dir_x, int dir_y, int m10, int m01, int lane);
-__device__ __forceinline__ int desc_bin(const int32_t* __restrict__ dir, int m10, int m01, int lane) {
-  return desc_bin(lane < GH_ORB_NBINS ? dir[2 * lane] : 0, lane < GH_ORB_NBINS ? dir[2 * lane + 1] : 0, m10, m01, lane);
-}
 // (dir_x, dir_y) = this lane's direction (lanes >= GH_ORB_NBINS: anything)
 __device__ __forceinline__ int desc_bin(int dir_x, int dir_y, int m10, int m01, int lane) {
   long long c = 0;
@@ -1579,7 +1204,7 @@ __device__ __forceinline__ int desc_bin(int dir_x, int dir_y, int m10, int m01, 
 }
 
 // The 7x7 blur of a 33 x 33 patch (+ 4 scratch rows) in LDS, rows of 9 dwords with patch column 0 at byte 0, into the
-// column-major 1 KB blurred patch bl (blur_offset_mfma) -- orb_describe's MFMA formulation.
+// column-major 1 KB blurred patch bl (blur_offset_mfma).
 __device__ __forceinline__ uint4 desc_blur_b(int lane) { return *reinterpret_cast<const uint4*>(kBlurB.w[lane]); }
 __device__ __forceinline__ void desc_blur_mfma(const uint8_t* patch, uint8_t* bl, int lane, const uint4 bw) {
   constexpr int kRowDw = 9;
@@ -1593,7 +1218,7 @@ __device__ __forceinline__ void desc_blur_mfma(const uint8_t* patch, uint8_t* bl
   //            blur rows 7 q .. 7 q + 6.  (Rows 33 .. 36 are uninitialised LDS: finite after the OR, and only feed outputs
   //            nobody reads.)
   //   v-pass   7 x 7 v_mad_u32_u24 straight on the accumulator bits (the 24-bit multiplier reads exactly 4 H): the rounded
-  //            result is the top byte of sum 4 H g + 2^23, as in the VALU variant.
+  //            result is the top byte of sum 4 H g + 2^23 ((4 s + 2^23) >> 24 == (s + 2^21) >> 22 for the blur sum s).
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   const int n16 = lane & 15, q4 = lane >> 4;
@@ -1623,8 +1248,8 @@ __device__ __forceinline__ void desc_blur_mfma(const uint8_t* patch, uint8_t* bl
   // The 49 multiply-adds of a column block are ONE asm statement that opens with its own wait states: the compiler's hazard
   // recogniser does not look inside asm statements, and a VALU read of an MFMA result needs up to 18 of them (an asm
   // v_mad_u32_u24 per term read the accumulators while the matrix core was still writing them; written with __umul24 the
-  // compiler emits v_mul_u32_u24 pairs + v_add3_u32 instead -- 136 instructions for these 98).  (The factor 4 of the VALU
-  // variant's weights is in the accumulator bits.)
+  // compiler emits v_mul_u32_u24 pairs + v_add3_u32 instead -- 136 instructions for these 98).  (The weights are the
+  // plain taps: the factor 4 that puts the rounded result in the top byte is in the accumulator bits.)
   const uint32_t gw0 = 144u, gw1 = 268u, gw2 = 391u, gw3 = 442u, c23 = 1u << 23;
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
@@ -1643,7 +1268,7 @@ __device__ __forceinline__ void desc_blur_mfma(const uint8_t* patch, uint8_t* bl
   }
 }
 
-// The same for the 45 x 45 patch of the continuous-steering mode (describe_kernel<19, true, true>): rows of 12 dwords, patch column
+// The same for the 45 x 45 patch of the continuous-steering mode (describe_kernel): rows of 12 dwords, patch column
 // 0 at byte 0, 49 rows allocated.  Three 16-column blocks (blur columns 0 .. 38 + scratch), each with its own K window (patch
 // columns 16 nb .. 16 nb + 31: past column 47 the window runs into the next row -- finite after the OR, under zero taps).  D row
 // m = 4 q + j of M-block mb is patch row 10 q + 4 mb + j: lane group q holds the 16 consecutive rows 10 q .. 10 q + 15 of its blur
@@ -1699,26 +1324,22 @@ __device__ __forceinline__ void desc_blur_mfma19(const uint8_t* patch, uint8_t* 
   }
 }
 
-template <int BR, bool STEER, bool MF = false>
-__global__ __launch_bounds__(256, (MF && BR == 19) ? 8 : 1) void describe_kernel(DescribeArgs a, DevTables tb, int K,
-                                                       const SelKp* __restrict__ sel,
-                                                       const int32_t* __restrict__ level_cnt,
-                                                       gh_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                       int32_t* __restrict__ counts, int n_frames,
-                                                       uint32_t* __restrict__ dbg) {
+// orb_describe of the continuous-steering mode (gh_orb_plan_set_steering(plan, 1)): one keypoint per wave, its 45 x 45 patch blurred
+// on MFMA (desc_blur_mfma19: 18.7 KB of LDS, 8 workgroups per CU).
+__global__ __launch_bounds__(256, 8) void describe_kernel(DescribeArgs a, DevTables tb, int K, const SelKp* __restrict__ sel,
+                                                          const int32_t* __restrict__ level_cnt,
+                                                          gh_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
+                                                          int32_t* __restrict__ counts, int n_frames,
+                                                          uint32_t* __restrict__ dbg) {
+  constexpr int BR = 19;  // radius of the rotated test points
   typedef DescGeom<BR> G;
-  constexpr int kC = G::kC, kPatch = G::kPatch, kPatchPitch = G::kPatchPitch, kRowDw = G::kRowDw, kBlur = G::kBlur,
-                kBlurPitch = G::kBlurPitch, kGroups = G::kGroups;
+  constexpr int kC = G::kC, kPatch = G::kPatch, kPatchPitch = G::kPatchPitch, kRowDw = G::kRowDw;
   static_assert(kPatch <= 64 && kC >= 16, "one lane per patch row; the radius-15 centroid disc lies inside the patch");
-  static_assert(!MF || (BR == 13 && !STEER) || (BR == 19 && STEER), "the MFMA blur is written for the 33 x 33 patch of the table mode and the 45 x 45 one of the continuous mode");
-  // MF: four more (uninitialised) rows below the patch -- the row map of the MFMA h-pass runs to row 36 with constant offsets
-  constexpr int kPatchRows = MF ? kPatch + 4 : kPatch;
+  // four more (uninitialised) rows below the patch -- the row map of the MFMA h-pass runs past it with constant offsets
+  constexpr int kPatchRows = kPatch + 4;
   __shared__ __attribute__((aligned(16))) uint8_t s_patch[4][kPatchRows * kPatchPitch + 28];  // + slack for the 16-B row reads
-  __shared__ __attribute__((aligned(16))) uint32_t s_h[4][MF ? (BR == 13 ? 256 : 48 * 48 / 4) : (kPatch + 1) * kBlurPitch];  // MF: the blurred patch (1 KB / 2.25 KB)
-  // VALU variant: the blurred patch REPLACES the raw one (last read by the h-pass, a wave barrier before the v-pass writes): 20.2 KB of
-  // LDS per workgroup in the table mode = 8 workgroups per CU instead of 6 (GSLAM_HIP_ORB_DESC_LDSPAD=3000 restores 6 for A/B runs)
-  static_assert(sizeof(s_patch[0]) >= kBlur * kBlurPitch + 12, "the blurred patch fits where the raw patch was");
-  static_assert((BR != 13 && !MF) || sizeof(s_patch) + sizeof(s_h) <= 20480, "8 workgroups per CU");
+  __shared__ __attribute__((aligned(16))) uint32_t s_h[4][48 * 48 / 4];  // the blurred patch (2.25 KB, blur_offset_mfma19)
+  static_assert(sizeof(s_patch) + sizeof(s_h) <= 20480, "8 workgroups per CU");
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int blocks_per_frame = (K + 3) >> 2;
   const int gid = xcd_strip_tile(blockIdx.x, blocks_per_frame * n_frames);
@@ -1757,153 +1378,60 @@ __global__ __launch_bounds__(256, (MF && BR == 19) ? 8 : 1) void describe_kernel
   const SelKp kp = sel[(size_t)b * K + slot];
   const LevelView lv = a.lv[l];
   const uint8_t* img = lv.base + (size_t)b * lv.frame_stride;
-  // kPatch x kPatch patch: each row is fetched as the kRowDw aligned dwords that cover it; the wanted bytes start at
-  // offset px0 & 3 (= px0 - pa) of the row in LDS.
+  // kPatch x kPatch patch: each row is fetched as the kRowDw aligned dwords that cover it (from column pa = px0 & ~3).
   const int px0 = (int)kp.x - kC, py0 = (int)kp.y - kC;
   const int pa = px0 & ~3;
   // lane r < kPatch fetches the whole row r (dwordx4 loads + a tail: 3 vector-memory instructions per wave instead of
-  // trips of address arithmetic + dword loads).  The table mode's patch (radius 16) never leaves the image (keypoints keep
-  // 19 px from the border); the radius-22 patch of the continuous mode can: such keypoints gather their patch byte by
-  // byte with BORDER_REFLECT_101 coordinates (what ORB-SLAM's padded pyramid holds there).
-  const bool inside = !STEER || (pa >= 0 && pa + kPatchPitch <= lv.pitch && px0 + kPatch <= lv.w && py0 >= 0 && py0 + kPatch <= lv.h);
+  // trips of address arithmetic + dword loads).  The radius-22 patch can leave the image (keypoints keep 19 px from the
+  // border): such keypoints gather their patch byte by byte with BORDER_REFLECT_101 coordinates (what ORB-SLAM's padded
+  // pyramid holds there).
+  const bool inside = pa >= 0 && pa + kPatchPitch <= lv.pitch && px0 + kPatch <= lv.w && py0 >= 0 && py0 + kPatch <= lv.h;
   if (lane < kPatch) {
     uint32_t* dst = reinterpret_cast<uint32_t*>(&s_patch[wv][lane * kPatchPitch]);
     if (inside) {
       struct __attribute__((packed, aligned(4))) RowN { uint32_t w[kRowDw]; };
       // (rows and pitch are < 2^24 and a level is < 4 GiB: a 32-bit offset on the full-rate 24-bit multiplier)
       const RowN row = *reinterpret_cast<const RowN*>(img + (__umul24((uint32_t)(py0 + lane), (uint32_t)lv.pitch) + (uint32_t)pa));
-      if constexpr (MF) {
-        // the MFMA operands are read as whole dwords: shift the row so that patch column 0 is byte 0 of its LDS row
-        const uint32_t sh = (uint32_t)(px0 - pa);
+      // the MFMA operands are read as whole dwords: shift the row so that patch column 0 is byte 0 of its LDS row
+      const uint32_t sh = (uint32_t)(px0 - pa);
 #pragma unroll
-        for (int c = 0; c < kRowDw; ++c) dst[c] = __builtin_amdgcn_alignbyte(c + 1 < kRowDw ? row.w[c + 1] : 0u, row.w[c], sh);
-      } else {
-#pragma unroll
-        for (int c = 0; c < kRowDw; ++c) dst[c] = row.w[c];
-      }
+      for (int c = 0; c < kRowDw; ++c) dst[c] = __builtin_amdgcn_alignbyte(c + 1 < kRowDw ? row.w[c + 1] : 0u, row.w[c], sh);
     } else {
       const uint8_t* rp = img + (size_t)orb_reflect101(py0 + lane, lv.h) * lv.pitch;
       for (int c = 0; c < kRowDw; ++c) {
         uint32_t w = 0;
-        for (int e = 0; e < 4; ++e) w |= (uint32_t)rp[orb_reflect101((MF ? px0 : pa) + 4 * c + e, lv.w)] << (8 * e);
+        for (int e = 0; e < 4; ++e) w |= (uint32_t)rp[orb_reflect101(px0 + 4 * c + e, lv.w)] << (8 * e);
         dst[c] = w;
       }
     }
   }
   __builtin_amdgcn_wave_barrier();
   int m10, m01;
-  desc_moments<kC, kRowDw>(s_patch[wv], MF ? 0u : (uint32_t)(px0 - pa), lane, &m10, &m01);
-  int bin = 0;
-  float angle = 0.0f;
-  if constexpr (STEER) {
-    angle = orb_fast_atan2_deg((float)m01, (float)m10);  // |m| < 2^24: the conversions are exact
-  } else {
-    bin = desc_bin(tb.dir, m10, m01, lane);
-    angle = 12.0f * (float)bin;
-  }
+  desc_moments<kC, kRowDw>(s_patch[wv], 0u, lane, &m10, &m01);
+  const float angle = orb_fast_atan2_deg((float)m01, (float)m10);  // |m| < 2^24: the conversions are exact
   // the four test words of this lane, requested before the blur so that their latency (an L2 hit each) hides under it instead
   // of forming a chain of four load -> test -> store round trips behind it
-  const uint32_t* pat = STEER ? reinterpret_cast<const uint32_t*>(tb.base_pattern)
-                              : reinterpret_cast<const uint32_t*>(tb.pattern) + (size_t)bin * 256;
+  const uint32_t* pat = reinterpret_cast<const uint32_t*>(tb.base_pattern);
   const uint32_t pws[4] = {pat[lane], pat[64 + lane], pat[128 + lane], pat[192 + lane]};
-  uint8_t* bl = MF ? reinterpret_cast<uint8_t*>(s_h[wv]) : s_patch[wv];
-  if constexpr (MF && BR == 13) {
-    desc_blur_mfma(s_patch[wv], bl, lane, desc_blur_b(lane));
-  } else if constexpr (MF) {
-    desc_blur_mfma19(s_patch[wv], bl, lane, desc_blur_b(lane));
-  } else {
-    // separable 7x7 integer Gaussian: patch rows 0..kPatch-1 x blur cols -> s_h, then blur rows -> the blurred patch
-    uint32_t* hb = s_h[wv];
-    constexpr int kRowsPerTrip = 64 / kGroups;
-    const int lrow = lane / kGroups, lgrp = lane - lrow * kGroups;
-    constexpr uint32_t g[7] = {144, 268, 391, 442, 391, 268, 144};
-    // Wide LDS accesses (the kernel is LDS-issue bound with byte reads): one work item = 4 adjacent outputs.
-    // h-pass: 4 dwords of the patch row -> 10 source bytes (v_alignbyte with the wave-uniform row offset)
-    //         -> 4 outputs stored as one 16-byte write;  v-pass: 7 x 16-byte reads down the 4 columns -> 4 outputs.
-    {
-      const uint32_t off = (uint32_t)(px0 - pa);  // 0..3, wave-uniform
-      const uint32_t* p32 = reinterpret_cast<const uint32_t*>(s_patch[wv]);
-      // lane -> (row of the trip, 4-column group), fixed for the whole kernel: kRowsPerTrip rows x kGroups groups per trip (63 / 60
-      // of the 64 lanes; same trip counts as a flat index, without a division by 7 / 10 in every trip)
-      for (int r = lrow; r < kPatch && lane < kRowsPerTrip * kGroups; r += kRowsPerTrip) {
-        const int gq = lgrp;  // outputs: blur cols 4 gq .. 4 gq + 3 of patch row r
-        const uint32_t* q = p32 + r * kRowDw + gq;
-        const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-        const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, off);  // source bytes 0..3 (patch col 4 gq + k)
-        const uint32_t w1 = __builtin_amdgcn_alignbyte(d2, d1, off);  // 4..7
-        const uint32_t w2 = __builtin_amdgcn_alignbyte(d3, d2, off);  // 8..11
-        // P[s] = {x[s], x[s+1]} as two 16-bit lanes (one v_perm each, straight from the 12-byte window); an output is
-        // 4 v_dot2_u32_u16 with the tap pairs (g0,g1) (g2,g3) (g4,g5) (g6,0) instead of 7 multiply-adds
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        u16x2 P[10];
-  #pragma unroll
-        for (int sft = 0; sft < 10; ++sft) {
-          // bytes sft, sft + 1 of {w0, w1, w2}: the perm sees 8 of the 12 bytes
-          const uint32_t lo_dw = sft < 7 ? w0 : w1, hi_dw = sft < 7 ? w1 : w2;
-          const uint32_t bsel = (uint32_t)(sft < 7 ? sft : sft - 4);
-          P[sft] = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(hi_dw, lo_dw, 0x0c000c00u | ((bsel + 1u) << 16) | bsel));
-        }
-        constexpr uint32_t g01 = 144u | (268u << 16), g23 = 391u | (442u << 16), g45 = 391u | (268u << 16), g6 = 144u;
-        uint4 o;
-        uint32_t acc[4];
-  #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          uint32_t t0 = __builtin_amdgcn_udot2(P[i], __builtin_bit_cast(u16x2, g01), 0u, false);
-          t0 = __builtin_amdgcn_udot2(P[i + 2], __builtin_bit_cast(u16x2, g23), t0, false);
-          t0 = __builtin_amdgcn_udot2(P[i + 4], __builtin_bit_cast(u16x2, g45), t0, false);
-          acc[i] = __builtin_amdgcn_udot2(P[i + 6], __builtin_bit_cast(u16x2, g6), t0, false);
-        }
-        o.x = acc[0]; o.y = acc[1]; o.z = acc[2]; o.w = acc[3];
-        *reinterpret_cast<uint4*>(&hb[r * kBlurPitch + 4 * gq]) = o;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // v-pass: one work item = 4 adjacent outputs of one blur row: 7 x 16-byte reads down the 4 columns, 28
-    // v_mad_u32_u24 (h sums < 2^20), weights x4 so that the rounded result is the top byte of the sum
-    // ((4 s + 2^23) >> 24 == (s + 2^21) >> 22; 4 * 2048 * 522240 + 2^23 < 2^32), one dword store.
-    for (int rb = lrow; rb < kBlur && lane < kRowsPerTrip * kGroups; rb += kRowsPerTrip) {
-      const int cg = lgrp;
-      uint32_t acc[4] = {1u << 23, 1u << 23, 1u << 23, 1u << 23};
-  #pragma unroll
-      for (int t = 0; t < 7; ++t) {
-        const uint4 hv = *reinterpret_cast<const uint4*>(&hb[(rb + t) * kBlurPitch + 4 * cg]);
-        acc[0] += __umul24(4u * g[t], hv.x);
-        acc[1] += __umul24(4u * g[t], hv.y);
-        acc[2] += __umul24(4u * g[t], hv.z);
-        acc[3] += __umul24(4u * g[t], hv.w);
-      }
-      *reinterpret_cast<uint32_t*>(&bl[rb * kBlurPitch + 4 * cg]) =
-          __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0703u) | (__builtin_amdgcn_perm(acc[3], acc[2], 0x0c0c0703u) << 16);
-    }
-  }
+  uint8_t* bl = reinterpret_cast<uint8_t*>(s_h[wv]);
+  desc_blur_mfma19(s_patch[wv], bl, lane, desc_blur_b(lane));
   __builtin_amdgcn_wave_barrier();
   // 256 binary tests, 64 per ballot
   uint8_t* drow = desc + ((size_t)b * K + pos) * 32;
   float cs = 1.0f, sn = 0.0f;
-  if constexpr (STEER) orb_sincos_deg(angle, &cs, &sn);
+  orb_sincos_deg(angle, &cs, &sn);
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) {
     const uint32_t pw = pws[gq];
-    int va, vb;
-    if constexpr (STEER) {
-      // pw = the unrotated test (ax, ay, bx, by) as four int8; (x', y') = (rint(x cos - y sin), rint(x sin + y cos)), ties to even
-      const float ax = (float)(int)(int8_t)(pw & 0xFFu), ay = (float)(int)(int8_t)((pw >> 8) & 0xFFu);
-      const float bx = (float)(int)(int8_t)((pw >> 16) & 0xFFu), by = (float)(int)(int8_t)(pw >> 24);
-      const int rax = (int)rintf(ax * cs - ay * sn), ray = (int)rintf(ax * sn + ay * cs);
-      const int rbx = (int)rintf(bx * cs - by * sn), rby = (int)rintf(bx * sn + by * cs);
-      if constexpr (MF) {
-        // blur_offset_mfma19: column-major, row r of a column at byte r + 2 (r / 10)  (r / 10 = 205 r >> 11 for r < 64)
-        const uint32_t ra = (uint32_t)(BR + ray), rb = (uint32_t)(BR + rby);
-        va = bl[__umul24((uint32_t)(BR + rax), 48u) + ra + 2u * (__umul24(ra, 205u) >> 11)];
-        vb = bl[__umul24((uint32_t)(BR + rbx), 48u) + rb + 2u * (__umul24(rb, 205u) >> 11)];
-      } else {
-        va = bl[(BR + ray) * kBlurPitch + BR + rax];
-        vb = bl[(BR + rby) * kBlurPitch + BR + rbx];
-      }
-    } else {
-      va = bl[pw & 0xFFFFu];  // byte offsets of the two sample points in the blurred patch
-      vb = bl[pw >> 16];
-    }
+    // pw = the unrotated test (ax, ay, bx, by) as four int8; (x', y') = (rint(x cos - y sin), rint(x sin + y cos)), ties to even
+    const float ax = (float)(int)(int8_t)(pw & 0xFFu), ay = (float)(int)(int8_t)((pw >> 8) & 0xFFu);
+    const float bx = (float)(int)(int8_t)((pw >> 16) & 0xFFu), by = (float)(int)(int8_t)(pw >> 24);
+    const int rax = (int)rintf(ax * cs - ay * sn), ray = (int)rintf(ax * sn + ay * cs);
+    const int rbx = (int)rintf(bx * cs - by * sn), rby = (int)rintf(bx * sn + by * cs);
+    // blur_offset_mfma19: column-major, row r of a column at byte r + 2 (r / 10)  (r / 10 = 205 r >> 11 for r < 64)
+    const uint32_t ra = (uint32_t)(BR + ray), rb = (uint32_t)(BR + rby);
+    const int va = bl[__umul24((uint32_t)(BR + rax), 48u) + ra + 2u * (__umul24(ra, 205u) >> 11)];
+    const int vb = bl[__umul24((uint32_t)(BR + rbx), 48u) + rb + 2u * (__umul24(rb, 205u) >> 11)];
     const uint64_t bits = __ballot(va < vb);
     if (lane == 0) *reinterpret_cast<uint64_t*>(drow + 8 * gq) = bits;
   }
@@ -1922,7 +1450,7 @@ __global__ __launch_bounds__(256, (MF && BR == 19) ? 8 : 1) void describe_kernel
 }
 
 // orb_describe of the default mode (30-bin table steering, blur on MFMA) as a SOFTWARE PIPELINE over the keypoints of a wave.
-// describe_kernel is one keypoint per wave and is bound by the latency of its dependent chain (selection record -> patch rows
+// One keypoint per wave (describe_kernel's form) is bound by the latency of its dependent chain (selection record -> patch rows
 // from HBM -> compute) at the hardware's 8 waves per SIMD; here a wave owns kDescPipe slots (slot0 + 4 j) and, while it
 // computes keypoint j, the patch rows of keypoint j + 1 are already in flight into registers and the selection record of
 // keypoint j + 2 into scalar registers.  Same arithmetic, same outputs (desc_moments / desc_bin / desc_blur_mfma).
@@ -2116,29 +1644,19 @@ struct gh_orb_plan {
   uint32_t* xwgt[kMaxL]{};
   uint32_t* mtab[kMaxL]{};   // MFMA resize: A operands per 8-column group of level l / window starts (ResizeTabs); null = not available
   uint32_t* mcw[kMaxL]{};
-  bool resize_mfma = true;   // GSLAM_HIP_ORB_RESIZE_MFMA=0: the fused resize of interior tiles on the VALU as well (rounds 2-4)
   uint32_t* cell_cnt = nullptr;
   uint32_t* cell_ent = nullptr;
   SelKp* sel = nullptr;
   int32_t* level_cnt = nullptr;
   const int32_t* own_gx[kMaxL] = {nullptr};  // fused pyramid: first owned output group / row per tile column / row of level l
   const int32_t* own_gy[kMaxL] = {nullptr};
-  bool fuse_pyramid = true;  // GSLAM_HIP_ORB_FUSE_PYRAMID=0 keeps the stand-alone resize launches (A/B measurements)
-  bool pyramid_ahead = false;  // GSLAM_HIP_ORB_FUSE_PYRAMID=2: the stand-alone resize chain runs AHEAD on its own stream, beside the FAST passes
-  hipStream_t pyr_stream = nullptr;
-  hipEvent_t ev_pyr[kMaxL]{}, ev_pyr_start = nullptr;
-  int desc_lds_pad = 0;      // GSLAM_HIP_ORB_DESC_LDSPAD: the same for orb_describe
-  int desc_mfma = 2;         // GSLAM_HIP_ORB_DESC_MFMA: 0 = the 7x7 blur of orb_describe on the VALU (rounds 1-4), 1 = h-pass on MFMA, one keypoint per wave, 2 = MFMA + software pipeline over 8 keypoints per wave
-  int lds_pad = 0;           // GSLAM_HIP_ORB_LDSPAD: extra dynamic LDS bytes per workgroup (occupancy experiments only)
-  int pass1 = 1;             // GSLAM_HIP_ORB_PASS1: 0 = packed 16-bit compass test (rounds 2-3), 1 = SWAR on 16-bit fields
-  bool pk_score = true;      // GSLAM_HIP_ORB_PKSCORE=0: arc scores with v_min3 / v_max3_u32 instead of packed fp16 minimum3 / maximum3
   int8_t* d_pattern = nullptr;
   int8_t* d_base_pattern = nullptr;  // the unrotated tests, 256 x 4 int8 (continuous steering)
   int8_t base_pattern[256 * 4] = {};
   bool base_pattern_fits_table = true;  // every 12-degree rotation stays within +-13 (the 30-bin table exists)
   int distribution = 0;              // gh_orb_plan_set_distribution: 0 = 32 x 32 cells + rank order, 1 = ORB-SLAM's cells + quadtree
   gh_qt_plan* qt = nullptr;          // buffers of mode 1 (orb_quadtree.hip)
-  uint8_t* score_plane = nullptr;    // mode 1: S of every level (fast_cells_kernel<.., PLANE>), allocated with qt; GSLAM_HIP_QT_PLANE=0: cells from the image
+  uint8_t* score_plane = nullptr;    // mode 1: S of every level (fast_cells_kernel<true>), allocated with qt
   size_t plane_off[kMaxL] = {}, plane_slab = 0;
   int plane_pitch[kMaxL] = {};
   int steer = 0;                     // gh_orb_plan_set_steering: 0 = 30 orientation bins, 1 = continuous (fastAtan2 + per-keypoint rotation)
@@ -2197,7 +1715,7 @@ extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
   GH_ENTER(c);
   hipStreamSynchronize(c->stream);
   void* ptrs[] = {p->pyr, p->cell_cnt, p->cell_ent, p->sel, p->level_cnt, p->d_pattern, p->d_base_pattern, p->d_dir, p->tabs,
-                  p->stage_img, p->stage_out, p->dbg};
+                  p->stage_img, p->stage_out, p->dbg, p->score_plane};
   for (void* q : ptrs)
     if (q) hipFree(q);
   if (p->stage_host) hipHostFree(p->stage_host);
@@ -2209,13 +1727,6 @@ extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
       hipEventDestroy(g.done);
     }
   if (p->cap_stream) hipStreamDestroy(p->cap_stream);
-  if (p->pyr_stream) {
-    hipStreamSynchronize(p->pyr_stream);
-    hipStreamDestroy(p->pyr_stream);
-  }
-  for (hipEvent_t e : p->ev_pyr)
-    if (e) hipEventDestroy(e);
-  if (p->ev_pyr_start) hipEventDestroy(p->ev_pyr_start);
   if (p->side) {
     hipStreamSynchronize(p->side);
     hipStreamDestroy(p->side);
@@ -2226,8 +1737,8 @@ extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
   delete p;
 }
 
-// The device copy of the test pattern holds, per (bin, test), the two byte offsets into the 27 x 28 blurred patch
-// ((13 + y) * kBlurPitch + 13 + x as two u16) instead of the four int8 coordinates: saves the sign extensions and
+// The device copy of the test pattern holds, per (bin, test), the two byte offsets into the blurred 27 x 27 patch
+// (blur_offset_mfma(13 + y, 13 + x) as two u16) instead of the four int8 coordinates: saves the sign extensions and
 // address arithmetic of 256 tests per keypoint.  rot = [30][256][4] rotated coordinates, each within +-13.
 static gh_status upload_pattern(gh_orb_plan* p, const int8_t* rot) {
   static_assert(sizeof(GH_ORB_PATTERN) == 30 * 256 * 4, "pattern table layout");
@@ -2235,8 +1746,8 @@ static gh_status upload_pattern(gh_orb_plan* p, const int8_t* rot) {
   for (int b = 0; b < 30; ++b)
     for (int t = 0; t < 256; ++t) {
       const int8_t* q = rot + ((size_t)b * 256 + t) * 4;
-      const uint32_t oa = p->desc_mfma ? (uint32_t)blur_offset_mfma(13 + q[1], 13 + q[0]) : (uint32_t)((13 + q[1]) * kBlurPitch + 13 + q[0]);
-      const uint32_t ob = p->desc_mfma ? (uint32_t)blur_offset_mfma(13 + q[3], 13 + q[2]) : (uint32_t)((13 + q[3]) * kBlurPitch + 13 + q[2]);
+      const uint32_t oa = (uint32_t)blur_offset_mfma(13 + q[1], 13 + q[0]);
+      const uint32_t ob = (uint32_t)blur_offset_mfma(13 + q[3], 13 + q[2]);
       off[b * 256 + t] = oa | (ob << 16);
     }
   return gh_dev_upload(p->ctx, p->d_pattern, off.data(), off.size() * sizeof(uint32_t));
@@ -2326,22 +1837,19 @@ extern "C" gh_status gh_orb_plan_set_distribution(gh_orb_plan* p, int mode) {
   gh_ctx* ctx = p->ctx;
   GH_ENTER(ctx);
   GH_CHECK_ARG(ctx, mode == 0 || mode == 1);
-  if (mode == 1 && !p->qt) {
+  if (mode == 1 && !p->score_plane) {  // the quadtree buffers and S of every level (fast_cells_kernel<true>)
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    GH_TRY(gh_qt_create(ctx, p->L, p->lw, p->lh, p->quota, p->max_batch, &p->qt, &p->bytes));
-    const char* e = getenv("GSLAM_HIP_QT_PLANE");
-    if (!(e && e[0] == '0') && p->pass1 != 0 && p->pk_score) {
-      size_t off = 0;
-      for (int l = 0; l < p->L; ++l) {
-        p->plane_pitch[l] = p->pitch[l] + 128;  // (a multiple of 64: rows start on a 64-byte boundary, like the tile rows)
-        p->plane_off[l] = off;
-        off += (size_t)p->plane_pitch[l] * p->lh[l];
-      }
-      p->plane_slab = (off + 255) & ~(size_t)255;
-      GH_TRY(plan_alloc(p, (size_t)p->max_batch * p->plane_slab, (void**)&p->score_plane));
-      GH_HIP(ctx, hipMemsetAsync(p->score_plane, 0, (size_t)p->max_batch * p->plane_slab, ctx->stream));
-      GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!p->qt) GH_TRY(gh_qt_create(ctx, p->L, p->lw, p->lh, p->quota, p->max_batch, &p->qt, &p->bytes));
+    size_t off = 0;
+    for (int l = 0; l < p->L; ++l) {
+      p->plane_pitch[l] = p->pitch[l] + 128;  // (a multiple of 64: rows start on a 64-byte boundary, like the tile rows)
+      p->plane_off[l] = off;
+      off += (size_t)p->plane_pitch[l] * p->lh[l];
     }
+    p->plane_slab = (off + 255) & ~(size_t)255;
+    GH_TRY(plan_alloc(p, (size_t)p->max_batch * p->plane_slab, (void**)&p->score_plane));
+    GH_HIP(ctx, hipMemsetAsync(p->score_plane, 0, (size_t)p->max_batch * p->plane_slab, ctx->stream));
+    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   p->distribution = mode;
   return GH_OK;
@@ -2367,16 +1875,6 @@ extern "C" gh_status gh_orb_plan_create(gh_ctx* ctx, int width, int height, int 
   p->h = height;
   p->max_batch = max_batch;
   p->prm = prm;
-  if (const char* e = getenv("GSLAM_HIP_ORB_FUSE_PYRAMID")) {
-    p->fuse_pyramid = atoi(e) == 1;
-    p->pyramid_ahead = atoi(e) == 2;
-  }
-  if (const char* e = getenv("GSLAM_HIP_ORB_PKSCORE")) p->pk_score = atoi(e) != 0;
-  if (const char* e = getenv("GSLAM_HIP_ORB_LDSPAD")) p->lds_pad = atoi(e) < 0 ? 0 : atoi(e);
-  if (const char* e = getenv("GSLAM_HIP_ORB_DESC_LDSPAD")) p->desc_lds_pad = atoi(e) < 0 ? 0 : atoi(e);
-  if (const char* e = getenv("GSLAM_HIP_ORB_RESIZE_MFMA")) p->resize_mfma = atoi(e) != 0;
-  if (const char* e = getenv("GSLAM_HIP_ORB_DESC_MFMA")) p->desc_mfma = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
-  if (const char* e = getenv("GSLAM_HIP_ORB_PASS1")) p->pass1 = atoi(e) != 0;
   const int L = p->L = prm.n_levels;
   // geometry (oracle step 1 / 5): exact integer arithmetic
   long long den = ipow(6, L) - ipow(5, L);
@@ -2506,7 +2004,7 @@ extern "C" gh_status gh_orb_plan_create(gh_ctx* ctx, int width, int height, int 
       };
       uint32_t* mt = htab.data() + tw;
       uint32_t* mc = htab.data() + tw + (size_t)ngr * 256;
-      bool ok = p->resize_mfma;
+      bool ok = true;
       for (int g = 0; g < ngr; ++g) {
         const int cw = (int)(xt[8 * g] >> 16) & ~7;
         mc[g] = (uint32_t)cw;
@@ -2754,16 +2252,11 @@ static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch,
     return e ? (e[0] == '0' ? 0 : 1) : -1;
   }();
   bool overlap = overlap_env < 0 ? (long long)batch * p->w * p->h >= (16LL << 20) : overlap_env == 1;  // >= 8 frames of 1080p
-  // (quadtree mode from the score plane: the cells of level l run on the same side stream beside the tile kernel of level l + 1)
-  // -- measured: 2.30 ms per 100 x 1080p against 2.23 on one stream (the two kernels do not overlap on this part, the events
-  // cost); kept behind GSLAM_HIP_QT_SIDE=1
-  static const bool qt_side_env = [] { const char* e = getenv("GSLAM_HIP_QT_SIDE"); return e && e[0] == '1'; }();
-  bool qt_side = qt_side_env && p->distribution != 0 && p->score_plane != nullptr && !p->capturing && overlap;
   if (p->capturing || p->distribution != 0) overlap = false;  // (a captured call is a small one: one select launch)
-  if ((overlap || qt_side) && !p->side) {
+  if (overlap && !p->side) {
     if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) {
       p->side = nullptr;
-      overlap = qt_side = false;
+      overlap = false;
     } else {
       bool ok = hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
       for (int l = 0; l < kMaxL && ok; ++l) ok = hipEventCreateWithFlags(&p->ev_level[l], hipEventDisableTiming) == hipSuccess;
@@ -2776,6 +2269,32 @@ static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch,
     StreamSwap(gh_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { c->stream = s; }
     ~StreamSwap() { c->stream = keep; }
   };
+  // fast_cells(l): FAST, NMS and the cell lists of level l -- or, plane, the level's score plane for the quadtree mode -- with
+  // level l + 1 of the pyramid produced inside the kernel
+  auto fast_level = [&](int l, bool plane) -> gh_status {
+    NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
+    if (l + 1 < L)
+      nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
+                     ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
+                     p->own_gx[l], p->own_gy[l], (l == 0 && aligned0) ? batch - 1 : -1};
+    const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
+    GH_CHECK_ARG(ctx, tiles < (1LL << 30));
+    const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
+    nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
+    nx.nbx_inv = magic_div(nbx, tpf);
+    const dim3 grid(8 * gh_div_up(tiles, 8));
+    if (plane) {
+      nx.plane = p->score_plane + p->plane_off[l];
+      nx.plane_frame_stride = p->plane_slab;
+      nx.plane_pitch = p->plane_pitch[l];
+      GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
+                p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
+    } else {
+      GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
+                p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
+    }
+    return GH_OK;
+  };
   // small calls: pyramid first, then every level in one FAST launch (GSLAM_HIP_ORB_ALL_LEVELS=0: A/B measurements)
   static const bool all_env = [] {
     const char* e = getenv("GSLAM_HIP_ORB_ALL_LEVELS");
@@ -2784,73 +2303,22 @@ static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch,
   const bool quadtree = p->distribution != 0;
   const bool all_levels = (all_env && (long long)batch * p->w * p->h <= (4LL << 20)) || quadtree;
   if (quadtree) {
-    // ORB-SLAM's distribution (oracle steps 4', 5'): the whole pyramid first, then cells + tree of orb_quadtree.hip leave sel /
-    // level_cnt as orb_select would
-    LevelView planes[kMaxL];
-    for (int l = 0; l < kMaxL; ++l) planes[l] = LevelView{nullptr, 0, 0, 0, 0};
-    if (p->score_plane != nullptr) {
-      // S of every level by the default mode's tile kernel (plane variant: no cell stage), the next level fused as there; a
-      // level whose cells do not fit the wave-per-cell kernel keeps the image path of orb_quadtree.hip.  The cells of level l
-      // (latency bound: LDS round trips per cell) run on the side stream beside the tile kernel of level l + 1 (VALU bound).
-      const bool side_ok = qt_side && p->side != nullptr && !dbg;
-      GH_TRY(gh_qt_begin(ctx, p->qt, batch));
-      auto cells_of = [&](int l, const LevelView* plane) -> gh_status {
-        if (!side_ok) return gh_qt_cells(ctx, p->qt, l, lv[l], plane, batch, p->prm.min_th_fast, p->prm.ini_th_fast);
-        GH_HIP(ctx, hipEventRecord(p->ev_level[l], ctx->stream));  // level l's image / plane (and the cleared counters) exist
-        GH_HIP(ctx, hipStreamWaitEvent(p->side, p->ev_level[l], 0));
-        StreamSwap sw(ctx, p->side);
-        return gh_qt_cells(ctx, p->qt, l, lv[l], plane, batch, p->prm.min_th_fast, p->prm.ini_th_fast);
-      };
-      for (int l = 0; l < L; ++l) {
-        const bool plane = p->ncx[l] != 0 && gh_qt_plane_ok(p->qt, l);
-        if (!plane) {
-          GH_TRY(cells_of(l, nullptr));
-          if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
-          continue;
-        }
-        NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-        if (l + 1 < L && p->fuse_pyramid)
-          nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
-                         ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
-                         p->own_gx[l], p->own_gy[l], (l == 0 && aligned0) ? batch - 1 : -1};
-        nx.plane = p->score_plane + p->plane_off[l];
-        nx.plane_frame_stride = p->plane_slab;
-        nx.plane_pitch = p->plane_pitch[l];
-        const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
-        GH_CHECK_ARG(ctx, tiles < (1LL << 30));
-        const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
-        nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
-        nx.nbx_inv = magic_div(nbx, tpf);
-        // GSLAM_HIP_ORB_PLANE_SW=1: the plane by the barrier-free sliding-window kernel (round-6 experiment), the next level by the
-        // stand-alone resize launch
-        const char* sw_env = getenv("GSLAM_HIP_ORB_PLANE_SW");  // (read per call: the experiment's A/B runs switch inside one process)
-        const int plane_sw = sw_env ? atoi(sw_env) : 0;  // bit 0: on; bits 1-3: A/B variants of the kernel
-        if (plane_sw & 1) {
-          const int nstrips = gh_div_up(p->lw[l] - 3, kSwOwn), nchunks = gh_div_up(p->lh[l] - kEdge, kSwRows);
-          const long long waves = (long long)nstrips * nchunks * batch;
-          GH_CHECK_ARG(ctx, waves < (1LL << 30));
-          GH_LAUNCH(ctx, "orb_fast_plane_sw", fast_plane_sw_kernel, dim3((unsigned)gh_div_up(waves, 4)), dim3(256), 0, lv[l],
-                    p->prm.min_th_fast, nstrips, nchunks, batch, nx.plane, nx.plane_frame_stride, nx.plane_pitch, plane_sw);
-          if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
-        } else {
-        GH_LAUNCH(ctx, "orb_fast_plane", (fast_cells_kernel<true, 1, true>), dim3(8 * gh_div_up(tiles, 8)), dim3(256), p->lds_pad, lv[l],
-                  p->ncx[l], p->ncy[l], p->prm.min_th_fast, p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame,
-                  p->cell_off[l], batch, nx, dbg);
-        if (l + 1 < L && !p->fuse_pyramid) GH_TRY(resize_standalone(l + 1));
-        }
-        planes[l] = LevelView{p->score_plane + p->plane_off[l], p->plane_slab, p->plane_pitch[l], p->lw[l], p->lh[l]};
-        GH_TRY(cells_of(l, &planes[l]));
+    // ORB-SLAM's distribution (oracle steps 4', 5'): S of every level by the tile kernel (plane variant: no cell stage), the next
+    // level fused as in the default mode; then cells + tree of orb_quadtree.hip leave sel / level_cnt as orb_select would.  A
+    // level whose cells do not fit the plane's cell kernel takes its cells from the image, and its successor from the
+    // stand-alone resize.
+    GH_TRY(gh_qt_begin(ctx, p->qt, batch));
+    for (int l = 0; l < L; ++l) {
+      if (p->ncx[l] == 0 || !gh_qt_plane_ok(p->qt, l)) {
+        GH_TRY(gh_qt_cells(ctx, p->qt, l, lv[l], nullptr, batch, p->prm.min_th_fast, p->prm.ini_th_fast));
+        if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
+        continue;
       }
-      if (side_ok) {
-        GH_HIP(ctx, hipEventRecord(p->ev_join, p->side));
-        GH_HIP(ctx, hipStreamWaitEvent(ctx->stream, p->ev_join, 0));
-      }
-      GH_TRY(gh_qt_tree(ctx, p->qt, batch, p->quota_off, K, p->sel, p->level_cnt));
-    } else {
-      for (int l = 1; l < L; ++l) GH_TRY(resize_standalone(l));
-      GH_TRY(gh_qt_enqueue(ctx, p->qt, lv, batch, p->prm.min_th_fast, p->prm.ini_th_fast, p->quota_off, K, p->sel, p->level_cnt, planes));
+      GH_TRY(fast_level(l, true));
+      const LevelView plane{p->score_plane + p->plane_off[l], p->plane_slab, p->plane_pitch[l], p->lw[l], p->lh[l]};
+      GH_TRY(gh_qt_cells(ctx, p->qt, l, lv[l], &plane, batch, p->prm.min_th_fast, p->prm.ini_th_fast));
     }
-    overlap = false;
+    GH_TRY(gh_qt_tree(ctx, p->qt, batch, p->quota_off, K, p->sel, p->level_cnt));
   } else if (all_levels) {
     for (int l = 1; l < L; ++l) GH_TRY(resize_standalone(l));
     AllLevels A;
@@ -2865,78 +2333,16 @@ static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch,
       if (l < L && p->ncx[l] != 0 && p->quota[l] > 0) tiles += gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
     }
     A.tile_start[kMaxL] = tiles;
-    if (tiles > 0) {
-#define GH_FAST_ALL(PK_, P1_)                                                                                            \
-  GH_LAUNCH(ctx, "orb_fast_cells", (fast_cells_all_kernel<PK_, P1_>), dim3(tiles), dim3(256), 0, A, p->prm.min_th_fast, \
-            p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, batch, dbg)
-      if (!p->pk_score) GH_FAST_ALL(false, 0);
-      else if (p->pass1 == 0) GH_FAST_ALL(true, 0);
-      else GH_FAST_ALL(true, 1);
-#undef GH_FAST_ALL
-    }
+    if (tiles > 0)
+      GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_all_kernel, dim3(tiles), dim3(256), 0, A, p->prm.min_th_fast, p->prm.ini_th_fast,
+                p->cell_cnt, p->cell_ent, p->cells_per_frame, batch, dbg);
     overlap = false;
   }
-  // pyramid ahead: levels 1 .. L-1 by the stand-alone resize kernel on a stream of their own, each FAST pass waits for its
-  // level only -- the memory-instruction-bound resize chain shares the CUs with the VALU-bound FAST passes of earlier levels
-  bool ahead = p->pyramid_ahead && !all_levels && !p->capturing && L > 1;
-  if (ahead && !p->pyr_stream) {
-    bool ok = hipStreamCreateWithFlags(&p->pyr_stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&p->ev_pyr_start, hipEventDisableTiming) == hipSuccess;
-    for (int l = 0; l < kMaxL && ok; ++l) ok = hipEventCreateWithFlags(&p->ev_pyr[l], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      ahead = false;
-    }
-  }
-  if (ahead) {
-    GH_HIP(ctx, hipEventRecord(p->ev_pyr_start, ctx->stream));  // level 0 (the caller's frames, or the staging copy) is ready
-    GH_HIP(ctx, hipStreamWaitEvent(p->pyr_stream, p->ev_pyr_start, 0));
-    StreamSwap sw(ctx, p->pyr_stream);
-    for (int l = 1; l < L; ++l) {
-      GH_TRY(resize_standalone(l));
-      GH_HIP(ctx, hipEventRecord(p->ev_pyr[l], p->pyr_stream));
-    }
-  }
+  // large calls: one FAST launch per level; a level without a FAST pass (no valid region or no quota) gets its successor from
+  // the stand-alone resize
   for (int l = 0; l < L && !all_levels; ++l) {
-    const bool fast = p->ncx[l] != 0 && p->quota[l] > 0;
-    if (ahead) {
-      if (l > 0) GH_HIP(ctx, hipStreamWaitEvent(ctx->stream, p->ev_pyr[l], 0));
-      if (fast) {
-        const NextLevel none{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-        const NextLevel& nx = none;
-        const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
-        GH_CHECK_ARG(ctx, tiles < (1LL << 30));
-        dim3 grid(8 * gh_div_up(tiles, 8));
-        if (!p->pk_score) GH_LAUNCH(ctx, "orb_fast_cells", (fast_cells_kernel<false, 0>), grid, dim3(256), p->lds_pad, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast, p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
-        else if (p->pass1 == 0) GH_LAUNCH(ctx, "orb_fast_cells", (fast_cells_kernel<true, 0>), grid, dim3(256), p->lds_pad, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast, p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
-        else GH_LAUNCH(ctx, "orb_fast_cells", (fast_cells_kernel<true, 1>), grid, dim3(256), p->lds_pad, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast, p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
-      }
-    } else if (!fast) {
-      if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
-    } else {
-      NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-      if (l + 1 < L && p->fuse_pyramid)
-        nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
-                       ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
-                       p->own_gx[l], p->own_gy[l], (l == 0 && aligned0) ? batch - 1 : -1};
-      const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
-      GH_CHECK_ARG(ctx, tiles < (1LL << 30));
-      dim3 grid(8 * gh_div_up(tiles, 8));
-      {
-        const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
-        nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
-        nx.nbx_inv = magic_div(nbx, tpf);
-      }
-#define GH_FAST(PK_, P1_)                                                                                                     \
-  GH_LAUNCH(ctx, "orb_fast_cells", (fast_cells_kernel<PK_, P1_>), grid, dim3(256), p->lds_pad, lv[l], p->ncx[l], p->ncy[l],            \
-            p->prm.min_th_fast, p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, \
-            dbg)
-      if (!p->pk_score) GH_FAST(false, 0);
-      else if (p->pass1 == 0) GH_FAST(true, 0);
-      else GH_FAST(true, 1);
-#undef GH_FAST
-      if (l + 1 < L && !p->fuse_pyramid) GH_TRY(resize_standalone(l + 1));
-    }
+    if (p->ncx[l] != 0 && p->quota[l] > 0) GH_TRY(fast_level(l, false));
+    else if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
     if (overlap) {  // (a level without a FAST pass still gets its level_cnt = 0 from select)
       GH_HIP(ctx, hipEventRecord(p->ev_level[l], ctx->stream));
       GH_HIP(ctx, hipStreamWaitEvent(p->side, p->ev_level[l], 0));
@@ -2951,36 +2357,26 @@ static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch,
     GH_TRY(launch_select(0, L));
   }
   if (!cached && dbg) GH_HIP(ctx, hipMemsetAsync(dbg + kDbgSelStreamed, 1, 1, ctx->stream));
-  {
-    DescribeArgs a;
-    for (int l = 0; l < kMaxL; ++l) {
-      a.lv[l] = l < L ? lv[l] : lv[0];
-      a.quota[l] = l < L ? p->quota[l] : 0;
-      a.quota_off[l] = l < L ? p->quota_off[l] : 0;
-      a.scale[l] = l < L ? p->scale[l] : 1.0f;
-    }
-    a.nlevels = L;
-    a.blk_off[0] = 0;
-    for (int l = 0; l < kMaxL; ++l) a.blk_off[l + 1] = a.blk_off[l] + (l < L ? gh_div_up(a.quota[l], 4 * kDescPipe) : 0);
-    DevTables tb{p->d_pattern, p->d_dir, p->d_base_pattern};
-    const long long blocks = (long long)gh_div_up(K, 4) * batch;
-    GH_CHECK_ARG(ctx, blocks < (1LL << 30));
-    if (p->steer == 0 && p->desc_mfma == 2) {
-      const long long pblocks = (long long)a.blk_off[L] * batch;
-      GH_LAUNCH(ctx, "orb_describe", describe_pipe_kernel, dim3(8 * gh_div_up(pblocks, 8)), dim3(256), p->desc_lds_pad, a, tb, K,
-                p->sel, p->level_cnt, kps_dev, desc_dev, counts_dev, batch, dbg);
-    } else if (p->steer == 0 && p->desc_mfma)
-      GH_LAUNCH(ctx, "orb_describe", (describe_kernel<13, false, true>), dim3(8 * gh_div_up(blocks, 8)), dim3(256), p->desc_lds_pad, a, tb, K,
-                p->sel, p->level_cnt, kps_dev, desc_dev, counts_dev, batch, dbg);
-    else if (p->steer == 0)
-      GH_LAUNCH(ctx, "orb_describe", (describe_kernel<13, false, false>), dim3(8 * gh_div_up(blocks, 8)), dim3(256), p->desc_lds_pad, a, tb, K,
-                p->sel, p->level_cnt, kps_dev, desc_dev, counts_dev, batch, dbg);
-    else if (p->desc_mfma)  // continuous steering: the 45 x 45 patch's blur on MFMA too (18.7 instead of 38 KB of LDS: 8 workgroups per CU)
-      GH_LAUNCH(ctx, "orb_describe", (describe_kernel<19, true, true>), dim3(8 * gh_div_up(blocks, 8)), dim3(256), 0, a, tb, K, p->sel,
-                p->level_cnt, kps_dev, desc_dev, counts_dev, batch, dbg);
-    else
-      GH_LAUNCH(ctx, "orb_describe", (describe_kernel<19, true, false>), dim3(8 * gh_div_up(blocks, 8)), dim3(256), 0, a, tb, K, p->sel,
-                p->level_cnt, kps_dev, desc_dev, counts_dev, batch, dbg);
+  DescribeArgs a;
+  for (int l = 0; l < kMaxL; ++l) {
+    a.lv[l] = l < L ? lv[l] : lv[0];
+    a.quota[l] = l < L ? p->quota[l] : 0;
+    a.quota_off[l] = l < L ? p->quota_off[l] : 0;
+    a.scale[l] = l < L ? p->scale[l] : 1.0f;
+  }
+  a.nlevels = L;
+  a.blk_off[0] = 0;
+  for (int l = 0; l < kMaxL; ++l) a.blk_off[l + 1] = a.blk_off[l] + (l < L ? gh_div_up(a.quota[l], 4 * kDescPipe) : 0);
+  const DevTables tb{p->d_pattern, p->d_dir, p->d_base_pattern};
+  const long long blocks = (long long)gh_div_up(K, 4) * batch;
+  GH_CHECK_ARG(ctx, blocks < (1LL << 30));
+  if (p->steer == 0) {  // 30-bin table steering: kDescPipe slots per wave, workgroups dealt per level
+    const long long pblocks = (long long)a.blk_off[L] * batch;
+    GH_LAUNCH(ctx, "orb_describe", describe_pipe_kernel, dim3(8 * gh_div_up(pblocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
+              kps_dev, desc_dev, counts_dev, batch, dbg);
+  } else {  // continuous steering: one keypoint per wave
+    GH_LAUNCH(ctx, "orb_describe", describe_kernel, dim3(8 * gh_div_up(blocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
+              kps_dev, desc_dev, counts_dev, batch, dbg);
   }
   return GH_OK;
 }

@@ -910,8 +910,8 @@ gh_status gh_qt_create(gh_ctx* ctx, int n_levels, const int* lw, const int* lh, 
   return GH_OK;
 }
 
-// The three parts of gh_qt_enqueue, for a caller that wants the cells of level l on another stream than the kernel that
-// produces level l + 1 (orb.hip): begin (counters), cells of one level, tree.  All on ctx->stream at the time of the call.
+// Steps 4' and 5' in three parts (orb.hip interleaves the cells of level l with the kernels that produce the levels): begin
+// (counters), cells of one level, tree.  All on ctx->stream at the time of the call.
 gh_status gh_qt_begin(gh_ctx* ctx, gh_qt_plan* q, int batch) {
   GH_CHECK_ARG(ctx, q && batch >= 1 && batch <= q->max_batch);
   if (!q->attr_set) {
@@ -961,13 +961,6 @@ gh_status gh_qt_tree(gh_ctx* ctx, gh_qt_plan* q, int batch, const int* quota_off
   else GH_QT_TREE(2048);
 #undef GH_QT_TREE
   return GH_OK;
-}
-
-gh_status gh_qt_enqueue(gh_ctx* ctx, gh_qt_plan* q, const LevelView* lv, int batch, int min_th, int ini_th,
-                        const int* quota_off, int K, SelKp* sel, int32_t* level_cnt, const LevelView* planes) {
-  GH_TRY(gh_qt_begin(ctx, q, batch));
-  for (int l = 0; l < q->L; ++l) GH_TRY(gh_qt_cells(ctx, q, l, lv[l], planes ? &planes[l] : nullptr, batch, min_th, ini_th));
-  return gh_qt_tree(ctx, q, batch, quota_off, K, sel, level_cnt);
 }
 
 gh_status gh_qt_check(gh_ctx* ctx, gh_qt_plan* q) {

@@ -12,12 +12,10 @@ from test_build_float_mode import LIB, LLVM, _code_objects
 
 # kernel-name fragment -> (max VGPRs + AGPRs, max bytes of scratch per work-item)
 BUDGET = {
-    "fast_cells_kernel": (72, 0),        # packed-16-bit variant: >= 6 waves per SIMD beside 24.5 KB of LDS per workgroup
+    "fast_cells_kernel": (72, 0),        # both instantiations (cell lists / score plane); the occupancy they need: test below
     "fast_cells_all_kernel": (72, 0),
-    "describe_kernelILi13ELb0ELb1E": (56, 0),   # the 30-bin table mode (default), h-pass of the blur on MFMA: 9 waves per SIMD, 9.5 KB of LDS
-    "describe_kernelILi13ELb0ELb0E": (48, 0),   # ... with the blur on the VALU (GSLAM_HIP_ORB_DESC_MFMA=0): 8 workgroups per CU with 20.1 KB of LDS
-    "describe_kernelILi19ELb1ELb0E": (96, 0),   # continuous steering (optional mode: 45 x 45 patch, 38 KB of LDS per workgroup)
-    "describe_pipe_kernel": (96, 0),            # the shipped default (software pipeline over 8 keypoints per wave): 5 waves per SIMD, no scratch
+    "describe_pipe_kernel": (96, 0),     # table mode, the default (software pipeline over 8 keypoints per wave): 5 waves per SIMD, no scratch
+    "describe_kernel": (64, 0),          # continuous steering (45 x 45 patch, blur h-pass on MFMA): 63 VGPRs, 18 736 B of LDS, 8 workgroups per CU
     "select_kernel": (128, 0),
     "resize_kernel": (64, 0),
     "bf_match_pairs_kernel": (64, 0),    # 8 waves per SIMD
@@ -72,7 +70,7 @@ def _kernels():
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="needs the ROCm llvm-readelf")
-def test_hot_kernels_stay_within_their_register_and_scratch_budgets():
+def test_shipped_hot_kernels_stay_within_their_register_and_scratch_budgets():
     assert os.path.exists(LIB), "build the library first (make lib)"
     rows = _kernels()
     assert len(rows) >= 60
@@ -88,13 +86,13 @@ def test_hot_kernels_stay_within_their_register_and_scratch_budgets():
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="needs the ROCm llvm-readelf")
-def test_swar_fast_cells_fits_eight_workgroups_per_cu():
-    """The shipped orb_fast_cells (SWAR pass 1, fast_cells_kernel<true, 1>) is latency sensitive: 6 -> 7 -> 8 workgroups per
-    CU measured 5.26 -> 4.82 -> 4.33 ms per 8 launches (profiles/orb_pass1_ab_r04.txt).  Eight 256-thread workgroups need
-    at most 64 VGPRs (8 waves per SIMD) and 160 KB / 8 = 20480 bytes of LDS each."""
+def test_both_fast_cells_kernels_fit_eight_workgroups_per_cu():
+    """orb_fast_cells (SWAR pass 1, fast_cells_kernel) is latency sensitive: 6 -> 7 -> 8 workgroups per CU measured
+    5.26 -> 4.82 -> 4.33 ms per 8 launches (profiles/orb_pass1_ab_r04.txt).  Eight 256-thread workgroups need at most 64 VGPRs
+    (8 waves per SIMD) and 160 KB / 8 = 20480 bytes of LDS each."""
     rows = _kernels()
-    # two variants: <.., PLANE = false> is the default mode's kernel, <.., PLANE = true> writes the score plane of the quadtree mode
-    hits = [r for n, r in rows.items() if "fast_cells_kernelILb1ELi1E" in n]
+    # two instantiations: <false> is the default mode's kernel, <true> writes the score plane of the quadtree mode
+    hits = [r for n, r in rows.items() if "17fast_cells_kernelI" in n]
     assert len(hits) == 2, [n for n in rows if "fast_cells" in n]
     for r in hits:
         assert int(r["vgpr_count"]) + int(r.get("agpr_count", 0)) <= 64, r
@@ -103,12 +101,12 @@ def test_swar_fast_cells_fits_eight_workgroups_per_cu():
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="needs the ROCm llvm-readelf")
-def test_quadtree_mode_kernels_keep_their_occupancy():
-    """Round 5b: the continuous-steering orb_describe with its blur on MFMA (describe_kernel<19, true, true>) holds 8 workgroups
-    per CU (18.7 KB of LDS instead of 38 KB, at most 64 VGPRs) and does not spill; the score-plane cell kernel keeps 7 (cells up
+def test_continuous_describe_and_plane_cell_kernels_keep_their_occupancy():
+    """Round 5b: the continuous-steering orb_describe with its blur on MFMA (describe_kernel) holds 8 workgroups per CU (18.7 KB
+    of LDS instead of 38 KB, at most 64 VGPRs) and does not spill; the score-plane cell kernel keeps 7 (cells up
     to 32 x 32) / 5 (up to 40 x 40) workgroups per CU (profiles/orb_slam_mode_r05.txt)."""
     rows = _kernels()
-    d19 = [r for n, r in rows.items() if "describe_kernelILi19ELb1ELb1E" in n]
+    d19 = [r for n, r in rows.items() if "15describe_kernelE" in n]
     assert len(d19) == 1, [n for n in rows if "describe_kernel" in n]
     assert int(d19[0]["vgpr_count"]) <= 64 and int(d19[0]["group_segment_fixed_size"]) <= 20480, d19[0]
     assert int(d19[0]["private_segment_fixed_size"]) == 0, d19[0]

@@ -4,7 +4,7 @@ Which code runs depends only on the call's pixel count, batch * w * h (gslam_amd
 orb_enqueue):
   <= 4 << 20   small: the whole pyramid by the stand-alone resize, every level in one fast_cells_all_kernel launch, one
                select; a captured graph replays the call
-  >  4 << 20   per-level: one fast_cells_kernel<PK, P1> launch per level, each building the next pyramid level inside
+  >  4 << 20   per-level: one fast_cells_kernel<false> launch per level, each building the next pyramid level inside
                the kernel (MFMA on interior tiles, VALU on edge tiles, split by own_gx / own_gy); a level with quota 0 or
                no cells gets the stand-alone resize instead
   >= 16 << 20  per-level, and select runs per level on a side stream joined by events (overlap)
@@ -291,7 +291,7 @@ def test_branch_census_per_level(ctx, oracle):
 @pytest.mark.parametrize("mode", ["steering", "quadtree"])
 def test_modes_at_overlap_size(ctx, oracle, mode):
     """55 x 640x480 mixed classes (an overlap-sized call) with continuous steering (the per-level path with the select
-    overlap, then describe_kernel<19, true, ..>) / ORB-SLAM's quadtree distribution (orb_enqueue's quadtree branch, which
+    overlap, then describe_kernel) / ORB-SLAM's quadtree distribution (orb_enqueue's quadtree branch, which
     runs at every call size and never overlaps select)."""
     B, w, h = 55, 640, 480
     assert overlap(B, w, h)
@@ -311,24 +311,11 @@ def test_modes_at_overlap_size(ctx, oracle, mode):
     _same(got, exp, f"{B} x {w}x{h} {mode}")
 
 
-# ---------------------------------------------------------------- I. A/B switches read at plan creation
-SWITCHES = [("GSLAM_HIP_ORB_FUSE_PYRAMID", "0"), ("GSLAM_HIP_ORB_FUSE_PYRAMID", "2"), ("GSLAM_HIP_ORB_RESIZE_MFMA", "0"),
-            ("GSLAM_HIP_ORB_DESC_MFMA", "0"), ("GSLAM_HIP_ORB_DESC_MFMA", "1"), ("GSLAM_HIP_ORB_PASS1", "0"),
-            ("GSLAM_HIP_ORB_PKSCORE", "0")]
-
-
-def test_plan_switches_give_the_default_bytes(ctx, oracle, monkeypatch):
-    """The baselines the DESIGN measurements compare against: each switch, on one per-level batch, gives the bytes of
-    the default plan (which equals the oracle)."""
+# ---------------------------------------------------------------- I. the default plan
+def test_default_plan_gives_the_oracle_bytes(ctx, oracle):
+    """One per-level batch through a plan with default parameters, against the oracle."""
     B, w, h = 14, 640, 480
     assert per_level(B, w, h)
     frames = _frames(w, h, B, offset=5, seed=4242)
-    for var, _ in SWITCHES:
-        monkeypatch.delenv(var, raising=False)
-    ref, _ = _gpu(ctx, frames)
-    _same(ref, _oracle(oracle, frames), f"{B} x {w}x{h} default plan")
-    for var, val in SWITCHES:
-        monkeypatch.setenv(var, val)
-        got, _ = _gpu(ctx, frames)
-        monkeypatch.delenv(var)
-        _same(got, ref, f"{var}={val} against the default plan")
+    got, _ = _gpu(ctx, frames)
+    _same(got, _oracle(oracle, frames), f"{B} x {w}x{h} default plan")
