@@ -12,12 +12,16 @@ frames at 1/2/4/8 GPUs"), descriptors and match records are exchanged with
 one RCCL all-gather each (north_star: "RCCL all-gather of descriptors/match pairs"), no other collective.
 
 Printed JSON line (rank 0; ONE compact line <= 8 KB, `compact_line`): metric = extract+match Mkeypoints/s over the whole job, plus
-  roofline      the dominant kernel's algorithmic bytes / its HIP-event time vs 8 TB/s HBM
+  roofline      the dominant kernel's algorithmic bytes / its HIP-event time (of the timed steps) vs 8 TB/s HBM
   cpu_baseline  the CPU oracle ("port": no ORB implementation exists in the reference tree) timed on
-                this box's host cores on a bounded sample of the same workload
-  top level     BF Gpairs/s and BA LM-iterations/s on C4 / C5
-The full record (the same keys + `extra`: every secondary leg, per-kernel times, notes) is written to
-gpurun_out/bench_full.json (`full_record` in the line names it); `--full-line` prints it on stdout instead.
+                the host's cores on a bounded sample of the same workload                   (--full)
+  top level     BF Gpairs/s and BA LM-iterations/s on C4 / C5                               (--full)
+
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line: nothing else.  `--full` adds
+every secondary leg and check -- the in-run parity against the oracle, the CPU baseline, the other sizes / configurations
+(C3, C4, C5, all-pairs, host-fed, latency, frame range, graph solvers, BoW, the other scaling mode at N > 1), the measured
+issue ceilings -- and writes the full record (the same keys + `extra`) to a side file that `full_record` in the line names;
+`--full-line` prints the record on stdout instead of the compact line.
 """
 import argparse
 import json
@@ -129,6 +133,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=1000, help="frames per GPU per step (C2: 1000); with --scaling strong: frames of the whole job")
     ap.add_argument("--no-other-scaling", action="store_true", help="N > 1: skip the second leg that runs the scaling mode not asked for")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every secondary leg and in-run check (the --no-* options switch single legs "
+                         "off again) and write the full record; without it the run measures the headline figure only")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every rank owns --frames frames (the driver's scaling bench); strong: the --frames frames of BASELINE "
                          "configs[1] are split over the ranks (1000 / N each), everything else unchanged")
@@ -211,6 +218,9 @@ def dump_outputs(out_dir, outs, matches, counts_all, pq, pt):
 
 def main():
     a = parse()
+    if not a.full:  # the headline figure only: every secondary leg off (the rest of main() checks a.full where no flag exists)
+        a.no_other_scaling = a.no_cpu_baseline = a.no_ba = a.no_bow = a.no_c3 = a.no_c5 = a.no_host_fed = a.no_range = True
+        a.no_all_pairs_full = True
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -218,8 +228,8 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         # RCCL's own account of the topology it found (rings / trees over xGMI, transports per peer) goes to a file per
-        # rank: the evidence to read after the first real N > 1 run.  GSLAM_BENCH_NCCL_LOG=0 switches it off.
-        if os.environ.get("GSLAM_BENCH_NCCL_LOG", "1") != "0" and not os.environ.get("GSLAM_BENCH_DRYRUN_BACKEND"):
+        # rank: the evidence to read after the first real N > 1 run (--full only).  GSLAM_BENCH_NCCL_LOG=0 switches it off.
+        if a.full and os.environ.get("GSLAM_BENCH_NCCL_LOG", "1") != "0" and not os.environ.get("GSLAM_BENCH_DRYRUN_BACKEND"):
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             os.environ.setdefault("NCCL_DEBUG", "INFO")
             os.environ.setdefault("NCCL_DEBUG_SUBSYS", "INIT,GRAPH")
@@ -386,7 +396,7 @@ def main():
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, last_out, (m_idx, m_d1, m_d2), g_counts, pq, pt)
     match_overlap = None
-    if overlap:
+    if overlap and a.full:
         # what a side stream would hide: the same steps with the matcher on the launch stream after the extraction and with
         # the matcher of step i on a side stream under the extraction of step i + 1
         def timed(fn, n):
@@ -448,7 +458,7 @@ def main():
     #      all-pairs result, equal for every world size that covers the same global frames.
     verify = None
     all_pairs_multi = None
-    if world > 1 or os.environ.get("GSLAM_BENCH_VERIFY"):
+    if a.full and (world > 1 or os.environ.get("GSLAM_BENCH_VERIFY")):
         import hashlib
         from gslam_amd.sharding import all_pairs_block
         finish_match_gather()
@@ -681,10 +691,11 @@ def main():
     # each instruction class, 8 waves / SIMD); the kernel's instruction count per launch comes from a separate
     # rocprofv3 --pmc pass (SQ_INSTS_VALU, profiles/sq_counters.json) and is labelled as such.
     probes = {}
-    try:
-        probes = ctx.valu_issue_probes()
-    except Exception as exc:  # noqa: BLE001
-        probes = {"error": repr(exc)}
+    if a.full:  # runs of their own
+        try:
+            probes = ctx.valu_issue_probes()
+        except Exception as exc:  # noqa: BLE001
+            probes = {"error": repr(exc)}
     spath = os.path.join(ROOT, "profiles", "sq_counters.json")
     if os.path.exists(spath) and "fast_cells mix" in probes:
         try:
@@ -746,13 +757,14 @@ def main():
     MFMA_I8_PEAK_TOPS = 5033.0  # v_mfma_i32_16x16x64_i8 at 16 clocks per SIMD (tools/mfma_probe.hip, profiles/mfma_probe_r03.txt)
     bf_kernel = "bf_match_pairs_mfma" if "bf_match_pairs_mfma" in prof else "bf_match_pairs"
     bf_ms = prof.get(bf_kernel, {}).get("total_ms", 0.0)
-    valu_ceiling = matcher.valu_probe()
+    valu_ceiling = matcher.valu_probe() if a.full else None  # a run of its own
     bf = {"Gpairs_per_s": round(n_pairs_step * a.steps / (bf_ms * 1e-3) / 1e9, 1) if bf_ms else None,
           "kernel": bf_kernel, "ms_per_step": round(bf_ms / a.steps, 4),
-          "bound": "mfma" if bf_kernel.endswith("mfma") else "valu", "valu_ceiling_Gpairs_per_s": round(valu_ceiling / 1e9, 1),
+          "bound": "mfma" if bf_kernel.endswith("mfma") else "valu",
+          "valu_ceiling_Gpairs_per_s": round(valu_ceiling / 1e9, 1) if valu_ceiling else None,
           "pairs_per_step": n_pairs_step, "schedule": "side stream under the next extraction" if overlap else "launch stream",
           "overlap": match_overlap}
-    if bf["Gpairs_per_s"]:
+    if bf["Gpairs_per_s"] and (bf_kernel.endswith("mfma") or valu_ceiling):
         # popcount kernel: against the measured xor + bcnt issue ceiling; MFMA kernel: 512 integer ops per descriptor pair
         # against the i8 MFMA peak (while it shares the chip with the next step's extraction)
         bf["frac"] = round(bf["Gpairs_per_s"] * 512e9 / (MFMA_I8_PEAK_TOPS * 1e12), 4) if bf_kernel.endswith("mfma") else \
@@ -761,91 +773,92 @@ def main():
                for k, v in prof.items()}
 
     # all-pairs stress of the matcher: every frame pair (i < j) among the first 128 frames
-    try:
-        from gslam_amd.sharding import all_pairs_block
-        nf = min(F, 128)
-        ai, aj = all_pairs_block(0, 1, nf, dev)
-        o_idx = torch.empty((ai.shape[0], K), dtype=torch.int32, device=dev)
-        o_d1 = torch.empty((ai.shape[0], K), dtype=torch.int16, device=dev)
-        o_d2 = torch.empty_like(o_d1)
-        matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2), mfma=False)
-        torch.cuda.synchronize()
-        ctx.prof_enable(True)
-        matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2), mfma=False)  # the popcount kernel (north_star's formulation)
-        ap = ctx.prof_collect()
-        ctx.prof_enable(False)
-        npairs_all = int((counts[ai.long()].to(torch.int64) * counts[aj.long()].to(torch.int64)).sum().item())
-        ms_all = ap["bf_match_pairs"]["total_ms"]
-        bf["all_pairs"] = {"frames": nf, "frame_pairs": int(ai.shape[0]), "pairs": npairs_all,
-                           "Gpairs_per_s": round(npairs_all / (ms_all * 1e-3) / 1e9, 1),
-                           "frac": round(npairs_all / (ms_all * 1e-3) / valu_ceiling, 4)}
-        # the same pairs through the exact integer MFMA formulation (bf_match_mfma.hip): reported BESIDE the popcount
-        # kernel, which stays the contract path; the two results must be identical
+    if a.full:  # runs of their own
         try:
-            q_idx, q_d1, q_d2 = torch.empty_like(o_idx), torch.empty_like(o_d1), torch.empty_like(o_d2)
-            matcher.match_pairs(desc, counts, ai, aj, out=(q_idx, q_d1, q_d2), mfma=True)
-            torch.cuda.synchronize()
-            ctx.prof_enable(True)
-            matcher.match_pairs(desc, counts, ai, aj, out=(q_idx, q_d1, q_d2), mfma=True)
-            apm = ctx.prof_collect()
-            ctx.prof_enable(False)
-            ms_m = apm["bf_match_pairs_mfma"]["total_ms"]
-            mfma_ops = npairs_all * 512  # algorithmic: 256 multiply-adds per descriptor pair
-            bf["all_pairs_mfma"] = {
-                "Gpairs_per_s": round(npairs_all / (ms_m * 1e-3) / 1e9, 1), "ms": round(ms_m, 3),
-                "identical_to_popcount": bool(torch.equal(q_idx, o_idx) and torch.equal(q_d1, o_d1) and torch.equal(q_d2, o_d2)),
-                "roofline": {"bound": "mfma", "unit": "TOP/s", "peak": MFMA_I8_PEAK_TOPS,
-                             "peak_source": "v_mfma_i32_16x16x64_i8 at 16 clocks per SIMD (tools/mfma_probe.hip, profiles/mfma_probe_r03.txt)",
-                             "achieved": round(mfma_ops / (ms_m * 1e-3) / 1e12, 1),
-                             "frac": round(mfma_ops / (ms_m * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS, 4)},
-                "what": "v_mfma_i32_16x16x64_i8, key = 4096 (hamming - |a| + 256) + tile straight from the accumulator, v_med3 + v_min per pair"}
-            del q_idx, q_d1, q_d2
-        except Exception as exc:
-            bf["all_pairs_mfma"] = {"error": repr(exc)}
-        del o_idx, o_d1, o_d2
-        # ... and the TRUE all-pairs configuration of BASELINE configs[1]: every frame pair (i < j) of the step's F frames
-        # (F = 1000: 499 500 frame pairs, 2.0e12 descriptor pairs; 8 GB of match records -- sized for the 288 GB of HBM)
-        if world == 1 and not a.no_all_pairs_full and F >= 256:
-            ai, aj = all_pairs_block(0, 1, F, dev)
+            from gslam_amd.sharding import all_pairs_block
+            nf = min(F, 128)
+            ai, aj = all_pairs_block(0, 1, nf, dev)
             o_idx = torch.empty((ai.shape[0], K), dtype=torch.int32, device=dev)
             o_d1 = torch.empty((ai.shape[0], K), dtype=torch.int16, device=dev)
             o_d2 = torch.empty_like(o_d1)
+            matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2), mfma=False)
             torch.cuda.synchronize()
             ctx.prof_enable(True)
-            matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2))  # the product entry: dispatches to the MFMA kernel
+            matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2), mfma=False)  # the popcount kernel (north_star's formulation)
             ap = ctx.prof_collect()
             ctx.prof_enable(False)
-            c64 = counts.to(torch.int64)
-            npairs_full = int((c64.sum() ** 2 - (c64 * c64).sum()).item() // 2)
-            k_full = "bf_match_pairs_mfma" if "bf_match_pairs_mfma" in ap else "bf_match_pairs"
-            ms_full = ap[k_full]["total_ms"]
-            # size-independent check: a frame matched against itself is not in the list, so no query may be unmatched
-            assert bool((o_idx[:, 0] >= 0).all()), "all-pairs: unmatched query in a non-empty pair"
-            bf["all_pairs_full"] = {"frames": F, "frame_pairs": int(ai.shape[0]), "pairs": npairs_full, "kernel": k_full,
-                                    "Gpairs_per_s": round(npairs_full / (ms_full * 1e-3) / 1e9, 1), "seconds": round(ms_full * 1e-3, 3),
-                                    "frac": round(npairs_full * 512 / (ms_full * 1e-3) / (MFMA_I8_PEAK_TOPS * 1e12), 4)
-                                    if k_full.endswith("mfma") else round(npairs_full / (ms_full * 1e-3) / valu_ceiling, 4),
-                                    "match_record_GB": round(ai.shape[0] * K * 8 / 1e9, 2)}
-            # the whole result again through the popcount kernel: every one of the 499 500 x K records must be identical
-            p_idx, p_d1, p_d2 = torch.empty_like(o_idx), torch.empty_like(o_d1), torch.empty_like(o_d2)
-            ctx.prof_enable(True)
-            matcher.match_pairs(desc, counts, ai, aj, out=(p_idx, p_d1, p_d2), mfma=False)
-            app = ctx.prof_collect()
-            ctx.prof_enable(False)
-            same = bool(torch.equal(p_idx, o_idx) and torch.equal(p_d1, o_d1) and torch.equal(p_d2, o_d2))
-            ms_pop = app["bf_match_pairs"]["total_ms"]
-            bf["all_pairs_full"]["popcount_kernel"] = {"seconds": round(ms_pop * 1e-3, 3),
-                                                       "Gpairs_per_s": round(npairs_full / (ms_pop * 1e-3) / 1e9, 1),
-                                                       "frac_of_valu_ceiling": round(npairs_full / (ms_pop * 1e-3) / valu_ceiling, 4)}
-            bf["all_pairs_full"]["identical_to_popcount"] = same
-            assert same, "all-pairs: the MFMA matcher and the popcount matcher disagree"
-            del p_idx, p_d1, p_d2
-            del o_idx, o_d1, o_d2, ai, aj
-            torch.cuda.empty_cache()
-    except AssertionError:
-        raise  # the two matcher formulations disagree: no bench line
-    except Exception as exc:
-        bf["all_pairs"] = {"error": repr(exc)}
+            npairs_all = int((counts[ai.long()].to(torch.int64) * counts[aj.long()].to(torch.int64)).sum().item())
+            ms_all = ap["bf_match_pairs"]["total_ms"]
+            bf["all_pairs"] = {"frames": nf, "frame_pairs": int(ai.shape[0]), "pairs": npairs_all,
+                               "Gpairs_per_s": round(npairs_all / (ms_all * 1e-3) / 1e9, 1),
+                               "frac": round(npairs_all / (ms_all * 1e-3) / valu_ceiling, 4)}
+            # the same pairs through the exact integer MFMA formulation (bf_match_mfma.hip): reported BESIDE the popcount
+            # kernel, which stays the contract path; the two results must be identical
+            try:
+                q_idx, q_d1, q_d2 = torch.empty_like(o_idx), torch.empty_like(o_d1), torch.empty_like(o_d2)
+                matcher.match_pairs(desc, counts, ai, aj, out=(q_idx, q_d1, q_d2), mfma=True)
+                torch.cuda.synchronize()
+                ctx.prof_enable(True)
+                matcher.match_pairs(desc, counts, ai, aj, out=(q_idx, q_d1, q_d2), mfma=True)
+                apm = ctx.prof_collect()
+                ctx.prof_enable(False)
+                ms_m = apm["bf_match_pairs_mfma"]["total_ms"]
+                mfma_ops = npairs_all * 512  # algorithmic: 256 multiply-adds per descriptor pair
+                bf["all_pairs_mfma"] = {
+                    "Gpairs_per_s": round(npairs_all / (ms_m * 1e-3) / 1e9, 1), "ms": round(ms_m, 3),
+                    "identical_to_popcount": bool(torch.equal(q_idx, o_idx) and torch.equal(q_d1, o_d1) and torch.equal(q_d2, o_d2)),
+                    "roofline": {"bound": "mfma", "unit": "TOP/s", "peak": MFMA_I8_PEAK_TOPS,
+                                 "peak_source": "v_mfma_i32_16x16x64_i8 at 16 clocks per SIMD (tools/mfma_probe.hip, profiles/mfma_probe_r03.txt)",
+                                 "achieved": round(mfma_ops / (ms_m * 1e-3) / 1e12, 1),
+                                 "frac": round(mfma_ops / (ms_m * 1e-3) / 1e12 / MFMA_I8_PEAK_TOPS, 4)},
+                    "what": "v_mfma_i32_16x16x64_i8, key = 4096 (hamming - |a| + 256) + tile straight from the accumulator, v_med3 + v_min per pair"}
+                del q_idx, q_d1, q_d2
+            except Exception as exc:
+                bf["all_pairs_mfma"] = {"error": repr(exc)}
+            del o_idx, o_d1, o_d2
+            # ... and the TRUE all-pairs configuration of BASELINE configs[1]: every frame pair (i < j) of the step's F frames
+            # (F = 1000: 499 500 frame pairs, 2.0e12 descriptor pairs; 8 GB of match records -- sized for the 288 GB of HBM)
+            if world == 1 and not a.no_all_pairs_full and F >= 256:
+                ai, aj = all_pairs_block(0, 1, F, dev)
+                o_idx = torch.empty((ai.shape[0], K), dtype=torch.int32, device=dev)
+                o_d1 = torch.empty((ai.shape[0], K), dtype=torch.int16, device=dev)
+                o_d2 = torch.empty_like(o_d1)
+                torch.cuda.synchronize()
+                ctx.prof_enable(True)
+                matcher.match_pairs(desc, counts, ai, aj, out=(o_idx, o_d1, o_d2))  # the product entry: dispatches to the MFMA kernel
+                ap = ctx.prof_collect()
+                ctx.prof_enable(False)
+                c64 = counts.to(torch.int64)
+                npairs_full = int((c64.sum() ** 2 - (c64 * c64).sum()).item() // 2)
+                k_full = "bf_match_pairs_mfma" if "bf_match_pairs_mfma" in ap else "bf_match_pairs"
+                ms_full = ap[k_full]["total_ms"]
+                # size-independent check: a frame matched against itself is not in the list, so no query may be unmatched
+                assert bool((o_idx[:, 0] >= 0).all()), "all-pairs: unmatched query in a non-empty pair"
+                bf["all_pairs_full"] = {"frames": F, "frame_pairs": int(ai.shape[0]), "pairs": npairs_full, "kernel": k_full,
+                                        "Gpairs_per_s": round(npairs_full / (ms_full * 1e-3) / 1e9, 1), "seconds": round(ms_full * 1e-3, 3),
+                                        "frac": round(npairs_full * 512 / (ms_full * 1e-3) / (MFMA_I8_PEAK_TOPS * 1e12), 4)
+                                        if k_full.endswith("mfma") else round(npairs_full / (ms_full * 1e-3) / valu_ceiling, 4),
+                                        "match_record_GB": round(ai.shape[0] * K * 8 / 1e9, 2)}
+                # the whole result again through the popcount kernel: every one of the 499 500 x K records must be identical
+                p_idx, p_d1, p_d2 = torch.empty_like(o_idx), torch.empty_like(o_d1), torch.empty_like(o_d2)
+                ctx.prof_enable(True)
+                matcher.match_pairs(desc, counts, ai, aj, out=(p_idx, p_d1, p_d2), mfma=False)
+                app = ctx.prof_collect()
+                ctx.prof_enable(False)
+                same = bool(torch.equal(p_idx, o_idx) and torch.equal(p_d1, o_d1) and torch.equal(p_d2, o_d2))
+                ms_pop = app["bf_match_pairs"]["total_ms"]
+                bf["all_pairs_full"]["popcount_kernel"] = {"seconds": round(ms_pop * 1e-3, 3),
+                                                           "Gpairs_per_s": round(npairs_full / (ms_pop * 1e-3) / 1e9, 1),
+                                                           "frac_of_valu_ceiling": round(npairs_full / (ms_pop * 1e-3) / valu_ceiling, 4)}
+                bf["all_pairs_full"]["identical_to_popcount"] = same
+                assert same, "all-pairs: the MFMA matcher and the popcount matcher disagree"
+                del p_idx, p_d1, p_d2
+                del o_idx, o_d1, o_d2, ai, aj
+                torch.cuda.empty_cache()
+        except AssertionError:
+            raise  # the two matcher formulations disagree: no bench line
+        except Exception as exc:
+            bf["all_pairs"] = {"error": repr(exc)}
 
     extra = {"bf_match": bf, "kernels": kernels, "roofline_pipeline": pipeline,
              "valu_issue_probes_Ginst_per_s": {k: (round(v / 1e9, 1) if isinstance(v, float) else v) for k, v in probes.items()}}
@@ -1696,6 +1709,7 @@ def main():
         "metric": "orb_extract_plus_bf_match_Mkeypoints_per_s", "value": round(value, 3), "unit": "Mkeypoints/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "full": a.full,  # false: the secondary figures below are null, not measured in this run
         "config": {"workload": f"C2: {F}x{W}x{H} frames per GPU" + (f" ({a.frames} in the job, split over the ranks)" if a.scaling == "strong" else "")
                                + f", {K} ORB kpts each, BF Hamming consecutive-pair match",
                    "frames_per_gpu": F, "width": W, "height": H, "kpts_per_frame": K,
@@ -1721,7 +1735,7 @@ def main():
         "host_fed_Mkeypoints_per_s": (extra.get("host_fed") or {}).get("Mkeypoints_per_s"),
         "extra": extra,
     }
-    line["full_record"] = write_full(line, world)
+    line["full_record"] = write_full(line, world) if a.full else None
     print(json.dumps(line if a.full_line else compact_line(line)), flush=True)
     if comm is not None:
         comm.close()

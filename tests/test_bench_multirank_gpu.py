@@ -15,7 +15,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--steps", "2", "--warmup", "1", "--width", "640", "--height", "480", "--kpts", "600", "--no-cpu-baseline", "--no-ba",
+# --full: the verify / all-pairs / other-scaling / C3 legs this test reads run only in a full run
+FLAGS = ["--full", "--steps", "2", "--warmup", "1", "--width", "640", "--height", "480", "--kpts", "600", "--no-cpu-baseline", "--no-ba",
          "--no-bow", "--no-c5", "--no-host-fed", "--no-all-pairs-full", "--no-range", "--full-line"]
 
 

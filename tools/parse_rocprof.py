@@ -83,7 +83,7 @@ def main():
     if stats:
         rows = list(csv.reader(open(stats[0])))
         with open(os.path.join(out_dir, f"{tag}_kernel_stats.csv"), "w", newline="") as f:
-            cmd = sys.argv[3] if len(sys.argv) > 3 else f"python bench.py --frames {frames} --no-cpu-baseline"
+            cmd = sys.argv[3] if len(sys.argv) > 3 else f"python bench.py --full --frames {frames} --no-cpu-baseline"
             f.write(f"# rocprofv3 --kernel-trace --stats --output-format csv -- {cmd}   (1x MI355X)\n")
             csv.writer(f).writerows(rows)
         print("wrote", f"profiles/{tag}_kernel_stats.csv")
