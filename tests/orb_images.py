@@ -89,6 +89,47 @@ def gradient_with_noise_patch(w, h, seed):
     return img
 
 
+MOTIF_OFFSETS = {  # companion blob of a motif, relative to its dot: the intensity centroid of the dot's radius-15 disc
+    "point": None,      # m10 = m01 = 0: fastAtan2 returns exactly 0
+    "right": (8, 0),    # m01 = 0, m10 > 0: 0
+    "down": (0, 8),     # m10 = 0, m01 > 0: 90
+    "left": (-8, 0),    # m01 = 0, m10 < 0: 180
+    "up": (0, -8),      # m10 = 0, m01 < 0: 270
+    "diag": (6, 6),     # m10 = m01 > 0: fastAtan2(1, 1) = 44.99...
+    "anti": (-6, 6),    # m10 = -m01 < 0: 135.00...
+}
+
+
+def symmetric_motifs(w, h, kinds, pitch=36, origin=(30, 30), phase=0):
+    """Isolated 1-px bright dots on black, each a FAST corner of score 255 whose radius-15 disc holds only its own motif: the
+    dot alone (point-symmetric patch) or with a 3 x 3 blob centred at MOTIF_OFFSETS[kind], which makes the patch
+    mirror-symmetric about one axis or one diagonal through the dot.  Kinds cycle over the lattice from `phase`.  Puts the
+    moments of continuous steering on the special values of fastAtan2 and of the sin / cos quadrant rule."""
+    img = np.zeros((h, w), np.uint8)
+    i = phase
+    for y in range(origin[1], h - 24, pitch):
+        for x in range(origin[0], w - 24, pitch):
+            img[y, x] = 255
+            off = MOTIF_OFFSETS[kinds[i % len(kinds)]]
+            if off is not None:
+                img[y + off[1] - 1:y + off[1] + 2, x + off[0] - 1:x + off[0] + 2] = 255
+            i += 1
+    return img
+
+
+def tie_images(w, h):
+    """Checkerboards of period 2 .. 6 and dot lattices of pitch 4 .. 12: equal responses everywhere, and quadtree nodes that
+    hold equal key counts -- the inputs on which the tie rules of ORB-SLAM's distribution (stage (B) order, per-node maximum,
+    the final cut) decide the output.  tests/test_orb_slam_mode_oracle.py counts those events on the CPU."""
+    out = {f"checker{p}": checkerboard(w, h, p, phase=(p // 2, p // 3)) for p in range(2, 7)}
+    out.update({f"dots{p}": dot_lattice(w, h, p, offset=(19 + p // 3, 20)) for p in (4, 5, 6, 7, 9, 12)})
+    return out
+
+
+TIE_SIZES = ((333, 257), (211, 403))
+TIE_K = (11, 16, 40, 300, 1500)  # 11 / 16: quotas of 1 .. 3, where "the n_l best of up to n_l + 3 nodes" decides
+
+
 def mixed(w, h, seed):
     """Quadrants of different classes in one frame."""
     img = noise(w, h, seed)
@@ -105,10 +146,17 @@ CLASSES = {
     "low_contrast": lambda w, h, s: low_contrast_noise(w, h, s),
     "checker1": lambda w, h, s: checkerboard(w, h, 1),
     "checker2": lambda w, h, s: checkerboard(w, h, 2, phase=(s % 2, (s // 2) % 2)),
+    "checker3": lambda w, h, s: checkerboard(w, h, 3, phase=(s % 3, (s // 3) % 3)),
+    "checker4": lambda w, h, s: checkerboard(w, h, 4, lo=30, hi=220, phase=(s % 4, 0)),
     "checker5": lambda w, h, s: checkerboard(w, h, 5, lo=10, hi=245),
+    "checker6": lambda w, h, s: checkerboard(w, h, 6, phase=(0, s % 6)),
     "step_edges": lambda w, h, s: step_edges(w, h, s),
     "dots8": lambda w, h, s: dot_lattice(w, h, 8),
     "dots11": lambda w, h, s: dot_lattice(w, h, 11, value=0, bg=255, size=2, offset=(17, 21)),
+    "dots5": lambda w, h, s: dot_lattice(w, h, 5, offset=(19 + s % 5, 19)),
+    "dots13": lambda w, h, s: dot_lattice(w, h, 13, value=200, bg=40, size=3, offset=(18, 18 + s % 13)),
+    "sym_point": lambda w, h, s: symmetric_motifs(w, h, ["point"], pitch=32 + s % 9),
+    "sym_axes": lambda w, h, s: symmetric_motifs(w, h, sorted(MOTIF_OFFSETS), phase=s % len(MOTIF_OFFSETS)),
     "few_corners": lambda w, h, s: few_corners(w, h, 12, s),
     "ramp_patch": lambda w, h, s: gradient_with_noise_patch(w, h, s),
     "mixed": lambda w, h, s: mixed(w, h, s),

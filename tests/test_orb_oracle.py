@@ -237,8 +237,14 @@ def _slam_candidates_py(S, ini_th):
     return out
 
 
-def _quadtree_py(cands, w, h, N):
-    """Step 5' as a level-synchronous set computation (no list, no pointers): a node is (x0, y0, x1, y1) -> [keys]."""
+def _quadtree_py(cands, w, h, N, stats=None):
+    """Step 5' as a level-synchronous set computation (no list, no pointers): a node is (x0, y0, x1, y1) -> [keys].
+    stats (a dict) counts the events where a tie rule decides: b_passes (passes of stage (B)), b_equal_counts (neighbours of
+    equal key count in a stage-(B) order), node_max_ties (nodes whose greatest S is held by more than one key), cut_ties
+    (the cut to N leaves out a node whose best S equals the last kept one's) and cuts (the tree ended above N)."""
+    st = stats if stats is not None else {}
+    for k in ("b_passes", "b_equal_counts", "node_max_ties", "cut_ties", "cuts"):
+        st.setdefault(k, 0)
     W2, H2 = w - 32, h - 32
     f32 = np.float32
     n_ini = max(1, int(np.floor(float(f32(W2) / f32(H2)) + 0.5)))
@@ -274,6 +280,8 @@ def _quadtree_py(cands, w, h, N):
             while not done:
                 before = len(nodes)
                 order = sorted(fresh, key=lambda b: (-len(nodes[b]), b[1], b[0]))
+                st["b_passes"] += 1
+                st["b_equal_counts"] += sum(len(nodes[p]) == len(nodes[q]) for p, q in zip(order, order[1:]))
                 fresh = set()
                 for b in order:
                     ch = split(b, nodes.pop(b))
@@ -284,7 +292,12 @@ def _quadtree_py(cands, w, h, N):
                 done = len(nodes) >= N or len(nodes) == before
             break
     win = [min(v, key=lambda k: (-k[2], k[1], k[0])) for v in nodes.values()]
-    win = sorted(win, key=lambda k: (-k[2], k[1], k[0]))[:N]
+    st["node_max_ties"] += sum(sum(k[2] == w_[2] for k in v) > 1 for v, w_ in zip(nodes.values(), win))
+    win = sorted(win, key=lambda k: (-k[2], k[1], k[0]))
+    if len(win) > N:
+        st["cuts"] += 1
+        st["cut_ties"] += int(win[N][2] == win[N - 1][2])
+    win = win[:N]
     return sorted(win, key=lambda k: (k[1], k[0]))
 
 
