@@ -8,6 +8,9 @@
 //     rejected), solves the minimal problem in f64 by Gaussian elimination (no library calls, no FMA contraction),
 //   * every hypothesis is scored against all N correspondences (squared error <= threshold^2), integer inlier counts,
 //   * winner = most inliers, lowest hypothesis index on ties; its model and inlier mask are returned.
+//   * no model = 0 inliers, model all zero, mask all zero: fewer rows than the sample, no regular hypothesis, an LMedS
+//     median that is undefined, a NOSAMPLE fit that is singular or not finite (NaN / Inf input: the eigenvector fits never
+//     refuse by themselves), or (E) a winner whose projection onto the essential manifold fails.
 // Models: H (4 pairs, 8x8 system, h33 = 1, forward transfer error), A2 (3 pairs, 2x3 affine), F (8 pairs, Hartley-
 // normalised 8x9 nullspace by full pivoting, Sampson error; rank 2 is not enforced), A3 (4 pairs, 3x4 affine, 3D).
 // CDNA4 mapping: one lane per hypothesis for the tiny dense solves, one workgroup per hypothesis for scoring
@@ -620,6 +623,8 @@ __global__ __launch_bounds__(256) void ransac_median_kernel(int model, const dou
     const unsigned long long hi_mask = pass == 7 ? 0ull : (~0ull << (8 * (pass + 1)));
     for (int i = tid; i < n; i += 256) {
       double e;
+      // (`e == e` states the rule "a NaN error counts as +inf" and matches the oracle line for line; it changes no result:
+      // errors carry no sign, so a NaN's bits are a key above 0x7FF0... as +inf's are, and the host refuses both alike)
       const unsigned long long b = (model_error(model, m, p, q, i, &e) && e == e) ? (unsigned long long)__double_as_longlong(e)
                                                                                  : 0x7FF0000000000000ull;
       if ((b & hi_mask) == prefix) atomicAdd(&hist[(unsigned)(b >> (8 * pass)) & 255u], 1u);
@@ -870,7 +875,10 @@ extern "C" gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double*
   if (sampling == GH_SAMPLE_NONE) {
     // the all-point fit is hypothesis 0; the device evaluates it against every correspondence (mask + inlier count)
     double m[12];
-    const bool ok = fit_all(model, src, dst, n, nm, m);
+    // (the eigenvector fits never refuse; on NaN / Inf input they hand back a model that is not finite, whose NaN payloads
+    // are the compiler's choice of operand order: such a fit is no model)
+    bool ok = fit_all(model, src, dst, n, nm, m);
+    for (int k = 0; k < 12; ++k) ok = ok && fabs(m[k]) <= 1.7976931348623157e308;
     if (hypotheses_used_out) *hypotheses_used_out = ok ? 1 : 0;
     if (!ok) {  // degenerate fit: outputs stay zero (cleared at entry); the upload from the pinned block must not outlive the call
       GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -948,8 +956,12 @@ extern "C" gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double*
     for (int i = 0; i < n; ++i) best[1] += hm[i] ? 1 : 0;
   }
   *inliers_out = best[1];
-  if (model == kModelE && !project_essential(model_out)) {  // the mask stays that of the scored 8-point estimate
+  if (model == kModelE && !project_essential(model_out)) {
+    // the scored 8-point estimate has no essential matrix near it (rank 1, or not finite): no model, and like every
+    // other no-model exit neither an inlier count nor a mask (the one copied out above belonged to the rejected estimate)
     for (int k = 0; k < 12; ++k) model_out[k] = 0.0;
+    if (mask_out)
+      for (int i = 0; i < n; ++i) mask_out[i] = 0;
     *inliers_out = 0;
   }
   return GH_OK;

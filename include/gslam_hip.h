@@ -457,7 +457,10 @@ gh_status gh_ransac_estimate_conf(gh_ctx* ctx, int model, const double* src, con
  *                     median is undefined.
  *   GH_SAMPLE_NONE    NOSAMPLE: no hypotheses -- the algebraic least-squares model of ALL correspondences (normal equations of
  *                     the minimal solver's rows for H / affine, smallest eigenvector of A^T A for F / E / PnP, Horn over all
- *                     pairs for SIM3, principal plane); mask / inliers by `threshold`; *hypotheses_used_out = 1. */
+ *                     pairs for SIM3, principal plane); mask / inliers by `threshold`; *hypotheses_used_out = 1.  A fit that
+ *                     is singular or not finite (NaN / Inf coordinates) is no model: zeros, *hypotheses_used_out = 0.
+ * In every mode "no model" means *inliers_out = 0, model_out all zero and mask_out all zero, also for GH_MODEL_ESSENTIAL when
+ * the winning estimate has no essential matrix near it (its projection fails). */
 #define GH_SAMPLE_RANSAC 0
 #define GH_SAMPLE_LMEDS 1
 #define GH_SAMPLE_NONE 2

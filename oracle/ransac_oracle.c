@@ -25,6 +25,8 @@
  *               sample point in front of the camera, rows made orthonormal by Gram-Schmidt (reflections rejected);
  *               model [R | t]; error = squared reprojection distance on the z = 1 plane, depth > 1e-12
  *   winner      most correspondences with error <= threshold^2; lowest hypothesis index on ties
+ *   no model    0 inliers, zero model, zero mask: n < s, no regular hypothesis, an undefined LMedS median, a NOSAMPLE fit
+ *               that is singular or not finite, or (E) a winner whose essential projection fails
  * All arithmetic is IEEE double without FMA contraction, in the order written here (the GPU kernels keep the same order).
  */
 #include <math.h>
@@ -545,7 +547,8 @@ int oracle_ransac_conf(int model, const double* p, const double* q, int n, doubl
   if (used_out) *used_out = h;
   if (best_h < 0) return 0;
   for (int k = 0; k < ms; ++k) model_out[k] = best_m[k];
-  if (model == 4 && !project_essential(model_out)) { /* the mask stays that of the scored 8-point estimate */
+  if (model == 4 && !project_essential(model_out)) { /* no essential matrix near the scored 8-point estimate: no model,
+                                                       * count 0 and a zero mask, as for every other no-model exit */
     memset(model_out, 0, 12 * sizeof(double));
     if (mask) memset(mask, 0, (size_t)n);
     return 0;
@@ -717,6 +720,8 @@ int oracle_estimate_ex(int model, const double* p, const double* q, int n, doubl
   memset(best_m, 0, sizeof(best_m));
   if (sampling == 2) {
     if (!fit_all(model, p, q, n, &nm, best_m)) return 0;
+    for (int k = 0; k < 12; ++k) /* a fit that is not finite (NaN / Inf input through the eigenvector fits) is no model */
+      if (!(fabs(best_m[k]) <= 1.7976931348623157e308)) return 0;
     if (used_out) *used_out = 1;
   } else {
     double best_med = INFINITY;
@@ -740,7 +745,7 @@ int oracle_estimate_ex(int model, const double* p, const double* q, int n, doubl
       if (!solve_model(model, p, q, idx, &nm, m)) continue;
       for (int i = 0; i < n; ++i) {
         double e;
-        errs[i] = (model_err(model, m, p, q, i, &e) && e == e) ? e : INFINITY;
+        errs[i] = (model_err(model, m, p, q, i, &e) && e == e) ? e : INFINITY; /* (NaN as +inf: both sort last and both are refused below) */
       }
       qsort(errs, (size_t)n, sizeof(double), cmp_double);
       double med = errs[n / 2];
