@@ -1201,10 +1201,9 @@ __global__ __launch_bounds__(256) void reduce_publish_kernel(const double* __res
   }
 }
 
-// Device buffers of one solve, bump-allocated from the context's grow-only arena (ctx->ba_arena); anything that does
-// not fit falls back to its own hipMalloc and is freed when the solve ends.
-// Sub-allocator over ONE device arena: the context's grow-only arena (one-shot gh_ba_solve calls reuse it from solve to
-// solve) or an arena owned by a gh_ba_graph (resident across solves, untouched by other solves on the context).
+// Device buffers of one solve, bump-allocated from ONE device arena: the context's grow-only arena (ctx->ba_arena; one-shot
+// gh_ba_solve calls reuse it from solve to solve) or an arena owned by a gh_ba_graph (resident across solves, untouched by
+// other solves on the context).  Anything that does not fit falls back to its own hipMalloc and is freed with the DevBuf.
 struct DevBuf {
   gh_ctx* ctx;
   void** arena;         // -> ctx->ba_arena or the graph's own
@@ -1378,9 +1377,8 @@ void build_schur_pairs(const gh_ba_problem* pr, int nc, const std::vector<int32_
                        const std::vector<int32_t>& plist, const std::vector<int32_t>& cstart,
                        const std::vector<int32_t>& clist, std::vector<int32_t>& pair_a, std::vector<int32_t>& pair_b,
                        std::vector<int32_t>& bstart, std::vector<int32_t>& bci, std::vector<int32_t>& bcj,
-                       const int32_t* pbslot) {
+                       const int32_t* pbslot, bool timing) {
   const int no = pr->n_obs;
-  const bool timing = getenv("GSLAM_HIP_BA_TIMING") != nullptr;
   const double t0 = now_ms();
   HostPool& pool = HostPool::get();
   int nchunk = no >= 20000 ? 2 * pool.size() : 1;  // two ranges per thread: the pair count per observation varies
@@ -1516,6 +1514,49 @@ extern "C" void gh_ba_default_options(gh_ba_options* o) {
 
 namespace {
 
+// The switches of a BA solve: the context's solver preference and the GSLAM_HIP_BA_* environment variables, read in ONE place
+// (ba_switches) at the top of every public BA call -- every call, never once per process: they may change between two solves.
+struct BaSwitches {
+  int solver = 0;            // ctx->ba_solver unless GSLAM_HIP_BA_SOLVER is set (d...: 1 dense, b...: 2 band, else 0 automatic)
+  bool arrow = true;         // GSLAM_HIP_BA_ARROW=0: loop closures -> dense, as in rounds 1-4 (A/B measurements)
+  bool reorder = true;       // GSLAM_HIP_BA_REORDER=0: the caller's camera order as it is (rounds 4-5; A/B measurements)
+  int dense_border = -1;     // GSLAM_HIP_BA_ARROW_DENSE_BORDER: -1 unset, 0 "0" (always the border structure), 1 else (never)
+  bool early_upload = true;  // GSLAM_HIP_BA_EARLY_UPLOAD=0: upload after the lists (A/B measurements)
+  bool csr_host = false;     // GSLAM_HIP_BA_CSR=host: host-built index lists for large graphs too
+  char pairs = 'a';          // GSLAM_HIP_BA_PAIRS: 'h' host build, 'c' check (both builds, compared), else 'a' (by size)
+  bool dense_s = false;      // GSLAM_HIP_BA_DENSE_S=1: the dense layout of S under the band solver (rounds 4-5, A/B)
+  bool speculate = true;     // GSLAM_HIP_BA_SPECULATE=0: no speculative linearisation
+  bool timing = false;       // GSLAM_HIP_BA_TIMING set: phase timings on stderr
+  // THE solver rule.  The reduced camera system couples two cameras only if they see a common point: with every point seen from
+  // cameras at most `cam_span` indices apart (a trajectory), S is a band of half-width 6 span + 5.  Tiles per superblock, 0 = dense.
+  int band_tiles(int n_band, int cam_span) const { return solver == 1 ? 0 : gh_cr_tiles(n_band, 6 * cam_span + 5); }
+  bool arrow_wanted() const { return arrow && solver != 1; }
+  // the structure of a border block, by default from 4 M entries on: at C4 + 20 closures, 0.8 M, the passes that find it cost what
+  // the border kernels save over a dozen iterations; at C5 + 50, 51 M, one iteration pays for them
+  bool border_structure(long long entries) const { return dense_border >= 0 ? dense_border == 0 : entries >= (4LL << 20); }
+};
+BaSwitches ba_switches(const gh_ctx* ctx) {
+  auto is_off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+  BaSwitches sw;
+  sw.solver = ctx->ba_solver;
+  if (const char* e = getenv("GSLAM_HIP_BA_SOLVER")) sw.solver = e[0] == 'd' ? 1 : (e[0] == 'b' ? 2 : 0);
+  sw.arrow = !is_off("GSLAM_HIP_BA_ARROW");
+  sw.reorder = !is_off("GSLAM_HIP_BA_REORDER");
+  if (const char* e = getenv("GSLAM_HIP_BA_ARROW_DENSE_BORDER")) sw.dense_border = e[0] == '0' ? 0 : 1;
+  sw.early_upload = !is_off("GSLAM_HIP_BA_EARLY_UPLOAD");
+  if (const char* e = getenv("GSLAM_HIP_BA_CSR")) sw.csr_host = e[0] == 'h';
+  if (const char* e = getenv("GSLAM_HIP_BA_PAIRS")) sw.pairs = e[0] == 'h' || e[0] == 'c' ? e[0] : 'a';
+  if (const char* e = getenv("GSLAM_HIP_BA_DENSE_S")) sw.dense_s = e[0] == '1';
+  sw.speculate = !is_off("GSLAM_HIP_BA_SPECULATE");
+  sw.timing = getenv("GSLAM_HIP_BA_TIMING") != nullptr;
+  return sw;
+}
+
+// Outputs of one linearisation (lin_kernel).  Two sets: the candidate state is linearised speculatively while the host decides.
+struct LinSet {
+  double *W = nullptr, *Hpp = nullptr, *gp = nullptr, *cpart = nullptr;
+};
+
 // Everything a solve keeps on the device.  A one-shot gh_ba_solve builds one on the stack over the context's arena; a
 // gh_ba_graph owns one (and its arena) so that the index lists, pair lists, chunk tables and all arrays stay in HBM
 // between the windowed solves of a SLAM back end (GSLAM/core/Optimizer.h:229 is called every few keyframes on a graph
@@ -1530,7 +1571,7 @@ struct BaSession {
   // 3 unknowns each follow the cameras' in the reduced system.  Never together with a camera border.
   std::vector<int32_t> border_pts;
   int32_t *d_bpts = nullptr, *d_pbslot = nullptr;
-  int span_measured = -1;  // >= 0: ba_order.hip has measured the camera span of the order in use (and checked every index): ba_run skips its pass
+  int span_measured = -1;  // >= 0: ba_order.hip has measured the camera span of the order in use (and checked every index): ba_check_problem skips its pass
   int reordered = 0; // the bandwidth-reducing order of ba_order.hip was applied (perm is then non-empty even without a border)
   double* d_arrow_ws = nullptr;
   // structure of the border rows of the reduced camera system (arrowhead solver): border_cam_nz[strip * nc_band + c] != 0 iff a
@@ -1551,363 +1592,284 @@ struct BaSession {
   SchurBlocks SB{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
   int nchunks = 0, nsegs = 0, nblocks = 0;
   bool device_pairs = false;
-  double *d_Hcc = nullptr, *d_gc = nullptr, *d_Hpp = nullptr, *d_gp = nullptr, *d_Hpi = nullptr, *d_S = nullptr, *d_dc = nullptr,
-         *d_dp = nullptr, *d_partial = nullptr, *d_out = nullptr, *d_work = nullptr, *d_dinv = nullptr, *d_W = nullptr,
-         *d_cpart = nullptr, *d_spart = nullptr, *d_xwork = nullptr, *d_xh = nullptr;
-  // second set of the linearisation's outputs: the candidate state is linearised speculatively while the host decides
-  double *d_W2 = nullptr, *d_Hpp2 = nullptr, *d_gp2 = nullptr, *d_cpart2 = nullptr;
+  double *d_Hcc = nullptr, *d_gc = nullptr, *d_Hpi = nullptr, *d_S = nullptr, *d_dc = nullptr, *d_dp = nullptr, *d_partial = nullptr,
+         *d_out = nullptr, *d_work = nullptr, *d_dinv = nullptr, *d_spart = nullptr, *d_xwork = nullptr;
+  LinSet lin[2];  // [0]: the linearisation of the current state; [1]: the speculative one (swapped in when its step is accepted)
   unsigned long long* d_keep = nullptr;  // {gradient maximum, damping flag} of the iteration, saved by backsub_update before it clears them
   unsigned long long* d_gmax = nullptr;
   int *d_bad = nullptr, *d_info = nullptr;
-  unsigned* d_flow = nullptr;
+  unsigned* d_flow = nullptr;  // state of the single-launch factorisation (null when the shape does not fit it, or after a time-out: ba_run)
+  double* d_xh = nullptr;      // ... and of the single-launch back-substitution
   size_t n_pairs = 0;
   // band solver (chol_cr.hip): tiles per superblock (0 = the dense factorisation), its inverted diagonal tiles and panels
   int cr_T = 0, cam_span = 0;
   int lda = 0;   // rows per column of d_S as allocated
   CrMap map;     // layout of d_S: dense (map.m == 0) or the band solver's compact columns
   double *d_cr_dinv = nullptr, *d_cr_W = nullptr;
+  int n_bpts() const { return (int)border_pts.size(); }  // (point border: never together with a camera border)
+  int n() const { return 6 * nc + 3 * n_bpts(); }        // unknowns of the reduced system
+  int n_band() const { return 6 * (nc - n_border); }     // (== n() unless the cameras are in arrow order / points form a border)
   ~BaSession() {
     delete db;
     if (arena) hipFree(arena);
   }
 };
 
-// pr == nullptr (graph sessions only): the values already on the device are solved as they are.  download: write the
-// result back into pr->cam_pose / pr->point_xyz.
-gh_status ba_run(gh_ctx* ctx, BaSession& S, gh_ba_problem* pr, const gh_ba_options* opt_in, gh_ba_summary* sum_out,
-                 bool download) {
-  gh_ba_options opt;
-  gh_ba_default_options(&opt);
-  if (opt_in) opt = *opt_in;
-  gh_ba_summary local_sum;
-  gh_ba_summary* sum = sum_out ? sum_out : &local_sum;
-  memset(sum, 0, sizeof(*sum));
-  GH_CHECK_ARG(ctx, pr != nullptr || S.ready);
-  const int nc = pr ? pr->n_cams : S.nc, np = pr ? pr->n_points : S.np, no = pr ? pr->n_obs : S.no;
-  GH_CHECK_ARG(ctx, nc >= 1 && np >= 0 && no >= 0 && nc <= (1 << 24));
-  if (pr) {
-    GH_CHECK_ARG(ctx, pr->cam_pose && pr->cam_dof && (np == 0 || pr->point_xyz));
-    GH_CHECK_ARG(ctx, no == 0 || (pr->obs_cam && pr->obs_point && pr->obs_xy));
-  }
-  if (S.ready) {  // a resident graph: same topology by contract, checked as far as the sizes go
-    GH_CHECK_ARG(ctx, nc == S.nc && np == S.np && no == S.no && (opt.deterministic != 0) == (S.deterministic != 0));
-    GH_CHECK_ARG(ctx, !pr || ((pr->obs_info != nullptr) == S.has_info && (pr->point_free != nullptr) == S.has_pfree));
-  } else {
-    // (the same pass finds how far apart, in camera indices, the observers of one point are: a band -> the band solver)
-    const int nc_band = nc - S.n_border;  // (arrow ordering: the border cameras are the last ones and do not count)
-    if (S.span_measured >= 0 && S.n_border == 0) {
-      S.cam_span = S.span_measured;  // (ba_order.hip: the same pass, on the pool threads, indices checked)
-    } else {
-      std::vector<int32_t> cam_lo((size_t)np, INT32_MAX), cam_hi((size_t)np, -1);
-      for (int k = 0; k < no; ++k) {
-        const int32_t c = pr->obs_cam[k], p = pr->obs_point[k];
-        GH_CHECK_ARG(ctx, c >= 0 && c < nc && p >= 0 && p < np);
-        if (c >= nc_band) continue;
-        if (c < cam_lo[p]) cam_lo[p] = c;
-        if (c > cam_hi[p]) cam_hi[p] = c;
-      }
-      int span = 0;
-      for (int p = 0; p < np; ++p)
-        if (cam_hi[p] >= 0 && cam_hi[p] - cam_lo[p] > span) span = cam_hi[p] - cam_lo[p];
-      S.cam_span = span;
-    }
-    S.border_cam_nz.clear();
-    // (GSLAM_HIP_BA_ARROW_DENSE_BORDER = 1: never, 0: always; default: when the border block has 4 M entries or more -- at C4 + 20
-    //  closures, 0.8 M, the two passes below cost what the border kernels save over a dozen iterations; at C5 + 50, 51 M, one
-    //  iteration pays for them)
-    const char* dense_border_env = getenv("GSLAM_HIP_BA_ARROW_DENSE_BORDER");
-    const bool want_structure = dense_border_env ? dense_border_env[0] == '0' : 36LL * S.n_border * nc_band >= (4LL << 20);
-    if (S.n_border > 0 && want_structure) {
-      // which (border strip, band camera) blocks of the reduced system can be non-zero: a common point (two more passes)
-      const int nbs = (6 * S.n_border + 15) / 16;
-      std::vector<int32_t> first((size_t)np, -1), next_of;   // per point: chain of its border observers
-      std::vector<int32_t> cam_of;
-      std::vector<uint8_t> has((size_t)np / 8 + 1, 0);        // (a bit per point: the test of the second pass stays in cache)
-      for (int k = 0; k < no; ++k) {
-        const int32_t c = pr->obs_cam[k];
-        if (c < nc_band) continue;
-        const int32_t p = pr->obs_point[k];
-        cam_of.push_back(c - nc_band);
-        next_of.push_back(first[p]);
-        first[p] = (int32_t)cam_of.size() - 1;
-        has[(size_t)p >> 3] |= (uint8_t)(1u << (p & 7));
-      }
-      S.border_cam_nz.assign((size_t)nbs * nc_band, 0);
-      for (int k = 0; k < no; ++k) {
-        const int32_t p = pr->obs_point[k];
-        if (!((has[(size_t)p >> 3] >> (p & 7)) & 1)) continue;
-        const int32_t c = pr->obs_cam[k];
-        if (c >= nc_band) continue;
-        for (int32_t e = first[p]; e >= 0; e = next_of[e]) {
-          const int r0 = 6 * cam_of[e];
-          S.border_cam_nz[(size_t)(r0 / 16) * nc_band + c] = 1;
-          S.border_cam_nz[(size_t)((r0 + 5) / 16) * nc_band + c] = 1;
-        }
-      }
-    }
-    // the same for a POINT border: border point b (rows 3 b .. 3 b + 2) only touches the columns of the cameras that see it
-    const int nbp0 = (int)S.border_pts.size();
-    const bool want_pstructure = dense_border_env ? dense_border_env[0] == '0' : 18LL * nbp0 * nc >= (4LL << 20);
-    if (nbp0 > 0 && want_pstructure) {
-      const int nbs = (3 * nbp0 + 15) / 16;
-      std::vector<int32_t> slot_of((size_t)np, -1);
-      for (int b = 0; b < nbp0; ++b) slot_of[S.border_pts[b]] = b;
-      S.border_cam_nz.assign((size_t)nbs * nc, 0);
-      for (int k = 0; k < no; ++k) {
-        const int32_t b = slot_of[pr->obs_point[k]];
-        if (b < 0) continue;
-        const int32_t c = pr->obs_cam[k];
-        S.border_cam_nz[(size_t)((3 * b) / 16) * nc + c] = 1;
-        S.border_cam_nz[(size_t)((3 * b + 2) / 16) * nc + c] = 1;
-      }
-    }
-  }
-  GH_HIP(ctx, hipSetDevice(ctx->device));
-  const double t_begin = now_ms();
-  const int n_bpts = (int)S.border_pts.size();  // (point border: never together with a camera border)
-  const int n = 6 * nc + 3 * n_bpts;
-  const int n_band = 6 * (nc - S.n_border);  // (== n unless the cameras are in arrow order / points form a border)
-  // one extra row carries the right-hand side through the factorisation; columns start on 128-byte lines
-  // (dense: n + 1 rows per column; band / arrowhead solver: compact columns, decided with the solver below -- cr_map.h)
-  int lda = S.ready ? S.lda : (n + 1 + 15) & ~15;
+// What set-up leaves on the host for the phases after it (first run of a session only; a resident solve keeps it empty).
+struct BaSetup {
+  std::vector<int32_t> pstart, plist, cstart, clist;      // index lists by point and by camera
+  std::vector<int32_t> pair_a, pair_b, bstart, bci, bcj;  // host-built pair lists (empty when only the device builds them)
+  std::vector<int32_t> pbslot;  // point border: slot of every point (-1: an ordinary point, eliminated by the Schur complement)
+  size_t pairs_ub = 0, blocks_ub = 0;  // device-built pair lists: upper bounds on pairs and blocks
+  bool pairs_check = false;            // GSLAM_HIP_BA_PAIRS=check: both builds, compared after the first cost
+  SchurBlocks SB_host{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};  // (check mode: the host-built tables beside the device-built ones)
+  struct RawPiece { char* dst; const char* src; size_t bytes; };
+  std::vector<RawPiece> raw_pieces;  // the caller's arrays as they lie on the device
+  bool early = false;                // ... go up WHILE the index lists are built
+  char* stage = nullptr;             // pinned staging image of the early upload
+  double t_begin = 0, t_csr = 0, t_lists = 0;
+};
 
-  // Everything the host reads back during an iteration (gradient maximum, factorisation / damping flags, candidate cost
-  // and model decrease) lands in ONE pinned block: copies into pageable memory are staged and block the host in the middle
-  // of the launch chain, which left the GPU idle while the rest of the iteration was being enqueued.
-  typedef HostVerdict Readback;  // cost, model, gmax_bits, info, bad, pair_counts[4] (device-built pair lists: pairs, blocks, segments), stamp
-  // The caller's arrays (8.9 MB at C4, pageable: 0.85-1.2 ms of staged copies when the driver does it) go up WHILE the host
-  // builds its index lists -- when the arena of an earlier solve is there to take them (a first solve, or one that has to
-  // grow the arena, uploads after the lists as before).  With enough pool threads the staging is ours: the arrays lie back
-  // to back on the device, four tasks copy a quarter of that image each into pinned memory and send it with one
-  // asynchronous copy.
-  const bool with_info = pr ? pr->obs_info != nullptr : S.has_info;
-  const size_t raw_bytes = 8 * ((size_t)nc * 7 * 2 + (size_t)np * 3 * 2 + (size_t)no * 2 + (with_info ? (size_t)no * 4 : 0)) +
-                           4 * ((size_t)nc + 2 * (size_t)no) + (size_t)np + 16 * 256;
-  const char* early_env = getenv("GSLAM_HIP_BA_EARLY_UPLOAD");  // "0": upload after the lists (A/B measurements)
-  DevBuf& db = *S.db;
-  bool early = !S.ready && *db.arena != nullptr && raw_bytes <= *db.arena_bytes && !(early_env && early_env[0] == '0');
-  Readback* rb = nullptr;  // (a pinned block of its own: nothing the staging below or a later gh_pinned does can move it)
-  char* stage = nullptr;
-  {
-    void* pp = nullptr;
-    GH_TRY(gh_readback_block(ctx, sizeof(Readback), &pp));
-    rb = (Readback*)pp;
-    if (early) {
-      GH_TRY(gh_pinned(ctx, raw_bytes, &pp));
-      stage = (char*)pp;
+// ---------------------------------------------------------------- set-up (once per topology)
+// Argument check of a new problem; the same pass finds how far apart, in camera indices, the observers of one point are
+// (a band -> the band solver).
+gh_status ba_check_problem(gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr) {
+  const int nc = pr->n_cams, np = pr->n_points, no = pr->n_obs;
+  GH_CHECK_ARG(ctx, nc >= 1 && np >= 0 && no >= 0 && nc <= (1 << 24));
+  GH_CHECK_ARG(ctx, pr->cam_pose && pr->cam_dof && (np == 0 || pr->point_xyz));
+  GH_CHECK_ARG(ctx, no == 0 || (pr->obs_cam && pr->obs_point && pr->obs_xy));
+  S.nc = nc;
+  S.np = np;
+  S.no = no;
+  S.has_info = pr->obs_info != nullptr;
+  S.has_pfree = pr->point_free != nullptr;
+  if (S.span_measured >= 0 && S.n_border == 0) {
+    S.cam_span = S.span_measured;  // (ba_order.hip: the same pass, on the pool threads, indices checked)
+    return GH_OK;
+  }
+  const int nc_band = nc - S.n_border;  // (arrow ordering: the border cameras are the last ones and do not count)
+  std::vector<int32_t> cam_lo((size_t)np, INT32_MAX), cam_hi((size_t)np, -1);
+  for (int k = 0; k < no; ++k) {
+    const int32_t c = pr->obs_cam[k], p = pr->obs_point[k];
+    GH_CHECK_ARG(ctx, c >= 0 && c < nc && p >= 0 && p < np);
+    if (c >= nc_band) continue;
+    if (c < cam_lo[p]) cam_lo[p] = c;
+    if (c > cam_hi[p]) cam_hi[p] = c;
+  }
+  int span = 0;
+  for (int p = 0; p < np; ++p)
+    if (cam_hi[p] >= 0 && cam_hi[p] - cam_lo[p] > span) span = cam_hi[p] - cam_lo[p];
+  S.cam_span = span;
+  return GH_OK;
+}
+
+// Which blocks of the border rows of the reduced system can be non-zero (S.border_cam_nz; empty = treat the border as dense).
+void ba_border_occupancy(BaSession& S, const gh_ba_problem* pr, const BaSwitches& sw) {
+  const int nc = S.nc, np = S.np, no = S.no, nc_band = nc - S.n_border;
+  S.border_cam_nz.clear();
+  if (S.n_border > 0 && sw.border_structure(36LL * S.n_border * nc_band)) {
+    // camera border: which (border strip, band camera) blocks can be non-zero: a common point (two more passes)
+    const int nbs = (6 * S.n_border + 15) / 16;
+    std::vector<int32_t> first((size_t)np, -1), next_of;   // per point: chain of its border observers
+    std::vector<int32_t> cam_of;
+    std::vector<uint8_t> has((size_t)np / 8 + 1, 0);        // (a bit per point: the test of the second pass stays in cache)
+    for (int k = 0; k < no; ++k) {
+      const int32_t c = pr->obs_cam[k];
+      if (c < nc_band) continue;
+      const int32_t p = pr->obs_point[k];
+      cam_of.push_back(c - nc_band);
+      next_of.push_back(first[p]);
+      first[p] = (int32_t)cam_of.size() - 1;
+      has[(size_t)p >> 3] |= (uint8_t)(1u << (p & 7));
+    }
+    S.border_cam_nz.assign((size_t)nbs * nc_band, 0);
+    for (int k = 0; k < no; ++k) {
+      const int32_t p = pr->obs_point[k];
+      if (!((has[(size_t)p >> 3] >> (p & 7)) & 1)) continue;
+      const int32_t c = pr->obs_cam[k];
+      if (c >= nc_band) continue;
+      for (int32_t e = first[p]; e >= 0; e = next_of[e]) {
+        const int r0 = 6 * cam_of[e];
+        S.border_cam_nz[(size_t)(r0 / 16) * nc_band + c] = 1;
+        S.border_cam_nz[(size_t)((r0 + 5) / 16) * nc_band + c] = 1;
+      }
     }
   }
-  double *&d_poses = S.d_poses, *&d_pts = S.d_pts, *&d_poses_new = S.d_poses_new, *&d_pts_new = S.d_pts_new, *&d_oxy = S.d_oxy,
-         *&d_oinfo = S.d_oinfo;
-  int32_t *&d_dof = S.d_dof, *&d_ocam = S.d_ocam, *&d_opt = S.d_opt, *&d_pstart = S.d_pstart, *&d_plist = S.d_plist,
-          *&d_cstart = S.d_cstart, *&d_clist = S.d_clist;
-  uint8_t*& d_pfree = S.d_pfree;
-  CamChunks& CC = S.CC;
-  SchurBlocks& SB = S.SB;
-  int &nchunks = S.nchunks, &nsegs = S.nsegs, &nblocks = S.nblocks;
-  bool& device_pairs = S.device_pairs;
-  double *&d_Hcc = S.d_Hcc, *&d_gc = S.d_gc, *&d_Hpp = S.d_Hpp, *&d_gp = S.d_gp, *&d_Hpi = S.d_Hpi, *&d_S = S.d_S, *&d_dc = S.d_dc,
-         *&d_dp = S.d_dp, *&d_partial = S.d_partial, *&d_out = S.d_out, *&d_work = S.d_work, *&d_dinv = S.d_dinv, *&d_W = S.d_W,
-         *&d_cpart = S.d_cpart, *&d_spart = S.d_spart, *&d_xwork = S.d_xwork, *&d_xh = S.d_xh;
-  double *&d_W2 = S.d_W2, *&d_Hpp2 = S.d_Hpp2, *&d_gp2 = S.d_gp2, *&d_cpart2 = S.d_cpart2;
-  unsigned long long*& d_gmax = S.d_gmax;
-  int *&d_bad = S.d_bad, *&d_info = S.d_info;
-  unsigned*& d_flow = S.d_flow;
-  int& cr_T = S.cr_T;
-  double *&d_cr_dinv = S.d_cr_dinv, *&d_cr_W = S.d_cr_W;
-  const int eval_blocks = gh_div_up(no > 0 ? no : 1, 256);
-  // (first run only, kept for the verbose / check paths below)
-  std::vector<int32_t> pair_a, pair_b, bstart, bci, bcj;
-  bool pairs_check = false;
-  SchurBlocks SB_host = SB;
-  double t_csr = t_begin, t_lists = t_begin;
-  if (!S.ready) {  // ================================================================ set-up (once per topology)
-  struct RawPiece {
-    char* dst;
-    const char* src;
-    size_t bytes;
-  };
-  std::vector<RawPiece> raw_pieces;
-  auto raw_arrays = [&](bool copy) -> gh_status {  // copy = false: allocate and note the pieces only
-    raw_pieces.clear();
-    auto put = [&](auto** out, auto* src, size_t count) -> gh_status {
-      GH_TRY(db.alloc(out, count));
-      if (count) raw_pieces.push_back(RawPiece{(char*)*out, (const char*)src, count * sizeof(**out)});
-      if (copy && count)
-        GH_HIP(ctx, hipMemcpyAsync(*out, src, count * sizeof(**out), hipMemcpyHostToDevice, ctx->stream));
-      return GH_OK;
-    };
-    GH_TRY(put(&d_poses, pr->cam_pose, (size_t)nc * 7));
-    GH_TRY(put(&d_pts, pr->point_xyz, (size_t)np * 3));
-    GH_TRY(put(&d_dof, pr->cam_dof, (size_t)nc));
-    if (pr->point_free) GH_TRY(put(&d_pfree, pr->point_free, (size_t)np));
-    GH_TRY(put(&d_ocam, pr->obs_cam, (size_t)no));
-    GH_TRY(put(&d_opt, pr->obs_point, (size_t)no));
-    GH_TRY(put(&d_oxy, pr->obs_xy, (size_t)no * 2));
-    if (pr->obs_info) GH_TRY(put(&d_oinfo, pr->obs_info, (size_t)no * 4));
-    GH_TRY(db.alloc(&d_poses_new, (size_t)nc * 7));
-    GH_TRY(db.alloc(&d_pts_new, (size_t)np * 3));
+  // the same for a POINT border: border point b (rows 3 b .. 3 b + 2) only touches the columns of the cameras that see it
+  const int nbp = S.n_bpts();
+  if (nbp > 0 && sw.border_structure(18LL * nbp * nc)) {
+    const int nbs = (3 * nbp + 15) / 16;
+    std::vector<int32_t> slot_of((size_t)np, -1);
+    for (int b = 0; b < nbp; ++b) slot_of[S.border_pts[b]] = b;
+    S.border_cam_nz.assign((size_t)nbs * nc, 0);
+    for (int k = 0; k < no; ++k) {
+      const int32_t b = slot_of[pr->obs_point[k]];
+      if (b < 0) continue;
+      const int32_t c = pr->obs_cam[k];
+      S.border_cam_nz[(size_t)((3 * b) / 16) * nc + c] = 1;
+      S.border_cam_nz[(size_t)((3 * b + 2) / 16) * nc + c] = 1;
+    }
+  }
+}
+
+// Arena bytes of a new session, reserved BEFORE anything but the caller's arrays is carved (it also decides whether an early
+// upload stands).  Nothing fails when this falls short of what the allocation phases below take -- the buffers past the end get
+// a hipMalloc of their own and the solve gets slower -- so every term names the allocations it stands for: keep them in step.
+size_t ba_arena_need(const gh_ctx* ctx, const BaSession& S, const BaSwitches& sw, const BaSetup& U) {
+  const int n = S.n(), n_band = S.n_band();
+  const size_t N = (size_t)n, NP = (size_t)S.np, NO = (size_t)S.no, NC = (size_t)S.nc, NB = (size_t)S.n_bpts();
+  const size_t host_pairs = U.pair_a.size(), host_blocks = U.bstart.size();
+  // ba_alloc_work: d_S as the dense lower triangle, or compact columns + d_cr_dinv, d_cr_W, d_arrow_ws, d_border_nz
+  const int T_plan = sw.band_tiles(n_band, S.cam_span);
+  size_t s_doubles = N * (N + 1) + 64;
+  if (T_plan) {
+    if (!sw.dense_s) s_doubles = N * (size_t)gh_cr_compact_lda(n_band, T_plan, n - n_band, nullptr);
+    s_doubles += gh_cr_dinv_doubles(n_band, T_plan) + gh_cr_panel_doubles(n_band, T_plan) +
+                 gh_arrow_ws_doubles(ctx, n_band, T_plan, n - n_band) + gh_cr_border_symbolic_bytes(n_band, T_plan, n - n_band) / 8 + 4 * 64;
+  }
+  return
+      // ba_raw_arrays: d_poses + d_poses_new, d_pts + d_pts_new, d_oxy, d_oinfo;  ba_alloc_work: d_Hcc; d_gc, d_dc, d_work; Hpp and d_Hpi;
+      // gp and d_dp; S with its workspaces; d_dinv, d_xwork and d_xh; W; d_partial; d_out, d_keep, d_gmax (the second LinSet and d_flow
+      // have no term: they live on the slack of the upper bounds and the eighth DevBuf::reserve adds)
+      8 * (2 * NC * 7 + 2 * NP * 3 + NO * 2 + (S.has_info ? NO * 4 : 0) + NC * 36 + N * 3 + NP * 9 * 2 + NP * 3 * 2 + s_doubles +
+           (N + 64) * 64 * 3 + NO * 18 + (NO / 256 + 2) * 2 + 8) +
+      // d_dof, d_ocam, d_opt;  ba_upload_tables: d_plist, d_clist, d_pstart, d_cstart; d_bad, d_info; the host-built pair_a / pair_b and
+      // bstart / bci / bcj;  d_pfree;  the 256-byte rounding of 64 allocations
+      4 * (NC + NO * 4 + NP + NC + 4 + host_pairs * 2 + host_blocks * 3) + NP + 64 * 256 +
+      // ba_upload_tables, point border: d_pbslot, d_bpts
+      (NB > 0 ? 4 * (NP + NB) + 1024 : 0) +
+      // build_schur_pairs_device: 7 arrays of pairs_ub ints, block / segment tables, scan scratch, and its 26 roundings
+      4 * (U.pairs_ub * 7 + U.blocks_ub * 5 + U.pairs_ub / kSchurSeg + NO + NO / 1024 + U.blocks_ub / 1024 + 2 * NC + 128) +
+      (S.device_pairs ? 26 * 256 : 0) +
+      // ba_upload_tables: the chunk tables (ch_cam, ch_q0; ch_first) and ba_alloc_work's cpart, per chunk (upper bounds)
+      (NO / kCamChunk + NC + 2) * (27 * 8 + 2 * 4) + (NC + 2) * 4 +
+      // the segment tables (seg_blk; seg_first) and d_spart, per segment (upper bounds), and 16 more roundings
+      (std::max(host_pairs, U.pairs_ub) / kSchurSeg + std::max(host_blocks, U.blocks_ub) + 2) * (42 * 8 + 4) + (host_blocks + 2) * 4 +
+      16 * 256;
+}
+
+// The caller's arrays, first in the arena and back to back.  copy = false: allocate and note the pieces only (the early upload stages them).
+gh_status ba_raw_arrays(gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr, BaSetup& U, bool copy) {
+  const size_t nc = (size_t)S.nc, np = (size_t)S.np, no = (size_t)S.no;
+  DevBuf& db = *S.db;
+  U.raw_pieces.clear();
+  auto put = [&](auto** out, auto* src, size_t count) -> gh_status {
+    GH_TRY(db.alloc(out, count));
+    if (count) U.raw_pieces.push_back(BaSetup::RawPiece{(char*)*out, (const char*)src, count * sizeof(**out)});
+    if (copy && count) GH_HIP(ctx, hipMemcpyAsync(*out, src, count * sizeof(**out), hipMemcpyHostToDevice, ctx->stream));
     return GH_OK;
   };
-  gh_status early_status = GH_OK;
-  // part u of U of the device image of the arrays: pageable -> pinned, then one asynchronous copy
-  auto stage_part = [&](int u, int U) -> gh_status {
-    char* base = raw_pieces.front().dst;
-    const size_t total = (size_t)(raw_pieces.back().dst - base) + raw_pieces.back().bytes;
-    const size_t b0 = (total * u / U) & ~(size_t)255, b1 = u + 1 == U ? total : (total * (u + 1) / U) & ~(size_t)255;
-    for (const RawPiece& pc : raw_pieces) {
+  GH_TRY(put(&S.d_poses, pr->cam_pose, nc * 7));
+  GH_TRY(put(&S.d_pts, pr->point_xyz, np * 3));
+  GH_TRY(put(&S.d_dof, pr->cam_dof, nc));
+  if (pr->point_free) GH_TRY(put(&S.d_pfree, pr->point_free, np));
+  GH_TRY(put(&S.d_ocam, pr->obs_cam, no));
+  GH_TRY(put(&S.d_opt, pr->obs_point, no));
+  GH_TRY(put(&S.d_oxy, pr->obs_xy, no * 2));
+  if (pr->obs_info) GH_TRY(put(&S.d_oinfo, pr->obs_info, no * 4));
+  GH_TRY(db.alloc(&S.d_poses_new, nc * 7));
+  GH_TRY(db.alloc(&S.d_pts_new, np * 3));
+  return GH_OK;
+}
+
+// Index lists by point and by camera, with the early upload of the caller's arrays beside them.  The arrays (8.9 MB at C4,
+// pageable: 0.85-1.2 ms of staged copies when the driver does it) go up WHILE the host builds its lists -- when the arena
+// of an earlier solve is there to take them (a first solve, or one that has to grow the arena, uploads after the lists).
+// With enough pool threads the staging is ours: the arrays lie back to back on the device, four tasks copy a quarter of
+// that image each into pinned memory and send it with one asynchronous copy.
+gh_status ba_index_lists(gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr, const BaSwitches& sw, BaSetup& U) {
+  const int nc = S.nc, np = S.np, no = S.no;
+  DevBuf& db = *S.db;
+  // each list by a team of pool tasks when the pool has a thread for every task of the region (the teams meet at spin barriers), else one task per list
+  HostPool& pool = HostPool::get();
+  constexpr int Tp = 6, Tc = 3, NU = 4;
+  const bool teams = no >= 20000 && pool.size() >= Tp + Tc + (U.early ? NU : 0);
+  gh_status part_status[NU] = {GH_OK, GH_OK, GH_OK, GH_OK}, csr_status[2] = {GH_OK, GH_OK}, early_status = GH_OK;
+  if (U.early && teams) {
+    GH_TRY(ba_raw_arrays(ctx, S, pr, U, false));
+    U.early = !U.raw_pieces.empty() && U.raw_pieces.front().dst >= (char*)*db.arena &&
+              U.raw_pieces.back().dst + U.raw_pieces.back().bytes <= (char*)*db.arena + *db.arena_bytes;
+    if (!U.early) db.used = 0;  // (cannot happen with an arena that holds the raw bytes; the plain path allocates again)
+  }
+  const int extra = U.early ? (teams ? NU : 1) : 0;
+  // part u of NU of the device image of the arrays: pageable -> pinned, then one asynchronous copy
+  auto stage_part = [&](int u) -> gh_status {
+    char* base = U.raw_pieces.front().dst;
+    const size_t total = (size_t)(U.raw_pieces.back().dst - base) + U.raw_pieces.back().bytes;
+    const size_t b0 = (total * u / NU) & ~(size_t)255, b1 = u + 1 == NU ? total : (total * (u + 1) / NU) & ~(size_t)255;
+    for (const BaSetup::RawPiece& pc : U.raw_pieces) {
       const size_t p0 = (size_t)(pc.dst - base), p1 = p0 + pc.bytes;
       const size_t lo = std::max(p0, b0), hi = std::min(p1, b1);
-      if (lo < hi) memcpy(stage + lo, pc.src + (lo - p0), hi - lo);
+      if (lo < hi) memcpy(U.stage + lo, pc.src + (lo - p0), hi - lo);
     }
-    if (b1 > b0) GH_HIP(ctx, hipMemcpyAsync(base + b0, stage + b0, b1 - b0, hipMemcpyHostToDevice, ctx->stream));
+    if (b1 > b0) GH_HIP(ctx, hipMemcpyAsync(base + b0, U.stage + b0, b1 - b0, hipMemcpyHostToDevice, ctx->stream));
     return GH_OK;
   };
-
-  std::vector<int32_t> pstart, plist, cstart, clist;
-  {
-    // index lists by point and by camera: each by a team of pool tasks when the pool has a thread for every task of the
-    // region (the teams meet at spin barriers), else one task per list
-    HostPool& pool = HostPool::get();
-    constexpr int Tp = 6, Tc = 3, U = 4;
-    const bool teams = no >= 20000 && pool.size() >= Tp + Tc + (early ? U : 0);
-    gh_status part_status[U] = {GH_OK, GH_OK, GH_OK, GH_OK};
-    if (early && teams) {
-      GH_TRY(raw_arrays(false));
-      early = !raw_pieces.empty() && raw_pieces.front().dst >= (char*)*db.arena &&
-              raw_pieces.back().dst + raw_pieces.back().bytes <= (char*)*db.arena + *db.arena_bytes;
-      if (!early) db.used = 0;  // (cannot happen with an arena that holds raw_bytes; the plain path allocates again)
-    }
-    const int extra = early ? (teams ? U : 1) : 0;
-    auto upload_task = [&](int u) {
-      (void)hipSetDevice(ctx->device);  // the current device is a per-thread setting
-      if (teams) part_status[u] = stage_part(u, U);
-      else early_status = raw_arrays(true);
-    };
-    // Large graphs: the two lists come from a stable radix sort on the GPU (csr_sort.hip) while the pool stages the raw
-    // arrays -- the host teams need ~60 ms for the 6 M observations of C5.  GSLAM_HIP_BA_CSR=host keeps the host lists.
-    const char* csr_env = getenv("GSLAM_HIP_BA_CSR");
-    const bool gpu_csr = no >= (1 << 20) && !(csr_env && csr_env[0] == 'h');
-    if (gpu_csr) {
-      pstart.assign((size_t)np + 1, 0);
-      cstart.assign((size_t)nc + 1, 0);
-      plist.resize((size_t)no);
-      clist.resize((size_t)no);
-      gh_status csr_status[2] = {GH_OK, GH_OK};
-      pool.run(2 + extra, [&](int t) {  // (the two sorts share the stream; their pageable host copies overlap)
-        (void)hipSetDevice(ctx->device);
-        if (t == 0) csr_status[0] = gh_csr_build_dev(ctx, pr->obs_point, no, np, pstart.data(), plist.data());
-        else if (t == 1) csr_status[1] = gh_csr_build_dev(ctx, pr->obs_cam, no, nc, cstart.data(), clist.data());
-        else upload_task(t - 2);
-      });
-      GH_TRY(csr_status[0]);
-      GH_TRY(csr_status[1]);
-      for (int u = 0; u < U; ++u) GH_TRY(part_status[u]);
-    } else if (teams) {
-      CsrShared shp, shc;
-      shp.reset(Tp, np);
-      shc.reset(Tc, nc);
-      pstart.assign((size_t)np + 1, 0);
-      cstart.assign((size_t)nc + 1, 0);
-      plist.resize((size_t)(no > 0 ? no : 1));
-      clist.resize((size_t)(no > 0 ? no : 1));
-      pool.run(Tp + Tc + extra, [&](int t) {
-        if (t < Tp) build_csr_task(pr->obs_point, no, np, pstart, plist, Tp, t, shp);
-        else if (t < Tp + Tc) build_csr_task(pr->obs_cam, no, nc, cstart, clist, Tc, t - Tp, shc);
-        else upload_task(t - Tp - Tc);
-      });
-      for (int u = 0; u < U; ++u) GH_TRY(part_status[u]);
-    } else {
-      pool.run(2 + extra, [&](int t) {
-        if (t == 0) build_csr(pr->obs_point, no, np, pstart, plist);
-        else if (t == 1) build_csr(pr->obs_cam, no, nc, cstart, clist);
-        else upload_task(0);
-      });
-    }
+  auto upload_task = [&](int u) {
+    (void)hipSetDevice(ctx->device);  // the current device is a per-thread setting
+    if (teams) part_status[u] = stage_part(u);
+    else early_status = ba_raw_arrays(ctx, S, pr, U, true);
+  };
+  // Large graphs: the two lists come from a stable radix sort on the GPU (csr_sort.hip) while the pool stages the raw
+  // arrays -- the host teams need ~60 ms for the 6 M observations of C5.  GSLAM_HIP_BA_CSR=host keeps the host lists.
+  const bool gpu_csr = no >= (1 << 20) && !sw.csr_host;
+  if (gpu_csr || teams) {  // (build_csr sizes its own)
+    U.pstart.assign((size_t)np + 1, 0);
+    U.cstart.assign((size_t)nc + 1, 0);
+    U.plist.resize((size_t)(no > 0 ? no : 1));
+    U.clist.resize((size_t)(no > 0 ? no : 1));
   }
+  if (teams && !gpu_csr) {
+    CsrShared shp, shc;
+    shp.reset(Tp, np);
+    shc.reset(Tc, nc);
+    pool.run(Tp + Tc + extra, [&](int t) {
+      if (t < Tp) build_csr_task(pr->obs_point, no, np, U.pstart, U.plist, Tp, t, shp);
+      else if (t < Tp + Tc) build_csr_task(pr->obs_cam, no, nc, U.cstart, U.clist, Tc, t - Tp, shc);
+      else upload_task(t - Tp - Tc);
+    });
+  } else {
+    pool.run(2 + extra, [&](int t) {  // (the two sorts share the stream; their pageable host copies overlap)
+      if (gpu_csr) (void)hipSetDevice(ctx->device);
+      if (t >= 2) upload_task(t - 2);
+      else if (!gpu_csr && t == 0) build_csr(pr->obs_point, no, np, U.pstart, U.plist);
+      else if (!gpu_csr) build_csr(pr->obs_cam, no, nc, U.cstart, U.clist);
+      else if (t == 0) csr_status[0] = gh_csr_build_dev(ctx, pr->obs_point, no, np, U.pstart.data(), U.plist.data());
+      else csr_status[1] = gh_csr_build_dev(ctx, pr->obs_cam, no, nc, U.cstart.data(), U.clist.data());
+    });
+  }
+  GH_TRY(csr_status[0]);
+  GH_TRY(csr_status[1]);
+  for (int u = 0; u < NU; ++u) GH_TRY(part_status[u]);
   GH_TRY(early_status);
-  if (const char* pe = getenv("GSLAM_HIP_BA_PAIRS"); pe && pe[0] == 'c') {  // check mode: the team-built lists against the serial ones
+  if (sw.pairs == 'c') {  // check mode: the team-built lists against the serial ones
     std::vector<int32_t> s0, l0, s1, l1;
     build_csr(pr->obs_point, no, np, s0, l0);
     build_csr(pr->obs_cam, no, nc, s1, l1);
-    if (s0 != pstart || s1 != cstart || !std::equal(plist.begin(), plist.begin() + no, l0.begin()) ||
-        !std::equal(clist.begin(), clist.begin() + no, l1.begin()))
+    if (s0 != U.pstart || s1 != U.cstart || !std::equal(U.plist.begin(), U.plist.begin() + no, l0.begin()) ||
+        !std::equal(U.clist.begin(), U.clist.begin() + no, l1.begin()))
       return gh_set_error(ctx, GH_ERR_NUMERIC, "index lists built by the pool teams differ from the serial lists");
   }
-  t_csr = now_ms();
+  U.t_csr = now_ms();
+  return GH_OK;
+}
 
-  // deterministic Schur: pair list sorted by destination block (built once; structure is iteration-invariant).  Large
-  // graphs build it on the GPU (build_schur_pairs_device); GSLAM_HIP_BA_PAIRS=host keeps the host build, =check runs both
-  // and compares them element for element (tests).
-  const char* pairs_env = getenv("GSLAM_HIP_BA_PAIRS");
-  const bool want_pairs = opt.deterministic && no > 0;
-  pairs_check = want_pairs && pairs_env && pairs_env[0] == 'c';
-  device_pairs = want_pairs && (no >= 20000 || pairs_check) && !(pairs_env && pairs_env[0] == 'h');
-  size_t pairs_ub = 0, blocks_ub = 0;
-  if (device_pairs) {
-    for (int p = 0; p < np; ++p) pairs_ub += (size_t)(pstart[p + 1] - pstart[p]) * (size_t)(pstart[p + 1] - pstart[p]);
-    blocks_ub = std::min(pairs_ub, (size_t)nc * ((size_t)nc + 1) / 2);
-    // (a camera shares points only with the cameras at most `span` positions before it -- and with the border cameras: without
-    //  this bound the segment tables of a 2 M-point graph reserved 24 GB for 0.5 M blocks)
-    blocks_ub = std::min(blocks_ub, (size_t)nc * ((size_t)S.cam_span + 1) + (size_t)S.n_border * (size_t)nc);
-    if (pairs_ub > (size_t)1 << 30 || nc > kPairSortMaxCams) device_pairs = false;  // 32-bit offsets, LDS cursors
-  }
-  std::vector<int32_t> pbslot_host;  // point border: slot of every point (-1: an ordinary point, eliminated by the Schur complement)
-  if (n_bpts > 0) {
-    pbslot_host.assign((size_t)np, -1);
-    for (int b = 0; b < n_bpts; ++b) pbslot_host[S.border_pts[b]] = b;
-  }
-  if (want_pairs && (!device_pairs || pairs_check))
-    build_schur_pairs(pr, nc, pstart, plist, cstart, clist, pair_a, pair_b, bstart, bci, bcj, n_bpts > 0 ? pbslot_host.data() : nullptr);
-  nblocks = (int)bci.size();
-  t_lists = now_ms();
-
-  // the linear solver this session will use (the same rule again further down, where its buffers are carved): the arena is sized
-  // for the band solver's COMPACT columns + workspaces when that is the one, for the dense lower triangle otherwise
-  auto planned_tiles = [&]() {
-    int want = ctx->ba_solver;
-    if (const char* e = getenv("GSLAM_HIP_BA_SOLVER")) want = e[0] == 'd' ? 1 : (e[0] == 'b' ? 2 : 0);
-    return want == 1 ? 0 : gh_cr_tiles(n_band, 6 * S.cam_span + 5);
-  };
-  {
-    const size_t N = (size_t)n, NP = (size_t)np, NO = (size_t)no, NC = (size_t)nc;
-    const int T_plan = planned_tiles();
-    size_t s_doubles = N * (N + 1) + 64;
-    if (T_plan) {
-      const char* de = getenv("GSLAM_HIP_BA_DENSE_S");
-      if (!(de && de[0] == '1')) s_doubles = N * (size_t)gh_cr_compact_lda(n_band, T_plan, n - n_band, nullptr);
-      s_doubles += gh_cr_dinv_doubles(n_band, T_plan) + gh_cr_panel_doubles(n_band, T_plan) +
-                   gh_arrow_ws_doubles(ctx, n_band, T_plan, n - n_band) + gh_cr_border_symbolic_bytes(n_band, T_plan, n - n_band) / 8 + 4 * 64;
-    }
-    const size_t need = 8 * (2 * NC * 7 + 2 * NP * 3 + NO * 2 + (pr->obs_info ? NO * 4 : 0) + NC * 36 + N * 3 + NP * 9 * 2 +
-                             NP * 3 * 2 + s_doubles + (N + 64) * 64 * 3 + NO * 18 + (NO / 256 + 2) * 2 + 8) +
-                        4 * (NC + NO * 4 + NP + NC + 4 + pair_a.size() * 2 + bstart.size() * 3) + NP + 64 * 256 +
-                        (n_bpts > 0 ? 4 * (NP + (size_t)n_bpts) + 1024 : 0) +
-                        // device-built pair lists: 7 arrays of pairs_ub ints, block / segment tables, scan scratch
-                        4 * (pairs_ub * 7 + blocks_ub * 5 + pairs_ub / kSchurSeg + NO + NO / 1024 + blocks_ub / 1024 + 2 * NC + 128) +
-                        (device_pairs ? 26 * 256 : 0) +
-                        // chunk / segment tables and their partial sums (upper bounds)
-                        (NO / kCamChunk + NC + 2) * (27 * 8 + 2 * 4) + (NC + 2) * 4 +
-                        (std::max(pair_a.size(), pairs_ub) / kSchurSeg + std::max(bstart.size(), blocks_ub) + 2) * (42 * 8 + 4) +
-                        (bstart.size() + 2) * 4 + 16 * 256;
-    if (early && need > *db.arena_bytes) {  // the arena has to grow: what went up early goes up again
-      early = false;
-      db.used = 0;
-    }
-    GH_TRY(db.reserve(need));
-  }
-  if (!early) GH_TRY(raw_arrays(true));
+// Upload of the index lists, the chunk and segment tables and the pair tables; the device build of the pair lists is
+// enqueued behind them (its counts come back with the first cost: ba_adopt_pairs).
+gh_status ba_upload_tables(gh_ctx* ctx, BaSession& S, const BaSwitches& sw, int32_t* pair_counts_pinned, BaSetup& U) {
+  const int nc = S.nc, no = S.no, nblocks = S.nblocks;
+  DevBuf& db = *S.db;
   const double t_u0 = now_ms();
-  GH_TRY(db.upload(&d_pstart, (const int32_t*)pstart.data(), pstart.size()));
-  GH_TRY(db.upload(&d_plist, (const int32_t*)plist.data(), plist.size()));
-  GH_TRY(db.upload(&d_cstart, (const int32_t*)cstart.data(), cstart.size()));
-  GH_TRY(db.upload(&d_clist, (const int32_t*)clist.data(), clist.size()));
+  GH_TRY(db.upload(&S.d_pstart, (const int32_t*)U.pstart.data(), U.pstart.size()));
+  GH_TRY(db.upload(&S.d_plist, (const int32_t*)U.plist.data(), U.plist.size()));
+  GH_TRY(db.upload(&S.d_cstart, (const int32_t*)U.cstart.data(), U.cstart.size()));
+  GH_TRY(db.upload(&S.d_clist, (const int32_t*)U.clist.data(), U.clist.size()));
   const double t_u1 = now_ms();
   // camera chunks (lin_cams) and Schur segments: fixed-size work items, independent of how skewed the graph is
   std::vector<int32_t> ch_cam, ch_q0, ch_first((size_t)nc + 1, 0), seg_blk, seg_first((size_t)nblocks + 1, 0);
   for (int c = 0; c < nc; ++c) {
     ch_first[c] = (int32_t)ch_cam.size();
-    for (int q = cstart[c]; q < cstart[c + 1]; q += kCamChunk) {
+    for (int q = U.cstart[c]; q < U.cstart[c + 1]; q += kCamChunk) {
       ch_cam.push_back(c);
       ch_q0.push_back(q);
     }
@@ -1915,489 +1877,566 @@ gh_status ba_run(gh_ctx* ctx, BaSession& S, gh_ba_problem* pr, const gh_ba_optio
   ch_first[nc] = (int32_t)ch_cam.size();
   for (int b = 0; b < nblocks; ++b) {
     seg_first[b] = (int32_t)seg_blk.size();
-    for (int e = bstart[b]; e < bstart[b + 1]; e += kSchurSeg) seg_blk.push_back(b);
+    for (int e = U.bstart[b]; e < U.bstart[b + 1]; e += kSchurSeg) seg_blk.push_back(b);
   }
   seg_first[nblocks] = (int32_t)seg_blk.size();
-  nchunks = (int)ch_cam.size();
-  nsegs = (int)seg_blk.size();
-  CC = CamChunks{nullptr, nullptr, nullptr, nchunks};
-  {
-    int32_t *d_cc, *d_cq, *d_cf;
-    GH_TRY(db.upload(&d_cc, (const int32_t*)ch_cam.data(), ch_cam.size()));
-    GH_TRY(db.upload(&d_cq, (const int32_t*)ch_q0.data(), ch_q0.size()));
-    GH_TRY(db.upload(&d_cf, (const int32_t*)ch_first.data(), ch_first.size()));
-    CC = CamChunks{d_cc, d_cq, d_cf, nchunks};
-  }
+  S.nchunks = (int)ch_cam.size();
+  S.nsegs = (int)seg_blk.size();
+  int32_t *d_cc, *d_cq, *d_cf;
+  GH_TRY(db.upload(&d_cc, (const int32_t*)ch_cam.data(), ch_cam.size()));
+  GH_TRY(db.upload(&d_cq, (const int32_t*)ch_q0.data(), ch_q0.size()));
+  GH_TRY(db.upload(&d_cf, (const int32_t*)ch_first.data(), ch_first.size()));
+  S.CC = CamChunks{d_cc, d_cq, d_cf, S.nchunks};
   const double t_u2 = now_ms();
-  SB = SchurBlocks{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nblocks, nsegs};
-  SB_host = SB;  // (check mode: the host-built tables beside the device-built ones)
-  S.d_pbslot = S.d_bpts = nullptr;
-  if (n_bpts > 0) {
-    GH_TRY(db.upload(&S.d_pbslot, (const int32_t*)pbslot_host.data(), pbslot_host.size()));
+  S.SB = SchurBlocks{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nblocks, S.nsegs};
+  U.SB_host = S.SB;
+  if (S.n_bpts() > 0) {
+    GH_TRY(db.upload(&S.d_pbslot, (const int32_t*)U.pbslot.data(), U.pbslot.size()));
     GH_TRY(db.upload(&S.d_bpts, (const int32_t*)S.border_pts.data(), S.border_pts.size()));
   }
-  if (device_pairs) {
+  if (S.device_pairs) {
     const double tq0 = now_ms();
-    GH_TRY(build_schur_pairs_device(ctx, db, nc, no, pairs_ub, blocks_ub, d_ocam, d_opt, d_pstart, d_plist, d_cstart, d_clist,
-                                    &SB, rb->pair_counts, S.d_pbslot));
-    if (getenv("GSLAM_HIP_BA_TIMING")) {
+    GH_TRY(build_schur_pairs_device(ctx, db, nc, no, U.pairs_ub, U.blocks_ub, S.d_ocam, S.d_opt, S.d_pstart, S.d_plist, S.d_cstart,
+                                    S.d_clist, &S.SB, pair_counts_pinned, S.d_pbslot));
+    if (sw.timing) {
       const double tq1 = now_ms();
       GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
       fprintf(stderr, "[gh_ba] device pair lists: enqueue %.2f ms, then %.2f ms until the stream is idle (ub %zu pairs, %zu blocks)\n",
-              tq1 - tq0, now_ms() - tq1, pairs_ub, blocks_ub);
+              tq1 - tq0, now_ms() - tq1, U.pairs_ub, U.blocks_ub);
     }
   }
-  if (nblocks > 0 && (!device_pairs || pairs_check)) {
+  if (nblocks > 0 && (!S.device_pairs || U.pairs_check)) {
     int32_t *d_pa, *d_pb, *d_bs, *d_bci, *d_bcj, *d_sb, *d_sf;
     GH_TRY(db.upload(&d_sb, (const int32_t*)seg_blk.data(), seg_blk.size()));
     GH_TRY(db.upload(&d_sf, (const int32_t*)seg_first.data(), seg_first.size()));
-    GH_TRY(db.upload(&d_pa, (const int32_t*)pair_a.data(), pair_a.size()));
-    GH_TRY(db.upload(&d_pb, (const int32_t*)pair_b.data(), pair_b.size()));
-    GH_TRY(db.upload(&d_bs, (const int32_t*)bstart.data(), bstart.size()));
-    GH_TRY(db.upload(&d_bci, (const int32_t*)bci.data(), bci.size()));
-    GH_TRY(db.upload(&d_bcj, (const int32_t*)bcj.data(), bcj.size()));
-    SB_host = SchurBlocks{d_pa, d_pb, d_bs, d_bci, d_bcj, d_sb, d_sf, nblocks, nsegs};
-    if (!device_pairs) SB = SB_host;
+    GH_TRY(db.upload(&d_pa, (const int32_t*)U.pair_a.data(), U.pair_a.size()));
+    GH_TRY(db.upload(&d_pb, (const int32_t*)U.pair_b.data(), U.pair_b.size()));
+    GH_TRY(db.upload(&d_bs, (const int32_t*)U.bstart.data(), U.bstart.size()));
+    GH_TRY(db.upload(&d_bci, (const int32_t*)U.bci.data(), U.bci.size()));
+    GH_TRY(db.upload(&d_bcj, (const int32_t*)U.bcj.data(), U.bcj.size()));
+    U.SB_host = SchurBlocks{d_pa, d_pb, d_bs, d_bci, d_bcj, d_sb, d_sf, nblocks, S.nsegs};
+    if (!S.device_pairs) S.SB = U.SB_host;
   }
-  const double t_u3 = now_ms();
-  if (getenv("GSLAM_HIP_BA_TIMING"))
-    fprintf(stderr, "[gh_ba] upload phase: reserve %.2f, index lists up %.2f, chunk tables %.2f, pair lists %.2f ms\n", t_u0 - t_lists,
-            t_u1 - t_u0, t_u2 - t_u1, t_u3 - t_u2);
-  GH_TRY(db.alloc(&d_Hcc, (size_t)nc * 36));
-  GH_TRY(db.alloc(&d_gc, (size_t)n));
-  GH_TRY(db.alloc(&d_Hpp, (size_t)np * 9));
-  GH_TRY(db.alloc(&d_gp, (size_t)np * 3));
-  GH_TRY(db.alloc(&d_Hpi, (size_t)np * 9));
-  GH_TRY(db.alloc(&d_dc, (size_t)n));
-  GH_TRY(db.alloc(&d_dp, (size_t)np * 3));
-  GH_TRY(db.alloc(&d_work, (size_t)n));
-  GH_TRY(db.alloc(&d_dinv, (size_t)gh_div_up(n, 64) * 4096));
-  GH_TRY(db.alloc(&d_W, (size_t)no * 18));
-  GH_TRY(db.alloc(&d_xwork, (size_t)2 * 64 * (n + 1)));
-  GH_TRY(db.alloc(&d_xh, (size_t)gh_div_up(n, 64) * 64));
-  d_flow = nullptr;  // state of the single-launch factorisation (null when the shape does not fit it)
-  if (const size_t words = gh_potrf_flow_words(ctx, n, 1)) GH_TRY(db.alloc(&d_flow, words));
-  {
-    // The reduced camera system couples two cameras only if they see a common point: with every point seen from cameras
-    // at most `span` indices apart (a trajectory), S is a band of half-width 6 span + 5 and the band solver applies.
-    const int span = S.cam_span;  // (found with the argument check)
-    int want = ctx->ba_solver;
-    if (const char* e = getenv("GSLAM_HIP_BA_SOLVER")) want = e[0] == 'd' ? 1 : (e[0] == 'b' ? 2 : 0);
-    (void)want;
-    cr_T = planned_tiles();
-    if (n_bpts > 0 && cr_T == 0)  // (ba_order.hip only proposes a point border to the band solver: the dense assembly has camera columns only)
-      return gh_set_error(ctx, GH_ERR_ARG, "gh_ba_solve: a point border without the band solver (internal)");
-    d_cr_dinv = d_cr_W = S.d_arrow_ws = nullptr;
-    S.map = CrMap{};
-    if (cr_T) {
-      // COMPACT columns: the band rows, one slot per reduction level for the fill, the border rows, the right-hand side --
-      // 0.93 GB at C5 where the dense lower triangle takes 28.8 GB (GSLAM_HIP_BA_DENSE_S=1: the dense layout of rounds 4-5, A/B)
-      const char* de = getenv("GSLAM_HIP_BA_DENSE_S");
-      if (!(de && de[0] == '1')) {
-        int brow = 0;
-        lda = gh_cr_compact_lda(n_band, cr_T, n - n_band, &brow);
-        S.map.m = 64 * cr_T;
-        S.map.n_band = n_band;
-        S.map.brow = brow;
-        S.map.levels = brow / (64 * cr_T) - 2;
+  if (sw.timing)
+    fprintf(stderr, "[gh_ba] upload phase: reserve %.2f, index lists up %.2f, chunk tables %.2f, pair lists %.2f ms\n", t_u0 - U.t_lists,
+            t_u1 - t_u0, t_u2 - t_u1, now_ms() - t_u2);
+  return GH_OK;
+}
+
+// The work buffers of the iterations.  In their middle: the linear solver and the layout of S this session will use
+// (BaSwitches::band_tiles, as ba_arena_need planned), S itself, the band solver's workspaces and the border's symbolic structure.
+gh_status ba_alloc_work(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, const BaSwitches& sw) {
+  const int nc = S.nc, np = S.np, no = S.no, n = S.n(), n_band = S.n_band();
+  DevBuf& db = *S.db;
+  GH_TRY(db.alloc(&S.d_Hcc, (size_t)nc * 36));
+  GH_TRY(db.alloc(&S.d_gc, (size_t)n));
+  GH_TRY(db.alloc(&S.lin[0].Hpp, (size_t)np * 9));
+  GH_TRY(db.alloc(&S.lin[0].gp, (size_t)np * 3));
+  GH_TRY(db.alloc(&S.d_Hpi, (size_t)np * 9));
+  GH_TRY(db.alloc(&S.d_dc, (size_t)n));
+  GH_TRY(db.alloc(&S.d_dp, (size_t)np * 3));
+  GH_TRY(db.alloc(&S.d_work, (size_t)n));
+  GH_TRY(db.alloc(&S.d_dinv, (size_t)gh_div_up(n, 64) * 4096));
+  GH_TRY(db.alloc(&S.lin[0].W, (size_t)no * 18));
+  GH_TRY(db.alloc(&S.d_xwork, (size_t)2 * 64 * (n + 1)));
+  GH_TRY(db.alloc(&S.d_xh, (size_t)gh_div_up(n, 64) * 64));
+  if (const size_t words = gh_potrf_flow_words(ctx, n, 1)) GH_TRY(db.alloc(&S.d_flow, words));
+  S.cr_T = sw.band_tiles(n_band, S.cam_span);
+  if (S.n_bpts() > 0 && S.cr_T == 0)  // (ba_order.hip only proposes a point border to the band solver: the dense assembly has camera columns only)
+    return gh_set_error(ctx, GH_ERR_ARG, "gh_ba_solve: a point border without the band solver (internal)");
+  // one extra row carries the right-hand side through the factorisation; columns start on 128-byte lines
+  // (dense: n + 1 rows per column; band / arrowhead solver: compact columns -- cr_map.h)
+  S.lda = (n + 1 + 15) & ~15;
+  if (S.cr_T && !sw.dense_s) {
+    // COMPACT columns: the band rows, one slot per reduction level for the fill, the border rows, the right-hand side --
+    // 0.93 GB at C5 where the dense lower triangle takes 28.8 GB (GSLAM_HIP_BA_DENSE_S=1: the dense layout of rounds 4-5, A/B)
+    int brow = 0;
+    S.lda = gh_cr_compact_lda(n_band, S.cr_T, n - n_band, &brow);
+    S.map.m = 64 * S.cr_T;
+    S.map.n_band = n_band;
+    S.map.brow = brow;
+    S.map.levels = brow / (64 * S.cr_T) - 2;
+  }
+  GH_TRY(db.alloc(&S.d_S, (size_t)n * S.lda));
+  if (S.cr_T) {
+    GH_TRY(db.alloc(&S.d_cr_dinv, gh_cr_dinv_doubles(n_band, S.cr_T)));
+    GH_TRY(db.alloc(&S.d_cr_W, gh_cr_panel_doubles(n_band, S.cr_T)));
+    // (band-only systems too: the reduction's last levels go to the dense path -- chol_cr.hip, DENSE TOP)
+    GH_TRY(db.alloc(&S.d_arrow_ws, gh_arrow_ws_doubles(ctx, n_band, S.cr_T, n - n_band)));
+    if (n_band < n && !S.border_cam_nz.empty()) {
+      // per (superblock, strip), through the levels of the reduction: the border kernels skip what stays zero
+      const int m = 64 * S.cr_T, N = gh_div_up(n_band, m), nbs = gh_div_up(n - n_band, 16), ncb = nc - S.n_border;
+      std::vector<uint8_t> init((size_t)N * nbs, 0), sym(gh_cr_border_symbolic_bytes(n_band, S.cr_T, n - n_band));
+      for (int t = 0; t < nbs; ++t)
+        for (int c = 0; c < ncb; ++c)
+          if (S.border_cam_nz[(size_t)t * ncb + c]) {
+            init[(size_t)((6 * c) / m) * nbs + t] = 1;
+            init[(size_t)((6 * c + 5) / m) * nbs + t] = 1;
+          }
+      gh_cr_border_symbolic(n_band, S.cr_T, n - n_band, init.data(), sym.data());
+      GH_TRY(db.alloc(&S.d_border_nz, sym.size()));
+      GH_HIP(ctx, hipMemcpy(S.d_border_nz, sym.data(), sym.size(), hipMemcpyHostToDevice));
+      if (opt.verbose) {
+        size_t nzc = 0;
+        for (size_t e = 0; e < (size_t)N * nbs; ++e) nzc += sym[e] != 0;
+        fprintf(stderr, "[gh_ba] border structure: %zu of %zu (superblock, 16-row strip) blocks can be non-zero when eliminated\n", nzc, (size_t)N * nbs);
       }
     }
-    S.lda = lda;
-    GH_TRY(db.alloc(&d_S, (size_t)n * lda));
-    if (cr_T) {
-      GH_TRY(db.alloc(&d_cr_dinv, gh_cr_dinv_doubles(n_band, cr_T)));
-      GH_TRY(db.alloc(&d_cr_W, gh_cr_panel_doubles(n_band, cr_T)));
-      // (band-only systems too: the reduction's last levels go to the dense path -- chol_cr.hip, DENSE TOP)
-      GH_TRY(db.alloc(&S.d_arrow_ws, gh_arrow_ws_doubles(ctx, n_band, cr_T, n - n_band)));
-      S.d_border_nz = nullptr;
-      if (n_band < n && !S.border_cam_nz.empty()) {
-        // per (superblock, strip), through the levels of the reduction: the border kernels skip what stays zero
-        const int m = 64 * cr_T, N = gh_div_up(n_band, m), nbs = gh_div_up(n - n_band, 16), ncb = nc - S.n_border;
-        std::vector<uint8_t> init((size_t)N * nbs, 0), sym(gh_cr_border_symbolic_bytes(n_band, cr_T, n - n_band));
-        for (int t = 0; t < nbs; ++t)
-          for (int c = 0; c < ncb; ++c)
-            if (S.border_cam_nz[(size_t)t * ncb + c]) {
-              init[(size_t)((6 * c) / m) * nbs + t] = 1;
-              init[(size_t)((6 * c + 5) / m) * nbs + t] = 1;
-            }
-        gh_cr_border_symbolic(n_band, cr_T, n - n_band, init.data(), sym.data());
-        GH_TRY(db.alloc(&S.d_border_nz, sym.size()));
-        GH_HIP(ctx, hipMemcpy(S.d_border_nz, sym.data(), sym.size(), hipMemcpyHostToDevice));
-        if (opt.verbose) {
-          size_t nzc = 0;
-          for (size_t e = 0; e < (size_t)N * nbs; ++e) nzc += sym[e] != 0;
-          fprintf(stderr, "[gh_ba] border structure: %zu of %zu (superblock, 16-row strip) blocks can be non-zero when eliminated\n", nzc, (size_t)N * nbs);
-        }
-      }
-    }
-    if (opt.verbose)
-      fprintf(stderr, "[gh_ba] band cameras of a point at most %d indices apart, %d border cameras: half-bandwidth %d of n = %d -> %s\n",
-              span, S.n_border, 6 * span + 5, n_band,
-              cr_T ? (n_band < n ? "arrowhead solver (block cyclic reduction + dense border)" : "band solver (block cyclic reduction)")
-                   : "dense factorisation");
-  }
-  GH_TRY(db.alloc(&d_cpart, (size_t)nchunks * 27));
-  GH_TRY(db.alloc(&d_cpart2, (size_t)nchunks * 27));
-  GH_TRY(db.alloc(&d_W2, (size_t)no * 18));
-  GH_TRY(db.alloc(&d_Hpp2, (size_t)np * 9));
-  GH_TRY(db.alloc(&d_gp2, (size_t)np * 3));
-  GH_TRY(db.alloc(&S.d_keep, 2));
-  d_spart = nullptr;
-  if (!device_pairs) GH_TRY(db.alloc(&d_spart, (size_t)nsegs * 42));
-  GH_TRY(db.alloc(&d_partial, (size_t)eval_blocks * 2));
-  GH_TRY(db.alloc(&d_out, 4));
-  GH_TRY(db.alloc(&d_gmax, 1));
-  GH_TRY(db.alloc(&d_bad, 1));
-  GH_TRY(db.alloc(&d_info, 1));
-  S.nc = nc;
-  S.np = np;
-  S.no = no;
-  S.deterministic = opt.deterministic;
-  S.has_info = pr->obs_info != nullptr;
-  S.has_pfree = pr->point_free != nullptr;
-  } else if (pr) {  // ============================================================== resident graph: new values only
-    auto up = [&](void* dst, const void* src, size_t bytes) -> gh_status {
-      if (bytes) GH_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-      return GH_OK;
-    };
-    GH_TRY(up(d_poses, pr->cam_pose, (size_t)nc * 7 * 8));
-    GH_TRY(up(d_pts, pr->point_xyz, (size_t)np * 3 * 8));
-    GH_TRY(up(d_dof, pr->cam_dof, (size_t)nc * 4));
-    if (pr->point_free) GH_TRY(up(d_pfree, pr->point_free, (size_t)np));
-    GH_TRY(up(d_oxy, pr->obs_xy, (size_t)no * 16));
-    if (pr->obs_info) GH_TRY(up(d_oinfo, pr->obs_info, (size_t)no * 32));
-  }
-
-  Problem P{nc, np, no, d_poses, d_dof, d_pts, d_pfree, d_ocam, d_opt, d_oxy, d_oinfo,
-            d_pstart, d_plist, d_cstart, d_clist, opt.huber_delta};
-  PointBorder PB;
-  PB.n_pts = n_bpts;
-  PB.pts = S.d_bpts;
-  PB.slot = S.d_pbslot;
-  PB.Hpp = d_Hpp;
-  PB.gp = d_gp;
-
-  auto eval_cost = [&](const double* poses_eval, const double* pts_eval, int with_model) -> gh_status {
-    GH_LAUNCH(ctx, "ba_eval", eval_kernel, dim3(eval_blocks), dim3(256), 0, P, poses_eval, pts_eval, d_dc, d_dp,
-              with_model, d_partial);
-    GH_LAUNCH(ctx, "ba_reduce", reduce_final_kernel, dim3(1), dim3(256), 0, d_partial, eval_blocks, d_out);
-    GH_HIP(ctx, hipMemcpyAsync(&rb->cost, d_out, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GH_OK;
-  };
-
-  GH_HIP(ctx, hipMemsetAsync(d_gmax, 0, sizeof(unsigned long long), ctx->stream));
-  GH_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
-  double h2[2];
-  const double t_upload = now_ms();
-  GH_TRY(eval_cost(d_poses, d_pts, 0));
-  h2[0] = rb->cost;
-  h2[1] = rb->model;
-  if (device_pairs && !S.ready) {  // the lists were built behind the uploads; their sizes came back with the first cost
-    {
-      if (pairs_check) {
-        auto same = [&](const int32_t* dev, const std::vector<int32_t>& host, size_t count, const char* what) -> gh_status {
-          std::vector<int32_t> got(count);
-          GH_HIP(ctx, hipMemcpy(got.data(), dev, count * sizeof(int32_t), hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < count; ++i)
-            if (got[i] != host[i])
-              return gh_set_error(ctx, GH_ERR_NUMERIC, "device-built %s differs from the host list at %zu: %d vs %d", what, i,
-                                  got[i], host[i]);
-          return GH_OK;
-        };
-        if (rb->pair_counts[0] != (int)pair_a.size() || rb->pair_counts[1] != (int)bci.size() || rb->pair_counts[2] != nsegs)
-          return gh_set_error(ctx, GH_ERR_NUMERIC, "device-built pair lists: %d pairs / %d blocks / %d segments, host %zu / %zu / %d",
-                              rb->pair_counts[0], rb->pair_counts[1], rb->pair_counts[2], pair_a.size(), bci.size(), nsegs);
-        GH_TRY(same(SB.pair_a, pair_a, pair_a.size(), "pair_a"));
-        GH_TRY(same(SB.pair_b, pair_b, pair_b.size(), "pair_b"));
-        GH_TRY(same(SB.bstart, bstart, bstart.size(), "bstart"));
-        GH_TRY(same(SB.bci, bci, bci.size(), "bci"));
-        GH_TRY(same(SB.bcj, bcj, bcj.size(), "bcj"));
-        std::vector<int32_t> sf((size_t)nblocks + 1), sb((size_t)nsegs);
-        GH_HIP(ctx, hipMemcpy(sf.data(), SB_host.seg_first, sf.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GH_HIP(ctx, hipMemcpy(sb.data(), SB_host.seg_blk, sb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GH_TRY(same(SB.seg_first, sf, sf.size(), "seg_first"));
-        GH_TRY(same(SB.seg_blk, sb, sb.size(), "seg_blk"));
-      }
-      nblocks = rb->pair_counts[1];
-      nsegs = rb->pair_counts[2];
-      SB.nblocks = nblocks;
-      SB.nsegs = nsegs;
-    }
-    GH_TRY(db.alloc(&d_spart, (size_t)nsegs * 42));
-    S.n_pairs = (size_t)rb->pair_counts[0];
-  } else if (!S.ready) {
-    S.n_pairs = pair_a.size();
   }
   if (opt.verbose)
-    fprintf(stderr, "[gh_ba] %s: index lists %.2f ms (csr %.2f; %zu Schur pairs, %d blocks), upload %.2f ms, first cost %.2f ms\n",
-            S.ready ? "resident graph" : "setup", t_lists - t_begin, t_csr - t_begin, S.n_pairs, nblocks, t_upload - t_lists,
-            now_ms() - t_upload);
-  S.ready = true;
-  ctx->ba_last_solver = cr_T ? (n_band < n ? 3 : 2) : 1;
-  ctx->ba_last_band_tiles = cr_T;
-  ctx->ba_last_cam_span = S.cam_span;
-  ctx->ba_last_border_cams = S.n_border;
-  ctx->ba_last_border_points = n_bpts;
-  ctx->ba_last_reordered = S.reordered;
-  double cost = h2[0];
-  sum->initial_cost = cost;
-  double radius = opt.initial_radius, decrease = 2.0;
-  bool need_lin = true;
-  bool cr_flow_ok = true;  // band / arrowhead solver: the dense top may use the single-launch kernels (until one of their waits expires)
-  int term = 0, it = 0;
+    fprintf(stderr, "[gh_ba] band cameras of a point at most %d indices apart, %d border cameras: half-bandwidth %d of n = %d -> %s\n",
+            S.cam_span, S.n_border, 6 * S.cam_span + 5, n_band,
+            S.cr_T ? (n_band < n ? "arrowhead solver (block cyclic reduction + dense border)" : "band solver (block cyclic reduction)")
+                   : "dense factorisation");
+  GH_TRY(db.alloc(&S.lin[0].cpart, (size_t)S.nchunks * 27));
+  GH_TRY(db.alloc(&S.lin[1].cpart, (size_t)S.nchunks * 27));
+  GH_TRY(db.alloc(&S.lin[1].W, (size_t)no * 18));
+  GH_TRY(db.alloc(&S.lin[1].Hpp, (size_t)np * 9));
+  GH_TRY(db.alloc(&S.lin[1].gp, (size_t)np * 3));
+  GH_TRY(db.alloc(&S.d_keep, 2));
+  // (device-built pair lists: d_spart is sized once their segment count is known -- ba_adopt_pairs)
+  if (!S.device_pairs) GH_TRY(db.alloc(&S.d_spart, (size_t)S.nsegs * 42));
+  GH_TRY(db.alloc(&S.d_partial, (size_t)gh_div_up(no > 0 ? no : 1, 256) * 2));
+  GH_TRY(db.alloc(&S.d_out, 4));
+  GH_TRY(db.alloc(&S.d_gmax, 1));
+  GH_TRY(db.alloc(&S.d_bad, 1));
+  GH_TRY(db.alloc(&S.d_info, 1));
+  return GH_OK;
+}
+
+// Set-up of a new session, everything that depends on the topology only: index lists, pair lists (planned, and built when
+// the host builds them), the arena, uploads, work buffers.
+gh_status ba_setup(gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr, const gh_ba_options& opt, const BaSwitches& sw,
+                   int32_t* pair_counts_pinned, BaSetup& U) {
+  DevBuf& db = *S.db;
+  const size_t nc = (size_t)S.nc, np = (size_t)S.np, no = (size_t)S.no;
+  // the caller's arrays as the early upload stages them: an arena of an earlier solve that holds them can take them now
+  const size_t raw_bytes = 8 * (nc * 7 * 2 + np * 3 * 2 + no * 2 + (S.has_info ? no * 4 : 0)) + 4 * (nc + 2 * no) + np + 16 * 256;
+  U.early = *db.arena != nullptr && raw_bytes <= *db.arena_bytes && sw.early_upload;
+  if (U.early) {
+    void* pinned = nullptr;
+    GH_TRY(gh_pinned(ctx, raw_bytes, &pinned));
+    U.stage = (char*)pinned;
+  }
+  GH_TRY(ba_index_lists(ctx, S, pr, sw, U));
+  // Deterministic Schur: pair list sorted by destination block (built once; structure is iteration-invariant).  Large graphs
+  // build it on the GPU (build_schur_pairs_device, enqueued by ba_upload_tables); GSLAM_HIP_BA_PAIRS=host keeps the host build,
+  // =check runs both and compares them element for element (tests).
+  const bool want_pairs = opt.deterministic && S.no > 0;
+  U.pairs_check = want_pairs && sw.pairs == 'c';
+  S.device_pairs = want_pairs && (S.no >= 20000 || U.pairs_check) && sw.pairs != 'h';
+  if (S.device_pairs) {
+    for (size_t p = 0; p < np; ++p) U.pairs_ub += (size_t)(U.pstart[p + 1] - U.pstart[p]) * (size_t)(U.pstart[p + 1] - U.pstart[p]);
+    U.blocks_ub = std::min(U.pairs_ub, nc * (nc + 1) / 2);
+    // (a camera shares points only with the cameras at most `span` positions before it -- and with the border cameras: without
+    //  this bound the segment tables of a 2 M-point graph reserved 24 GB for 0.5 M blocks)
+    U.blocks_ub = std::min(U.blocks_ub, nc * ((size_t)S.cam_span + 1) + (size_t)S.n_border * nc);
+    if (U.pairs_ub > (size_t)1 << 30 || S.nc > kPairSortMaxCams) S.device_pairs = false;  // 32-bit offsets, LDS cursors
+  }
+  if (S.n_bpts() > 0) {
+    U.pbslot.assign(np, -1);
+    for (int b = 0; b < S.n_bpts(); ++b) U.pbslot[S.border_pts[b]] = b;
+  }
+  if (want_pairs && (!S.device_pairs || U.pairs_check))
+    build_schur_pairs(pr, S.nc, U.pstart, U.plist, U.cstart, U.clist, U.pair_a, U.pair_b, U.bstart, U.bci, U.bcj,
+                      S.n_bpts() > 0 ? U.pbslot.data() : nullptr, sw.timing);
+  S.nblocks = (int)U.bci.size();
+  U.t_lists = now_ms();
+  const size_t need = ba_arena_need(ctx, S, sw, U);
+  if (U.early && need > *db.arena_bytes) {  // the arena has to grow: what went up early goes up again
+    U.early = false;
+    db.used = 0;
+  }
+  GH_TRY(db.reserve(need));
+  if (!U.early) GH_TRY(ba_raw_arrays(ctx, S, pr, U, true));
+  GH_TRY(ba_upload_tables(ctx, S, sw, pair_counts_pinned, U));
+  GH_TRY(ba_alloc_work(ctx, S, opt, sw));
+  S.deterministic = opt.deterministic;
+  return GH_OK;
+}
+
+// ---------------------------------------------------------------- the LM loop
+// State of the loop across iterations.
+struct LmLoop {
+  Problem P;
+  PointBorder PB;
+  HostVerdict* rb;  // cost, model, gmax_bits, info, bad, pair_counts[4] (device-built pair lists: pairs, blocks, segments), stamp
+  int eval_blocks;
   // Speculative linearisation: behind the candidate cost's read-back the stream goes on to linearise the CANDIDATE state
   // into the second buffer set while the host waits for that cost (an event, not the stream) and decides -- the ~30 us of
   // host turnaround per iteration are then GPU work the next iteration needs anyway if the step is accepted (most are; a
   // rejected step's speculation is dropped).  Same kernel, same inputs: the LM trace is bit-identical.
-  const bool speculate = [] { const char* e = getenv("GSLAM_HIP_BA_SPECULATE"); return !(e && e[0] == '0'); }() && (np > 0 || nchunks > 0);
+  bool speculate;
+  double cost = 0, radius = 0, decrease = 2.0;
+  bool need_lin = true;
   bool spec_ready = false;  // the second buffer set holds the linearisation of what is now the current state
+  bool cr_flow_ok = true;   // band / arrowhead solver: the dense top may use the single-launch kernels (until one of their waits expires; per solve)
   unsigned stamp = 0;
-  rb->stamp = 0;  // (nothing is in flight: the first cost above ended with a stream synchronisation)
+  int term = 0;
+};
+// One candidate step, from enqueueing to the host's verdict.
+struct LmStep {
+  bool fresh_lin = false, publish = false, spec_launched = false;
+  double t_solve0 = 0;
+  std::unique_lock<std::mutex> flow_lock;  // (one single-launch factorisation at a time per process, until the iteration's synchronisation: chol.hip)
+};
+
+gh_status ba_eval_cost(gh_ctx* ctx, BaSession& S, LmLoop& L, const double* poses_eval, const double* pts_eval, int with_model) {
+  GH_LAUNCH(ctx, "ba_eval", eval_kernel, dim3(L.eval_blocks), dim3(256), 0, L.P, poses_eval, pts_eval, S.d_dc, S.d_dp,
+            with_model, S.d_partial);
+  GH_LAUNCH(ctx, "ba_reduce", reduce_final_kernel, dim3(1), dim3(256), 0, S.d_partial, L.eval_blocks, S.d_out);
+  GH_HIP(ctx, hipMemcpyAsync(&L.rb->cost, S.d_out, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return GH_OK;
+}
+
+// The lists were built behind the uploads; their sizes came back with the first cost.  Check mode compares them with the
+// host-built ones element for element.
+gh_status ba_adopt_pairs(gh_ctx* ctx, BaSession& S, const HostVerdict* rb, const BaSetup& U) {
+  if (!S.device_pairs) {
+    S.n_pairs = U.pair_a.size();
+    return GH_OK;
+  }
+  if (U.pairs_check) {
+    auto same = [&](const int32_t* dev, const std::vector<int32_t>& host, size_t count, const char* what) -> gh_status {
+      std::vector<int32_t> got(count);
+      GH_HIP(ctx, hipMemcpy(got.data(), dev, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < count; ++i)
+        if (got[i] != host[i])
+          return gh_set_error(ctx, GH_ERR_NUMERIC, "device-built %s differs from the host list at %zu: %d vs %d", what, i,
+                              got[i], host[i]);
+      return GH_OK;
+    };
+    if (rb->pair_counts[0] != (int)U.pair_a.size() || rb->pair_counts[1] != (int)U.bci.size() || rb->pair_counts[2] != S.nsegs)
+      return gh_set_error(ctx, GH_ERR_NUMERIC, "device-built pair lists: %d pairs / %d blocks / %d segments, host %zu / %zu / %d",
+                          rb->pair_counts[0], rb->pair_counts[1], rb->pair_counts[2], U.pair_a.size(), U.bci.size(), S.nsegs);
+    GH_TRY(same(S.SB.pair_a, U.pair_a, U.pair_a.size(), "pair_a"));
+    GH_TRY(same(S.SB.pair_b, U.pair_b, U.pair_b.size(), "pair_b"));
+    GH_TRY(same(S.SB.bstart, U.bstart, U.bstart.size(), "bstart"));
+    GH_TRY(same(S.SB.bci, U.bci, U.bci.size(), "bci"));
+    GH_TRY(same(S.SB.bcj, U.bcj, U.bcj.size(), "bcj"));
+    std::vector<int32_t> sf((size_t)S.nblocks + 1), sb((size_t)S.nsegs);
+    GH_HIP(ctx, hipMemcpy(sf.data(), U.SB_host.seg_first, sf.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GH_HIP(ctx, hipMemcpy(sb.data(), U.SB_host.seg_blk, sb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GH_TRY(same(S.SB.seg_first, sf, sf.size(), "seg_first"));
+    GH_TRY(same(S.SB.seg_blk, sb, sb.size(), "seg_blk"));
+  }
+  S.nblocks = S.SB.nblocks = rb->pair_counts[1];
+  S.nsegs = S.SB.nsegs = rb->pair_counts[2];
+  GH_TRY(S.db->alloc(&S.d_spart, (size_t)S.nsegs * 42));
+  S.n_pairs = (size_t)rb->pair_counts[0];
+  return GH_OK;
+}
+
+// Enqueue one candidate step: linearisation (or the adopted speculation), damping, assembly of the reduced camera system,
+// factorisation and solve, back-substitution, the candidate's cost and -- when the verdict is published to pinned memory --
+// the speculative linearisation of the candidate.  Nothing here waits for the device.
+gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, LmLoop& L, int it, LmStep& step) {
+  const int nc = S.nc, np = S.np, no = S.no, n = S.n(), n_band = S.n_band(), lda = S.lda, cr_T = S.cr_T, n_bpts = S.n_bpts();
+  const double radius = L.radius;
+  if (L.need_lin) {  // (d_gmax and d_bad are zero here: cleared before the loop and by every backsub_update launch)
+    if (L.spec_ready) {
+      std::swap(S.lin[0], S.lin[1]);  // the speculation was of this state: adopt it
+    } else if (np > 0 || S.nchunks > 0) {
+      GH_LAUNCH(ctx, "ba_lin", lin_kernel, dim3(S.nchunks + gh_div_up(np, 256)), dim3(256), 0, L.P, S.CC, S.lin[0].cpart,
+                S.lin[0].W, S.lin[0].Hpp, S.lin[0].gp, S.d_gmax);
+    }
+    // (the camera-side reduction shares its launch with the point-side damping below)
+  }
+  L.spec_ready = false;
+  step.fresh_lin = L.need_lin;
+  L.need_lin = false;
+  step.publish = L.speculate && it + 1 < opt.max_iterations;  // this iteration's verdict goes to the host by reduce_publish_kernel
+  const LinSet& lin = S.lin[0];
+  if (step.fresh_lin) {
+    const int nrb = gh_div_up(nc, 8);
+    GH_LAUNCH(ctx, "ba_damp_points", lin_reduce_damp_kernel, dim3(nrb + gh_div_up(np, 256)), dim3(256), 0, nc, S.CC,
+              (const double*)lin.cpart, S.d_Hcc, S.d_gc, S.d_gmax, nrb, np, (const double*)lin.Hpp, radius, S.d_Hpi, S.d_bad);
+    // the gradient test is evaluated at the iteration's single synchronisation point; if it fires, the step
+    // computed meanwhile is simply dropped (same decisions as testing here, one host round trip less)
+    if (!step.publish)
+      GH_HIP(ctx, hipMemcpyAsync(&L.rb->gmax_bits, S.d_gmax, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  } else if (np > 0) {
+    GH_LAUNCH(ctx, "ba_damp_points", damp_points_kernel, dim3(gh_div_up(np, 256)), dim3(256), 0, np, lin.Hpp, radius, S.d_Hpi,
+              S.d_bad);
+  }
+  L.PB.Hpp = lin.Hpp;  // (the linearisation's buffer sets swap when a speculative linearisation is adopted)
+  L.PB.gp = lin.gp;
+  const bool slim_init = S.d_flow != nullptr || cr_T != 0;  // both solvers read the lower tiles only
+  const bool fused_seed = slim_init && no > 0 && opt.deterministic;  // then the seed rides with the segment sums below
+  const int gx = cr_T ? 1 : gh_div_up(n + 1, 2048);  // workgroups per column of the seed (the band solver's: one)
+  bool solve_state_ready = false;  // set when schur_reduce_kernel has cleared what the single-launch solve kernels need
+  if (slim_init) {
+    if (!fused_seed)
+      GH_LAUNCH(ctx, "ba_schur_diag", schur_init_kernel, dim3((unsigned)gx * (unsigned)n), dim3(256), 0, n, lda, S.d_Hcc, S.d_gc,
+                radius, S.d_S, S.d_dc, 64 * cr_T, n_band, gx, S.map, L.PB);
+  } else {
+    int pend = gh_prof_begin(ctx, "ba_schur_zero");
+    hipError_t me = hipMemsetAsync(S.d_S, 0, (size_t)n * lda * sizeof(double), ctx->stream);
+    gh_prof_end(ctx, pend);
+    GH_HIP(ctx, me);
+    GH_LAUNCH(ctx, "ba_schur_diag", schur_diag_kernel, dim3(nc), dim3(64), 0, nc, S.d_Hcc, S.d_gc, radius, S.d_S, lda, S.d_dc);
+  }
+  if (no > 0) {
+    if (opt.deterministic) {
+      const unsigned nsb = 8u * (unsigned)gh_div_up(S.nsegs, 32);
+      if (fused_seed) {
+        GH_LAUNCH(ctx, "ba_schur_blocks", schur_blocks_init_kernel, dim3(nsb + (unsigned)gx * (unsigned)n), dim3(256), 0, L.P,
+                  S.SB, S.d_Hpi, lin.gp, (const double*)lin.W, S.d_spart, nsb, n, lda, (const double*)S.d_Hcc,
+                  (const double*)S.d_gc, radius, S.d_S, S.d_dc, gx, 64 * cr_T, n_band, S.map, L.PB);
+      } else {
+        GH_LAUNCH(ctx, "ba_schur_blocks", schur_blocks_kernel, dim3(nsb), dim3(256), 0, L.P, S.SB, S.d_Hpi, lin.gp,
+                  (const double*)lin.W, S.d_spart);
+      }
+      const int nred = gh_div_up(S.nblocks, 4);
+      SolveState st{nullptr, 0u, nullptr, 0u, S.d_info};
+      if (S.d_flow) {
+        st.flow_flags = S.d_flow;
+        st.n_flow = (unsigned)gh_potrf_flow_flag_words(n, 1);
+      }
+      if (S.d_xh) {
+        st.xh_words = reinterpret_cast<unsigned*>(S.d_xh);
+        st.n_xh = (unsigned)gh_div_up(n, 64) * 64u * 2u;
+      }
+      const unsigned words = st.n_flow > st.n_xh ? st.n_flow : st.n_xh;
+      GH_LAUNCH(ctx, "ba_schur_reduce", schur_reduce_kernel, dim3(nred + gh_div_up((int)(words ? words : 1u), 256)),
+                dim3(256), 0, S.SB, (const double*)S.d_spart, S.d_S, lda, S.d_dc, n, nred, st, S.map);
+      solve_state_ready = true;
+    } else {
+      GH_LAUNCH(ctx, "ba_schur_atomic", schur_atomic_kernel, dim3(gh_div_up(no, 256)), dim3(256), 0, L.P, S.d_Hpi, lin.gp,
+                S.d_S, lda, S.d_dc, (const double*)lin.W, S.map, (const int32_t*)S.d_pbslot);
+    }
+  }
+  if (n_bpts > 0)  // E of the point border: W^T of the border points' observations into the border rows of their cameras' columns
+    GH_LAUNCH(ctx, "ba_border_points", border_points_kernel, dim3(n_bpts), dim3(64), 0, L.P, L.PB, (const double*)lin.W, S.d_S, lda,
+              n_band, S.map);
+  step.t_solve0 = now_ms();
+  if (S.d_flow || cr_T)  // (band / arrowhead: the dense top may run as the single-launch factorisation)
+    step.flow_lock = std::unique_lock<std::mutex>(gh_potrf_flow_mutex(ctx->device));
+  // The whole candidate step is enqueued without waiting for the factorisation flags (the kernels have no
+  // data-dependent control flow, so a failed factorisation only produces numbers that are then ignored): one host
+  // synchronisation per iteration instead of three.
+  // rhs -> row n of S: already there when schur_init_kernel + schur_reduce_kernel wrote it
+  if (!(slim_init && opt.deterministic))
+    GH_LAUNCH(ctx, "ba_rhs_row", rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, S.d_dc, S.d_S, lda, n, S.map);
+  if (cr_T) {  // (n_band == n: a band without a border)
+    GH_TRY(gh_arrow_solve_dev_impl(ctx, S.d_S, n_band, n - n_band, lda, cr_T, S.d_cr_dinv, S.d_cr_W, S.d_arrow_ws, S.d_dc, S.d_info,
+                                   solve_state_ready, L.cr_flow_ok, S.d_border_nz, S.map.m != 0));
+  } else {
+    GH_TRY(gh_potrf_dev_impl(ctx, S.d_S, n, lda, S.d_info, 1, S.d_dinv, S.d_xwork, S.d_flow, false, solve_state_ready));
+    // y = L^-1 b is row n of the factored matrix; the back-substitution reads it in place
+    GH_TRY(gh_potrs_bwd_dev_impl(ctx, S.d_S, n, lda, S.d_dc, S.d_work, S.d_dinv, S.d_S + n, lda, S.d_xh, S.d_info, solve_state_ready));
+  }
+  if (!step.publish) {
+    GH_HIP(ctx, hipMemcpyAsync(&L.rb->info, S.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GH_HIP(ctx, hipMemcpyAsync(&L.rb->bad, S.d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GH_LAUNCH(ctx, "ba_backsub", backsub_update_kernel, dim3(gh_div_up(nc > np ? nc : np, 256)), dim3(256), 0, L.P, S.d_Hpi, lin.gp,
+            S.d_dc, S.d_dp, (const double*)lin.W, S.d_poses_new, S.d_pts_new, S.d_bad, S.d_gmax, step.publish ? S.d_keep : nullptr,
+            (const int32_t*)S.d_pbslot, n_band);
+  if (step.publish) {
+    const unsigned want = ++L.stamp;
+    GH_LAUNCH(ctx, "ba_eval", eval_kernel, dim3(L.eval_blocks), dim3(256), 0, L.P, (const double*)S.d_poses_new,
+              (const double*)S.d_pts_new, S.d_dc, S.d_dp, 1, S.d_partial);
+    GH_LAUNCH(ctx, "ba_reduce", reduce_publish_kernel, dim3(1), dim3(256), 0, (const double*)S.d_partial, L.eval_blocks,
+              (const unsigned long long*)S.d_keep, (const int*)S.d_info, L.rb, want);
+    Problem Pn = L.P;
+    Pn.poses = S.d_poses_new;
+    Pn.pts = S.d_pts_new;
+    GH_LAUNCH(ctx, "ba_lin", lin_kernel, dim3(S.nchunks + gh_div_up(np, 256)), dim3(256), 0, Pn, S.CC, S.lin[1].cpart, S.lin[1].W,
+              S.lin[1].Hpp, S.lin[1].gp, S.d_gmax);  // (d_gmax was cleared by backsub_update above: exactly what a linearisation at the top would find)
+    step.spec_launched = true;
+  }
+  return GH_OK;
+}
+
+// The iteration's one synchronisation: the verdict's stamp in pinned memory (bounded: a fault in a kernel must not hang us).
+// Spin with `pause` for about 2 ms (a C4 iteration is 0.6 ms: the stamp is there within the spin and the host adds no
+// latency), then back off -- yield, and from 20 ms on sleep 50 us per poll: an iteration of a large dense problem (C5: 1 s)
+// no longer pins a host core at 100 % for its whole length.
+gh_status ba_wait_verdict(gh_ctx* ctx, const HostVerdict* rb, unsigned want) {
+  const double t_spin = now_ms();
+  unsigned spins = 0;
+  int phase = 0;  // 0 pause, 1 yield, 2 sleep
+  while (rb->stamp != want) {
+    if (phase == 0) {
+      __builtin_ia32_pause();
+      if ((++spins & 0x3FFu) == 0u && now_ms() - t_spin > 2.0) phase = 1;
+    } else {
+      const double waited = now_ms() - t_spin;
+      if (waited > 10000.0) break;
+      if (phase == 1) {
+        std::this_thread::yield();
+        if (waited > 20.0) phase = 2;
+      } else {
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+      }
+    }
+  }
+  if (rb->stamp != want) {
+    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rb->stamp != want) return gh_set_error(ctx, GH_ERR_HIP, "gh_ba_solve: the iteration's verdict never reached the host");
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return GH_OK;
+}
+
+// A bounded wait inside one of the single-launch kernels expired (chol.hip: the launch could not get all its workgroups resident,
+// e.g. another process holds part of the GPU): the iteration is repeated on the launch-per-step path, and the solve stays on it.
+// d_flow and d_xh are SESSION fields: a resident graph stays on that path for the rest of its life (cr_flow_ok is per solve).
+gh_status ba_leave_single_launch(gh_ctx* ctx, BaSession& S, LmLoop& L, const LmStep& step) {
+  S.d_flow = nullptr;
+  S.d_xh = nullptr;
+  L.cr_flow_ok = false;  // (band / arrowhead: the dense top stays off the single-launch kernels)
+  if (step.fresh_lin) L.need_lin = true;  // (cheap, and keeps the gradient read-back of this iteration in place)
+  if (step.spec_launched)  // the speculation wrote the gradient maximum the repeated linearisation accumulates into
+    GH_HIP(ctx, hipMemsetAsync(S.d_gmax, 0, sizeof(unsigned long long), ctx->stream));
+  return GH_OK;
+}
+
+// Accept or reject the candidate the verdict in L.rb speaks of, and update the trust region.  true: the solve has
+// terminated (L.term says why).
+bool ba_decide(BaSession& S, const gh_ba_options& opt, gh_ba_summary* sum, LmLoop& L, const LmStep& step, int it) {
+  const bool ok = L.rb->info == 0 && L.rb->bad == 0;
+  double new_cost = L.cost, model = 0, rho = -1;
+  if (ok) {
+    new_cost = L.rb->cost;
+    model = L.rb->model;
+    rho = model > 0 ? (L.cost - new_cost) / model : -1;
+    if (!(new_cost == new_cost)) rho = -1;  // NaN guard
+  }
+  const bool acc = ok && rho > opt.min_relative_decrease;
+  if (sum->trace_len < GH_BA_MAX_TRACE) {
+    sum->trace_cost[sum->trace_len] = new_cost;
+    sum->trace_radius[sum->trace_len] = L.radius;
+    sum->trace_accepted[sum->trace_len] = (uint8_t)acc;
+    sum->trace_len++;
+  }
+  if (opt.verbose)
+    fprintf(stderr, "[gh_ba] it %3d cost %.9e -> %.9e model %.3e rho %.3f radius %.3e %s\n", it, L.cost, new_cost, model, rho,
+            L.radius, acc ? "accepted" : (ok ? "rejected" : "solve failed"));
+  if (!acc) {
+    L.radius = L.radius / L.decrease;
+    L.decrease *= 2.0;
+    if (L.radius < 1e-32) L.term = 3;
+    return L.term == 3;
+  }
+  const double dcost = L.cost - new_cost;
+  std::swap(S.d_poses, S.d_poses_new);
+  std::swap(S.d_pts, S.d_pts_new);
+  L.P.poses = S.d_poses;
+  L.P.pts = S.d_pts;
+  const double t = 2.0 * rho - 1.0;
+  L.radius = L.radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
+  if (L.radius > 1e16) L.radius = 1e16;
+  L.decrease = 2.0;
+  sum->accepted++;
+  L.need_lin = true;
+  L.spec_ready = step.spec_launched;
+  const double prev = L.cost;
+  L.cost = new_cost;
+  if (fabs(dcost) <= opt.function_tolerance * prev) L.term = 1;
+  return L.term == 1;
+}
+
+// One solve of a session.  A new session (S.ready false) comes with its problem and is set up first; a resident one
+// (graph sessions only) comes with pr == nullptr and the values already on the device are solved as they are.
+// download: write the result back into pr->cam_pose / pr->point_xyz.
+gh_status ba_run(gh_ctx* ctx, BaSession& S, gh_ba_problem* pr, const BaSwitches& sw, const gh_ba_options* opt_in,
+                 gh_ba_summary* sum_out, bool download) {
+  gh_ba_options opt;
+  gh_ba_default_options(&opt);
+  if (opt_in) opt = *opt_in;
+  gh_ba_summary local_sum;
+  gh_ba_summary* sum = sum_out ? sum_out : &local_sum;
+  memset(sum, 0, sizeof(*sum));
+  GH_CHECK_ARG(ctx, (pr != nullptr) != S.ready);
+  if (pr) {
+    GH_TRY(ba_check_problem(ctx, S, pr));
+    ba_border_occupancy(S, pr, sw);
+  } else {  // a resident graph: same topology by construction
+    GH_CHECK_ARG(ctx, (opt.deterministic != 0) == (S.deterministic != 0));
+  }
+  GH_HIP(ctx, hipSetDevice(ctx->device));
+  BaSetup U;
+  U.t_begin = U.t_csr = U.t_lists = now_ms();
+  // Everything the host reads back during an iteration (gradient maximum, factorisation / damping flags, candidate cost
+  // and model decrease) lands in ONE pinned block of its own (nothing the staging below or a later gh_pinned does can
+  // move it): copies into pageable memory are staged and block the host in the middle of the launch chain.
+  void* pinned = nullptr;
+  GH_TRY(gh_readback_block(ctx, sizeof(HostVerdict), &pinned));
+  LmLoop L{};
+  L.rb = (HostVerdict*)pinned;
+  if (pr) GH_TRY(ba_setup(ctx, S, pr, opt, sw, L.rb->pair_counts, U));
+  const int nc = S.nc, np = S.np, no = S.no, n = S.n();
+  L.P = Problem{nc, np, no, S.d_poses, S.d_dof, S.d_pts, S.d_pfree, S.d_ocam, S.d_opt, S.d_oxy, S.d_oinfo,
+                S.d_pstart, S.d_plist, S.d_cstart, S.d_clist, opt.huber_delta};
+  L.PB = PointBorder{S.n_bpts(), S.d_bpts, S.d_pbslot, S.lin[0].Hpp, S.lin[0].gp};
+  L.eval_blocks = gh_div_up(no > 0 ? no : 1, 256);
+  GH_HIP(ctx, hipMemsetAsync(S.d_gmax, 0, sizeof(unsigned long long), ctx->stream));
+  GH_HIP(ctx, hipMemsetAsync(S.d_bad, 0, sizeof(int), ctx->stream));
+  const double t_upload = now_ms();
+  GH_TRY(ba_eval_cost(ctx, S, L, S.d_poses, S.d_pts, 0));
+  L.cost = sum->initial_cost = L.rb->cost;
+  if (pr) GH_TRY(ba_adopt_pairs(ctx, S, L.rb, U));
+  if (opt.verbose)
+    fprintf(stderr, "[gh_ba] %s: index lists %.2f ms (csr %.2f; %zu Schur pairs, %d blocks), upload %.2f ms, first cost %.2f ms\n",
+            S.ready ? "resident graph" : "setup", U.t_lists - U.t_begin, U.t_csr - U.t_begin, S.n_pairs, S.nblocks,
+            t_upload - U.t_lists, now_ms() - t_upload);
+  S.ready = true;
+  ctx->ba_last_solver = S.cr_T ? (S.n_band() < n ? 3 : 2) : 1;
+  ctx->ba_last_band_tiles = S.cr_T;
+  ctx->ba_last_cam_span = S.cam_span;
+  ctx->ba_last_border_cams = S.n_border;
+  ctx->ba_last_border_points = S.n_bpts();
+  ctx->ba_last_reordered = S.reordered;
+  L.radius = opt.initial_radius;
+  L.speculate = sw.speculate && (np > 0 || S.nchunks > 0);
+  L.rb->stamp = 0;  // (nothing is in flight: the first cost above ended with a stream synchronisation)
+  int it = 0;
   const double t_loop = now_ms();
   for (it = 0; it < opt.max_iterations; ++it) {
-    if (need_lin) {  // (d_gmax and d_bad are zero here: cleared before the loop and by every backsub_update launch)
-      if (spec_ready) {
-        std::swap(d_W, d_W2);
-        std::swap(d_Hpp, d_Hpp2);
-        std::swap(d_gp, d_gp2);
-        std::swap(d_cpart, d_cpart2);
-      } else if (np > 0 || nchunks > 0) {
-        GH_LAUNCH(ctx, "ba_lin", lin_kernel, dim3(nchunks + gh_div_up(np, 256)), dim3(256), 0, P, CC, d_cpart, d_W, d_Hpp, d_gp,
-                  d_gmax);
-      }
-      // (the camera-side reduction shares its launch with the point-side damping below)
-    }
-    spec_ready = false;
-    const bool fresh_lin = need_lin;
-    need_lin = false;
-    const bool publish = speculate && it + 1 < opt.max_iterations;  // this iteration's verdict goes to the host by reduce_publish_kernel
-    if (fresh_lin) {
-      const int nrb = gh_div_up(nc, 8);
-      GH_LAUNCH(ctx, "ba_damp_points", lin_reduce_damp_kernel, dim3(nrb + gh_div_up(np, 256)), dim3(256), 0, nc, CC,
-                (const double*)d_cpart, d_Hcc, d_gc, d_gmax, nrb, np, (const double*)d_Hpp, radius, d_Hpi, d_bad);
-      // the gradient test is evaluated at the iteration's single synchronisation point below; if it fires, the step
-      // computed meanwhile is simply dropped (same decisions as testing here, one host round trip less)
-      if (!publish) GH_HIP(ctx, hipMemcpyAsync(&rb->gmax_bits, d_gmax, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    } else if (np > 0) {
-      GH_LAUNCH(ctx, "ba_damp_points", damp_points_kernel, dim3(gh_div_up(np, 256)), dim3(256), 0, np, d_Hpp, radius,
-                d_Hpi, d_bad);
-    }
-    PB.Hpp = d_Hpp;  // (the linearisation's buffer sets swap when a speculative linearisation is adopted)
-    PB.gp = d_gp;
-    const bool slim_init = d_flow != nullptr || cr_T != 0;  // both solvers read the lower tiles only
-    const bool fused_seed = slim_init && no > 0 && opt.deterministic;  // then the seed rides with the segment sums below
-    bool solve_state_ready = false;  // set when schur_reduce_kernel has cleared what the single-launch solve kernels need
-    if (slim_init) {
-      if (!fused_seed)
-      {
-        const int gx = cr_T ? 1 : gh_div_up(n + 1, 2048);
-        GH_LAUNCH(ctx, "ba_schur_diag", schur_init_kernel, dim3((unsigned)gx * (unsigned)n), dim3(256), 0, n, lda, d_Hcc,
-                  d_gc, radius, d_S, d_dc, 64 * cr_T, n_band, gx, S.map, PB);
-      }
-    } else {
-      int pend = gh_prof_begin(ctx, "ba_schur_zero");
-      hipError_t me = hipMemsetAsync(d_S, 0, (size_t)n * lda * sizeof(double), ctx->stream);
-      gh_prof_end(ctx, pend);
-      GH_HIP(ctx, me);
-      GH_LAUNCH(ctx, "ba_schur_diag", schur_diag_kernel, dim3(nc), dim3(64), 0, nc, d_Hcc, d_gc, radius, d_S, lda, d_dc);
-    }
-    if (no > 0) {
-      if (opt.deterministic) {
-        const unsigned nsb = 8u * (unsigned)gh_div_up(nsegs, 32);
-        if (fused_seed) {
-          const int gx = cr_T ? 1 : gh_div_up(n + 1, 2048);  // (the band solver's seed: one workgroup per column)
-          GH_LAUNCH(ctx, "ba_schur_blocks", schur_blocks_init_kernel, dim3(nsb + (unsigned)gx * (unsigned)n), dim3(256), 0, P,
-                    SB, d_Hpi, d_gp, (const double*)d_W, d_spart, nsb, n, lda, (const double*)d_Hcc, (const double*)d_gc,
-                    radius, d_S, d_dc, gx, 64 * cr_T, n_band, S.map, PB);
-        } else {
-          GH_LAUNCH(ctx, "ba_schur_blocks", schur_blocks_kernel, dim3(nsb), dim3(256), 0, P, SB, d_Hpi, d_gp,
-                    (const double*)d_W, d_spart);
-        }
-        {
-          const int nred = gh_div_up(nblocks, 4);
-          SolveState st{nullptr, 0u, nullptr, 0u, d_info};
-          if (d_flow) {
-            st.flow_flags = d_flow;
-            st.n_flow = (unsigned)gh_potrf_flow_flag_words(n, 1);
-          }
-          if (d_xh) {
-            st.xh_words = reinterpret_cast<unsigned*>(d_xh);
-            st.n_xh = (unsigned)gh_div_up(n, 64) * 64u * 2u;
-          }
-          const unsigned words = st.n_flow > st.n_xh ? st.n_flow : st.n_xh;
-          GH_LAUNCH(ctx, "ba_schur_reduce", schur_reduce_kernel, dim3(nred + gh_div_up((int)(words ? words : 1u), 256)),
-                    dim3(256), 0, SB, (const double*)d_spart, d_S, lda, d_dc, n, nred, st, S.map);
-          solve_state_ready = true;
-        }
-      } else {
-        GH_LAUNCH(ctx, "ba_schur_atomic", schur_atomic_kernel, dim3(gh_div_up(no, 256)), dim3(256), 0, P, d_Hpi, d_gp,
-                  d_S, lda, d_dc, (const double*)d_W, S.map, (const int32_t*)S.d_pbslot);
-      }
-    }
-    if (n_bpts > 0)  // E of the point border: W^T of the border points' observations into the border rows of their cameras' columns
-      GH_LAUNCH(ctx, "ba_border_points", border_points_kernel, dim3(n_bpts), dim3(64), 0, P, PB, (const double*)d_W, d_S, lda, n_band,
-                S.map);
-    const double t_solve0 = now_ms();
-    // (one single-launch factorisation at a time per process, until this iteration's synchronisation: see chol.hip)
-    std::unique_lock<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device), std::defer_lock);
-    if (d_flow || cr_T) flow_lock.lock();  // (band / arrowhead: the dense top may run as the single-launch factorisation)
-    // The whole candidate step is enqueued without waiting for the factorisation flags (the kernels have no
-    // data-dependent control flow, so a failed factorisation only produces numbers that are then ignored): one host
-    // synchronisation per iteration instead of three.
-    // rhs -> row n of S: already there when schur_init_kernel + schur_reduce_kernel wrote it
-    if (!(slim_init && opt.deterministic))
-      GH_LAUNCH(ctx, "ba_rhs_row", rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, d_dc, d_S, lda, n, S.map);
-    if (cr_T) {  // (n_band == n: a band without a border)
-      GH_TRY(gh_arrow_solve_dev_impl(ctx, d_S, n_band, n - n_band, lda, cr_T, d_cr_dinv, d_cr_W, S.d_arrow_ws, d_dc, d_info,
-                                     solve_state_ready, cr_flow_ok, S.d_border_nz, S.map.m != 0));
-    } else {
-    GH_TRY(gh_potrf_dev_impl(ctx, d_S, n, lda, d_info, 1, d_dinv, d_xwork, d_flow, false, solve_state_ready));
-    // y = L^-1 b is row n of the factored matrix; the back-substitution reads it in place
-    GH_TRY(gh_potrs_bwd_dev_impl(ctx, d_S, n, lda, d_dc, d_work, d_dinv, d_S + n, lda, d_xh, d_info, solve_state_ready));
-    }
-    if (!publish) {
-      GH_HIP(ctx, hipMemcpyAsync(&rb->info, d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-      GH_HIP(ctx, hipMemcpyAsync(&rb->bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    GH_LAUNCH(ctx, "ba_backsub", backsub_update_kernel, dim3(gh_div_up(nc > np ? nc : np, 256)), dim3(256), 0, P, d_Hpi,
-              d_gp, d_dc, d_dp, (const double*)d_W, d_poses_new, d_pts_new, d_bad, d_gmax, publish ? S.d_keep : nullptr,
-              (const int32_t*)S.d_pbslot, n_band);
-    bool spec_launched = false;
-    if (publish) {
-      const unsigned want = ++stamp;
-      GH_LAUNCH(ctx, "ba_eval", eval_kernel, dim3(eval_blocks), dim3(256), 0, P, (const double*)d_poses_new,
-                (const double*)d_pts_new, d_dc, d_dp, 1, d_partial);
-      GH_LAUNCH(ctx, "ba_reduce", reduce_publish_kernel, dim3(1), dim3(256), 0, (const double*)d_partial, eval_blocks,
-                (const unsigned long long*)S.d_keep, (const int*)d_info, rb, want);
-      Problem Pn = P;
-      Pn.poses = d_poses_new;
-      Pn.pts = d_pts_new;
-      GH_LAUNCH(ctx, "ba_lin", lin_kernel, dim3(nchunks + gh_div_up(np, 256)), dim3(256), 0, Pn, CC, d_cpart2, d_W2, d_Hpp2,
-                d_gp2, d_gmax);  // (d_gmax was cleared by backsub_update above: exactly what a linearisation at the top would find)
-      spec_launched = true;
-      // the iteration's one synchronisation: the verdict's stamp in pinned memory (bounded: a fault in a kernel must not hang us)
-      {
-        // Spin with `pause` for about 2 ms (a C4 iteration is 0.6 ms: the stamp is there within the spin and the host adds no
-        // latency), then back off -- yield, and from 20 ms on sleep 50 us per poll: an iteration of a large dense problem (C5: 1 s)
-        // no longer pins a host core at 100 % for its whole length.
-        const double t_spin = now_ms();
-        unsigned spins = 0;
-        int phase = 0;  // 0 pause, 1 yield, 2 sleep
-        while (rb->stamp != want) {
-          if (phase == 0) {
-            __builtin_ia32_pause();
-            if ((++spins & 0x3FFu) == 0u && now_ms() - t_spin > 2.0) phase = 1;
-          } else {
-            const double waited = now_ms() - t_spin;
-            if (waited > 10000.0) break;
-            if (phase == 1) {
-              std::this_thread::yield();
-              if (waited > 20.0) phase = 2;
-            } else {
-              std::this_thread::sleep_for(std::chrono::microseconds(50));
-            }
-          }
-        }
-        if (rb->stamp != want) {
-          GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-          if (rb->stamp != want) return gh_set_error(ctx, GH_ERR_HIP, "gh_ba_solve: the iteration's verdict never reached the host");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-    } else {
-      GH_TRY(eval_cost(d_poses_new, d_pts_new, 1));  // the iteration's one synchronisation
-    }
-    if (flow_lock.owns_lock()) flow_lock.unlock();
-    h2[0] = rb->cost;
-    h2[1] = rb->model;
-    sum->solve_ms_total += now_ms() - t_solve0;
-    if (fresh_lin) {
+    LmStep step;
+    GH_TRY(ba_enqueue_step(ctx, S, opt, L, it, step));
+    // the iteration's one synchronisation
+    if (step.publish) GH_TRY(ba_wait_verdict(ctx, L.rb, L.stamp));
+    else GH_TRY(ba_eval_cost(ctx, S, L, S.d_poses_new, S.d_pts_new, 1));
+    if (step.flow_lock.owns_lock()) step.flow_lock.unlock();
+    sum->solve_ms_total += now_ms() - step.t_solve0;
+    if (step.fresh_lin) {
       double gmax;
-      memcpy(&gmax, &rb->gmax_bits, sizeof(double));
+      memcpy(&gmax, &L.rb->gmax_bits, sizeof(double));
       if (gmax <= opt.gradient_tolerance) {
-        term = 2;
+        L.term = 2;
         break;
       }
     }
-    if (rb->info > n && (cr_T ? cr_flow_ok : (d_flow || d_xh))) {
-      // A bounded wait inside one of the single-launch kernels expired (chol.hip: the launch could not get all its
-      // workgroups resident, e.g. another process holds part of the GPU).  Nothing was decided yet: repeat this iteration
-      // on the launch-per-step path and stay on it for the rest of the solve.
-      if (opt.verbose) fprintf(stderr, "[gh_ba] it %3d: single-launch solve timed out (info %d), repeating on the launch path\n", it, rb->info);
-      d_flow = nullptr;
-      d_xh = nullptr;
-      cr_flow_ok = false;  // (band / arrowhead: the dense top stays off the single-launch kernels)
-      if (fresh_lin) need_lin = true;  // (cheap, and keeps the gradient read-back of this iteration in place)
-      if (spec_launched) {  // the speculation wrote the gradient maximum the repeated linearisation accumulates into
-        GH_HIP(ctx, hipMemsetAsync(d_gmax, 0, sizeof(unsigned long long), ctx->stream));
-      }
+    if (L.rb->info > n && (S.cr_T ? L.cr_flow_ok : (S.d_flow || S.d_xh))) {  // nothing was decided yet: repeat this iteration
+      if (opt.verbose) fprintf(stderr, "[gh_ba] it %3d: single-launch solve timed out (info %d), repeating on the launch path\n", it, L.rb->info);
+      GH_TRY(ba_leave_single_launch(ctx, S, L, step));
       --it;
       continue;
     }
-    const bool ok = rb->info == 0 && rb->bad == 0;
-    double new_cost = cost, model = 0, rho = -1;
-    if (ok) {
-      new_cost = h2[0];
-      model = h2[1];
-      rho = model > 0 ? (cost - new_cost) / model : -1;
-      if (!(new_cost == new_cost)) rho = -1;  // NaN guard
-    }
-    const bool acc = ok && rho > opt.min_relative_decrease;
-    if (sum->trace_len < GH_BA_MAX_TRACE) {
-      sum->trace_cost[sum->trace_len] = new_cost;
-      sum->trace_radius[sum->trace_len] = radius;
-      sum->trace_accepted[sum->trace_len] = (uint8_t)acc;
-      sum->trace_len++;
-    }
-    if (opt.verbose)
-      fprintf(stderr, "[gh_ba] it %3d cost %.9e -> %.9e model %.3e rho %.3f radius %.3e %s\n", it, cost, new_cost,
-              model, rho, radius, acc ? "accepted" : (ok ? "rejected" : "solve failed"));
-    if (acc) {
-      const double dcost = cost - new_cost;
-      std::swap(d_poses, d_poses_new);
-      std::swap(d_pts, d_pts_new);
-      P.poses = d_poses;
-      P.pts = d_pts;
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      if (radius > 1e16) radius = 1e16;
-      decrease = 2.0;
-      sum->accepted++;
-      need_lin = true;
-      spec_ready = spec_launched;
-      const double prev = cost;
-      cost = new_cost;
-      if (fabs(dcost) <= opt.function_tolerance * prev) {
-        term = 1;
-        ++it;
-        break;
-      }
-    } else {
-      radius = radius / decrease;
-      decrease *= 2.0;
-      if (radius < 1e-32) {
-        term = 3;
-        ++it;
-        break;
-      }
+    if (ba_decide(S, opt, sum, L, step, it)) {
+      ++it;
+      break;
     }
   }
   sum->iterations = it;
-  sum->termination = term;
-  sum->final_cost = cost;
+  sum->termination = L.term;
+  sum->final_cost = L.cost;
   const double t_loop_end = now_ms();
   if (download && pr) {
-    GH_HIP(ctx, hipMemcpyAsync(pr->cam_pose, d_poses, (size_t)nc * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GH_HIP(ctx, hipMemcpyAsync(pr->cam_pose, S.d_poses, (size_t)nc * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (np > 0)
-      GH_HIP(ctx, hipMemcpyAsync(pr->point_xyz, d_pts, (size_t)np * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      GH_HIP(ctx, hipMemcpyAsync(pr->point_xyz, S.d_pts, (size_t)np * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }
   GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  sum->total_ms = now_ms() - t_begin;
-  if (getenv("GSLAM_HIP_BA_TIMING"))
+  sum->total_ms = now_ms() - U.t_begin;
+  if (sw.timing)
     fprintf(stderr, "[gh_ba] whole solve %.2f ms: lists + early upload %.2f, to the first cost %.2f, first cost %.2f, iterations %.2f, result download %.2f\n",
-            sum->total_ms, t_lists - t_begin, t_upload - t_lists, t_loop - t_upload, t_loop_end - t_loop, now_ms() - t_loop_end);
-  return term == 3 ? GH_ERR_NUMERIC : GH_OK;
+            sum->total_ms, U.t_lists - U.t_begin, t_upload - U.t_lists, t_loop - t_upload, t_loop_end - t_loop, now_ms() - t_loop_end);
+  return L.term == 3 ? GH_ERR_NUMERIC : GH_OK;
 }
 
 // (the camera order -- band / arrow / bandwidth-reducing -- lives in ba_order.hip)
@@ -2430,22 +2469,15 @@ struct ArrowProblem {
     pr.obs_cam = ocam.data();
   }
 };
-bool ba_arrow_wanted(const gh_ctx* ctx) {
-  int want = ctx->ba_solver;
-  if (const char* e = getenv("GSLAM_HIP_BA_SOLVER")) want = e[0] == 'd' ? 1 : (e[0] == 'b' ? 2 : 0);
-  if (const char* e = getenv("GSLAM_HIP_BA_ARROW")) if (e[0] == '0') return false;  // A/B measurements: loop closures -> dense, as in rounds 1-4
-  return want != 1;
-}
 // the camera order of a new graph (ba_order.hip): S.perm / S.n_border / S.reordered
-void ba_choose_order(const gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr) {
-  if (!(pr->n_cams > 0 && pr->cam_pose && pr->cam_dof && pr->obs_cam && pr->obs_point && ba_arrow_wanted(ctx))) return;
-  const char* e = getenv("GSLAM_HIP_BA_REORDER");  // "0": the caller's camera order as it is (rounds 4-5; A/B measurements)
+void ba_choose_order(BaSession& S, const gh_ba_problem* pr, const BaSwitches& sw) {
+  if (!(pr->n_cams > 0 && pr->cam_pose && pr->cam_dof && pr->obs_cam && pr->obs_point && sw.arrow_wanted())) return;
   const double t0 = now_ms();
-  S.n_border = gh_ba_order_cameras(pr, S.perm, &S.reordered, !(e && e[0] == '0'), &S.span_measured, &S.border_pts);
-  if (getenv("GSLAM_HIP_BA_TIMING"))
+  S.n_border = gh_ba_order_cameras(pr, S.perm, &S.reordered, sw.reorder, &S.span_measured, &S.border_pts);
+  if (sw.timing)
     fprintf(stderr, "[gh_ba] camera order: %.2f ms (%s, %d border cameras)\n", now_ms() - t0,
             S.reordered ? "bandwidth-reducing order applied" : (S.perm.empty() ? "caller's order" : "arrow order"), S.n_border);
-  if (getenv("GSLAM_HIP_BA_TIMING") && !S.border_pts.empty())
+  if (sw.timing && !S.border_pts.empty())
     fprintf(stderr, "[gh_ba] border: %zu long-range points stay out of the Schur complement\n", S.border_pts.size());
 }
 
@@ -2461,21 +2493,18 @@ extern "C" gh_status gh_ba_solve(gh_ctx* ctx, gh_ba_problem* pr, const gh_ba_opt
   const double t_call = now_ms();
   gh_ba_summary local_sum;
   if (!sum_out) sum_out = &local_sum;
-  ba_choose_order(ctx, S, pr);
-  if (S.perm.empty()) {
-    const double t_order = now_ms() - t_call;
-    const gh_status st = ba_run(ctx, S, pr, opt_in, sum_out, true);
-    sum_out->total_ms += t_order;
-    return st;
-  }
+  const BaSwitches sw = ba_switches(ctx);
+  ba_choose_order(S, pr, sw);
   ArrowProblem ap(ctx);
-  ap.build(pr, S.perm);
+  if (!S.perm.empty()) ap.build(pr, S.perm);
   const double t_order = now_ms() - t_call;
-  const gh_status st = ba_run(ctx, S, &ap.pr, opt_in, sum_out, true);
+  const gh_status st = ba_run(ctx, S, S.perm.empty() ? pr : &ap.pr, sw, opt_in, sum_out, true);
+  sum_out->total_ms += t_order;
+  if (S.perm.empty()) return st;
   const double t_back = now_ms();
   for (int c = 0; c < pr->n_cams; ++c) memcpy(pr->cam_pose + (size_t)S.perm[c] * 7, &ap.pose[(size_t)c * 7], 7 * sizeof(double));
-  sum_out->total_ms += t_order + (now_ms() - t_back);
-  if (getenv("GSLAM_HIP_BA_TIMING")) fprintf(stderr, "[gh_ba] camera order + renumbered problem: %.2f ms of the call\n", t_order);
+  sum_out->total_ms += now_ms() - t_back;
+  if (sw.timing) fprintf(stderr, "[gh_ba] camera order + renumbered problem: %.2f ms of the call\n", t_order);
   return st;
 }
 
@@ -2505,12 +2534,13 @@ extern "C" gh_status gh_ba_graph_create(gh_ctx* ctx, const gh_ba_problem* proble
   gh_ba_summary sum;
   gh_ba_problem pr = *problem;
   ArrowProblem ap(ctx);
-  ba_choose_order(ctx, g->S, &pr);
+  const BaSwitches sw = ba_switches(ctx);
+  ba_choose_order(g->S, &pr, sw);
   if (!g->S.perm.empty()) {
     ap.build(problem, g->S.perm);
     pr = ap.pr;
   }
-  const gh_status st = ba_run(ctx, g->S, &pr, &o, &sum, false);
+  const gh_status st = ba_run(ctx, g->S, &pr, sw, &o, &sum, false);
   if (st != GH_OK) {
     delete g;
     return st;
@@ -2570,7 +2600,7 @@ extern "C" gh_status gh_ba_graph_update(gh_ba_graph* g, const double* cam_pose, 
 extern "C" gh_status gh_ba_graph_solve(gh_ba_graph* g, const gh_ba_options* options, gh_ba_summary* summary) {
   if (!g) return GH_ERR_ARG;
   GH_ENTER(g->ctx);
-  return ba_run(g->ctx, g->S, nullptr, options, summary, false);
+  return ba_run(g->ctx, g->S, nullptr, ba_switches(g->ctx), options, summary, false);
 }
 
 extern "C" gh_status gh_ba_graph_read(gh_ba_graph* g, double* cam_pose, double* point_xyz) {

@@ -80,7 +80,7 @@ int range_threads() {
 // observation list for them: the scan is sequential, the thread's part of lo / hi (8 MB / threads at C5) stays in its cache, no
 // atomics, nothing to merge.  (Slices of the observation list with full-size arrays per thread were slower than one thread in
 // the build container: eight 8 MB working sets fall out of the last-level cache.)  Serial by default: see range_threads.
-// false: an index out of range (ba_run reports it).
+// false: an index out of range (ba_check_problem in ba.hip reports it).
 bool point_ranges(const gh_ba_problem* pr, const int32_t* pos, std::vector<int32_t>& lo, std::vector<int32_t>& hi) {
   const int nc = pr->n_cams, np = pr->n_points, no = pr->n_obs;
   HostPool& pool = HostPool::get();
@@ -217,7 +217,7 @@ int arrow_order(const gh_ba_problem* pr, const int32_t* pos, std::vector<int32_t
   for (int c = 0; c < nc; ++c)
     if (border[c]) perm[w++] = c;
   // (the band part's span after the compact renumbering: at most kBandSpan by construction, at least what the short points have;
-  //  ba_run measures it exactly on the renumbered graph)
+  //  ba_check_problem in ba.hip measures it exactly on the renumbered graph)
   *span_out = -1;
   return nb;
 }
@@ -521,7 +521,7 @@ int gh_ba_order_cameras(const gh_ba_problem* pr, std::vector<int32_t>& perm, int
   }
   Candidate& C = use_b ? B : A;
   if (use_b && reordered) *reordered = 1;
-  if (C.cost < 0) {  // (the caller's order, no band: the dense solver; ba_run still wants the span it measured)
+  if (C.cost < 0) {  // (the caller's order, no band: the dense solver; ba_check_problem still wants the span it measured)
     if (band_span) *band_span = C.span;
     return 0;
   }

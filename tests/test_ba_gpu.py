@@ -94,9 +94,12 @@ def test_ba_step_behind_the_camera_is_rejected(ctx, oracle):
     assert gp[1][0, 2] > 1e-9 and gp[2].final_cost < 1e-20 * gp[2].initial_cost
 
 
-def test_ba_deterministic_mode_is_bitwise_reproducible(ctx):
+@pytest.mark.parametrize("n_cams,n_points", [(40, 3000), (130, 4000)])
+def test_ba_deterministic_mode_is_bitwise_reproducible(ctx, n_cams, n_points):
+    """Two solves on one context.  18 000 observations stay just under the 20 000 at which the team-built index lists, the
+    staged early upload (second solve: the arena of the first is there) and the device-built pair lists start; 24 000 take them."""
     from gslam_amd import ba
-    g = make_graph(40, 3000, n_obs_per_point=6, seed=4)
+    g = make_graph(n_cams, n_points, n_obs_per_point=6, seed=4)
     a = ba.solve(ctx, g, ba.default_options(max_iterations=10, deterministic=1))
     b = ba.solve(ctx, g, ba.default_options(max_iterations=10, deterministic=1))
     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
