@@ -26,6 +26,7 @@
 #include "common.h"
 #include "cr_map.h"
 #include "host_pool.h"
+#include "lm_rule.h"
 
 gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_dev, int extra_rows, double* dinv,
                             double* xwork, unsigned* flow_state, bool store_diag, bool state_ready);
@@ -2057,7 +2058,7 @@ gh_status ba_setup(gh_ctx* ctx, BaSession& S, const gh_ba_problem* pr, const gh_
 
 // ---------------------------------------------------------------- the LM loop
 // State of the loop across iterations.
-struct LmLoop {
+struct LmLoop : LmRule {  // (cost, radius, decrease, term: lm_rule.h)
   Problem P;
   PointBorder PB;
   HostVerdict* rb;  // cost, model, gmax_bits, info, bad, pair_counts[4] (device-built pair lists: pairs, blocks, segments), stamp
@@ -2067,12 +2068,10 @@ struct LmLoop {
   // host turnaround per iteration are then GPU work the next iteration needs anyway if the step is accepted (most are; a
   // rejected step's speculation is dropped).  Same kernel, same inputs: the LM trace is bit-identical.
   bool speculate;
-  double cost = 0, radius = 0, decrease = 2.0;
   bool need_lin = true;
   bool spec_ready = false;  // the second buffer set holds the linearisation of what is now the current state
   bool cr_flow_ok = true;   // band / arrowhead solver: the dense top may use the single-launch kernels (until one of their waits expires; per solve)
   unsigned stamp = 0;
-  int term = 0;
 };
 // One candidate step, from enqueueing to the host's verdict.
 struct LmStep {
@@ -2298,45 +2297,15 @@ gh_status ba_leave_single_launch(gh_ctx* ctx, BaSession& S, LmLoop& L, const LmS
 // terminated (L.term says why).
 bool ba_decide(BaSession& S, const gh_ba_options& opt, gh_ba_summary* sum, LmLoop& L, const LmStep& step, int it) {
   const bool ok = L.rb->info == 0 && L.rb->bad == 0;
-  double new_cost = L.cost, model = 0, rho = -1;
-  if (ok) {
-    new_cost = L.rb->cost;
-    model = L.rb->model;
-    rho = model > 0 ? (L.cost - new_cost) / model : -1;
-    if (!(new_cost == new_cost)) rho = -1;  // NaN guard
+  if (L.step(opt, sum, "gh_ba", it, ok, L.rb->cost, L.rb->model)) {
+    std::swap(S.d_poses, S.d_poses_new);
+    std::swap(S.d_pts, S.d_pts_new);
+    L.P.poses = S.d_poses;
+    L.P.pts = S.d_pts;
+    L.need_lin = true;
+    L.spec_ready = step.spec_launched;
   }
-  const bool acc = ok && rho > opt.min_relative_decrease;
-  if (sum->trace_len < GH_BA_MAX_TRACE) {
-    sum->trace_cost[sum->trace_len] = new_cost;
-    sum->trace_radius[sum->trace_len] = L.radius;
-    sum->trace_accepted[sum->trace_len] = (uint8_t)acc;
-    sum->trace_len++;
-  }
-  if (opt.verbose)
-    fprintf(stderr, "[gh_ba] it %3d cost %.9e -> %.9e model %.3e rho %.3f radius %.3e %s\n", it, L.cost, new_cost, model, rho,
-            L.radius, acc ? "accepted" : (ok ? "rejected" : "solve failed"));
-  if (!acc) {
-    L.radius = L.radius / L.decrease;
-    L.decrease *= 2.0;
-    if (L.radius < 1e-32) L.term = 3;
-    return L.term == 3;
-  }
-  const double dcost = L.cost - new_cost;
-  std::swap(S.d_poses, S.d_poses_new);
-  std::swap(S.d_pts, S.d_pts_new);
-  L.P.poses = S.d_poses;
-  L.P.pts = S.d_pts;
-  const double t = 2.0 * rho - 1.0;
-  L.radius = L.radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-  if (L.radius > 1e16) L.radius = 1e16;
-  L.decrease = 2.0;
-  sum->accepted++;
-  L.need_lin = true;
-  L.spec_ready = step.spec_launched;
-  const double prev = L.cost;
-  L.cost = new_cost;
-  if (fabs(dcost) <= opt.function_tolerance * prev) L.term = 1;
-  return L.term == 1;
+  return L.term != 0;
 }
 
 // One solve of a session.  A new session (S.ready false) comes with its problem and is set up first; a resident one
@@ -2802,7 +2771,7 @@ __global__ __launch_bounds__(256) void pnp_lm_kernel(const double* __restrict__ 
       v[1] = model;
       pnp_block_sum<2>(v, s_red, s_tot);
     }
-    if (tid == 0) {
+    if (tid == 0) {  // the step rule of lm_rule.h (LmRule::step), restated for the device: keep the two alike
       const double cost = s_cost, radius = s_radius;
       double new_cost = cost, model = 0, rho = -1;
       if (ok) {

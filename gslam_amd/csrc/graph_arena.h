@@ -8,6 +8,9 @@
 // block and sent with ONE DMA when they lie back to back in the arena (they do when they are allocated first).
 //
 // Two passes over the same allocation code: measure (sizes only, no memory is touched) -> reserve() -> the real pass.
+// That code is ONE list per solver, and the list notes each upload in the statement that allocates its array, so the
+// uploads follow each other in the arena by construction: GraphDev::alloc (posegraph.hip) for the graph solvers, which
+// calls BsSolver::alloc_dev / note_uploads (bsparse.hip) for the lists of the block-sparse solver.
 // Arrays above kBigBytes (the dense keyframe system of a large graph) keep their own hipMalloc / hipFree: their
 // allocation time is nothing beside their factorisation, and the arena would pin that much HBM for the life of the
 // context.  GSLAM_HIP_PG_ARENA=0 gives every array its own hipMalloc and every upload its own copy (A/B measurements).

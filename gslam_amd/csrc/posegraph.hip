@@ -25,6 +25,7 @@
 
 #include "bsparse.h"
 #include "common.h"
+#include "lm_rule.h"
 
 namespace {
 
@@ -1427,19 +1428,142 @@ __global__ __launch_bounds__(256) void gr_reduce_kernel(const double* __restrict
   if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 
-}  // namespace
+// ---------------------------------------------------------------- gh_graph_solve: the host side, phase by phase
+// Sizes and switches of one solve.
+struct GraphShape {
+  int nf = 0, nx = 0, ni = 0, no = 0, nlm = 0, ms = 2;  // keyframes, XYZ / inverse-depth points, observations; doubles per measurement
+  bool with_cam = false;                                // free intrinsics: they follow the keyframes in the reduced system
+  int n = 0, lda = 0, rec = kObsRec;
+  int ne = 0, n_pairs = 0;  // pose edges and their distinct frame pairs (PoseHost)
+  bool sparse = false;      // block-sparse linear solver (graph_plan_sparse)
+  bool det = false;         // reproducible accumulation of the landmark part (DetAcc)
+  explicit GraphShape(const gh_graph_problem* gpr)
+      : nf(gpr->pg.n_frames), nx(gpr->n_xyz), ni(gpr->n_idp), no(gpr->n_obs), nlm(nx + ni), ms(gpr->projection ? 3 : 2),
+        with_cam(gpr->intrinsics != nullptr && no > 0), n(7 * nf + (with_cam ? 9 : 0)),
+        lda((n + 1 + 15) & ~15),  // one spare row: the right-hand side rides through the factorisation (gh_potrf_solve_dev)
+        rec(with_cam ? kObsRecCam : kObsRec) {}
+  size_t nlm1() const { return (size_t)std::max(nlm, 1); }
+  size_t no1() const { return (size_t)std::max(no, 1); }
+  size_t nx1() const { return (size_t)std::max(nx, 1); }
+  size_t ni1() const { return (size_t)std::max(ni, 1); }
+  int n_items() const { return ne + no; }  // terms of the model decrease: pose edges, then observations
+  int n_part() const { return gh_div_up(std::max(n_items(), std::max(no, 1)), 1024); }
+  int eb() const { return gh_div_up(ne > 0 ? ne : 1, 64); }
+  int eb4() const { return gh_div_up(ne > 0 ? ne : 1, 4); }
+  int ob() const { return gh_div_up(no > 0 ? no : 1, 128); }  // workgroups of gr_obs_lin (two waves each)
+};
 
-extern "C" gh_status gh_graph_solve(gh_ctx* ctx, gh_graph_problem* gpr, const gh_ba_options* opt_in, gh_ba_summary* sum_out) {
-  if (!ctx || !gpr) return GH_ERR_ARG;
-  GH_ENTER(ctx);
-  gh_pg_problem* pr = &gpr->pg;
-  gh_ba_options opt;
-  gh_ba_default_options(&opt);
-  if (opt_in) opt = *opt_in;
-  gh_ba_summary local;
-  gh_ba_summary* sum = sum_out ? sum_out : &local;
-  memset(sum, 0, sizeof(*sum));
-  const int nf = pr->n_frames, nx = gpr->n_xyz, ni = gpr->n_idp, no = gpr->n_obs, nlm = nx + ni;
+// What the host builds from the problem before anything is allocated.
+struct GraphHost {
+  PoseHost PH;
+  std::vector<int32_t> lstart, llist;  // observations grouped by landmark (XYZ points first), in observation order
+  std::vector<int64_t> bs_off;         // block-sparse address tables: where pg_assemble_bs stores each block (BsDest)
+  std::vector<int32_t> bs_sp, bs_sq;
+};
+
+// Everything the host reads back inside the loop lands in the context's pinned block: plain DMAs, no staged copies into
+// pageable memory.
+struct GraphReadback {
+  double out4[4];
+  unsigned long long gmax_bits;
+  int info;
+  int32_t bs_flag;
+};
+
+// The device arrays of one solve.  The arena places each array by the ORDER of alloc(): the uploaded arrays first, so
+// that they form one run of the arena and travel in one DMA; then the lists of the block-sparse solver (the same way),
+// then the work arrays.
+struct GraphDev {
+  // uploaded: pose graph
+  double *S = nullptr, *meas = nullptr, *info = nullptr;
+  int32_t *dof = nullptr, *etype = nullptr, *ei = nullptr, *ej = nullptr, *vstart = nullptr, *vlist = nullptr, *pstart = nullptr,
+          *plist = nullptr, *prow = nullptr, *pcol = nullptr;
+  // uploaded: landmarks
+  double *xyz = nullptr, *rho = nullptr, *anchor = nullptr, *oxy = nullptr, *oinfo = nullptr, *cam = nullptr;
+  int32_t *host = nullptr, *okind = nullptr, *opoint = nullptr, *oframe = nullptr, *lstart = nullptr, *llist = nullptr;
+  uint8_t *xfree = nullptr, *ifree = nullptr;
+  // uploaded: block-sparse address tables
+  int64_t* bs_off = nullptr;
+  int32_t *bs_sp = nullptr, *bs_sq = nullptr;
+  // work arrays
+  double *Snew = nullptr, *rec = nullptr, *cost_e = nullptr, *g = nullptr, *d = nullptr, *out = nullptr, *xyz_new = nullptr,
+         *rho_new = nullptr, *orec = nullptr, *Hpp = nullptr, *gp = nullptr, *Hinv = nullptr, *dlm = nullptr, *term = nullptr,
+         *part = nullptr, *Wh = nullptr, *cam_new = nullptr, *Wc = nullptr, *cam_part = nullptr, *H = nullptr, *Hd = nullptr;
+  unsigned long long* gmax = nullptr;
+  int32_t *lmdim = nullptr, *hrep = nullptr;
+  uint8_t* valid = nullptr;
+  // DetAcc: two matrix-shaped and two vector-shaped accumulators, the bound
+  double *acc_hi = nullptr, *acc_lo = nullptr, *vacc = nullptr;
+  unsigned long long* bound = nullptr;
+
+  // Run twice (graph_arena.h): once measuring, once for real.  An uploaded array is allocated and its upload noted (real
+  // pass) in ONE statement, so the order of the uploads is the order of the allocations by construction.
+  bool alloc(GraphArena& A, const GraphShape& Z, const gh_graph_problem* gpr, const GraphHost& Hh, BsSolver& BS) {
+    const gh_pg_problem* pr = &gpr->pg;
+    const PoseHost& PH = Hh.PH;
+    const size_t nf = (size_t)Z.nf, nx = (size_t)Z.nx, ni = (size_t)Z.ni, no = (size_t)Z.no, n = (size_t)Z.n;
+    const size_t nx1 = Z.nx1(), ni1 = Z.ni1(), no1 = Z.no1(), nlm1 = Z.nlm1(), ne1 = PH.etype.size(), nn = n * Z.lda;
+    // room elements of *arr, the first `count` of them uploaded from src
+    auto up = [&A](auto** arr, size_t room, const void* src, size_t count) -> bool {
+      if (!A.alloc(arr, room)) return false;
+      if (!A.measuring) A.upload(*arr, src, count * sizeof(**arr));
+      return true;
+    };
+    auto upv = [&up](auto** arr, const auto& v) -> bool { return up(arr, v.size(), v.data(), v.size()); };
+    // the block-sparse solver's own lists: allocated there, their uploads noted behind the tables' (real pass)
+    auto bs_lists = [&A, &BS]() -> bool {
+      if (!BS.alloc_dev(A)) return false;
+      if (!A.measuring) BS.note_uploads(A);
+      return true;
+    };
+    return up(&S, nf * 8, pr->frame_sim3, nf * 8) && up(&dof, nf, pr->frame_dof, nf) && upv(&meas, PH.meas) &&
+           (!PH.any_info || upv(&info, PH.info)) && upv(&etype, PH.etype) && upv(&ei, PH.ei) && upv(&ej, PH.ej) &&
+           upv(&vstart, PH.vstart) && upv(&vlist, PH.vlist) && upv(&pstart, PH.pstart) && upv(&plist, PH.plist) &&
+           upv(&prow, PH.prow) && upv(&pcol, PH.pcol) &&
+           // landmarks
+           up(&xyz, nx1 * 3, gpr->xyz, nx * 3) && up(&rho, ni1, gpr->idp_rho, ni) && up(&anchor, ni1 * 3, gpr->idp_anchor, ni * 3) &&
+           up(&host, ni1, gpr->idp_host, ni) && up(&oxy, no1 * 3, gpr->projection ? gpr->obs_bearing : gpr->obs_xy, no * Z.ms) &&
+           (!gpr->obs_info || up(&oinfo, no1 * 4, gpr->obs_info, no * 4)) && up(&okind, no1, gpr->obs_kind, no) &&
+           up(&opoint, no1, gpr->obs_point, no) && up(&oframe, no1, gpr->obs_frame, no) && upv(&lstart, Hh.lstart) &&
+           upv(&llist, Hh.llist) && (!gpr->xyz_free || up(&xfree, nx1, gpr->xyz_free, nx)) &&
+           (!gpr->idp_free || up(&ifree, ni1, gpr->idp_free, ni)) && (!Z.with_cam || up(&cam, 9, gpr->intrinsics, 9)) &&
+           // block-sparse tables, then the solver's own lists
+           (!Z.sparse || (upv(&bs_off, Hh.bs_off) && upv(&bs_sp, Hh.bs_sp) && upv(&bs_sq, Hh.bs_sq) && bs_lists())) &&
+           // work arrays
+           A.alloc(&Snew, nf * 8) && A.alloc(&rec, (size_t)kEdgeRec * ne1) && A.alloc(&cost_e, ne1) && A.alloc(&g, n) &&
+           A.alloc(&d, n) && A.alloc(&out, 4) && A.alloc(&gmax, 1) && A.alloc(&xyz_new, nx1 * 3) && A.alloc(&rho_new, ni1) &&
+           A.alloc(&orec, no1 * Z.rec) && A.alloc(&Hpp, nlm1 * 9) && A.alloc(&gp, nlm1 * 3) && A.alloc(&Hinv, nlm1 * 9) &&
+           A.alloc(&dlm, nlm1 * 3) && A.alloc(&term, (size_t)std::max(Z.n_items(), 1)) && A.alloc(&part, (size_t)Z.n_part()) &&
+           A.alloc(&lmdim, nlm1) && A.alloc(&hrep, nlm1) && A.alloc(&Wh, nlm1 * 7) && A.alloc(&valid, no1) &&
+           (!Z.with_cam || (A.alloc(&cam_new, 9) && A.alloc(&Wc, nlm1 * 27) && A.alloc(&cam_part, (size_t)kCamPart * 2 * Z.ob()))) &&
+           (Z.sparse || (A.alloc(&H, nn) && A.alloc(&Hd, nn))) &&
+           // DetAcc
+           (!Z.det || (A.alloc(&acc_hi, nn) && A.alloc(&acc_lo, nn) && A.alloc(&vacc, 2 * n) && A.alloc(&bound, 1)));
+  }
+};
+
+// One solve: what its phases share.
+struct GraphRun {
+  GraphShape Z;
+  GraphDev D;
+  BsSolver BS;
+  PgGraph G;
+  PgLists Ls;
+  GrLandmarks LM;
+  DetAcc DA{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  GraphReadback* rb = nullptr;
+  explicit GraphRun(const gh_graph_problem* gpr) : Z(gpr) {}
+};
+
+// State of the LM loop across iterations (cost, radius, decrease, term: lm_rule.h).
+struct GraphLoop : LmRule {
+  bool need_lin = true;
+  bool fresh_gmax = false;  // a gradient maximum is on its way to the host: tested behind the solve's synchronisation
+};
+
+gh_status graph_check_problem(gh_ctx* ctx, const gh_graph_problem* gpr, const GraphShape& Z) {
+  const gh_pg_problem* pr = &gpr->pg;
+  const int nf = Z.nf, nx = Z.nx, ni = Z.ni, no = Z.no;
   GH_CHECK_ARG(ctx, nf >= 1 && nf <= (1 << 20) && pr->frame_sim3 && pr->frame_dof && pr->n_se3 >= 0 && pr->n_sim3 >= 0 && pr->n_gps >= 0);
   GH_CHECK_ARG(ctx, pr->n_se3 == 0 || (pr->se3_first && pr->se3_second && pr->se3_meas));
   GH_CHECK_ARG(ctx, pr->n_sim3 == 0 || (pr->sim3_first && pr->sim3_second && pr->sim3_meas));
@@ -1448,399 +1572,361 @@ extern "C" gh_status gh_graph_solve(gh_ctx* ctx, gh_graph_problem* gpr, const gh
   GH_CHECK_ARG(ctx, nx >= 0 && ni >= 0 && no >= 0 && (nx == 0 || gpr->xyz) && (ni == 0 || (gpr->idp_host && gpr->idp_anchor && gpr->idp_rho)));
   GH_CHECK_ARG(ctx, gpr->projection == 0 || gpr->projection == 1);
   // camera self-calibration (BundleGraph::camera + cameraDOF): pixels through the camera model, pinhole projection only
-  const bool with_cam = gpr->intrinsics != nullptr && no > 0;
   if (gpr->intrinsics) {
     if (gpr->projection != 0) return gh_set_error(ctx, GH_ERR_ARG, "gh_graph_solve: intrinsics need the pinhole projection");
     GH_CHECK_ARG(ctx, gpr->intrinsics[0] != 0.0 && gpr->intrinsics[1] != 0.0 && (gpr->intrinsics_free & ~0x1FF) == 0);
   }
-  const double* obs_meas = gpr->projection ? gpr->obs_bearing : gpr->obs_xy;
-  const int ms = gpr->projection ? 3 : 2;
-  GH_CHECK_ARG(ctx, no == 0 || (gpr->obs_kind && gpr->obs_point && gpr->obs_frame && obs_meas));
+  GH_CHECK_ARG(ctx, no == 0 || (gpr->obs_kind && gpr->obs_point && gpr->obs_frame && (gpr->projection ? gpr->obs_bearing : gpr->obs_xy)));
   for (int f = 0; f < nf; ++f) GH_CHECK_ARG(ctx, pr->frame_sim3[8 * (size_t)f + 7] > 0);
   for (int p = 0; p < ni; ++p) GH_CHECK_ARG(ctx, gpr->idp_host[p] >= 0 && gpr->idp_host[p] < nf && gpr->idp_rho[p] > 0);
-  const double t_begin = now_ms_pg();
-  PoseHost PH;
-  GH_TRY(PH.build(ctx, pr));
-  const int ne = PH.ne;
-  // observations grouped by landmark (XYZ points first), in observation order
-  std::vector<int32_t> lstart((size_t)nlm + 2, 0), llist((size_t)(no ? no : 1), 0);
-  for (int k = 0; k < no; ++k) {
+  return GH_OK;
+}
+
+// The per-observation range check.  It runs after the pose-edge lists are built, where it always ran: an input with a bad edge
+// and a bad observation is refused for the edge, and total_ms covers this loop.
+gh_status graph_check_observations(gh_ctx* ctx, const gh_graph_problem* gpr, const GraphShape& Z) {
+  for (int k = 0; k < Z.no; ++k) {
     const int kind = gpr->obs_kind[k], p = gpr->obs_point[k], f = gpr->obs_frame[k];
-    GH_CHECK_ARG(ctx, (kind == 0 || kind == 1) && p >= 0 && p < (kind == 0 ? nx : ni) && f >= 0 && f < nf);
-    lstart[(kind == 0 ? p : nx + p) + 1]++;
+    GH_CHECK_ARG(ctx, (kind == 0 || kind == 1) && p >= 0 && p < (kind == 0 ? Z.nx : Z.ni) && f >= 0 && f < Z.nf);
   }
-  for (int p = 0; p < nlm; ++p) lstart[p + 1] += lstart[p];
-  {
-    std::vector<int32_t> fill(lstart.begin(), lstart.end() - 1);
-    for (int k = 0; k < no; ++k) llist[fill[gpr->obs_kind[k] == 0 ? gpr->obs_point[k] : nx + gpr->obs_point[k]]++] = k;
-  }
-  const int n = 7 * nf + (with_cam ? 9 : 0);  // the intrinsics follow the keyframes
-  const int rec = with_cam ? kObsRecCam : kObsRec;
-  const int lda = (n + 1 + 15) & ~15;  // one spare row: the right-hand side rides through the factorisation (gh_potrf_solve_dev)
-  // A large pose graph (no landmarks) is solved block-sparse: bsparse.h.  GSLAM_HIP_PG_SPARSE_MIN = keyframes from which
-  // it is used (0: always; default 384 -- below it the dense system is a single-launch factorisation and bitwise
-  // reproducible), GSLAM_HIP_PG_ROOT = keyframes kept for the dense root.
+  return GH_OK;
+}
+
+void graph_landmark_lists(const gh_graph_problem* gpr, const GraphShape& Z, GraphHost& Hh) {
+  const int nx = Z.nx, no = Z.no;
+  Hh.lstart.assign((size_t)Z.nlm + 2, 0);
+  Hh.llist.assign((size_t)(no ? no : 1), 0);
+  auto landmark = [&](int k) { return gpr->obs_kind[k] == 0 ? gpr->obs_point[k] : nx + gpr->obs_point[k]; };
+  for (int k = 0; k < no; ++k) Hh.lstart[landmark(k) + 1]++;
+  for (int p = 0; p < Z.nlm; ++p) Hh.lstart[p + 1] += Hh.lstart[p];
+  std::vector<int32_t> fill(Hh.lstart.begin(), Hh.lstart.end() - 1);
+  for (int k = 0; k < no; ++k) Hh.llist[fill[landmark(k)]++] = k;
+}
+
+// A large pose graph (no landmarks) is solved block-sparse: bsparse.h.  GSLAM_HIP_PG_SPARSE_MIN = keyframes from which
+// it is used (0: always; default 384 -- below it the dense system is a single-launch factorisation and bitwise
+// reproducible), GSLAM_HIP_PG_ROOT = keyframes kept for the dense root.  Sets Z.sparse; then the elimination order, the
+// solver's lists and the address of every block pg_assemble_bs stores.
+gh_status graph_plan_sparse(gh_ctx* ctx, GraphShape& Z, GraphHost& Hh, BsSolver& BS, bool verbose) {
   int sparse_min = 384, root_min = 128;
   if (const char* e = getenv("GSLAM_HIP_PG_SPARSE_MIN")) sparse_min = atoi(e);
   if (const char* e = getenv("GSLAM_HIP_PG_ROOT")) root_min = std::max(1, atoi(e));
-  const bool sparse = nlm == 0 && nf >= sparse_min && sparse_min >= 0;
-  BsSolver BS;
-  std::vector<int64_t> bs_off;
-  std::vector<int32_t> bs_sp, bs_sq;
-  if (sparse) {
-    BS.P.build(nf, PH.n_pairs, PH.prow.data(), PH.pcol.data(), root_min, 64);
-    GH_TRY(BS.prepare_host(ctx));
-    const size_t nb = (size_t)nf + PH.n_pairs;
-    bs_off.resize(nb);
-    bs_sp.resize(nb);
-    bs_sq.resize(nb);
-    for (int f = 0; f < nf; ++f) {
-      size_t o = 0;
-      int cs = 7;
-      GH_CHECK_ARG(ctx, BS.block_addr(BS.P.pos[f], BS.P.pos[f], &o, &cs));
-      bs_off[f] = (int64_t)o;
-      bs_sp[f] = 1;
-      bs_sq[f] = cs;
-    }
-    for (int k = 0; k < PH.n_pairs; ++k) {
-      const int pa = BS.P.pos[PH.prow[k]], pb = BS.P.pos[PH.pcol[k]];
-      size_t o = 0;
-      int cs = 7;
-      GH_CHECK_ARG(ctx, BS.block_addr(std::max(pa, pb), std::min(pa, pb), &o, &cs));
-      bs_off[nf + k] = (int64_t)o;
-      bs_sp[nf + k] = pa > pb ? 1 : cs;  // p indexes the pair's ROW frame: the block's row when that frame comes later in the order
-      bs_sq[nf + k] = pa > pb ? cs : 1;
-    }
-    if (opt.verbose)
-      fprintf(stderr, "[gh_graph] block-sparse: %d keyframes -> %d sparse columns in %d rounds, %d blocks, root %d\n", nf, BS.P.ns,
-              BS.P.n_rounds, BS.P.n_slots, BS.P.nr);
+  Z.sparse = Z.nlm == 0 && Z.nf >= sparse_min && sparse_min >= 0;
+  if (!Z.sparse) return GH_OK;
+  const PoseHost& PH = Hh.PH;
+  const int nf = Z.nf;
+  BS.P.build(nf, PH.n_pairs, PH.prow.data(), PH.pcol.data(), root_min, 64);
+  GH_TRY(BS.prepare_host(ctx));
+  const size_t nb = (size_t)nf + PH.n_pairs;
+  Hh.bs_off.resize(nb);
+  Hh.bs_sp.resize(nb);
+  Hh.bs_sq.resize(nb);
+  for (int f = 0; f < nf; ++f) {
+    size_t o = 0;
+    int cs = 7;
+    GH_CHECK_ARG(ctx, BS.block_addr(BS.P.pos[f], BS.P.pos[f], &o, &cs));
+    Hh.bs_off[f] = (int64_t)o;
+    Hh.bs_sp[f] = 1;
+    Hh.bs_sq[f] = cs;
   }
-  const int ob_alloc = gh_div_up(no > 0 ? no : 1, 128);  // workgroups of gr_obs_lin (two waves each)
-  const int n_items = ne + no, n_part = gh_div_up(std::max(n_items, std::max(no, 1)), 1024);
-  GraphArena A(ctx);
-  double *d_S, *d_Snew, *d_meas, *d_info = nullptr, *d_rec, *d_cost_e, *d_H = nullptr, *d_Hd = nullptr, *d_g, *d_d, *d_out;
-  double *d_xyz, *d_xyz_new, *d_rho, *d_rho_new, *d_anchor, *d_oxy, *d_oinfo = nullptr, *d_orec, *d_Hpp, *d_gp, *d_Hinv, *d_dlm, *d_term,
-      *d_part, *d_Wh, *d_cam = nullptr, *d_cam_new = nullptr, *d_Wc = nullptr, *d_cam_part = nullptr;
-  int32_t *d_dof, *d_etype, *d_ei, *d_ej, *d_vstart, *d_vlist, *d_pstart, *d_plist, *d_prow, *d_pcol, *d_host, *d_okind, *d_opoint,
-      *d_oframe, *d_lstart, *d_llist, *d_lmdim, *d_hrep;
-  uint8_t *d_xfree = nullptr, *d_ifree = nullptr, *d_valid;
-  unsigned long long* d_gmax;
-  // reproducible accumulation of the landmark part (DetAcc): two matrix-shaped and two vector-shaped accumulators, the bound
-  const bool det = opt.deterministic != 0 && !sparse && no > 0;
-  double *d_acc_hi = nullptr, *d_acc_lo = nullptr, *d_vacc = nullptr;
-  unsigned long long* d_bound = nullptr;
-  int64_t* d_bs_off = nullptr;
-  int32_t *d_bs_sp = nullptr, *d_bs_sq = nullptr;
-  const size_t nlm1 = (size_t)std::max(nlm, 1), no1 = (size_t)std::max(no, 1), nx1 = (size_t)std::max(nx, 1), ni1 = (size_t)std::max(ni, 1);
-  // Run twice (graph_arena.h): once measuring, once for real.  The uploaded arrays come first, in the order of the uploads
-  // below, so that they form one run of the arena and travel in one DMA; then the lists of the block-sparse solver (the
-  // same way), then the work arrays.
-  auto alloc_all = [&]() -> bool {
-    return A.alloc(&d_S, (size_t)nf * 8) && A.alloc(&d_dof, (size_t)nf) && A.alloc(&d_meas, PH.meas.size()) &&
-           (!PH.any_info || A.alloc(&d_info, PH.info.size())) && A.alloc(&d_etype, PH.etype.size()) && A.alloc(&d_ei, PH.etype.size()) &&
-           A.alloc(&d_ej, PH.etype.size()) && A.alloc(&d_vstart, PH.vstart.size()) && A.alloc(&d_vlist, PH.vlist.size()) &&
-           A.alloc(&d_pstart, PH.pstart.size()) && A.alloc(&d_plist, PH.plist.size()) && A.alloc(&d_prow, PH.prow.size()) &&
-           A.alloc(&d_pcol, PH.pcol.size()) && A.alloc(&d_xyz, nx1 * 3) && A.alloc(&d_rho, ni1) && A.alloc(&d_anchor, ni1 * 3) &&
-           A.alloc(&d_host, ni1) && A.alloc(&d_oxy, no1 * 3) && (!gpr->obs_info || A.alloc(&d_oinfo, no1 * 4)) && A.alloc(&d_okind, no1) &&
-           A.alloc(&d_opoint, no1) && A.alloc(&d_oframe, no1) && A.alloc(&d_lstart, lstart.size()) && A.alloc(&d_llist, llist.size()) &&
-           (!gpr->xyz_free || A.alloc(&d_xfree, nx1)) && (!gpr->idp_free || A.alloc(&d_ifree, ni1)) &&
-           (!with_cam || A.alloc(&d_cam, 9)) &&
-           (!sparse || (A.alloc(&d_bs_off, bs_off.size()) && A.alloc(&d_bs_sp, bs_sp.size()) && A.alloc(&d_bs_sq, bs_sq.size()) &&
-                        BS.alloc_dev(A))) &&
-           // work arrays
-           A.alloc(&d_Snew, (size_t)nf * 8) && A.alloc(&d_rec, (size_t)kEdgeRec * PH.etype.size()) && A.alloc(&d_cost_e, PH.etype.size()) &&
-           A.alloc(&d_g, (size_t)n) && A.alloc(&d_d, (size_t)n) && A.alloc(&d_out, 4) && A.alloc(&d_gmax, 1) && A.alloc(&d_xyz_new, nx1 * 3) &&
-           A.alloc(&d_rho_new, ni1) && A.alloc(&d_orec, no1 * rec) && A.alloc(&d_Hpp, nlm1 * 9) && A.alloc(&d_gp, nlm1 * 3) &&
-           A.alloc(&d_Hinv, nlm1 * 9) && A.alloc(&d_dlm, nlm1 * 3) && A.alloc(&d_term, (size_t)std::max(n_items, 1)) &&
-           A.alloc(&d_part, (size_t)n_part) && A.alloc(&d_lmdim, nlm1) && A.alloc(&d_hrep, nlm1) && A.alloc(&d_Wh, nlm1 * 7) &&
-           A.alloc(&d_valid, no1) && (!with_cam || (A.alloc(&d_cam_new, 9) && A.alloc(&d_Wc, nlm1 * 27) && A.alloc(&d_cam_part, (size_t)kCamPart * 2 * ob_alloc))) && (sparse || (A.alloc(&d_H, (size_t)n * lda) && A.alloc(&d_Hd, (size_t)n * lda))) &&
-           (!det || (A.alloc(&d_acc_hi, (size_t)n * lda) && A.alloc(&d_acc_lo, (size_t)n * lda) && A.alloc(&d_vacc, (size_t)2 * n) && A.alloc(&d_bound, 1)));
-  };
-  alloc_all();  // measuring pass
-  GH_TRY(A.reserve());
-  if (!alloc_all())
-    return gh_set_error(ctx, GH_ERR_NOMEM, "gh_graph_solve: device allocation failed (dense keyframe system: %d x %d doubles)", n, lda);
-  A.upload(d_S, pr->frame_sim3, (size_t)nf * 64);
-  A.upload(d_dof, pr->frame_dof, (size_t)nf * 4);
-  A.upload(d_meas, PH.meas.data(), PH.meas.size() * 8);
-  if (PH.any_info) A.upload(d_info, PH.info.data(), PH.info.size() * 8);
-  A.upload(d_etype, PH.etype.data(), PH.etype.size() * 4);
-  A.upload(d_ei, PH.ei.data(), PH.ei.size() * 4);
-  A.upload(d_ej, PH.ej.data(), PH.ej.size() * 4);
-  A.upload(d_vstart, PH.vstart.data(), PH.vstart.size() * 4);
-  A.upload(d_vlist, PH.vlist.data(), PH.vlist.size() * 4);
-  A.upload(d_pstart, PH.pstart.data(), PH.pstart.size() * 4);
-  A.upload(d_plist, PH.plist.data(), PH.plist.size() * 4);
-  A.upload(d_prow, PH.prow.data(), PH.prow.size() * 4);
-  A.upload(d_pcol, PH.pcol.data(), PH.pcol.size() * 4);
-  A.upload(d_xyz, gpr->xyz, (size_t)nx * 24);
-  A.upload(d_rho, gpr->idp_rho, (size_t)ni * 8);
-  A.upload(d_anchor, gpr->idp_anchor, (size_t)ni * 24);
-  A.upload(d_host, gpr->idp_host, (size_t)ni * 4);
-  A.upload(d_oxy, obs_meas, (size_t)no * ms * 8);
-  if (gpr->obs_info) A.upload(d_oinfo, gpr->obs_info, (size_t)no * 32);
-  A.upload(d_okind, gpr->obs_kind, (size_t)no * 4);
-  A.upload(d_opoint, gpr->obs_point, (size_t)no * 4);
-  A.upload(d_oframe, gpr->obs_frame, (size_t)no * 4);
-  A.upload(d_lstart, lstart.data(), lstart.size() * 4);
-  A.upload(d_llist, llist.data(), llist.size() * 4);
-  if (gpr->xyz_free) A.upload(d_xfree, gpr->xyz_free, (size_t)nx);
-  if (gpr->idp_free) A.upload(d_ifree, gpr->idp_free, (size_t)ni);
-  if (with_cam) A.upload(d_cam, gpr->intrinsics, 72);
-  if (sparse) {
-    A.upload(d_bs_off, bs_off.data(), bs_off.size() * 8);
-    A.upload(d_bs_sp, bs_sp.data(), bs_sp.size() * 4);
-    A.upload(d_bs_sq, bs_sq.data(), bs_sq.size() * 4);
-    BS.note_uploads(A);
+  for (int k = 0; k < PH.n_pairs; ++k) {
+    const int pa = BS.P.pos[PH.prow[k]], pb = BS.P.pos[PH.pcol[k]];
+    size_t o = 0;
+    int cs = 7;
+    GH_CHECK_ARG(ctx, BS.block_addr(std::max(pa, pb), std::min(pa, pb), &o, &cs));
+    Hh.bs_off[nf + k] = (int64_t)o;
+    Hh.bs_sp[nf + k] = pa > pb ? 1 : cs;  // p indexes the pair's ROW frame: the block's row when that frame comes later in the order
+    Hh.bs_sq[nf + k] = pa > pb ? cs : 1;
   }
-  GH_TRY(A.flush());
-  if (sparse) GH_TRY(BS.clear_values(ctx));
-  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // Everything the host reads back inside the loop lands in the context's pinned block (free again after the
-  // synchronisation above; nothing below asks for it): plain DMAs, no staged copies into pageable memory.
-  struct Readback {
-    double out4[4];
-    unsigned long long gmax_bits;
-    int info;
-    int32_t bs_flag;
-  };
-  Readback* rb = nullptr;
-  {
-    void* hp = nullptr;
-    GH_TRY(gh_readback_block(ctx, sizeof(Readback), &hp));  // (its own block: later gh_pinned requests cannot move it)
-    rb = static_cast<Readback*>(hp);
-    memset(rb, 0, sizeof(*rb));
-  }
-  if (sparse) BS.h_flag = &rb->bs_flag;
-  double* host4 = rb->out4;
+  if (verbose)
+    fprintf(stderr, "[gh_graph] block-sparse: %d keyframes -> %d sparse columns in %d rounds, %d blocks, root %d\n", nf, BS.P.ns,
+            BS.P.n_rounds, BS.P.n_slots, BS.P.nr);
+  return GH_OK;
+}
 
-  DetAcc DA{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  if (det) {
-    // contributions to one word: a keyframe's diagonal block takes one per observation slot in gr_frame_rows and one per slot
-    // pair of a landmark in gr_schur (<= slots x the landmark's slots in that keyframe, usually 1); the intrinsics block one per
-    // wave of landmarks.  K = ceil(log2(4 x the busiest keyframe's slots + waves + 16))
-    std::vector<int> slots((size_t)nf, 0);
-    for (int k = 0; k < no; ++k) {
-      const int fj = gpr->obs_frame[k];
-      if (fj >= 0 && fj < nf) ++slots[fj];
-      if (gpr->obs_kind[k] == 1) {
-        const int p = gpr->obs_point[k];
-        const int h = (p >= 0 && p < ni) ? gpr->idp_host[p] : -1;
-        if (h >= 0 && h < nf && h != fj) ++slots[h];
-      }
+// Bit budget K of the reproducible accumulation.  Contributions to one word: a keyframe's diagonal block takes one per
+// observation slot in gr_frame_rows and one per slot pair of a landmark in gr_schur (<= slots x the landmark's slots in that
+// keyframe, usually 1); the intrinsics block one per wave of landmarks.
+// K = ceil(log2(4 x the busiest keyframe's slots + waves + 16))
+int graph_det_budget(const gh_graph_problem* gpr, const GraphShape& Z) {
+  const int nf = Z.nf, ni = Z.ni;
+  std::vector<int> slots((size_t)nf, 0);
+  for (int k = 0; k < Z.no; ++k) {
+    const int fj = gpr->obs_frame[k];
+    if (fj >= 0 && fj < nf) ++slots[fj];
+    if (gpr->obs_kind[k] == 1) {
+      const int p = gpr->obs_point[k];
+      const int h = (p >= 0 && p < ni) ? gpr->idp_host[p] : -1;
+      if (h >= 0 && h < nf && h != fj) ++slots[h];
     }
-    long long most = 16;
-    for (int f = 0; f < nf; ++f) most = std::max<long long>(most, slots[f]);
-    most = 4 * most + nlm / 64 + 16;
-    int K = 0;
-    while ((1ll << K) < most) ++K;
-    DA = DetAcc{d_acc_hi, d_acc_lo, d_vacc, d_vacc + n, d_bound, K};
   }
-  PgGraph G{nf, ne, d_dof, d_etype, d_ei, d_ej, d_meas, d_info};
-  PgLists Ls{d_vstart, d_vlist, d_pstart, d_plist, d_prow, d_pcol, PH.n_pairs};
-  GrLandmarks LM{nx, ni, no, d_xfree, d_host, d_anchor, d_ifree, d_okind, d_opoint, d_oframe, d_oxy, d_oinfo, d_lstart, d_llist,
-                 opt.huber_delta, gpr->projection, with_cam ? 1 : 0, with_cam ? gpr->intrinsics_free : 0, nf, rec};
-  const int eb = gh_div_up(ne > 0 ? ne : 1, 64), eb4 = gh_div_up(ne > 0 ? ne : 1, 4), ob = gh_div_up(no > 0 ? no : 1, 128);
-  // sum of v[0..count) into d_out[slot]: fixed order (1024 per block, then the partials one after the other)
-  auto reduce_to = [&](const double* v, int count, int slot) -> gh_status {
-    const int nb = gh_div_up(count > 0 ? count : 1, 1024);
-    GH_LAUNCH(ctx, "gr_reduce", gr_reduce_kernel, dim3(nb), dim3(256), 0, v, count, d_part);
-    GH_LAUNCH(ctx, "pg_sum", pg_sum_kernel, dim3(1), dim3(64), 0, (const double*)d_part, nb, d_out, slot);
-    return GH_OK;
-  };
-  // d_out[0] = cost of the pose edges, d_out[2] = cost of the observations at (S, xyz, rho)
-  auto enqueue_cost = [&](const double* S_dev, const double* xyz_dev, const double* rho_dev, const double* cam_dev,
-                          const uint8_t* was_valid) -> gh_status {
-    if (ne > 0) GH_LAUNCH(ctx, "pg_cost", pg_cost_kernel, dim3(eb), dim3(64), 0, G, S_dev, d_cost_e);
-    GH_TRY(reduce_to(d_cost_e, ne, 0));
-    if (no > 0) GH_LAUNCH(ctx, "gr_cost", gr_cost_kernel, dim3(ob), dim3(128), 0, LM, (const int32_t*)d_dof, S_dev, xyz_dev, rho_dev, cam_dev, was_valid, d_term);
-    GH_TRY(reduce_to(d_term, no, 2));
-    return GH_OK;
-  };
-  GH_TRY(enqueue_cost(d_S, d_xyz, d_rho, d_cam, nullptr));
-  GH_HIP(ctx, hipMemcpyAsync(host4, d_out, 32, hipMemcpyDeviceToHost, ctx->stream));
+  long long most = 16;
+  for (int f = 0; f < nf; ++f) most = std::max<long long>(most, slots[f]);
+  most = 4 * most + Z.nlm / 64 + 16;
+  int K = 0;
+  while ((1ll << K) < most) ++K;
+  return K;
+}
+
+// sum of v[0..count) into D.out[slot]: fixed order (1024 per block, then the partials one after the other)
+gh_status graph_reduce_to(gh_ctx* ctx, GraphRun& R, const double* v, int count, int slot) {
+  const int nb = gh_div_up(count > 0 ? count : 1, 1024);
+  GH_LAUNCH(ctx, "gr_reduce", gr_reduce_kernel, dim3(nb), dim3(256), 0, v, count, R.D.part);
+  GH_LAUNCH(ctx, "pg_sum", pg_sum_kernel, dim3(1), dim3(64), 0, (const double*)R.D.part, nb, R.D.out, slot);
+  return GH_OK;
+}
+
+// D.out[0] = cost of the pose edges, D.out[2] = cost of the observations at (S, xyz, rho)
+gh_status graph_enqueue_cost(gh_ctx* ctx, GraphRun& R, const double* S_dev, const double* xyz_dev, const double* rho_dev,
+                             const double* cam_dev, const uint8_t* was_valid) {
+  const GraphShape& Z = R.Z;
+  GraphDev& D = R.D;
+  if (Z.ne > 0) GH_LAUNCH(ctx, "pg_cost", pg_cost_kernel, dim3(Z.eb()), dim3(64), 0, R.G, S_dev, D.cost_e);
+  GH_TRY(graph_reduce_to(ctx, R, D.cost_e, Z.ne, 0));
+  if (Z.no > 0)
+    GH_LAUNCH(ctx, "gr_cost", gr_cost_kernel, dim3(Z.ob()), dim3(128), 0, R.LM, (const int32_t*)D.dof, S_dev, xyz_dev, rho_dev, cam_dev,
+              was_valid, D.term);
+  GH_TRY(graph_reduce_to(ctx, R, D.term, Z.no, 2));
+  return GH_OK;
+}
+
+// Linearise at the current state: H, g, the landmarks' H_pp / g_p, the observation records; the gradient maximum is
+// read back asynchronously.
+gh_status graph_enqueue_linearise(gh_ctx* ctx, GraphRun& R, GraphLoop& L) {
+  const GraphShape& Z = R.Z;
+  GraphDev& D = R.D;
+  const int nf = Z.nf, no = Z.no, nlm = Z.nlm, n = Z.n, lda = Z.lda;
+  if (Z.sparse) GH_HIP(ctx, hipMemsetAsync(R.BS.d_H, 0, R.BS.n_vals * sizeof(double), ctx->stream));
+  else GH_HIP(ctx, hipMemsetAsync(D.H, 0, (size_t)n * lda * sizeof(double), ctx->stream));
+  GH_HIP(ctx, hipMemsetAsync(D.gmax, 0, 8, ctx->stream));
+  GH_HIP(ctx, hipMemsetAsync(D.Hpp, 0, Z.nlm1() * 72, ctx->stream));
+  GH_HIP(ctx, hipMemsetAsync(D.gp, 0, Z.nlm1() * 24, ctx->stream));
+  if (Z.det) {
+    GH_HIP(ctx, hipMemsetAsync(D.acc_hi, 0, (size_t)n * lda * sizeof(double), ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.acc_lo, 0, (size_t)n * lda * sizeof(double), ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.vacc, 0, (size_t)2 * n * sizeof(double), ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.bound, 0, 8, ctx->stream));
+  }
+  if (Z.ne > 0) GH_LAUNCH(ctx, "pg_edge", pg_edge_kernel, dim3(Z.eb4()), dim3(64), 0, R.G, (const double*)D.S, D.rec, D.cost_e);
+  // stores the pose-edge sums into every diagonal block, every edge pair block and g (zeros where there is no edge)
+  if (Z.sparse)
+    GH_LAUNCH(ctx, "pg_assemble_bs", pg_assemble_bs_kernel, dim3(nf + Z.n_pairs), dim3(64), 0, R.G, R.Ls, (const double*)D.rec, R.BS.d_H,
+              BsDest{D.bs_off, D.bs_sp, D.bs_sq}, D.g);
+  else
+    GH_LAUNCH(ctx, "pg_assemble", pg_assemble_kernel, dim3(nf + Z.n_pairs), dim3(64), 0, R.G, R.Ls, (const double*)D.rec, D.H, lda, D.g,
+              D.gmax);
+  if (Z.with_cam) GH_HIP(ctx, hipMemsetAsync(D.g + 7 * nf, 0, 72, ctx->stream));  // (pg_assemble stores the keyframe rows only)
+  if (no > 0)
+    GH_LAUNCH(ctx, "gr_obs_lin", gr_obs_lin_kernel, dim3(Z.ob()), dim3(128), 0, R.LM, (const int32_t*)D.dof, (const double*)D.S,
+              (const double*)D.xyz, (const double*)D.rho, (const double*)D.cam, D.orec, D.valid, D.H, lda, D.g, D.Hpp, D.gp, D.cam_part,
+              D.bound);
+  if (Z.det && nlm > 0)
+    GH_LAUNCH(ctx, "gr_lm_sum", gr_lm_sum_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+              (const double*)D.orec, D.Hpp, D.gp);
+  if (Z.with_cam)
+    GH_LAUNCH(ctx, "gr_cam_fold", gr_cam_fold_kernel, dim3(1), dim3(1024), 0, (const double*)D.cam_part, 2 * Z.ob(), nf, D.H, lda, D.g);
+  if (no > 0)
+    GH_LAUNCH(ctx, "gr_frame_rows", gr_frame_rows_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+              (const double*)D.orec, D.H, lda, D.g, R.DA);
+  if (Z.det)  // H += hi + lo, g likewise; the accumulators are cleared again for the Schur products of the iterations
+    GH_LAUNCH(ctx, "gr_det_fold", gr_det_fold_kernel, dim3(gh_div_up((long long)n * lda + n, 256)), dim3(256), 0, D.H,
+              (const double*)D.acc_hi, (const double*)D.acc_lo, n, lda, D.g, (const double*)D.vacc, (const double*)(D.vacc + n), n);
+  GH_HIP(ctx, hipMemsetAsync(D.gmax, 0, 8, ctx->stream));
+  GH_LAUNCH(ctx, "gr_gmax", gr_gmax_kernel, dim3(gh_div_up(n + 3 * nlm, 256)), dim3(256), 0, (const double*)D.g, n, (const double*)D.gp,
+            3 * nlm, D.gmax);
+  // (read behind the linear solve, which synchronises anyway: if the gradient test fires, the step computed meanwhile is
+  //  simply dropped -- same decisions, one host round trip less per iteration)
+  GH_HIP(ctx, hipMemcpyAsync(&R.rb->gmax_bits, D.gmax, 8, hipMemcpyDeviceToHost, ctx->stream));
+  L.fresh_gmax = true;
+  L.need_lin = false;
+  return GH_OK;
+}
+
+// The damped reduced system of this radius: Hd = H + D / radius, d = g; then the landmarks are eliminated into it.
+gh_status graph_enqueue_system(gh_ctx* ctx, GraphRun& R, double radius) {
+  const GraphShape& Z = R.Z;
+  GraphDev& D = R.D;
+  const int no = Z.no, nlm = Z.nlm, n = Z.n, lda = Z.lda;
+  if (!Z.sparse)
+    GH_LAUNCH(ctx, "pg_damp", pg_damp_kernel, dim3(gh_div_up((long long)n * lda, 256)), dim3(256), 0, (const double*)D.H, D.Hd, n, lda,
+              (const double*)D.g, D.d, radius);
+  if (nlm == 0) return GH_OK;
+  if (Z.det) {
+    GH_HIP(ctx, hipMemsetAsync(D.acc_hi, 0, (size_t)n * lda * sizeof(double), ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.acc_lo, 0, (size_t)n * lda * sizeof(double), ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.vacc, 0, (size_t)2 * n * sizeof(double), ctx->stream));
+  }
+  GH_LAUNCH(ctx, "gr_lm_prepare", gr_lm_prepare_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+            (const double*)D.Hpp, (const double*)D.orec, radius, D.Hinv, D.lmdim, D.Wh, D.hrep, D.Wc);
+  if (no > 0)
+    GH_LAUNCH(ctx, "gr_schur", gr_schur_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+              (const double*)D.orec, (const double*)D.Hinv, (const int32_t*)D.lmdim, (const double*)D.Wh, (const int32_t*)D.hrep,
+              (const double*)D.gp, D.Hd, lda, D.d, R.DA);
+  if (Z.with_cam)
+    GH_LAUNCH(ctx, "gr_schur_cam", gr_schur_cam_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+              (const double*)D.orec, (const double*)D.Hinv, (const int32_t*)D.lmdim, (const double*)D.Wh, (const int32_t*)D.hrep,
+              (const double*)D.Wc, D.Hd, lda, R.DA);
+  if (Z.with_cam)
+    GH_LAUNCH(ctx, "gr_schur_cam_cc", gr_schur_cam_cc_kernel, dim3(gh_div_up(nlm, 128)), dim3(128), 0, R.LM, (const double*)D.Hinv,
+              (const int32_t*)D.lmdim, (const double*)D.Wc, (const double*)D.gp, D.Hd, lda, D.d, R.DA);
+  if (Z.det)
+    GH_LAUNCH(ctx, "gr_det_fold", gr_det_fold_kernel, dim3(gh_div_up((long long)n * lda + n, 256)), dim3(256), 0, D.Hd,
+              (const double*)D.acc_hi, (const double*)D.acc_lo, n, lda, D.d, (const double*)D.vacc, (const double*)(D.vacc + n), n);
+  return GH_OK;
+}
+
+// Factorise and solve, block-sparse or dense; both end with a stream synchronisation.  *info != 0: the system was not
+// positive definite at this radius.
+gh_status graph_linear_solve(gh_ctx* ctx, GraphRun& R, double radius, int* info) {
+  if (R.Z.sparse) return R.BS.factor_solve(ctx, radius, R.D.g, R.D.d, info);
+  R.rb->info = 0;
+  GH_TRY(gh_potrf_solve_dev(ctx, R.D.Hd, R.Z.n, R.Z.lda, R.D.d, &R.rb->info));
+  *info = R.rb->info;
+  return GH_OK;
+}
+
+// The trial step: back-substitution of the landmarks, model decrease (D.out[1]), the candidate state and its cost; the
+// three sums come back in one 32-byte copy.  Waits for the device.
+gh_status graph_enqueue_trial(gh_ctx* ctx, GraphRun& R, int cam_free) {
+  const GraphShape& Z = R.Z;
+  GraphDev& D = R.D;
+  const int nf = Z.nf, nlm = Z.nlm, n_items = Z.n_items();
+  if (nlm > 0)
+    GH_LAUNCH(ctx, "gr_backsub", gr_backsub_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, R.LM, (const uint8_t*)D.valid,
+              (const double*)D.orec, (const double*)D.Hinv, (const int32_t*)D.lmdim, (const double*)D.gp, (const double*)D.d, D.dlm);
+  if (n_items > 0)
+    GH_LAUNCH(ctx, "gr_model", gr_model_kernel, dim3(gh_div_up(n_items, 256)), dim3(256), 0, R.G, R.LM, (const double*)D.rec,
+              (const uint8_t*)D.valid, (const double*)D.orec, (const double*)D.d, (const double*)D.dlm, D.term);
+  GH_TRY(graph_reduce_to(ctx, R, D.term, n_items, 1));
+  GH_LAUNCH(ctx, "pg_update", pg_update_kernel, dim3(gh_div_up(nf, 256)), dim3(256), 0, nf, (const int32_t*)D.dof, (const double*)D.S,
+            (const double*)D.d, D.Snew);
+  if (nlm > 0)
+    GH_LAUNCH(ctx, "gr_update", gr_update_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, Z.nx, Z.ni, (const double*)D.xyz,
+              (const double*)D.rho, (const double*)D.dlm, D.xyz_new, D.rho_new, (const double*)D.cam, (const double*)(D.d + 7 * nf),
+              cam_free, D.cam_new);
+  GH_TRY(graph_enqueue_cost(ctx, R, D.Snew, D.xyz_new, D.rho_new, D.cam_new, D.valid));
+  GH_HIP(ctx, hipMemcpyAsync(R.rb->out4, D.out, 32, hipMemcpyDeviceToHost, ctx->stream));
   GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  double cost = host4[0] + host4[2];
-  sum->initial_cost = cost;
-  double radius = opt.initial_radius, decrease = 2.0;
-  bool need_lin = true, fresh_gmax = false;
-  int term = 0, it = 0;
+  return GH_OK;
+}
+
+// Accept or reject the trial the read-back block speaks of (ok: there was one), and update the trust region.  true: the
+// solve has terminated (L.term says why).
+bool graph_decide(GraphRun& R, const gh_ba_options& opt, gh_ba_summary* sum, GraphLoop& L, bool ok, int it) {
+  if (L.step(opt, sum, "gh_graph", it, ok, R.rb->out4[0] + R.rb->out4[2], R.rb->out4[1])) {
+    std::swap(R.D.S, R.D.Snew);
+    std::swap(R.D.xyz, R.D.xyz_new);
+    std::swap(R.D.rho, R.D.rho_new);
+    std::swap(R.D.cam, R.D.cam_new);
+    L.need_lin = true;
+  }
+  return L.term != 0;
+}
+
+// results: through the pinned block too (the read-back words are not needed any more)
+gh_status graph_download(gh_ctx* ctx, const GraphRun& R, gh_graph_problem* gpr) {
+  const GraphShape& Z = R.Z;
+  const GraphDev& D = R.D;
+  const size_t bS = (size_t)Z.nf * 64, bX = (size_t)Z.nx * 24, bR = (size_t)Z.ni * 8;
+  const size_t oX = (bS + 255) & ~(size_t)255, oR = oX + ((bX + 255) & ~(size_t)255), oC = oR + ((bR + 255) & ~(size_t)255);
+  void* hp = nullptr;
+  GH_TRY(gh_pinned(ctx, oC + 72 + 256, &hp));
+  char* h = static_cast<char*>(hp);
+  GH_HIP(ctx, hipMemcpyAsync(h, D.S, bS, hipMemcpyDeviceToHost, ctx->stream));
+  if (Z.nx) GH_HIP(ctx, hipMemcpyAsync(h + oX, D.xyz, bX, hipMemcpyDeviceToHost, ctx->stream));
+  if (Z.ni) GH_HIP(ctx, hipMemcpyAsync(h + oR, D.rho, bR, hipMemcpyDeviceToHost, ctx->stream));
+  if (Z.with_cam) GH_HIP(ctx, hipMemcpyAsync(h + oC, D.cam, 72, hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(gpr->pg.frame_sim3, h, bS);
+  if (Z.nx) memcpy(gpr->xyz, h + oX, bX);
+  if (Z.ni) memcpy(gpr->idp_rho, h + oR, bR);
+  if (Z.with_cam) memcpy(gpr->intrinsics, h + oC, 72);
+  return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_graph_solve(gh_ctx* ctx, gh_graph_problem* gpr, const gh_ba_options* opt_in, gh_ba_summary* sum_out) {
+  if (!ctx || !gpr) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  gh_ba_options opt;
+  gh_ba_default_options(&opt);
+  if (opt_in) opt = *opt_in;
+  gh_ba_summary local;
+  gh_ba_summary* sum = sum_out ? sum_out : &local;
+  memset(sum, 0, sizeof(*sum));
+  GraphRun R(gpr);
+  GraphShape& Z = R.Z;
+  GraphDev& D = R.D;
+  GH_TRY(graph_check_problem(ctx, gpr, Z));
+  const double t_begin = now_ms_pg();
+  // plan: edge and landmark lists, the linear solver, the accumulation mode
+  GraphHost Hh;
+  GH_TRY(Hh.PH.build(ctx, &gpr->pg));
+  Z.ne = Hh.PH.ne;
+  Z.n_pairs = Hh.PH.n_pairs;
+  GH_TRY(graph_check_observations(ctx, gpr, Z));
+  graph_landmark_lists(gpr, Z, Hh);
+  GH_TRY(graph_plan_sparse(ctx, Z, Hh, R.BS, opt.verbose != 0));
+  Z.det = opt.deterministic != 0 && !Z.sparse && Z.no > 0;
+  // allocate and upload
+  GraphArena A(ctx);
+  D.alloc(A, Z, gpr, Hh, R.BS);  // measuring pass
+  GH_TRY(A.reserve());
+  if (!D.alloc(A, Z, gpr, Hh, R.BS))
+    return gh_set_error(ctx, GH_ERR_NOMEM, "gh_graph_solve: device allocation failed (dense keyframe system: %d x %d doubles)", Z.n, Z.lda);
+  GH_TRY(A.flush());
+  if (Z.sparse) GH_TRY(R.BS.clear_values(ctx));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  {  // (the pinned block is free again after the synchronisation above; nothing below asks for it before the download)
+    void* hp = nullptr;
+    GH_TRY(gh_readback_block(ctx, sizeof(GraphReadback), &hp));  // (its own block: later gh_pinned requests cannot move it)
+    R.rb = static_cast<GraphReadback*>(hp);
+    memset(R.rb, 0, sizeof(*R.rb));
+  }
+  if (Z.sparse) R.BS.h_flag = &R.rb->bs_flag;
+  const int cam_free = Z.with_cam ? gpr->intrinsics_free : 0;
+  if (Z.det) R.DA = DetAcc{D.acc_hi, D.acc_lo, D.vacc, D.vacc + Z.n, D.bound, graph_det_budget(gpr, Z)};
+  R.G = PgGraph{Z.nf, Z.ne, D.dof, D.etype, D.ei, D.ej, D.meas, D.info};
+  R.Ls = PgLists{D.vstart, D.vlist, D.pstart, D.plist, D.prow, D.pcol, Z.n_pairs};
+  R.LM = GrLandmarks{Z.nx, Z.ni, Z.no, D.xfree, D.host, D.anchor, D.ifree, D.okind, D.opoint, D.oframe, D.oxy, D.oinfo, D.lstart, D.llist,
+                     opt.huber_delta, gpr->projection, Z.with_cam ? 1 : 0, cam_free, Z.nf, Z.rec};
+  // first cost
+  GH_TRY(graph_enqueue_cost(ctx, R, D.S, D.xyz, D.rho, D.cam, nullptr));
+  GH_HIP(ctx, hipMemcpyAsync(R.rb->out4, D.out, 32, hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  GraphLoop L;
+  L.cost = sum->initial_cost = R.rb->out4[0] + R.rb->out4[2];
+  L.radius = opt.initial_radius;
+  int it = 0;
   for (it = 0; it < opt.max_iterations; ++it) {
-    if (need_lin) {
-      if (sparse) GH_HIP(ctx, hipMemsetAsync(BS.d_H, 0, BS.n_vals * sizeof(double), ctx->stream));
-      else GH_HIP(ctx, hipMemsetAsync(d_H, 0, (size_t)n * lda * sizeof(double), ctx->stream));
-      GH_HIP(ctx, hipMemsetAsync(d_gmax, 0, 8, ctx->stream));
-      GH_HIP(ctx, hipMemsetAsync(d_Hpp, 0, nlm1 * 72, ctx->stream));
-      GH_HIP(ctx, hipMemsetAsync(d_gp, 0, nlm1 * 24, ctx->stream));
-      if (det) {
-        GH_HIP(ctx, hipMemsetAsync(d_acc_hi, 0, (size_t)n * lda * sizeof(double), ctx->stream));
-        GH_HIP(ctx, hipMemsetAsync(d_acc_lo, 0, (size_t)n * lda * sizeof(double), ctx->stream));
-        GH_HIP(ctx, hipMemsetAsync(d_vacc, 0, (size_t)2 * n * sizeof(double), ctx->stream));
-        GH_HIP(ctx, hipMemsetAsync(d_bound, 0, 8, ctx->stream));
-      }
-      if (ne > 0) GH_LAUNCH(ctx, "pg_edge", pg_edge_kernel, dim3(eb4), dim3(64), 0, G, (const double*)d_S, d_rec, d_cost_e);
-      // stores the pose-edge sums into every diagonal block, every edge pair block and g (zeros where there is no edge)
-      if (sparse)
-        GH_LAUNCH(ctx, "pg_assemble_bs", pg_assemble_bs_kernel, dim3(nf + PH.n_pairs), dim3(64), 0, G, Ls, (const double*)d_rec, BS.d_H,
-                  BsDest{d_bs_off, d_bs_sp, d_bs_sq}, d_g);
-      else
-        GH_LAUNCH(ctx, "pg_assemble", pg_assemble_kernel, dim3(nf + PH.n_pairs), dim3(64), 0, G, Ls, (const double*)d_rec, d_H, lda,
-                  d_g, d_gmax);
-      if (with_cam) GH_HIP(ctx, hipMemsetAsync(d_g + 7 * nf, 0, 72, ctx->stream));  // (pg_assemble stores the keyframe rows only)
-      if (no > 0)
-        GH_LAUNCH(ctx, "gr_obs_lin", gr_obs_lin_kernel, dim3(ob), dim3(128), 0, LM, (const int32_t*)d_dof, (const double*)d_S,
-                  (const double*)d_xyz, (const double*)d_rho, (const double*)d_cam, d_orec, d_valid, d_H, lda, d_g, d_Hpp, d_gp, d_cam_part,
-                  d_bound);
-      if (det && nlm > 0)
-        GH_LAUNCH(ctx, "gr_lm_sum", gr_lm_sum_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                  (const double*)d_orec, d_Hpp, d_gp);
-      if (with_cam)
-        GH_LAUNCH(ctx, "gr_cam_fold", gr_cam_fold_kernel, dim3(1), dim3(1024), 0, (const double*)d_cam_part, 2 * ob, nf, d_H, lda, d_g);
-      if (no > 0)
-        GH_LAUNCH(ctx, "gr_frame_rows", gr_frame_rows_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                  (const double*)d_orec, d_H, lda, d_g, DA);
-      if (det) {  // H += hi + lo, g likewise; the accumulators are cleared again for the Schur products of the iterations
-        GH_LAUNCH(ctx, "gr_det_fold", gr_det_fold_kernel, dim3(gh_div_up((long long)n * lda + n, 256)), dim3(256), 0, d_H,
-                  (const double*)d_acc_hi, (const double*)d_acc_lo, n, lda, d_g, (const double*)d_vacc, (const double*)(d_vacc + n), n);
-      }
-      GH_HIP(ctx, hipMemsetAsync(d_gmax, 0, 8, ctx->stream));
-      GH_LAUNCH(ctx, "gr_gmax", gr_gmax_kernel, dim3(gh_div_up(n + 3 * nlm, 256)), dim3(256), 0, (const double*)d_g, n,
-                (const double*)d_gp, 3 * nlm, d_gmax);
-      // (read behind the solve below, which synchronises anyway: if the gradient test fires, the step computed meanwhile is
-      //  simply dropped -- same decisions, one host round trip less per iteration)
-      GH_HIP(ctx, hipMemcpyAsync(&rb->gmax_bits, d_gmax, 8, hipMemcpyDeviceToHost, ctx->stream));
-      fresh_gmax = true;
-      need_lin = false;
-    }
-    if (!sparse)
-      GH_LAUNCH(ctx, "pg_damp", pg_damp_kernel, dim3(gh_div_up((long long)n * lda, 256)), dim3(256), 0, (const double*)d_H, d_Hd,
-                n, lda, (const double*)d_g, d_d, radius);
-    if (nlm > 0) {
-      if (det) {
-        GH_HIP(ctx, hipMemsetAsync(d_acc_hi, 0, (size_t)n * lda * sizeof(double), ctx->stream));
-        GH_HIP(ctx, hipMemsetAsync(d_acc_lo, 0, (size_t)n * lda * sizeof(double), ctx->stream));
-        GH_HIP(ctx, hipMemsetAsync(d_vacc, 0, (size_t)2 * n * sizeof(double), ctx->stream));
-      }
-      GH_LAUNCH(ctx, "gr_lm_prepare", gr_lm_prepare_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                (const double*)d_Hpp, (const double*)d_orec, radius, d_Hinv, d_lmdim, d_Wh, d_hrep, d_Wc);
-      if (no > 0)
-        GH_LAUNCH(ctx, "gr_schur", gr_schur_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                  (const double*)d_orec, (const double*)d_Hinv, (const int32_t*)d_lmdim, (const double*)d_Wh, (const int32_t*)d_hrep,
-                  (const double*)d_gp, d_Hd, lda, d_d, DA);
-      if (with_cam)
-        GH_LAUNCH(ctx, "gr_schur_cam", gr_schur_cam_kernel, dim3(gh_div_up(16 * no, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                  (const double*)d_orec, (const double*)d_Hinv, (const int32_t*)d_lmdim, (const double*)d_Wh, (const int32_t*)d_hrep,
-                  (const double*)d_Wc, d_Hd, lda, DA);
-      if (with_cam)
-        GH_LAUNCH(ctx, "gr_schur_cam_cc", gr_schur_cam_cc_kernel, dim3(gh_div_up(nlm, 128)), dim3(128), 0, LM, (const double*)d_Hinv,
-                  (const int32_t*)d_lmdim, (const double*)d_Wc, (const double*)d_gp, d_Hd, lda, d_d, DA);
-      if (det)
-        GH_LAUNCH(ctx, "gr_det_fold", gr_det_fold_kernel, dim3(gh_div_up((long long)n * lda + n, 256)), dim3(256), 0, d_Hd,
-                  (const double*)d_acc_hi, (const double*)d_acc_lo, n, lda, d_d, (const double*)d_vacc, (const double*)(d_vacc + n), n);
-    }
+    if (L.need_lin) GH_TRY(graph_enqueue_linearise(ctx, R, L));
+    GH_TRY(graph_enqueue_system(ctx, R, L.radius));
     int info = 0;
     const double t_s0 = now_ms_pg();
-    if (sparse) {
-      GH_TRY(BS.factor_solve(ctx, radius, d_g, d_d, &info));
-    } else {
-      rb->info = 0;
-      GH_TRY(gh_potrf_solve_dev(ctx, d_Hd, n, lda, d_d, &rb->info));
-      info = rb->info;
-    }
+    GH_TRY(graph_linear_solve(ctx, R, L.radius, &info));
     sum->solve_ms_total += now_ms_pg() - t_s0;
-    if (fresh_gmax) {  // (both solve paths end with a stream synchronisation: the gradient maximum is on the host)
-      fresh_gmax = false;
+    if (L.fresh_gmax) {  // (both solve paths end with a stream synchronisation: the gradient maximum is on the host)
+      L.fresh_gmax = false;
       double gmax;
-      memcpy(&gmax, &rb->gmax_bits, 8);
+      memcpy(&gmax, &R.rb->gmax_bits, 8);
       if (gmax <= opt.gradient_tolerance) {
-        term = 2;
+        L.term = 2;
         break;
       }
     }
-    const bool okf = info == 0;
-    double new_cost = cost, model = 0, rho = -1;
-    if (okf) {
-      if (nlm > 0)
-        GH_LAUNCH(ctx, "gr_backsub", gr_backsub_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, LM, (const uint8_t*)d_valid,
-                  (const double*)d_orec, (const double*)d_Hinv, (const int32_t*)d_lmdim, (const double*)d_gp, (const double*)d_d, d_dlm);
-      if (n_items > 0)
-        GH_LAUNCH(ctx, "gr_model", gr_model_kernel, dim3(gh_div_up(n_items, 256)), dim3(256), 0, G, LM, (const double*)d_rec,
-                  (const uint8_t*)d_valid, (const double*)d_orec, (const double*)d_d, (const double*)d_dlm, d_term);
-      GH_TRY(reduce_to(d_term, n_items, 1));
-      GH_LAUNCH(ctx, "pg_update", pg_update_kernel, dim3(gh_div_up(nf, 256)), dim3(256), 0, nf, (const int32_t*)d_dof,
-                (const double*)d_S, (const double*)d_d, d_Snew);
-      if (nlm > 0)
-        GH_LAUNCH(ctx, "gr_update", gr_update_kernel, dim3(gh_div_up(nlm, 256)), dim3(256), 0, nx, ni, (const double*)d_xyz,
-                  (const double*)d_rho, (const double*)d_dlm, d_xyz_new, d_rho_new, (const double*)d_cam,
-                  (const double*)(d_d + 7 * nf), with_cam ? gpr->intrinsics_free : 0, d_cam_new);
-      GH_TRY(enqueue_cost(d_Snew, d_xyz_new, d_rho_new, d_cam_new, d_valid));
-      GH_HIP(ctx, hipMemcpyAsync(host4, d_out, 32, hipMemcpyDeviceToHost, ctx->stream));
-      GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      new_cost = host4[0] + host4[2];
-      model = host4[1];
-      rho = model > 0 ? (cost - new_cost) / model : -1;
-      if (!(new_cost == new_cost)) rho = -1;
-    }
-    const bool acc = okf && rho > opt.min_relative_decrease;
-    if (sum->trace_len < GH_BA_MAX_TRACE) {
-      sum->trace_cost[sum->trace_len] = new_cost;
-      sum->trace_radius[sum->trace_len] = radius;
-      sum->trace_accepted[sum->trace_len] = (uint8_t)acc;
-      sum->trace_len++;
-    }
-    if (opt.verbose)
-      fprintf(stderr, "[gh_graph] it %3d cost %.9e -> %.9e model %.3e rho %.3f radius %.3e %s\n", it, cost, new_cost, model, rho,
-              radius, acc ? "accepted" : (okf ? "rejected" : "solve failed"));
-    if (acc) {
-      const double dcost = cost - new_cost;
-      std::swap(d_S, d_Snew);
-      std::swap(d_xyz, d_xyz_new);
-      std::swap(d_rho, d_rho_new);
-      std::swap(d_cam, d_cam_new);
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      if (radius > 1e16) radius = 1e16;
-      decrease = 2.0;
-      sum->accepted++;
-      need_lin = true;
-      const double prev = cost;
-      cost = new_cost;
-      if (fabs(dcost) <= opt.function_tolerance * prev) {
-        term = 1;
-        ++it;
-        break;
-      }
-    } else {
-      radius = radius / decrease;
-      decrease *= 2.0;
-      if (radius < 1e-32) {
-        term = 3;
-        ++it;
-        break;
-      }
+    if (info == 0) GH_TRY(graph_enqueue_trial(ctx, R, cam_free));
+    if (graph_decide(R, opt, sum, L, info == 0, it)) {
+      ++it;
+      break;
     }
   }
   sum->iterations = it;
-  sum->termination = term;
-  sum->final_cost = cost;
-  {  // results: through the pinned block too (the read-back words are not needed any more)
-    const size_t bS = (size_t)nf * 64, bX = (size_t)nx * 24, bR = (size_t)ni * 8;
-    const size_t oX = (bS + 255) & ~(size_t)255, oR = oX + ((bX + 255) & ~(size_t)255), oC = oR + ((bR + 255) & ~(size_t)255);
-    void* hp = nullptr;
-    GH_TRY(gh_pinned(ctx, oC + 72 + 256, &hp));
-    char* h = static_cast<char*>(hp);
-    GH_HIP(ctx, hipMemcpyAsync(h, d_S, bS, hipMemcpyDeviceToHost, ctx->stream));
-    if (nx) GH_HIP(ctx, hipMemcpyAsync(h + oX, d_xyz, bX, hipMemcpyDeviceToHost, ctx->stream));
-    if (ni) GH_HIP(ctx, hipMemcpyAsync(h + oR, d_rho, bR, hipMemcpyDeviceToHost, ctx->stream));
-    if (with_cam) GH_HIP(ctx, hipMemcpyAsync(h + oC, d_cam, 72, hipMemcpyDeviceToHost, ctx->stream));
-    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(pr->frame_sim3, h, bS);
-    if (nx) memcpy(gpr->xyz, h + oX, bX);
-    if (ni) memcpy(gpr->idp_rho, h + oR, bR);
-    if (with_cam) memcpy(gpr->intrinsics, h + oC, 72);
-  }
+  sum->termination = L.term;
+  sum->final_cost = L.cost;
+  GH_TRY(graph_download(ctx, R, gpr));
   sum->total_ms = now_ms_pg() - t_begin;
-  return term == 3 ? GH_ERR_NUMERIC : GH_OK;
+  return L.term == 3 ? GH_ERR_NUMERIC : GH_OK;
 }
 
 // The pose graph alone is the general graph without landmarks (no atomics are involved then: the assembly is the

@@ -102,11 +102,21 @@ def test_graph_arena_bit_identical_to_one_allocation_per_array(ctx, monkeypatch)
     """graph_arena.h: the arrays of a solve bump-allocated from the context's grow-only arena and the uploads sent as one
     staged DMA must not change a bit against one hipMalloc / one copy per array (GSLAM_HIP_PG_ARENA=0) -- on the dense and
     the block-sparse path, on an arena that has to grow, one that is reused with the previous solve's contents in it, and
-    one that is larger than the solve (a small graph after a large one)."""
+    one that is larger than the solve (a small graph after a large one).  The same for the general graph (landmark,
+    intrinsics and reproducible-accumulation arrays, deterministic = 1): landmarks only with no pose edge and no
+    inverse-depth point (the max(., 1) sizes), pose edges + 2 x 2 informations, and that graph with free intrinsics."""
     from gslam_amd import ba, posegraph
+    from gslam_amd.pg_synth import make_landmark_graph, with_camera
     graphs = [make_pose_graph(nf, loops, kind=kind, seed=31 + nf, noise=0.01, perturb=0.04, scale_drift=0.1, gps_every=gps,
                               with_info=info)
               for nf, loops, kind, gps, info in ((60, 10, "mixed", 6, True), (500, 70, "sim3", 0, False), (90, 12, "se3", 0, False))]
+    _, start_l, dof_l, only_landmarks = make_landmark_graph(n_frames=12, n_xyz=150, n_idp=0, kind="se3", seed=43, noise=1e-3)
+    _, start_m, dof_m, mixed = make_landmark_graph(n_frames=12, n_xyz=80, n_idp=80, kind="sim3", seed=44, noise=1e-3,
+                                                   pose_edges=True, with_info=True)
+    cam = np.array([520.0, 515.0, 318.0, 242.0, -0.28, 0.09, 1.2e-3, -8e-4, -0.01])
+    calib = with_camera(mixed, cam, cam * np.array([1.03, 0.97, 1.01, 0.99, 1, 1, 1, 1, 1]), 0b000001111, pixel_noise=0.2, seed=2)
+    assert "se3" not in only_landmarks and "sim3" not in only_landmarks and len(mixed["sim3"][0]) > 0
+    general = [(start_l, dof_l, only_landmarks, 0.0), (start_m, dof_m, mixed, 0.0), (start_m, dof_m, calib, 2.0)]
 
     def run_all():
         out = []
@@ -114,6 +124,11 @@ def test_graph_arena_bit_identical_to_one_allocation_per_array(ctx, monkeypatch)
             S, sm, st = posegraph.solve(ctx, start, dof, prob, ba.default_options(max_iterations=6))
             assert st == 0
             out.append((S.tobytes(), list(sm.trace_cost[:sm.trace_len]), sm.iterations))
+        for start, dof, prob, huber in general:
+            *state, sm, st = posegraph.solve_graph(ctx, start, dof, prob, ba.default_options(max_iterations=8, huber_delta=huber))
+            assert st == 0 and sm.trace_len > 0
+            out.append(([a.tobytes() for a in state], list(sm.trace_cost[:sm.trace_len]), list(sm.trace_radius[:sm.trace_len]),
+                        list(sm.trace_accepted[:sm.trace_len]), sm.iterations))
         return out
 
     monkeypatch.setenv("GSLAM_HIP_PG_ARENA", "0")
