@@ -1637,6 +1637,7 @@ struct gh_orb_plan {
   size_t lvl_off[kMaxL]{};  // offset of level l inside one frame's pyramid slab
   size_t slab = 0;
   int cells_per_frame = 0;
+  int max_level_cells = 0;  // cells of the largest level: decides cached / streamed select (orb_schedule)
   uint8_t* pyr = nullptr;
   uint32_t* xtab[kMaxL]{};
   uint32_t* ytab[kMaxL]{};
@@ -1668,7 +1669,7 @@ struct gh_orb_plan {
   // single-frame host entry point: device staging (image; count | keypoints | descriptors in ONE block so that the
   // results come back in one copy) and a pinned host mirror of the result block
   // small calls are launch-bound (11 launches for a 640x480 frame whose kernels take a few microseconds each): the launch
-  // sequence of a call is captured once per argument set and replayed as ONE hipGraph launch (gh_orb_extract_dev)
+  // sequence of a call is captured once per argument set and replayed as ONE hipGraph launch (graphs_replay)
   struct CallGraph {
     const void *gray, *kps, *desc, *counts;
     int batch, row_stride;
@@ -1684,8 +1685,8 @@ struct gh_orb_plan {
   std::vector<CallGraph> graphs, retired;
   long long graph_hits = 0, graph_misses = 0;
   hipStream_t cap_stream = nullptr;  // the capture runs on a stream of the plan, never on the caller's (another host thread may be enqueuing there)
-  bool graphs_off = false, capturing = false;
-  // batched calls: select(level l) runs on a side stream beside fast_cells(l + 1 ..) (gh_orb_extract_dev)
+  bool graphs_off = false;
+  // batched calls: select(level l) runs on a side stream beside fast_cells(l + 1 ..) (orb_schedule, enqueue_per_level)
   hipStream_t side = nullptr;
   hipEvent_t ev_level[kMaxL]{}, ev_join = nullptr;
   uint8_t* stage_img = nullptr;
@@ -1709,6 +1710,8 @@ static gh_status plan_alloc(gh_orb_plan* p, size_t bytes, void** out) {
   return s;
 }
 
+static void graphs_drop_all(gh_orb_plan* p);  // (the graph cache, below)
+
 extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
   if (!p) return;
   gh_ctx* c = p->ctx;
@@ -1720,12 +1723,7 @@ extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
     if (q) hipFree(q);
   if (p->stage_host) hipHostFree(p->stage_host);
   gh_qt_destroy(p->qt);
-  for (auto* v : {&p->graphs, &p->retired})
-    for (auto& g : *v) {
-      hipEventSynchronize(g.done);  // (the caller may have moved the context to another stream since the last launch)
-      hipGraphExecDestroy(g.exec);
-      hipEventDestroy(g.done);
-    }
+  graphs_drop_all(p);
   if (p->cap_stream) hipStreamDestroy(p->cap_stream);
   if (p->side) {
     hipStreamSynchronize(p->side);
@@ -1820,15 +1818,23 @@ extern "C" gh_status gh_orb_plan_set_steering(gh_orb_plan* p, int mode) {
     return gh_set_error(ctx, GH_ERR_ARG, "the installed test pattern has points beyond radius 13.49: it only works with continuous steering");
   GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   p->steer = mode;
-  // (graphs captured for the other mode hold the other kernel)
-  for (auto* v : {&p->graphs, &p->retired})
-    for (auto& g : *v) {
-      hipEventSynchronize(g.done);
-      hipGraphExecDestroy(g.exec);
-      hipEventDestroy(g.done);
-    }
-  p->graphs.clear();
-  p->retired.clear();
+  graphs_drop_all(p);  // (graphs captured for the other mode hold the other kernel)
+  return GH_OK;
+}
+
+// mode 1: S of every level (fast_cells_kernel<true>), one slab per frame, zeroed
+static gh_status plan_alloc_score_plane(gh_orb_plan* p) {
+  gh_ctx* ctx = p->ctx;
+  size_t off = 0;
+  for (int l = 0; l < p->L; ++l) {
+    p->plane_pitch[l] = p->pitch[l] + 128;  // (a multiple of 64: rows start on a 64-byte boundary, like the tile rows)
+    p->plane_off[l] = off;
+    off += (size_t)p->plane_pitch[l] * p->lh[l];
+  }
+  p->plane_slab = (off + 255) & ~(size_t)255;
+  GH_TRY(plan_alloc(p, (size_t)p->max_batch * p->plane_slab, (void**)&p->score_plane));
+  GH_HIP(ctx, hipMemsetAsync(p->score_plane, 0, (size_t)p->max_batch * p->plane_slab, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GH_OK;
 }
 
@@ -1837,22 +1843,259 @@ extern "C" gh_status gh_orb_plan_set_distribution(gh_orb_plan* p, int mode) {
   gh_ctx* ctx = p->ctx;
   GH_ENTER(ctx);
   GH_CHECK_ARG(ctx, mode == 0 || mode == 1);
-  if (mode == 1 && !p->score_plane) {  // the quadtree buffers and S of every level (fast_cells_kernel<true>)
+  if (mode == 1 && !p->score_plane) {  // the quadtree buffers and the score planes
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!p->qt) GH_TRY(gh_qt_create(ctx, p->L, p->lw, p->lh, p->quota, p->max_batch, &p->qt, &p->bytes));
-    size_t off = 0;
-    for (int l = 0; l < p->L; ++l) {
-      p->plane_pitch[l] = p->pitch[l] + 128;  // (a multiple of 64: rows start on a 64-byte boundary, like the tile rows)
-      p->plane_off[l] = off;
-      off += (size_t)p->plane_pitch[l] * p->lh[l];
-    }
-    p->plane_slab = (off + 255) & ~(size_t)255;
-    GH_TRY(plan_alloc(p, (size_t)p->max_batch * p->plane_slab, (void**)&p->score_plane));
-    GH_HIP(ctx, hipMemsetAsync(p->score_plane, 0, (size_t)p->max_batch * p->plane_slab, ctx->stream));
-    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GH_TRY(plan_alloc_score_plane(p));
   }
   p->distribution = mode;
   return GH_OK;
+}
+
+// ---- plan creation: parameter checks, level geometry, table sizing, allocation, one builder per kind of table, uploads
+static gh_status plan_check_params(gh_ctx* ctx, int width, int height, int max_batch, const gh_orb_params& prm) {
+  GH_CHECK_ARG(ctx, width >= 2 * kEdge + 1 && height >= 2 * kEdge + 1 && width <= 16384 && height <= 16384);
+  GH_CHECK_ARG(ctx, max_batch >= 1 && max_batch <= 65535);
+  GH_CHECK_ARG(ctx, prm.n_levels >= 1 && prm.n_levels <= kMaxL && prm.n_features >= 1 && prm.n_features <= (1 << 20));
+  GH_CHECK_ARG(ctx, prm.min_th_fast >= 1 && prm.ini_th_fast >= prm.min_th_fast && prm.ini_th_fast <= 254);
+  return GH_OK;
+}
+
+// geometry (oracle step 1 / 5): sizes, pitches, slab offsets, quotas, cell grids and scales in exact integer arithmetic
+static void plan_geometry(gh_orb_plan* p) {
+  const int L = p->L, K = p->prm.n_features;
+  const long long den = ipow(6, L) - ipow(5, L);
+  int qsum = 0;
+  size_t off = 0;
+  int coff = 0;
+  for (int l = 0; l < L; ++l) {
+    long long p5 = ipow(5, l), p6 = ipow(6, l);
+    p->lw[l] = (int)((2LL * p->w * p5 + p6) / (2 * p6));
+    p->lh[l] = (int)((2LL * p->h * p5 + p6) / (2 * p6));
+    p->pitch[l] = (p->lw[l] + 63) & ~63;
+    p->lvl_off[l] = off;
+    off += (size_t)p->pitch[l] * p->lh[l];
+    off = (off + 255) & ~(size_t)255;
+    if (l < L - 1) {
+      long long num = (long long)K * ipow(5, l) * ipow(6, L - 1 - l);
+      p->quota[l] = (int)((2 * num + den) / (2 * den));
+      if (p->quota[l] > K - qsum) p->quota[l] = K - qsum;
+      qsum += p->quota[l];
+    } else {
+      p->quota[l] = K - qsum > 0 ? K - qsum : 0;
+    }
+    p->scale[l] = l == 0 ? 1.0f : p->scale[l - 1] * 1.2f;
+    const int vw = p->lw[l] - 2 * kEdge, vh = p->lh[l] - 2 * kEdge;
+    p->ncx[l] = vw > 0 ? (vw + kCell - 1) / kCell : 0;
+    p->ncy[l] = vh > 0 ? (vh + kCell - 1) / kCell : 0;
+    if (p->ncx[l] == 0 || p->ncy[l] == 0) p->ncx[l] = p->ncy[l] = 0;
+    p->cell_off[l] = coff;
+    coff += p->ncx[l] * p->ncy[l];
+    if (p->ncx[l] * p->ncy[l] > p->max_level_cells) p->max_level_cells = p->ncx[l] * p->ncy[l];
+  }
+  // a level without a valid region selects nothing: its quota is simply unused (as in the oracle)
+  int qo = 0;
+  for (int l = 0; l < L; ++l) {
+    p->quota_off[l] = qo;
+    qo += p->quota[l];
+  }
+  p->slab = off + 256;  // tail pad: the tile loader may read a clamped dword at the very end
+  p->cells_per_frame = coff > 0 ? coff : 1;
+}
+
+// Words of each kind of table.  Every table starts 32-byte aligned, so each is padded to a multiple of 8 words.  The sizing
+// (plan_table_words) and the builders (plan_build_tables checks each against its cursor) both go through these.
+static size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
+// source index / fraction per output column or row of a level
+static size_t axis_words(int n_dst) { return pad8((size_t)n_dst); }
+// selector + weight per padded output column
+static size_t lerp_words(int wd) { return 2 * pad8((size_t)wd); }
+// the MFMA resize's A operands (256 words per 8-column group) and window starts (one word per group)
+static size_t mfma_words(int wd) {
+  const size_t ngr = ((size_t)wd + 7) / 8;
+  return ngr * 256 + pad8(ngr);
+}
+// ownership of the next level by the tile columns / rows of fast_cells: one word per tile + 1
+static size_t own_words(int ncells) { return pad8((size_t)(ncells + 1) / 2 + 1); }
+
+static size_t plan_table_words(const gh_orb_plan* p) {
+  size_t words = 0;
+  for (int l = 1; l < p->L; ++l) words += axis_words(p->lw[l]) + lerp_words(p->lw[l]) + axis_words(p->lh[l]);
+  for (int l = 1; l < p->L; ++l) words += mfma_words(p->lw[l]);
+  for (int l = 0; l + 1 < p->L; ++l) words += own_words(p->ncx[l]) + own_words(p->ncy[l]);
+  return words;
+}
+
+static gh_status plan_allocate(gh_orb_plan* p, size_t tab_words) {
+  const size_t B = (size_t)p->max_batch;
+  const int K = p->prm.n_features;
+  GH_TRY(plan_alloc(p, B * p->slab, (void**)&p->pyr));
+  GH_TRY(plan_alloc(p, B * p->cells_per_frame * kCellRec * sizeof(uint32_t), (void**)&p->cell_cnt));
+  GH_TRY(plan_alloc(p, B * p->cells_per_frame * kCap * sizeof(uint32_t), (void**)&p->cell_ent));
+  GH_TRY(plan_alloc(p, B * K * sizeof(SelKp), (void**)&p->sel));
+  GH_TRY(plan_alloc(p, B * kMaxL * sizeof(int32_t), (void**)&p->level_cnt));
+  GH_TRY(plan_alloc(p, sizeof(GH_ORB_PATTERN), (void**)&p->d_pattern));
+  GH_TRY(plan_alloc(p, 256 * 4, (void**)&p->d_base_pattern));
+  GH_TRY(plan_alloc(p, sizeof(GH_ORB_DIR), (void**)&p->d_dir));
+  return plan_alloc(p, tab_words * sizeof(uint32_t), (void**)&p->tabs);
+}
+
+// Axis table of one level: per output column (x_axis) or row, source index << 16 | 11-bit fraction of the lerp.  The pads
+// of an x table continue with the next source column, fraction 0, so that the per-thread window bounds hold; the pads of
+// a y table replicate the last row.
+static void build_axis_table(std::vector<uint32_t>& htab, size_t& tw, int n_src, int n_dst, bool x_axis) {
+  for (int x = 0; x < n_dst; ++x) {
+    long long P = ((long long)(2 * x + 1) * n_src * 2048) / (2LL * n_dst) - 1024;
+    if (P < 0) P = 0;
+    int sx = (int)(P >> 11), fx = (int)(P & 2047);
+    if (sx >= n_src - 1) {
+      sx = n_src - 1;
+      fx = 0;
+    }
+    htab[tw++] = ((uint32_t)sx << 16) | (uint32_t)fx;
+  }
+  while (tw & 7) {  // keeps every table 32-byte aligned
+    htab[tw] = x_axis ? ((htab[tw - 1] >> 16) + 1u) << 16 : htab[tw - 1];
+    ++tw;
+  }
+}
+
+// The per-column selector / weight tables derived from the x table `t` of nx_pad entries (ResizeTabs).  False when the
+// table breaks the window contract of resize_kernel: within a group of 8 columns, taps of columns 0..3 lie in window
+// bytes 0..7 and taps of columns 4..7 in bytes 4..11 (true for the 1.2 scale).
+static bool build_lerp_tables(std::vector<uint32_t>& htab, size_t& tw, size_t x0, size_t nx_pad, int n_src) {
+  const uint32_t* t = htab.data() + x0;
+  for (size_t g = 0; g + 8 <= nx_pad; g += 8)
+    for (int i = 0; i < 8; ++i) {
+      const int o = (int)(t[g + i] >> 16) - (int)(t[g] >> 16) - (i >= 4 ? 4 : 0);
+      if (o < 0 || o + 1 > 7) return false;
+    }
+  for (size_t c = 0; c < nx_pad; ++c) {
+    const int sx = (int)(t[c] >> 16), sx0 = (int)(t[c & ~(size_t)7] >> 16), hi = (c & 7) >= 4 ? 4 : 0;
+    const int o = sx - sx0 - hi;
+    int sx1 = sx + 1 < n_src ? sx + 1 : n_src - 1;
+    if (sx1 < sx) sx1 = sx;  // pad entries past the last source column
+    const int o1 = sx1 - sx0 - hi;
+    const uint32_t fx = t[c] & 0xFFFFu;
+    htab[tw + c] = 0x0c000c00u | ((uint32_t)(o1 & 7) << 16) | (uint32_t)(o & 7);
+    htab[tw + nx_pad + c] = (fx << 16) | (2048u - fx);
+  }
+  tw += 2 * nx_pad;
+  return true;
+}
+
+// fp16 bits of an integer weight, 0 <= v <= 2048: exact
+static uint32_t f16_of(int v) {
+  if (v == 0) return 0u;
+  int e = 0;
+  while ((v >> (e + 1)) != 0) ++e;
+  const int mant = e <= 10 ? (v << (10 - e)) : (v >> (e - 10));  // (v = 2048 has e = 11: a shift by -1 is undefined)
+  return (uint32_t)(((e + 15) << 10) | (mant & 0x3FF));
+}
+
+// MFMA resize tables of level l (as a destination): see ResizeTabs / resize_tile_mfma.  The level goes without them
+// (mtab = mcw = null) when the 32-column K window of a group cannot hold both taps of all its columns.
+static void build_mfma_tables(gh_orb_plan* p, int l, std::vector<uint32_t>& htab, size_t& tw) {
+  const uint32_t* xt = htab.data() + (p->xtab[l] - p->tabs);
+  const int wd = p->lw[l], ngr = (wd + 7) / 8, n_src = p->lw[l - 1];
+  uint32_t* mt = htab.data() + tw;
+  uint32_t* mc = htab.data() + tw + (size_t)ngr * 256;
+  bool ok = true;
+  for (int g = 0; g < ngr; ++g) {
+    const int cw = (int)(xt[8 * g] >> 16) & ~7;
+    mc[g] = (uint32_t)cw;
+    for (int lane = 0; lane < 64; ++lane) {
+      const int m = lane & 15, x = 8 * g + m;
+      uint32_t wds[4] = {0, 0, 0, 0};
+      if (x < wd) {
+        const int sx = (int)(xt[x] >> 16), fx = (int)(xt[x] & 0xFFFFu);
+        const int k0 = sx - cw, k1 = (sx + 1 < n_src ? sx + 1 : n_src - 1) - cw;
+        if (k0 < 0 || k1 > 31) ok = false;  // the 32-column K window must hold both taps of all 16 columns
+        for (int e = 0; e < 8; ++e) {
+          const int k = 8 * (lane >> 4) + e;
+          int wgt = 0;
+          if (k == k0) wgt += 2048 - fx;
+          if (k == k1) wgt += fx;  // (k1 == k0 at the right border, where fx = 0)
+          wds[e >> 1] |= f16_of(wgt) << (16 * (e & 1));
+        }
+      }
+      for (int e = 0; e < 4; ++e) mt[((size_t)g * 64 + lane) * 4 + e] = wds[e];
+    }
+  }
+  p->mtab[l] = ok ? p->tabs + tw : nullptr;
+  p->mcw[l] = ok ? p->tabs + tw + (size_t)ngr * 256 : nullptr;
+  tw += mfma_words(wd);
+}
+
+// Ownership of level l + 1 inside fast_cells(l): tile column bx (level-l columns 64 bx .. 64 bx + 63 plus halo) owns
+// the output 8-groups whose first source column lies in [64 bx, 64 bx + 64); tile row by (rows from 64 by + 15) the
+// output rows whose source row lies in [64 by + 15, 64 by + 79); the first / last tile row and the last tile column
+// also take what lies outside every tile.  Any partition is CORRECT (resize_item reads global memory); this one
+// makes the reads hit the lines the tile load has just fetched.
+static void build_own_tables(gh_orb_plan* p, int l, std::vector<uint32_t>& htab, size_t& tw) {
+  const int nbx = (p->ncx[l] + 1) / 2, nby = (p->ncy[l] + 1) / 2;
+  const uint32_t* xt = htab.data() + (p->xtab[l + 1] - p->tabs);
+  const uint32_t* yt = htab.data() + (p->ytab[l + 1] - p->tabs);
+  const int ngroups = (p->lw[l + 1] + 7) / 8, hd = p->lh[l + 1];
+  p->own_gx[l] = reinterpret_cast<const int32_t*>(p->tabs + tw);
+  int g = 0;
+  for (int bx = 0; bx <= nbx; ++bx) {
+    if (bx == nbx) g = ngroups;
+    else
+      while (bx > 0 && g < ngroups && (int)(xt[8 * g] >> 16) < 64 * bx) ++g;
+    htab[tw++] = (uint32_t)g;
+  }
+  while (tw & 7) htab[tw++] = (uint32_t)ngroups;
+  p->own_gy[l] = reinterpret_cast<const int32_t*>(p->tabs + tw);
+  int y = 0;
+  for (int by = 0; by <= nby; ++by) {
+    if (by == nby) y = hd;
+    else
+      while (by > 0 && y < hd && (int)(yt[y] >> 16) < 64 * by + 15) ++y;
+    htab[tw++] = (uint32_t)y;
+  }
+  while (tw & 7) htab[tw++] = (uint32_t)hd;
+}
+
+// Fills the host copy of the table block and points the plan's table pointers into the device copy.  Layout: per level
+// x | selector | weight | y, then the MFMA tables of every level, then the ownership tables.  The cursor tw must end at
+// the size plan_table_words planned.
+static gh_status plan_build_tables(gh_orb_plan* p, std::vector<uint32_t>& htab, size_t tab_words) {
+  const int L = p->L;
+  size_t tw = 0;
+  for (int l = 1; l < L; ++l) {
+    p->xtab[l] = p->tabs + tw;
+    build_axis_table(htab, tw, p->lw[l - 1], p->lw[l], true);
+    const size_t nx_pad = axis_words(p->lw[l]);
+    p->xsel[l] = p->tabs + tw;
+    p->xwgt[l] = p->tabs + tw + nx_pad;
+    if (!build_lerp_tables(htab, tw, tw - nx_pad, nx_pad, p->lw[l - 1]))
+      return gh_set_error(p->ctx, GH_ERR_ARG, "resize table violates the 8-column window contract (level size ratio is not ~1.2)");
+    p->ytab[l] = p->tabs + tw;
+    build_axis_table(htab, tw, p->lh[l - 1], p->lh[l], false);
+  }
+  for (int l = 1; l < L; ++l) build_mfma_tables(p, l, htab, tw);
+  for (int l = 0; l + 1 < L; ++l) build_own_tables(p, l, htab, tw);
+  if (tw != tab_words) return gh_set_error(p->ctx, GH_ERR_ARG, "gh_orb_plan_create: the tables take %zu words, %zu were planned", tw, tab_words);
+  return GH_OK;
+}
+
+static gh_status plan_upload(gh_orb_plan* p, const std::vector<uint32_t>& htab) {
+  gh_ctx* ctx = p->ctx;
+  GH_TRY(gh_dev_upload(ctx, p->tabs, htab.data(), htab.size() * sizeof(uint32_t)));
+  GH_TRY(upload_pattern(p, &GH_ORB_PATTERN[0][0][0]));
+  memcpy(p->base_pattern, &GH_ORB_PATTERN[0][0][0], sizeof(p->base_pattern));  // bin 0 = the unrotated tests
+  GH_TRY(gh_dev_upload(ctx, p->d_base_pattern, p->base_pattern, sizeof(p->base_pattern)));
+  return gh_dev_upload(ctx, p->d_dir, GH_ORB_DIR, sizeof(GH_ORB_DIR));
+}
+
+static gh_status plan_init(gh_orb_plan* p) {
+  plan_geometry(p);
+  const size_t tab_words = plan_table_words(p);
+  std::vector<uint32_t> htab(tab_words ? tab_words : 1);
+  GH_TRY(plan_allocate(p, htab.size()));
+  GH_TRY(plan_build_tables(p, htab, tab_words));
+  return plan_upload(p, htab);
 }
 
 extern "C" gh_status gh_orb_plan_create(gh_ctx* ctx, int width, int height, int max_batch,
@@ -1863,10 +2106,7 @@ extern "C" gh_status gh_orb_plan_create(gh_ctx* ctx, int width, int height, int 
   gh_orb_params prm;
   gh_orb_default_params(&prm);
   if (params) prm = *params;
-  GH_CHECK_ARG(ctx, width >= 2 * kEdge + 1 && height >= 2 * kEdge + 1 && width <= 16384 && height <= 16384);
-  GH_CHECK_ARG(ctx, max_batch >= 1 && max_batch <= 65535);
-  GH_CHECK_ARG(ctx, prm.n_levels >= 1 && prm.n_levels <= kMaxL && prm.n_features >= 1 && prm.n_features <= (1 << 20));
-  GH_CHECK_ARG(ctx, prm.min_th_fast >= 1 && prm.ini_th_fast >= prm.min_th_fast && prm.ini_th_fast <= 254);
+  GH_TRY(plan_check_params(ctx, width, height, max_batch, prm));
   GH_HIP(ctx, hipSetDevice(ctx->device));
   gh_orb_plan* p = new (std::nothrow) gh_orb_plan();
   if (!p) return GH_ERR_NOMEM;
@@ -1875,196 +2115,8 @@ extern "C" gh_status gh_orb_plan_create(gh_ctx* ctx, int width, int height, int 
   p->h = height;
   p->max_batch = max_batch;
   p->prm = prm;
-  const int L = p->L = prm.n_levels;
-  // geometry (oracle step 1 / 5): exact integer arithmetic
-  long long den = ipow(6, L) - ipow(5, L);
-  int qsum = 0;
-  size_t off = 0;
-  int coff = 0;
-  for (int l = 0; l < L; ++l) {
-    long long p5 = ipow(5, l), p6 = ipow(6, l);
-    p->lw[l] = (int)((2LL * width * p5 + p6) / (2 * p6));
-    p->lh[l] = (int)((2LL * height * p5 + p6) / (2 * p6));
-    p->pitch[l] = (p->lw[l] + 63) & ~63;
-    p->lvl_off[l] = off;
-    off += (size_t)p->pitch[l] * p->lh[l];
-    off = (off + 255) & ~(size_t)255;
-    if (l < L - 1) {
-      long long num = (long long)prm.n_features * ipow(5, l) * ipow(6, L - 1 - l);
-      p->quota[l] = (int)((2 * num + den) / (2 * den));
-      if (p->quota[l] > prm.n_features - qsum) p->quota[l] = prm.n_features - qsum;
-      qsum += p->quota[l];
-    } else {
-      p->quota[l] = prm.n_features - qsum > 0 ? prm.n_features - qsum : 0;
-    }
-    p->scale[l] = l == 0 ? 1.0f : p->scale[l - 1] * 1.2f;
-    const int vw = p->lw[l] - 2 * kEdge, vh = p->lh[l] - 2 * kEdge;
-    p->ncx[l] = vw > 0 ? (vw + kCell - 1) / kCell : 0;
-    p->ncy[l] = vh > 0 ? (vh + kCell - 1) / kCell : 0;
-    if (p->ncx[l] == 0 || p->ncy[l] == 0) p->ncx[l] = p->ncy[l] = 0;
-    p->cell_off[l] = coff;
-    coff += p->ncx[l] * p->ncy[l];
-  }
-  // a level without a valid region selects nothing: its quota is simply unused (as in the oracle)
-  int qo = 0;
-  for (int l = 0; l < L; ++l) {
-    p->quota_off[l] = qo;
-    qo += p->quota[l];
-  }
-  p->slab = off + 256;  // tail pad: the tile loader may read a clamped dword at the very end
-  p->cells_per_frame = coff > 0 ? coff : 1;
-  gh_status st = GH_OK;
-  const size_t B = (size_t)max_batch;
-  const int K = prm.n_features;
-  // resize tables
-  size_t tab_words = 0;
-  // every table starts 32-byte aligned; x tables are padded to a multiple of 8 entries (pads continue with the next
-  // source column, fraction 0, so that the per-thread window bounds hold), y tables to a multiple of 4 (last replicated)
-  for (int l = 1; l < L; ++l) tab_words += 3 * (((size_t)p->lw[l] + 7) & ~(size_t)7) + (((size_t)p->lh[l] + 7) & ~(size_t)7);
-  // + the MFMA resize's A operands (256 words per 8-column group) and window starts (one word per group, padded to 8)
-  for (int l = 1; l < L; ++l) {
-    const size_t ngr = ((size_t)p->lw[l] + 7) / 8;
-    tab_words += ngr * 256 + ((ngr + 7) & ~(size_t)7);
-  }
-  // + per source level l < L - 1: ownership of level l + 1 by the tile columns / rows of fast_cells(l), padded to 8 words
-  for (int l = 0; l + 1 < L; ++l)
-    tab_words += (((size_t)(p->ncx[l] + 1) / 2 + 1 + 7) & ~(size_t)7) + (((size_t)(p->ncy[l] + 1) / 2 + 1 + 7) & ~(size_t)7);
-  std::vector<uint32_t> htab(tab_words ? tab_words : 1);
-  do {
-    if ((st = plan_alloc(p, B * p->slab, (void**)&p->pyr)) != GH_OK) break;
-    if ((st = plan_alloc(p, B * p->cells_per_frame * kCellRec * sizeof(uint32_t), (void**)&p->cell_cnt)) != GH_OK) break;
-    if ((st = plan_alloc(p, B * p->cells_per_frame * kCap * sizeof(uint32_t), (void**)&p->cell_ent)) != GH_OK) break;
-    if ((st = plan_alloc(p, B * K * sizeof(SelKp), (void**)&p->sel)) != GH_OK) break;
-    if ((st = plan_alloc(p, B * kMaxL * sizeof(int32_t), (void**)&p->level_cnt)) != GH_OK) break;
-    if ((st = plan_alloc(p, sizeof(GH_ORB_PATTERN), (void**)&p->d_pattern)) != GH_OK) break;
-    if ((st = plan_alloc(p, 256 * 4, (void**)&p->d_base_pattern)) != GH_OK) break;
-    if ((st = plan_alloc(p, sizeof(GH_ORB_DIR), (void**)&p->d_dir)) != GH_OK) break;
-    if ((st = plan_alloc(p, htab.size() * sizeof(uint32_t), (void**)&p->tabs)) != GH_OK) break;
-    size_t tw = 0;
-    for (int l = 1; l < L; ++l) {
-      for (int axis = 0; axis < 2; ++axis) {
-        const int n_src = axis == 0 ? p->lw[l - 1] : p->lh[l - 1];
-        const int n_dst = axis == 0 ? p->lw[l] : p->lh[l];
-        (axis == 0 ? p->xtab[l] : p->ytab[l]) = p->tabs + tw;
-        for (int x = 0; x < n_dst; ++x) {
-          long long P = ((long long)(2 * x + 1) * n_src * 2048) / (2LL * n_dst) - 1024;
-          if (P < 0) P = 0;
-          int sx = (int)(P >> 11), fx = (int)(P & 2047);
-          if (sx >= n_src - 1) {
-            sx = n_src - 1;
-            fx = 0;
-          }
-          htab[tw++] = ((uint32_t)sx << 16) | (uint32_t)fx;
-        }
-        while (tw & 7) {  // keeps every table 32-byte aligned
-          htab[tw] = axis == 0 ? ((htab[tw - 1] >> 16) + 1u) << 16 : htab[tw - 1];
-          ++tw;
-        }
-        if (axis == 0) {
-          // window contract of resize_kernel: within a group of 8 columns, taps of columns 0..3 lie in window bytes
-          // 0..7 and taps of columns 4..7 in bytes 4..11 (true for the 1.2 scale; refuse anything else loudly)
-          const size_t x0 = (size_t)(p->xtab[l] - p->tabs), nx_pad = tw - x0;
-          const uint32_t* t = htab.data() + x0;
-          for (size_t g = 0; g + 8 <= nx_pad; g += 8)
-            for (int i = 0; i < 8; ++i) {
-              const int o = (int)(t[g + i] >> 16) - (int)(t[g] >> 16) - (i >= 4 ? 4 : 0);
-              if (o < 0 || o + 1 > 7) st = GH_ERR_ARG;
-            }
-          // the per-column selector / weight tables derived from it (ResizeTabs)
-          p->xsel[l] = p->tabs + tw;
-          p->xwgt[l] = p->tabs + tw + nx_pad;
-          for (size_t c = 0; c < nx_pad; ++c) {
-            const int sx = (int)(t[c] >> 16), sx0 = (int)(t[c & ~(size_t)7] >> 16), hi = (c & 7) >= 4 ? 4 : 0;
-            const int o = sx - sx0 - hi;
-            int sx1 = sx + 1 < n_src ? sx + 1 : n_src - 1;
-            if (sx1 < sx) sx1 = sx;  // pad entries past the last source column
-            const int o1 = sx1 - sx0 - hi;
-            const uint32_t fx = t[c] & 0xFFFFu;
-            htab[tw + c] = 0x0c000c00u | ((uint32_t)(o1 & 7) << 16) | (uint32_t)(o & 7);
-            htab[tw + nx_pad + c] = (fx << 16) | (2048u - fx);
-          }
-          tw += 2 * nx_pad;
-        }
-      }
-    }
-    if (st != GH_OK) {
-      gh_set_error(ctx, st, "resize table violates the 8-column window contract (level size ratio is not ~1.2)");
-      break;
-    }
-    // MFMA resize tables of level l (as a destination): see ResizeTabs / resize_tile_mfma
-    for (int l = 1; l < L; ++l) {
-      const uint32_t* xt = htab.data() + (p->xtab[l] - p->tabs);
-      const int wd = p->lw[l], ngr = (wd + 7) / 8, n_src = p->lw[l - 1];
-      auto f16_of = [](int v) -> uint32_t {  // 0 <= v <= 2048: exact
-        if (v == 0) return 0u;
-        int e = 0;
-        while ((v >> (e + 1)) != 0) ++e;
-        const int mant = e <= 10 ? (v << (10 - e)) : (v >> (e - 10));  // (v = 2048 has e = 11: a shift by -1 is undefined)
-        return (uint32_t)(((e + 15) << 10) | (mant & 0x3FF));
-      };
-      uint32_t* mt = htab.data() + tw;
-      uint32_t* mc = htab.data() + tw + (size_t)ngr * 256;
-      bool ok = true;
-      for (int g = 0; g < ngr; ++g) {
-        const int cw = (int)(xt[8 * g] >> 16) & ~7;
-        mc[g] = (uint32_t)cw;
-        for (int lane = 0; lane < 64; ++lane) {
-          const int m = lane & 15, x = 8 * g + m;
-          uint32_t wds[4] = {0, 0, 0, 0};
-          if (x < wd) {
-            const int sx = (int)(xt[x] >> 16), fx = (int)(xt[x] & 0xFFFFu);
-            const int k0 = sx - cw, k1 = (sx + 1 < n_src ? sx + 1 : n_src - 1) - cw;
-            if (k0 < 0 || k1 > 31) ok = false;  // the 32-column K window must hold both taps of all 16 columns
-            for (int e = 0; e < 8; ++e) {
-              const int k = 8 * (lane >> 4) + e;
-              int wgt = 0;
-              if (k == k0) wgt += 2048 - fx;
-              if (k == k1) wgt += fx;  // (k1 == k0 at the right border, where fx = 0)
-              wds[e >> 1] |= f16_of(wgt) << (16 * (e & 1));
-            }
-          }
-          for (int e = 0; e < 4; ++e) mt[((size_t)g * 64 + lane) * 4 + e] = wds[e];
-        }
-      }
-      p->mtab[l] = ok ? p->tabs + tw : nullptr;
-      p->mcw[l] = ok ? p->tabs + tw + (size_t)ngr * 256 : nullptr;
-      tw += (size_t)ngr * 256 + (((size_t)ngr + 7) & ~(size_t)7);
-    }
-    // ownership of level l + 1 inside fast_cells(l): tile column bx (level-l columns 64 bx .. 64 bx + 63 plus halo) owns
-    // the output 8-groups whose first source column lies in [64 bx, 64 bx + 64); tile row by (rows from 64 by + 15) the
-    // output rows whose source row lies in [64 by + 15, 64 by + 79); the first / last tile row and the last tile column
-    // also take what lies outside every tile.  Any partition is CORRECT (resize_item reads global memory); this one
-    // makes the reads hit the lines the tile load has just fetched.
-    for (int l = 0; l + 1 < L; ++l) {
-      const int nbx = (p->ncx[l] + 1) / 2, nby = (p->ncy[l] + 1) / 2;
-      const uint32_t* xt = htab.data() + (p->xtab[l + 1] - p->tabs);
-      const uint32_t* yt = htab.data() + (p->ytab[l + 1] - p->tabs);
-      const int ngroups = (p->lw[l + 1] + 7) / 8, hd = p->lh[l + 1];
-      p->own_gx[l] = reinterpret_cast<const int32_t*>(p->tabs + tw);
-      int g = 0;
-      for (int bx = 0; bx <= nbx; ++bx) {
-        if (bx == nbx) g = ngroups;
-        else
-          while (bx > 0 && g < ngroups && (int)(xt[8 * g] >> 16) < 64 * bx) ++g;
-        htab[tw++] = (uint32_t)g;
-      }
-      while (tw & 7) htab[tw++] = (uint32_t)ngroups;
-      p->own_gy[l] = reinterpret_cast<const int32_t*>(p->tabs + tw);
-      int y = 0;
-      for (int by = 0; by <= nby; ++by) {
-        if (by == nby) y = hd;
-        else
-          while (by > 0 && y < hd && (int)(yt[y] >> 16) < 64 * by + 15) ++y;
-        htab[tw++] = (uint32_t)y;
-      }
-      while (tw & 7) htab[tw++] = (uint32_t)hd;
-    }
-    if ((st = gh_dev_upload(ctx, p->tabs, htab.data(), htab.size() * sizeof(uint32_t))) != GH_OK) break;
-    if ((st = upload_pattern(p, &GH_ORB_PATTERN[0][0][0])) != GH_OK) break;
-    memcpy(p->base_pattern, &GH_ORB_PATTERN[0][0][0], sizeof(p->base_pattern));  // bin 0 = the unrotated tests
-    if ((st = gh_dev_upload(ctx, p->d_base_pattern, p->base_pattern, sizeof(p->base_pattern))) != GH_OK) break;
-    if ((st = gh_dev_upload(ctx, p->d_dir, GH_ORB_DIR, sizeof(GH_ORB_DIR))) != GH_OK) break;
-  } while (0);
+  p->L = prm.n_levels;
+  const gh_status st = plan_init(p);
   if (st != GH_OK) {
     gh_orb_plan_destroy(p);
     return st;
@@ -2083,8 +2135,429 @@ extern "C" gh_status gh_orb_plan_level(const gh_orb_plan* p, int level, int* w, 
 
 extern "C" size_t gh_orb_plan_device_bytes(const gh_orb_plan* p) { return p ? p->bytes : 0; }
 
-static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch, size_t frame_stride, int row_stride,
-                             gh_keypoint* kps_dev, uint8_t* desc_dev, int32_t* counts_dev);
+// ---- the schedule of one call
+// Which launches a call makes is decided HERE, once, from the plan, the batch, the alignment of the caller's buffer and the
+// state of the context; gh_orb_extract_dev and the enqueue functions below only read the result.  (Every schedule computes the
+// same bytes: a wrong choice costs speed alone, which tests/test_orb_schedule_gpu.py pins by counting launches.)
+constexpr long long kAllLevelsMaxPx = 4LL << 20;   // up to two 1080p frames: launch-bound
+constexpr long long kOverlapMinPx = 16LL << 20;    // >= 8 frames of 1080p
+constexpr int kSelCachedMaxCells = kSelCached * 256;
+
+// The A/B switches of the schedule, read once per process.
+struct OrbEnv {
+  bool graph;          // GSLAM_HIP_ORB_GRAPH=0: always launch kernel by kernel
+  bool all_levels;     // GSLAM_HIP_ORB_ALL_LEVELS=0: small calls take the per-level schedule too
+  int select_overlap;  // GSLAM_HIP_ORB_SELECT_OVERLAP=0 / 1 forces the select overlap off / on; -1 (unset): by size
+  bool select_cached;  // GSLAM_HIP_ORB_SELECT_CACHED=0: stream the cell records
+};
+static const OrbEnv& orb_env() {
+  static const OrbEnv env = [] {
+    auto is0 = [](const char* e) { return e && e[0] == '0'; };
+    const char* ov = getenv("GSLAM_HIP_ORB_SELECT_OVERLAP");
+    return OrbEnv{!is0(getenv("GSLAM_HIP_ORB_GRAPH")), !is0(getenv("GSLAM_HIP_ORB_ALL_LEVELS")), ov ? (ov[0] == '0' ? 0 : 1) : -1,
+                  !is0(getenv("GSLAM_HIP_ORB_SELECT_CACHED"))};
+  }();
+  return env;
+}
+
+struct OrbSchedule {
+  // kAllLevels  small calls: the pyramid by the stand-alone resize, then every level in ONE FAST launch, one select
+  // kPerLevel   large calls: one FAST launch per level, each building the next level inside the kernel
+  // kQuadtree   ORB-SLAM's distribution (gh_orb_plan_set_distribution(plan, 1))
+  enum Kind { kAllLevels, kPerLevel, kQuadtree } kind;
+  bool graph;       // replay the call as one captured hipGraph (small calls are launch-bound)
+  bool overlap;     // kPerLevel: select(l) on the side stream beside fast_cells(l + 1 ..) instead of one select at the end
+  bool sel_cached;  // select_kernel<true>: no level has more cells than its registers hold
+  bool zero_copy0;  // level 0 is read from the caller's buffer, not staged through the plan's slab
+};
+
+// The side stream of the select overlap and its events, created at the first call that wants them.  *ok = false when the
+// stream cannot be had (the call then selects at the end).
+static gh_status orb_side_stream(gh_orb_plan* p, bool* ok) {
+  *ok = true;
+  if (p->side) return GH_OK;
+  if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) {
+    p->side = nullptr;
+    *ok = false;
+    return GH_OK;
+  }
+  bool ev = hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
+  for (int l = 0; l < kMaxL && ev; ++l) ev = hipEventCreateWithFlags(&p->ev_level[l], hipEventDisableTiming) == hipSuccess;
+  if (!ev) return gh_set_error(p->ctx, GH_ERR_HIP, "gh_orb_extract_dev: event creation failed");
+  return GH_OK;
+}
+
+static gh_status orb_schedule(gh_orb_plan* p, int batch, const uint8_t* gray_dev, size_t frame_stride, int row_stride, OrbSchedule* s) {
+  const gh_ctx* ctx = p->ctx;
+  const OrbEnv& env = orb_env();
+  const long long px = (long long)batch * p->w * p->h;
+  const bool small = px <= kAllLevelsMaxPx;
+  s->kind = p->distribution != 0 ? OrbSchedule::kQuadtree : (env.all_levels && small ? OrbSchedule::kAllLevels : OrbSchedule::kPerLevel);
+  // a plan whose caller never repeats an argument set has stopped capturing (graphs_off); the profiler and the debug counters
+  // need the launches themselves
+  s->graph = p->distribution == 0 && env.graph && small && !p->graphs_off && !ctx->prof_on && !p->dbg_on && ctx->stream != nullptr;
+  // select(l) needs fast_cells(l) only, and it is a latency-bound kernel (histogram + three passes over the cell
+  // records): in a batched call it runs on a side stream beside the VALU-bound fast_cells of the levels that follow,
+  // instead of as one launch behind the last level.  Small calls (below 16 Mpixel) keep the one launch (8 more launches and
+  // 9 event operations would cost more than the overlap gives), and so does a captured call.
+  s->overlap = s->kind == OrbSchedule::kPerLevel && !s->graph && (env.select_overlap < 0 ? px >= kOverlapMinPx : env.select_overlap == 1);
+  if (s->overlap) GH_TRY(orb_side_stream(p, &s->overlap));
+  s->sel_cached = p->max_level_cells <= kSelCachedMaxCells && env.select_cached;
+  // zero-copy level 0 reads whole 16-byte windows of every padded row, the last row included, so it needs the full
+  // row_stride * h bytes of every frame to be readable; a single frame handed over with a smaller frame_stride (an ROI
+  // view whose allocation ends at (h-1) * row_stride + w) is staged through the plan's own level-0 slab instead
+  s->zero_copy0 = ((uintptr_t)gray_dev & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
+                  frame_stride >= (size_t)row_stride * p->h;
+  return GH_OK;
+}
+
+// ---- the enqueue: one call's launches, kernel by kernel, on ctx->stream
+struct OrbCall {
+  gh_orb_plan* p;
+  const uint8_t* gray;
+  int batch;
+  size_t frame_stride;
+  int row_stride;
+  gh_keypoint* kps;
+  uint8_t* desc;
+  int32_t* counts;
+  OrbSchedule s;
+  LevelView lv[kMaxL];  // (orb_level_views)
+  uint32_t* dbg;        // the plan's debug counters while they are on, else null
+};
+
+struct StreamSwap {  // GH_LAUNCH launches (and profiles) on ctx->stream
+  gh_ctx* c;
+  hipStream_t keep;
+  StreamSwap(gh_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { c->stream = s; }
+  ~StreamSwap() { c->stream = keep; }
+};
+
+// the views of every level; level 0 is the caller's buffer or, staged, a copy of it in the plan's slab
+static gh_status orb_level_views(OrbCall& c) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  if (c.s.zero_copy0) {
+    c.lv[0] = {c.gray, c.frame_stride, c.row_stride, p->w, p->h};
+  } else {
+    dim3 grid(gh_div_up(p->w, 256), p->h, c.batch);
+    GH_LAUNCH(ctx, "orb_copy_level0", copy_rows_kernel, grid, dim3(256), 0, c.gray, c.frame_stride, c.row_stride,
+              p->pyr + p->lvl_off[0], p->slab, p->pitch[0], p->w, p->h);
+    c.lv[0] = {p->pyr + p->lvl_off[0], p->slab, p->pitch[0], p->w, p->h};
+  }
+  for (int l = 1; l < p->L; ++l) c.lv[l] = {p->pyr + p->lvl_off[l], p->slab, p->pitch[l], p->lw[l], p->lh[l]};
+  return GH_OK;
+}
+
+// Level l + 1 is produced inside fast_cells(l) (see the kernel); a level whose predecessor runs no FAST pass (no valid
+// region or no quota) is produced by the stand-alone resize launch instead.
+static gh_status resize_standalone(const OrbCall& c, int l) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  const int gpr = gh_div_up(p->lw[l], kResizeCols), nrg = gh_div_up(p->lh[l], kResizeRows);
+  const int n_items = gpr * nrg;
+  const uint32_t inv = (uint32_t)((0x100000000ull + (uint64_t)gpr - 1) / (uint64_t)gpr);  // exact for item < 2^32 / gpr
+  GH_CHECK_ARG(ctx, (uint64_t)n_items * (uint64_t)gpr < 0x100000000ull);
+  // only the caller's own level-0 buffer can end right after its last row
+  const int unsafe_frame = (l == 1 && c.s.zero_copy0) ? c.batch - 1 : -1;
+  GH_LAUNCH(ctx, "orb_resize", resize_kernel, dim3(gh_div_up(n_items, 256), c.batch), dim3(256), 0, c.lv[l - 1],
+            p->pyr + p->lvl_off[l], p->slab, p->pitch[l], p->lw[l], p->lh[l],
+            ResizeTabs{p->xtab[l], p->xsel[l], p->xwgt[l], p->ytab[l]}, gpr, inv, n_items, unsafe_frame);
+  return GH_OK;
+}
+
+static SelectArgs select_args(const gh_orb_plan* p) {
+  SelectArgs sa;
+  for (int l = 0; l < kMaxL; ++l) {
+    sa.ncells[l] = l < p->L ? p->ncx[l] * p->ncy[l] : 0;
+    sa.cell_off[l] = l < p->L ? p->cell_off[l] : 0;
+    sa.ncx[l] = l < p->L && p->ncx[l] > 0 ? p->ncx[l] : 1;
+    sa.quota[l] = l < p->L ? p->quota[l] : 0;
+    sa.quota_off[l] = l < p->L ? p->quota_off[l] : 0;
+  }
+  return sa;
+}
+
+// select of levels l0 .. l0 + nl - 1
+static gh_status launch_select(const OrbCall& c, const SelectArgs& sa, int l0, int nl) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  if (c.s.sel_cached)
+    GH_LAUNCH(ctx, "orb_select", select_kernel<true>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0);
+  else
+    GH_LAUNCH(ctx, "orb_select", select_kernel<false>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0);
+  return GH_OK;
+}
+
+// what fast_cells(l) needs to produce level l + 1, and the magic divisors of its `tiles` tile ids
+static NextLevel next_level_args(const OrbCall& c, int l, long long tiles) {
+  const gh_orb_plan* p = c.p;
+  NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
+  if (l + 1 < p->L)
+    nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
+                   ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
+                   p->own_gx[l], p->own_gy[l], (l == 0 && c.s.zero_copy0) ? c.batch - 1 : -1};
+  const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
+  nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
+  nx.nbx_inv = magic_div(nbx, tpf);
+  return nx;
+}
+
+// fast_cells(l): FAST, NMS and the cell lists of level l -- or, plane, the level's score plane for the quadtree mode -- with
+// level l + 1 of the pyramid produced inside the kernel
+static gh_status fast_level(const OrbCall& c, int l, bool plane) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * c.batch;
+  GH_CHECK_ARG(ctx, tiles < (1LL << 30));
+  NextLevel nx = next_level_args(c, l, tiles);
+  const dim3 grid(8 * gh_div_up(tiles, 8));
+  if (plane) {
+    nx.plane = p->score_plane + p->plane_off[l];
+    nx.plane_frame_stride = p->plane_slab;
+    nx.plane_pitch = p->plane_pitch[l];
+    GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg);
+  } else {
+    GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg);
+  }
+  return GH_OK;
+}
+
+// ORB-SLAM's distribution (oracle steps 4', 5'): S of every level by the tile kernel (plane variant: no cell stage), the next
+// level fused as in the default mode; then cells + tree of orb_quadtree.hip leave sel / level_cnt as orb_select would.  A
+// level whose cells do not fit the plane's cell kernel takes its cells from the image, and its successor from the
+// stand-alone resize.
+static gh_status enqueue_quadtree(const OrbCall& c) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  GH_TRY(gh_qt_begin(ctx, p->qt, c.batch));
+  for (int l = 0; l < p->L; ++l) {
+    if (p->ncx[l] == 0 || !gh_qt_plane_ok(p->qt, l)) {
+      GH_TRY(gh_qt_cells(ctx, p->qt, l, c.lv[l], nullptr, c.batch, p->prm.min_th_fast, p->prm.ini_th_fast));
+      if (l + 1 < p->L) GH_TRY(resize_standalone(c, l + 1));
+      continue;
+    }
+    GH_TRY(fast_level(c, l, true));
+    const LevelView plane{p->score_plane + p->plane_off[l], p->plane_slab, p->plane_pitch[l], p->lw[l], p->lh[l]};
+    GH_TRY(gh_qt_cells(ctx, p->qt, l, c.lv[l], &plane, c.batch, p->prm.min_th_fast, p->prm.ini_th_fast));
+  }
+  return gh_qt_tree(ctx, p->qt, c.batch, p->quota_off, p->prm.n_features, p->sel, p->level_cnt);
+}
+
+// the levels of fast_cells_all_kernel and the first tile of each; *tiles = tiles of the launch
+static AllLevels all_levels_args(const OrbCall& c, int* tiles_out) {
+  const gh_orb_plan* p = c.p;
+  const int L = p->L;
+  AllLevels A;
+  A.n_levels = L;
+  int tiles = 0;
+  for (int l = 0; l < kMaxL; ++l) {
+    A.tile_start[l] = tiles;
+    A.lv[l] = c.lv[l < L ? l : 0];
+    A.ncx[l] = l < L ? p->ncx[l] : 0;
+    A.ncy[l] = l < L ? p->ncy[l] : 0;
+    A.cell_off[l] = l < L ? p->cell_off[l] : 0;
+    if (l < L && p->ncx[l] != 0 && p->quota[l] > 0) tiles += gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * c.batch;
+  }
+  A.tile_start[kMaxL] = tiles;
+  *tiles_out = tiles;
+  return A;
+}
+
+// small calls: pyramid first, then every level in one FAST launch, one select
+static gh_status enqueue_all_levels(const OrbCall& c) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  for (int l = 1; l < p->L; ++l) GH_TRY(resize_standalone(c, l));
+  int tiles = 0;
+  const AllLevels A = all_levels_args(c, &tiles);
+  if (tiles > 0)
+    GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_all_kernel, dim3(tiles), dim3(256), 0, A, p->prm.min_th_fast, p->prm.ini_th_fast,
+              p->cell_cnt, p->cell_ent, p->cells_per_frame, c.batch, c.dbg);
+  return launch_select(c, select_args(p), 0, p->L);
+}
+
+// large calls: one FAST launch per level; a level without a FAST pass (no valid region or no quota) gets its successor from
+// the stand-alone resize.  With the overlap, select(l) follows fast_cells(l) on the side stream and the caller's stream
+// joins behind the last one; without it one select takes every level at the end.
+static gh_status enqueue_per_level(const OrbCall& c) {
+  gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  const SelectArgs sa = select_args(p);
+  for (int l = 0; l < p->L; ++l) {
+    if (p->ncx[l] != 0 && p->quota[l] > 0) GH_TRY(fast_level(c, l, false));
+    else if (l + 1 < p->L) GH_TRY(resize_standalone(c, l + 1));
+    if (c.s.overlap) {  // (a level without a FAST pass still gets its level_cnt = 0 from select)
+      GH_HIP(ctx, hipEventRecord(p->ev_level[l], ctx->stream));
+      GH_HIP(ctx, hipStreamWaitEvent(p->side, p->ev_level[l], 0));
+      StreamSwap sw(ctx, p->side);
+      GH_TRY(launch_select(c, sa, l, 1));
+    }
+  }
+  if (!c.s.overlap) return launch_select(c, sa, 0, p->L);
+  GH_HIP(ctx, hipEventRecord(p->ev_join, p->side));
+  GH_HIP(ctx, hipStreamWaitEvent(ctx->stream, p->ev_join, 0));
+  return GH_OK;
+}
+
+static DescribeArgs describe_args(const OrbCall& c) {
+  const gh_orb_plan* p = c.p;
+  const int L = p->L;
+  DescribeArgs a;
+  for (int l = 0; l < kMaxL; ++l) {
+    a.lv[l] = l < L ? c.lv[l] : c.lv[0];
+    a.quota[l] = l < L ? p->quota[l] : 0;
+    a.quota_off[l] = l < L ? p->quota_off[l] : 0;
+    a.scale[l] = l < L ? p->scale[l] : 1.0f;
+  }
+  a.nlevels = L;
+  a.blk_off[0] = 0;
+  for (int l = 0; l < kMaxL; ++l) a.blk_off[l + 1] = a.blk_off[l] + (l < L ? gh_div_up(a.quota[l], 4 * kDescPipe) : 0);
+  return a;
+}
+
+static gh_status enqueue_describe(const OrbCall& c) {
+  const gh_orb_plan* p = c.p;
+  gh_ctx* ctx = p->ctx;
+  const int K = p->prm.n_features;
+  const DescribeArgs a = describe_args(c);
+  const DevTables tb{p->d_pattern, p->d_dir, p->d_base_pattern};
+  const long long blocks = (long long)gh_div_up(K, 4) * c.batch;
+  GH_CHECK_ARG(ctx, blocks < (1LL << 30));
+  if (p->steer == 0) {  // 30-bin table steering: kDescPipe slots per wave, workgroups dealt per level
+    const long long pblocks = (long long)a.blk_off[p->L] * c.batch;
+    GH_LAUNCH(ctx, "orb_describe", describe_pipe_kernel, dim3(8 * gh_div_up(pblocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
+              c.kps, c.desc, c.counts, c.batch, c.dbg);
+  } else {  // continuous steering: one keypoint per wave
+    GH_LAUNCH(ctx, "orb_describe", describe_kernel, dim3(8 * gh_div_up(blocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
+              c.kps, c.desc, c.counts, c.batch, c.dbg);
+  }
+  return GH_OK;
+}
+
+static gh_status orb_enqueue(OrbCall& c) {
+  gh_ctx* ctx = c.p->ctx;
+  c.dbg = c.p->dbg_on ? c.p->dbg : nullptr;
+  GH_TRY(orb_level_views(c));
+  switch (c.s.kind) {
+    case OrbSchedule::kQuadtree: GH_TRY(enqueue_quadtree(c)); break;
+    case OrbSchedule::kAllLevels: GH_TRY(enqueue_all_levels(c)); break;
+    case OrbSchedule::kPerLevel: GH_TRY(enqueue_per_level(c)); break;
+  }
+  if (!c.s.sel_cached && c.dbg) GH_HIP(ctx, hipMemsetAsync(c.dbg + kDbgSelStreamed, 1, 1, ctx->stream));
+  return enqueue_describe(c);
+}
+
+// ---- the graph cache: small calls are replayed as ONE hipGraph launch per argument set (gh_orb_plan::CallGraph)
+static void graph_destroy(gh_orb_plan::CallGraph& g) {
+  hipGraphExecDestroy(g.exec);
+  hipEventDestroy(g.done);
+}
+
+// every cached graph goes, each after its last launch (the caller may have moved the context to another stream since)
+static void graphs_drop_all(gh_orb_plan* p) {
+  for (auto* v : {&p->graphs, &p->retired}) {
+    for (auto& g : *v) {
+      hipEventSynchronize(g.done);
+      graph_destroy(g);
+    }
+    v->clear();
+  }
+}
+
+static gh_orb_plan::CallGraph* graphs_find(gh_orb_plan* p, const OrbCall& c) {
+  for (auto& g : p->graphs)
+    if (g.gray == c.gray && g.kps == c.kps && g.desc == c.desc && g.counts == c.counts && g.batch == c.batch &&
+        g.row_stride == c.row_stride && g.frame_stride == c.frame_stride)
+      return &g;
+  return nullptr;
+}
+
+// retired graphs whose last launch has completed can go now
+static void graphs_reap(gh_orb_plan* p) {
+  for (size_t k = 0; k < p->retired.size();) {
+    if (hipEventQuery(p->retired[k].done) == hipSuccess) {
+      graph_destroy(p->retired[k]);
+      p->retired.erase(p->retired.begin() + (long)k);
+    } else {
+      (void)hipGetLastError();
+      ++k;
+    }
+  }
+}
+
+// First call with these arguments: capture the launch sequence on the plan's own stream (nothing executes during the
+// capture, and nobody else can enqueue there) and cache the instantiated graph; the oldest of a full ring retires.
+// *out stays null when the runtime refuses any step (status GH_OK) or the enqueue fails (its status).
+static gh_status graphs_capture(gh_orb_plan* p, OrbCall& c, gh_orb_plan::CallGraph** out) {
+  gh_ctx* ctx = p->ctx;
+  *out = nullptr;
+  if (!p->cap_stream && hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    p->cap_stream = nullptr;
+    return GH_OK;
+  }
+  if (hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
+    (void)hipGetLastError();
+    return GH_OK;
+  }
+  gh_status st;
+  {
+    StreamSwap sw(ctx, p->cap_stream);
+    st = orb_enqueue(c);
+  }
+  hipGraph_t graph = nullptr;
+  const hipError_t ee = hipStreamEndCapture(p->cap_stream, &graph);
+  hipGraphExec_t exec = nullptr;
+  hipEvent_t done = nullptr;
+  if (st != GH_OK || ee != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess ||
+      hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    if (exec) hipGraphExecDestroy(exec);
+    if (graph) hipGraphDestroy(graph);
+    return st;
+  }
+  hipGraphDestroy(graph);
+  if ((int)p->graphs.size() >= gh_orb_plan::kGraphRing) {  // the oldest set goes; its exec may still be queued on the stream
+    p->retired.push_back(p->graphs.front());
+    p->graphs.erase(p->graphs.begin());
+  }
+  p->graphs.push_back({c.gray, c.kps, c.desc, c.counts, c.batch, c.row_stride, c.frame_stride, exec, done});
+  *out = &p->graphs.back();
+  return GH_OK;
+}
+
+// The call as one graph launch: the cached graph of its argument set, or a new capture.  *replayed = false hands the call
+// back to the kernel-by-kernel path, and the plan has stopped capturing: after kGraphGiveUp misses that outnumber the hits
+// four to one (the caller's argument sets do not repeat: capturing costs more than it saves), or when a capture failed.
+static gh_status graphs_replay(gh_orb_plan* p, OrbCall& c, bool* replayed) {
+  gh_ctx* ctx = p->ctx;
+  *replayed = false;
+  gh_orb_plan::CallGraph* g = graphs_find(p, c);
+  if (g) {
+    ++p->graph_hits;
+  } else {
+    graphs_reap(p);
+    ++p->graph_misses;
+    if (p->graph_misses >= gh_orb_plan::kGraphGiveUp && p->graph_misses > 4 * p->graph_hits) {
+      p->graphs_off = true;
+      return GH_OK;
+    }
+    const gh_status st = graphs_capture(p, c, &g);
+    if (!g) {
+      p->graphs_off = true;
+      return st;
+    }
+  }
+  GH_HIP(ctx, hipGraphLaunch(g->exec, ctx->stream));
+  GH_HIP(ctx, hipEventRecord(g->done, ctx->stream));
+  *replayed = true;
+  return GH_OK;
+}
 
 extern "C" gh_status gh_orb_extract_dev(gh_orb_plan* p, const uint8_t* gray_dev, int batch, size_t frame_stride,
                                         int row_stride, gh_keypoint* kps_dev, uint8_t* desc_dev,
@@ -2099,286 +2572,22 @@ extern "C" gh_status gh_orb_extract_dev(gh_orb_plan* p, const uint8_t* gray_dev,
   GH_CHECK_ARG(ctx, (uint64_t)row_stride * (uint64_t)p->h < (1ull << 32));
   GH_CHECK_ARG(ctx, frame_stride >= (size_t)row_stride * p->h || batch == 1);
   GH_CHECK_ARG(ctx, ((uintptr_t)desc_dev & 7) == 0 && ((uintptr_t)kps_dev & 3) == 0);
-  // GSLAM_HIP_ORB_GRAPH=0: always launch kernel by kernel (A/B measurements)
-  static const bool graph_env = [] {
-    const char* e = getenv("GSLAM_HIP_ORB_GRAPH");
-    return !(e && e[0] == '0');
-  }();
-  const bool small = (long long)batch * p->w * p->h <= (4LL << 20);  // up to two 1080p frames: launch-bound
-  if (p->distribution != 0) {
-    // quadtree mode: when the plan's key budget cut a candidate list below its worst case, a list that overflowed is an error of
-    // THIS call -- it waits for its own kernels.  Otherwise (every plan whose worst case fits 4 GB: 1080p up to ~400 frames per
-    // call) nothing can overflow and the call is asynchronous like the default mode's.
-    GH_TRY(orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev));
-    if (!gh_qt_can_overflow(p->qt)) return GH_OK;
-    GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return gh_qt_check(ctx, p->qt);
+  OrbCall c{p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev};
+  GH_TRY(orb_schedule(p, batch, gray_dev, frame_stride, row_stride, &c.s));
+  if (c.s.graph) {
+    bool replayed = false;
+    GH_TRY(graphs_replay(p, c, &replayed));
+    if (replayed) return GH_OK;
+    // the one fall-back to the kernel-by-kernel path: the plan has stopped capturing, and the call is scheduled as such
+    GH_TRY(orb_schedule(p, batch, gray_dev, frame_stride, row_stride, &c.s));
   }
-  if (!(graph_env && small && !p->graphs_off && !ctx->prof_on && !p->dbg_on && ctx->stream != nullptr))
-    return orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  for (auto& g : p->graphs)
-    if (g.gray == gray_dev && g.kps == kps_dev && g.desc == desc_dev && g.counts == counts_dev && g.batch == batch &&
-        g.row_stride == row_stride && g.frame_stride == frame_stride) {
-      ++p->graph_hits;
-      GH_HIP(ctx, hipGraphLaunch(g.exec, ctx->stream));
-      GH_HIP(ctx, hipEventRecord(g.done, ctx->stream));
-      return GH_OK;
-    }
-  // retired graphs whose last launch has completed can go now
-  for (size_t k = 0; k < p->retired.size();) {
-    if (hipEventQuery(p->retired[k].done) == hipSuccess) {
-      hipGraphExecDestroy(p->retired[k].exec);
-      hipEventDestroy(p->retired[k].done);
-      p->retired.erase(p->retired.begin() + (long)k);
-    } else {
-      (void)hipGetLastError();
-      ++k;
-    }
-  }
-  ++p->graph_misses;
-  if (p->graph_misses >= gh_orb_plan::kGraphGiveUp && p->graph_misses > 4 * p->graph_hits) {
-    p->graphs_off = true;  // the caller's argument sets do not repeat: capturing costs more than it saves
-    return orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  }
-  // first call with these arguments: capture the launch sequence on the plan's own stream (nothing executes during the
-  // capture, and nobody else can enqueue there), then replay it on the caller's
-  if (!p->cap_stream && hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    p->cap_stream = nullptr;
-    p->graphs_off = true;
-    return orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  }
-  if (hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
-    (void)hipGetLastError();
-    p->graphs_off = true;
-    return orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  }
-  hipStream_t const user_stream = ctx->stream;
-  ctx->stream = p->cap_stream;
-  p->capturing = true;
-  const gh_status st = orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  p->capturing = false;
-  ctx->stream = user_stream;
-  hipGraph_t graph = nullptr;
-  const hipError_t ee = hipStreamEndCapture(p->cap_stream, &graph);
-  hipGraphExec_t exec = nullptr;
-  hipEvent_t done = nullptr;
-  if (st != GH_OK || ee != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess ||
-      hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    if (exec) hipGraphExecDestroy(exec);
-    if (graph) hipGraphDestroy(graph);
-    p->graphs_off = true;
-    if (st != GH_OK) return st;
-    return orb_enqueue(p, gray_dev, batch, frame_stride, row_stride, kps_dev, desc_dev, counts_dev);
-  }
-  hipGraphDestroy(graph);
-  if ((int)p->graphs.size() >= gh_orb_plan::kGraphRing) {  // the oldest set goes; its exec may still be queued on the stream
-    p->retired.push_back(p->graphs.front());
-    p->graphs.erase(p->graphs.begin());
-  }
-  p->graphs.push_back({gray_dev, kps_dev, desc_dev, counts_dev, batch, row_stride, frame_stride, exec, done});
-  GH_HIP(ctx, hipGraphLaunch(exec, ctx->stream));
-  GH_HIP(ctx, hipEventRecord(done, ctx->stream));
-  return GH_OK;
-}
-
-static gh_status orb_enqueue(gh_orb_plan* p, const uint8_t* gray_dev, int batch, size_t frame_stride, int row_stride,
-                             gh_keypoint* kps_dev, uint8_t* desc_dev, int32_t* counts_dev) {
-  gh_ctx* ctx = p->ctx;
-  const int L = p->L, K = p->prm.n_features;
-
-  LevelView lv[kMaxL];
-  // zero-copy level 0 reads whole 16-byte windows of every padded row, the last row included, so it needs the full
-  // row_stride * h bytes of every frame to be readable; a single frame handed over with a smaller frame_stride (an ROI
-  // view whose allocation ends at (h-1) * row_stride + w) is staged through the plan's own level-0 slab instead
-  const bool aligned0 = ((uintptr_t)gray_dev & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
-                        frame_stride >= (size_t)row_stride * p->h;
-  if (aligned0) {
-    lv[0] = {gray_dev, frame_stride, row_stride, p->w, p->h};
-  } else {
-    dim3 grid(gh_div_up(p->w, 256), p->h, batch);
-    GH_LAUNCH(ctx, "orb_copy_level0", copy_rows_kernel, grid, dim3(256), 0, gray_dev, frame_stride, row_stride,
-              p->pyr + p->lvl_off[0], p->slab, p->pitch[0], p->w, p->h);
-    lv[0] = {p->pyr + p->lvl_off[0], p->slab, p->pitch[0], p->w, p->h};
-  }
-  for (int l = 1; l < L; ++l) lv[l] = {p->pyr + p->lvl_off[l], p->slab, p->pitch[l], p->lw[l], p->lh[l]};
-  uint32_t* dbg = p->dbg_on ? p->dbg : nullptr;
-
-  // Level l + 1 is produced inside fast_cells(l) (see the kernel); a level whose predecessor runs no FAST pass (no valid
-  // region or no quota) is produced by the stand-alone resize launch instead.
-  auto resize_standalone = [&](int l) -> gh_status {
-    const int gpr = gh_div_up(p->lw[l], kResizeCols), nrg = gh_div_up(p->lh[l], kResizeRows);
-    const int n_items = gpr * nrg;
-    const uint32_t inv = (uint32_t)((0x100000000ull + (uint64_t)gpr - 1) / (uint64_t)gpr);  // exact for item < 2^32 / gpr
-    GH_CHECK_ARG(ctx, (uint64_t)n_items * (uint64_t)gpr < 0x100000000ull);
-    // only the caller's own level-0 buffer can end right after its last row
-    const int unsafe_frame = (l == 1 && aligned0) ? batch - 1 : -1;
-    GH_LAUNCH(ctx, "orb_resize", resize_kernel, dim3(gh_div_up(n_items, 256), batch), dim3(256), 0, lv[l - 1],
-              p->pyr + p->lvl_off[l], p->slab, p->pitch[l], p->lw[l], p->lh[l],
-              ResizeTabs{p->xtab[l], p->xsel[l], p->xwgt[l], p->ytab[l]}, gpr, inv, n_items, unsafe_frame);
-    return GH_OK;
-  };
-  SelectArgs sa;
-  for (int l = 0; l < kMaxL; ++l) {
-    sa.ncells[l] = l < L ? p->ncx[l] * p->ncy[l] : 0;
-    sa.cell_off[l] = l < L ? p->cell_off[l] : 0;
-    sa.ncx[l] = l < L && p->ncx[l] > 0 ? p->ncx[l] : 1;
-    sa.quota[l] = l < L ? p->quota[l] : 0;
-    sa.quota_off[l] = l < L ? p->quota_off[l] : 0;
-  }
-  int max_cells = 0;
-  for (int l = 0; l < L; ++l) max_cells = sa.ncells[l] > max_cells ? sa.ncells[l] : max_cells;
-  static const bool no_cache = [] {
-    const char* e = getenv("GSLAM_HIP_ORB_SELECT_CACHED");  // "0": stream the records (A/B measurements)
-    return e && e[0] == '0';
-  }();
-  const bool cached = max_cells <= kSelCached * 256 && !no_cache;
-  auto launch_select = [&](int l0, int nl) -> gh_status {
-    if (cached)
-      GH_LAUNCH(ctx, "orb_select", select_kernel<true>, dim3(nl, batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-                p->cells_per_frame, K, p->sel, p->level_cnt, dbg, l0);
-    else
-      GH_LAUNCH(ctx, "orb_select", select_kernel<false>, dim3(nl, batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-                p->cells_per_frame, K, p->sel, p->level_cnt, dbg, l0);
-    return GH_OK;
-  };
-  // select(l) needs fast_cells(l) only, and it is a latency-bound kernel (histogram + three passes over the cell
-  // records): in a batched call it runs on a side stream beside the VALU-bound fast_cells of the levels that follow,
-  // instead of as one launch behind the last level.  Small calls (below 16 Mpixel) keep the one launch (8 more launches and
-  // 9 event operations would cost more than the overlap gives).  GSLAM_HIP_ORB_SELECT_OVERLAP=0 / 1 forces either.
-  static const int overlap_env = [] {
-    const char* e = getenv("GSLAM_HIP_ORB_SELECT_OVERLAP");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  bool overlap = overlap_env < 0 ? (long long)batch * p->w * p->h >= (16LL << 20) : overlap_env == 1;  // >= 8 frames of 1080p
-  if (p->capturing || p->distribution != 0) overlap = false;  // (a captured call is a small one: one select launch)
-  if (overlap && !p->side) {
-    if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) {
-      p->side = nullptr;
-      overlap = false;
-    } else {
-      bool ok = hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
-      for (int l = 0; l < kMaxL && ok; ++l) ok = hipEventCreateWithFlags(&p->ev_level[l], hipEventDisableTiming) == hipSuccess;
-      if (!ok) return gh_set_error(ctx, GH_ERR_HIP, "gh_orb_extract_dev: event creation failed");
-    }
-  }
-  struct StreamSwap {  // GH_LAUNCH launches (and profiles) on ctx->stream
-    gh_ctx* c;
-    hipStream_t keep;
-    StreamSwap(gh_ctx* c_, hipStream_t s) : c(c_), keep(c_->stream) { c->stream = s; }
-    ~StreamSwap() { c->stream = keep; }
-  };
-  // fast_cells(l): FAST, NMS and the cell lists of level l -- or, plane, the level's score plane for the quadtree mode -- with
-  // level l + 1 of the pyramid produced inside the kernel
-  auto fast_level = [&](int l, bool plane) -> gh_status {
-    NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-    if (l + 1 < L)
-      nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
-                     ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
-                     p->own_gx[l], p->own_gy[l], (l == 0 && aligned0) ? batch - 1 : -1};
-    const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
-    GH_CHECK_ARG(ctx, tiles < (1LL << 30));
-    const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
-    nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
-    nx.nbx_inv = magic_div(nbx, tpf);
-    const dim3 grid(8 * gh_div_up(tiles, 8));
-    if (plane) {
-      nx.plane = p->score_plane + p->plane_off[l];
-      nx.plane_frame_stride = p->plane_slab;
-      nx.plane_pitch = p->plane_pitch[l];
-      GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-                p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
-    } else {
-      GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-                p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], batch, nx, dbg);
-    }
-    return GH_OK;
-  };
-  // small calls: pyramid first, then every level in one FAST launch (GSLAM_HIP_ORB_ALL_LEVELS=0: A/B measurements)
-  static const bool all_env = [] {
-    const char* e = getenv("GSLAM_HIP_ORB_ALL_LEVELS");
-    return !(e && e[0] == '0');
-  }();
-  const bool quadtree = p->distribution != 0;
-  const bool all_levels = (all_env && (long long)batch * p->w * p->h <= (4LL << 20)) || quadtree;
-  if (quadtree) {
-    // ORB-SLAM's distribution (oracle steps 4', 5'): S of every level by the tile kernel (plane variant: no cell stage), the next
-    // level fused as in the default mode; then cells + tree of orb_quadtree.hip leave sel / level_cnt as orb_select would.  A
-    // level whose cells do not fit the plane's cell kernel takes its cells from the image, and its successor from the
-    // stand-alone resize.
-    GH_TRY(gh_qt_begin(ctx, p->qt, batch));
-    for (int l = 0; l < L; ++l) {
-      if (p->ncx[l] == 0 || !gh_qt_plane_ok(p->qt, l)) {
-        GH_TRY(gh_qt_cells(ctx, p->qt, l, lv[l], nullptr, batch, p->prm.min_th_fast, p->prm.ini_th_fast));
-        if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
-        continue;
-      }
-      GH_TRY(fast_level(l, true));
-      const LevelView plane{p->score_plane + p->plane_off[l], p->plane_slab, p->plane_pitch[l], p->lw[l], p->lh[l]};
-      GH_TRY(gh_qt_cells(ctx, p->qt, l, lv[l], &plane, batch, p->prm.min_th_fast, p->prm.ini_th_fast));
-    }
-    GH_TRY(gh_qt_tree(ctx, p->qt, batch, p->quota_off, K, p->sel, p->level_cnt));
-  } else if (all_levels) {
-    for (int l = 1; l < L; ++l) GH_TRY(resize_standalone(l));
-    AllLevels A;
-    A.n_levels = L;
-    int tiles = 0;
-    for (int l = 0; l < kMaxL; ++l) {
-      A.tile_start[l] = tiles;
-      A.lv[l] = lv[l < L ? l : 0];
-      A.ncx[l] = l < L ? p->ncx[l] : 0;
-      A.ncy[l] = l < L ? p->ncy[l] : 0;
-      A.cell_off[l] = l < L ? p->cell_off[l] : 0;
-      if (l < L && p->ncx[l] != 0 && p->quota[l] > 0) tiles += gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * batch;
-    }
-    A.tile_start[kMaxL] = tiles;
-    if (tiles > 0)
-      GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_all_kernel, dim3(tiles), dim3(256), 0, A, p->prm.min_th_fast, p->prm.ini_th_fast,
-                p->cell_cnt, p->cell_ent, p->cells_per_frame, batch, dbg);
-    overlap = false;
-  }
-  // large calls: one FAST launch per level; a level without a FAST pass (no valid region or no quota) gets its successor from
-  // the stand-alone resize
-  for (int l = 0; l < L && !all_levels; ++l) {
-    if (p->ncx[l] != 0 && p->quota[l] > 0) GH_TRY(fast_level(l, false));
-    else if (l + 1 < L) GH_TRY(resize_standalone(l + 1));
-    if (overlap) {  // (a level without a FAST pass still gets its level_cnt = 0 from select)
-      GH_HIP(ctx, hipEventRecord(p->ev_level[l], ctx->stream));
-      GH_HIP(ctx, hipStreamWaitEvent(p->side, p->ev_level[l], 0));
-      StreamSwap sw(ctx, p->side);
-      GH_TRY(launch_select(l, 1));
-    }
-  }
-  if (overlap) {
-    GH_HIP(ctx, hipEventRecord(p->ev_join, p->side));
-    GH_HIP(ctx, hipStreamWaitEvent(ctx->stream, p->ev_join, 0));
-  } else if (!quadtree) {
-    GH_TRY(launch_select(0, L));
-  }
-  if (!cached && dbg) GH_HIP(ctx, hipMemsetAsync(dbg + kDbgSelStreamed, 1, 1, ctx->stream));
-  DescribeArgs a;
-  for (int l = 0; l < kMaxL; ++l) {
-    a.lv[l] = l < L ? lv[l] : lv[0];
-    a.quota[l] = l < L ? p->quota[l] : 0;
-    a.quota_off[l] = l < L ? p->quota_off[l] : 0;
-    a.scale[l] = l < L ? p->scale[l] : 1.0f;
-  }
-  a.nlevels = L;
-  a.blk_off[0] = 0;
-  for (int l = 0; l < kMaxL; ++l) a.blk_off[l + 1] = a.blk_off[l] + (l < L ? gh_div_up(a.quota[l], 4 * kDescPipe) : 0);
-  const DevTables tb{p->d_pattern, p->d_dir, p->d_base_pattern};
-  const long long blocks = (long long)gh_div_up(K, 4) * batch;
-  GH_CHECK_ARG(ctx, blocks < (1LL << 30));
-  if (p->steer == 0) {  // 30-bin table steering: kDescPipe slots per wave, workgroups dealt per level
-    const long long pblocks = (long long)a.blk_off[L] * batch;
-    GH_LAUNCH(ctx, "orb_describe", describe_pipe_kernel, dim3(8 * gh_div_up(pblocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
-              kps_dev, desc_dev, counts_dev, batch, dbg);
-  } else {  // continuous steering: one keypoint per wave
-    GH_LAUNCH(ctx, "orb_describe", describe_kernel, dim3(8 * gh_div_up(blocks, 8)), dim3(256), 0, a, tb, K, p->sel, p->level_cnt,
-              kps_dev, desc_dev, counts_dev, batch, dbg);
-  }
-  return GH_OK;
+  GH_TRY(orb_enqueue(c));
+  // quadtree mode: when the plan's key budget cut a candidate list below its worst case, a list that overflowed is an error of
+  // THIS call -- it waits for its own kernels.  Otherwise (every plan whose worst case fits 4 GB: 1080p up to ~400 frames per
+  // call) nothing can overflow and the call is asynchronous like the default mode's.
+  if (c.s.kind != OrbSchedule::kQuadtree || !gh_qt_can_overflow(p->qt)) return GH_OK;
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return gh_qt_check(ctx, p->qt);
 }
 
 #ifdef GH_ORB_PHASES

@@ -88,171 +88,14 @@ __device__ __forceinline__ int fast_score_px(const uint8_t* q, int pitch, int mi
   return best;
 }
 
-// The two halves of fast_score_px for the wave-per-cell kernel: the compass test, and the arc score of a survivor.
-__device__ __forceinline__ bool fast_compass_px(const uint8_t* q, int pitch, int min_th) {
-  const int c = q[0];
-  const int d0 = (int)q[-3 * pitch] - c, d4 = (int)q[3] - c, d8 = (int)q[3 * pitch] - c, d12 = (int)q[-3] - c;
-  const int nb = (d0 > min_th) + (d4 > min_th) + (d8 > min_th) + (d12 > min_th);
-  const int nd = (d0 < -min_th) + (d4 < -min_th) + (d8 < -min_th) + (d12 < -min_th);
-  return nb >= 2 || nd >= 2;
-}
-__device__ __forceinline__ int fast_arc_score_px(const uint8_t* q, int pitch) {
-  const int c = q[0];
-  int d[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) d[i] = (int)q[kRing.dy[i] * pitch + kRing.dx[i]] - c;
-  int lo[16], hi[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    lo[i] = min(d[i], d[(i + 1) & 15]);
-    hi[i] = max(d[i], d[(i + 1) & 15]);
-  }
-  int lo4[16], hi4[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    lo4[i] = min(lo[i], lo[(i + 2) & 15]);
-    hi4[i] = max(hi[i], hi[(i + 2) & 15]);
-  }
-  int best = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int mn = min(min(lo4[i], lo4[(i + 4) & 15]), d[(i + 8) & 15]);
-    const int mx = max(max(hi4[i], hi4[(i + 4) & 15]), d[(i + 8) & 15]);
-    best = max(best, max(mn, -mx));
-  }
-  return best;
-}
-
-// step 4', cells up to kWcMax x kWcMax: one wave per cell, four cells per workgroup (independent: no block-wide barrier)
-constexpr int kWcMax = 32;
-constexpr int kWRowDw = 11;                    // dwords per tile row: (3 bytes of alignment + 32 + 6 + 3) / 4
-constexpr int kWImgPitch = 4 * kWRowDw;        // 44
-constexpr int kWSPitch = 36;                   // score plane (kWcMax + 2)^2 with a zero border, padded rows
-struct WaveCellLds {
-  uint32_t img[(kWcMax + 6) * kWRowDw];        // 1672 B; dead after the arc scores: the list of suppressed maxima (at most
-                                               // 16 x 16 words) takes its place
-  uint32_t S[(kWcMax + 2) * kWSPitch / 4];     // 1224 B
-  uint16_t queue[kWcMax * kWcMax];             // compass survivors, (y << 5) | x: 2048 B
-};
-static_assert(sizeof(WaveCellLds) * 4 <= 20 * 1024, "eight workgroups per CU");
-static_assert((kWcMax / 2) * (kWcMax / 2) <= (kWcMax + 6) * kWRowDw, "the maxima fit where the tile was");
-
-__global__ __launch_bounds__(256, 8) void slam_cells_wave_kernel(LevelView lv, int ncols, int ncells, int wc, int hc, int min_th,
-                                                              int ini_th, uint32_t* __restrict__ keys, size_t keys_per_frame,
-                                                              uint32_t cap, uint32_t* __restrict__ key_cnt, int level,
-                                                              uint32_t* __restrict__ flags) {
-  __shared__ WaveCellLds sh[4];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y;
-  const int cell = (int)blockIdx.x * 4 + wv;
-  if (cell >= ncells) return;  // (wave-uniform)
-  WaveCellLds& L = sh[wv];
-  uint32_t* list = L.img;
-  const int ci = cell / ncols, cj = cell - ci * ncols;
-  const int x0 = kEdge + cj * wc, y0 = kEdge + ci * hc;
-  const int x1 = min(x0 + wc, lv.w - kEdge), y1 = min(y0 + hc, lv.h - kEdge);
-  const int cw = x1 - x0, ch = y1 - y0;
-  if (cw <= 0 || ch <= 0) return;
-  const uint8_t* img = lv.base + (size_t)b * lv.frame_stride;
-  // tile rows y0 - 3 .. y1 + 2 as the aligned dwords that cover columns x0 - 3 .. x1 + 2 (the level's pitch is a multiple of
-  // 4 and rows are padded to it: checked at the launch); pixel (r, c) of the tile is byte r * 44 + al + c
-  const int xa = (x0 - 3) & ~3, al = (x0 - 3) & 3;
-  const int ndw = (al + cw + 6 + 3) >> 2, nrow = ch + 6;
-  for (int idx = lane; idx < nrow * kWRowDw; idx += 64) {
-    // idx / 11 on the 24-bit multiplier (full rate; a division by a constant costs a quarter-rate v_mul_hi_u32): exact for
-    // idx < 418 since 5958 / 65536 - 1 / 11 = 2.8e-6
-    const int r = (int)(__umul24((uint32_t)idx, 5958u) >> 16), d = idx - r * kWRowDw;
-    // (rows and pitch are < 2^24, a level is < 4 GiB: 32-bit offset on the full-rate 24-bit multiplier)
-    if (d < ndw) L.img[idx] = *reinterpret_cast<const uint32_t*>(img + (__umul24((uint32_t)(y0 - 3 + r), (uint32_t)lv.pitch) + (uint32_t)(xa + 4 * d)));
-  }
-  for (int idx = lane; idx < (int)(sizeof(L.S) / 4); idx += 64) L.S[idx] = 0u;
-  __builtin_amdgcn_wave_barrier();
-  const uint8_t* I = reinterpret_cast<const uint8_t*>(L.img) + 3 * kWImgPitch + al + 3;  // pixel (0, 0) of the cell
-  uint8_t* S = reinterpret_cast<uint8_t*>(L.S) + kWSPitch + 1;                            // score of cell pixel (0, 0)
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  // compass test on every pixel, survivors queued
-  const int npx = cw * ch;
-  const uint32_t inv = (65536u + (uint32_t)cw - 1u) / (uint32_t)cw;  // p / cw == (p * inv) >> 16 for p < 1024, cw <= 32
-  int nq = 0;
-  for (int base = 0; base < npx; base += 64) {
-    const int p = base + lane;
-    bool pass = false;
-    uint32_t yx = 0;
-    if (p < npx) {
-      const int y = (int)(__umul24((uint32_t)p, inv) >> 16), x = p - (int)__umul24((uint32_t)y, (uint32_t)cw);
-      yx = (uint32_t)((y << 5) | x);
-      pass = fast_compass_px(I + y * kWImgPitch + x, kWImgPitch, min_th);
-    }
-    const uint64_t m = __ballot(pass);
-    if (pass) L.queue[nq + __popcll(m & lt_mask)] = (uint16_t)yx;
-    nq += __popcll(m);
-  }
-  __builtin_amdgcn_wave_barrier();
-  // arc score of the survivors
-  for (int base = 0; base < nq; base += 64) {
-    const int i = base + lane;
-    if (i < nq) {
-      const int yx = L.queue[i], y = yx >> 5, x = yx & 31;
-      const int s = fast_arc_score_px(I + y * kWImgPitch + x, kWImgPitch);
-      S[y * kWSPitch + x] = (uint8_t)(s > min_th ? min(s, 255) : 0);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  // 8-neighbour suppression inside the cell (the border of the score plane is zero: pixels outside the cell do not compete)
-  int n = 0;
-  bool strong = false;
-  for (int base = 0; base < nq; base += 64) {
-    const int i = base + lane;
-    bool ismax = false;
-    uint32_t key = 0;
-    int s = 0;
-    if (i < nq) {
-      const int yx = L.queue[i], y = yx >> 5, x = yx & 31;
-      const uint8_t* sp = S + y * kWSPitch + x;
-      s = sp[0];
-      if (s != 0) {
-        const int n0 = sp[-kWSPitch - 1], n1 = sp[-kWSPitch], n2 = sp[-kWSPitch + 1], n3 = sp[-1], n4 = sp[1],
-                  n5 = sp[kWSPitch - 1], n6 = sp[kWSPitch], n7 = sp[kWSPitch + 1];
-        ismax = max(max(max(n0, n1), max(n2, n3)), max(max(n4, n5), max(n6, n7))) < s;
-        key = ((uint32_t)s << 24) | ((uint32_t)(y0 + y) << 12) | (uint32_t)(x0 + x);
-      }
-    }
-    const uint64_t m = __ballot(ismax);
-    if (ismax) list[n + __popcll(m & lt_mask)] = key;
-    n += __popcll(m);
-    strong = strong || __ballot(ismax && s > ini_th) != 0ull;
-  }
-  __builtin_amdgcn_wave_barrier();
-  // a strong corner silences the weak ones of the cell
-  int kept = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int e = base + lane;
-    kept += __popcll(__ballot(e < n && (!strong || (int)(list[e] >> 24) > ini_th)));
-  }
-  if (kept == 0) return;
-  uint32_t slot0 = 0;
-  if (lane == 0) slot0 = atomicAdd(&key_cnt[b * kMaxL + level], (uint32_t)kept);
-  slot0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot0);
-  uint32_t* out = keys + (size_t)b * keys_per_frame;
-  for (int base = 0; base < n; base += 64) {
-    const int e = base + lane;
-    const uint32_t v = e < n ? list[e] : 0u;
-    const bool keep = e < n && (!strong || (int)(v >> 24) > ini_th);
-    const uint64_t m = __ballot(keep);
-    if (keep) {
-      const uint32_t slot = slot0 + (uint32_t)__popcll(m & lt_mask);
-      if (slot < cap) out[slot] = v;
-      else atomicOr(flags, 1u);  // reported by gh_qt_check: never a silent drop
-    }
-    slot0 += (uint32_t)__popcll(m);
-  }
-}
+constexpr int kWcMax = 32;  // cells up to kWcMax x kWcMax take slam_cells_plane_kernel<false>, larger ones <true>
 
 // step 4' from a SCORE PLANE (round 5): orb.hip's 64 x 64 tile kernel -- the default mode's FAST passes: SWAR compass test,
 // packed arc scores, the next pyramid level fused -- writes S (oracle step 2 / 3: the score where it exceeds min_th, else 0)
 // for the whole level (fast_cells_kernel<.., PLANE>), and a wave per cell only does what the cell decides: 8-neighbour
 // suppression against a zero border, the 20 -> 7 fallback, the key list.  The oracle is written the same way
-// (oracle_orb_slam_candidates reads S).  Against slam_cells_wave_kernel the image is read once per level instead of 1.44
-// times (36 x 36 tiles for 30 x 30 cells), the compass test runs 4 pixels per instruction, and seven resize launches go.
+// (oracle_orb_slam_candidates reads S).  Against FAST per cell on the image itself the image is read once per level instead
+// of 1.44 times (36 x 36 tiles for 30 x 30 cells), the compass test runs 4 pixels per instruction, and seven resize launches go.
 // Plane pixel (y, x) of a frame lives at plane[y * pitch + x + kQtPlaneX] (orb_quadtree.h).
 // Two size classes (template BIG): cells up to 32 x 32 -- every level of a large image -- and up to 40 x 40: ORB-SLAM's cell is
 // ceil(W / floor(W / 30)) pixels, i.e. 33 .. 36 where a side holds fewer than 15 cells (the upper levels of 1080p, most levels of
@@ -927,7 +770,6 @@ gh_status gh_qt_cells(gh_ctx* ctx, gh_qt_plan* q, int l, const LevelView& img, c
   uint32_t* flags = q->key_cnt + (size_t)q->max_batch * kMaxL;
   const QtLevel& v = q->args.lv[l];
   if (v.quota <= 0) return GH_OK;
-  static const bool wave_cells = getenv("GSLAM_HIP_QT_WAVE_CELLS") == nullptr || atoi(getenv("GSLAM_HIP_QT_WAVE_CELLS")) != 0;  // (A/B switch)
   if (plane != nullptr && plane->base != nullptr) {  // the level's score plane exists (gh_qt_plane_ok): cells from it
     if (v.wc <= kWcMax && v.hc <= kWcMax)
       GH_LAUNCH(ctx, "orb_slam_cells", slam_cells_plane_kernel<false>, dim3(gh_div_up(v.ncols * v.nrows, 4 * kPlaneCellsPerWave), batch),
@@ -937,11 +779,7 @@ gh_status gh_qt_cells(gh_ctx* ctx, gh_qt_plan* q, int l, const LevelView& img, c
       GH_LAUNCH(ctx, "orb_slam_cells", slam_cells_plane_kernel<true>, dim3(gh_div_up(v.ncols * v.nrows, 4 * kPlaneCellsPerWave), batch),
                 dim3(256), 0, *plane, v.ncols, v.ncols * v.nrows, v.wc, v.hc, ini_th, q->keys + v.key_off, q->keys_per_frame, v.cap,
                 q->key_cnt, l, flags);
-  } else if (wave_cells && v.wc <= kWcMax && v.hc <= kWcMax && (img.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(img.base) & 3) == 0 &&
-             (img.frame_stride & 3) == 0) {
-    GH_LAUNCH(ctx, "orb_slam_cells", slam_cells_wave_kernel, dim3(gh_div_up(v.ncols * v.nrows, 4), batch), dim3(256), 0, img, v.ncols,
-              v.ncols * v.nrows, v.wc, v.hc, min_th, ini_th, q->keys + v.key_off, q->keys_per_frame, v.cap, q->key_cnt, l, flags);
-  } else {
+  } else {  // no plane: a live level reaches here with cells above kPcBig (gh_qt_plane_ok), one workgroup per cell on the image
     GH_LAUNCH(ctx, "orb_slam_cells", slam_cells_kernel, dim3(v.ncols * v.nrows, batch), dim3(256), 0, img, v.ncols, v.wc, v.hc, min_th,
               ini_th, q->keys + v.key_off, q->keys_per_frame, v.cap, q->key_cnt, l, flags);
   }

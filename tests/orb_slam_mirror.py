@@ -31,10 +31,9 @@ def n_roots(lw, lh):
 
 
 def cell_kernel(oracle, lw, lh, quota):
-    """Which kernel takes the level's cells (orb.hip orb_enqueue's quadtree branch + gh_qt_cells): None (quota 0),
+    """Which kernel takes the level's cells (orb.hip enqueue_quadtree + gh_qt_cells): None (quota 0),
     'plane32' (slam_cells_plane_kernel<false>), 'plane40' (<true>) or 'image' (slam_cells_kernel, which reads the level
-    itself).  slam_cells_wave_kernel cannot be reached: it needs a level without a plane but with a quota, i.e. wc or hc > 40,
-    above its own 32 limit."""
+    itself: a level without a plane but with a quota, i.e. wc or hc > 40)."""
     if not live(lw, lh, quota):
         return None
     _, _, wc, hc = oracle.orb_slam_grid(lw, lh)

@@ -23,7 +23,6 @@ BUDGET = {
     "describe_pipe_kernel": 3,
     "describe_kernelE": 0,               # continuous-steering descriptors
     "resize_kernel": 0,
-    "slam_cells_wave_kernel": 0,         # quadtree mode
 }
 
 

@@ -6,7 +6,6 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORB = open(os.path.join(ROOT, "gslam_amd", "csrc", "orb.hip")).read()
-QT = open(os.path.join(ROOT, "gslam_amd", "csrc", "orb_quadtree.hip")).read()
 
 
 def _exact(mult, shift, divisor, n_end):
@@ -29,15 +28,3 @@ def test_pass1_row_of_item_is_item_div_17():
 def test_pass2_row_of_position_is_position_div_68():
     assert "15421u) >> 20" in ORB and "kScoreW == 68" in ORB
     assert _exact(15421, 20, 68, 68 * 72)
-
-
-def test_quadtree_tile_row_is_index_div_11():
-    assert "__umul24((uint32_t)idx, 5958u) >> 16" in QT and "constexpr int kWRowDw = 11;" in QT
-    assert _exact(5958, 16, 11, (32 + 6) * 11)
-
-
-def test_quadtree_pixel_row_is_pixel_div_cell_width():
-    assert "(65536u + (uint32_t)cw - 1u) / (uint32_t)cw" in QT
-    for cw in range(1, 33):
-        inv = (65536 + cw - 1) // cw
-        assert inv <= 1 << 16 and all((p * inv) >> 16 == p // cw for p in range(32 * 32))

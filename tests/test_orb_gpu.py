@@ -262,7 +262,7 @@ def test_roi_view_whose_allocation_ends_at_the_last_pixel(ctx, oracle):
 
 
 def test_small_call_graph_cache_survives_fresh_and_rotating_buffers(ctx):
-    """The hipGraph replay of small calls (gh_orb_extract_dev): (a) more rotating output sets than the cache holds -- evicted
+    """The hipGraph replay of small calls (orb.hip graphs_replay): (a) more rotating output sets than the cache holds -- evicted
     graphs are retired, not destroyed under a queued launch; (b) fresh output buffers every call -- the plan gives up
     capturing; the records stay identical throughout."""
     import torch

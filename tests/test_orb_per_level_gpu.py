@@ -1,7 +1,7 @@
 """Adversarial GPU parity of the ORB front end on the per-level path of gh_orb_extract_dev, the path of large calls.
 
-Which code runs depends only on the call's pixel count, batch * w * h (gslam_amd/csrc/orb.hip, gh_orb_extract_dev and
-orb_enqueue):
+Which code runs depends only on the call's pixel count, batch * w * h (gslam_amd/csrc/orb.hip, orb_schedule; the launch
+counts of each schedule are pinned by tests/test_orb_schedule_gpu.py):
   <= 4 << 20   small: the whole pyramid by the stand-alone resize, every level in one fast_cells_all_kernel launch, one
                select; a captured graph replays the call
   >  4 << 20   per-level: one fast_cells_kernel<false> launch per level, each building the next pyramid level inside
@@ -24,10 +24,10 @@ from orb_images import CLASSES
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(CLASSES)
-# the dispatch thresholds of orb.hip: `small` / `all_levels` (gh_orb_extract_dev, orb_enqueue) and `overlap` (orb_enqueue)
+# the dispatch thresholds of orb.hip (orb_schedule): kAllLevelsMaxPx and kOverlapMinPx
 SMALL_MAX_PX = 4 << 20
 OVERLAP_MIN_PX = 16 << 20
-SEL_CACHED_CELLS = 8 * 256  # orb.hip kSelCached * 256: larger levels take the streaming select
+SEL_CACHED_CELLS = 8 * 256  # orb.hip kSelCachedMaxCells = kSelCached * 256: larger levels take the streaming select
 
 
 def per_level(batch, w, h):
@@ -291,7 +291,7 @@ def test_branch_census_per_level(ctx, oracle):
 @pytest.mark.parametrize("mode", ["steering", "quadtree"])
 def test_modes_at_overlap_size(ctx, oracle, mode):
     """55 x 640x480 mixed classes (an overlap-sized call) with continuous steering (the per-level path with the select
-    overlap, then describe_kernel) / ORB-SLAM's quadtree distribution (orb_enqueue's quadtree branch, which
+    overlap, then describe_kernel) / ORB-SLAM's quadtree distribution (enqueue_quadtree, which
     runs at every call size and never overlaps select)."""
     B, w, h = 55, 640, 480
     assert overlap(B, w, h)
