@@ -91,7 +91,7 @@ $(PLUGDIR)/libgslam_estimator.so: gslam_amd/plugin/estimator_plugin.cpp include/
 	@mkdir -p $(PLUGDIR)
 	g++ $(PLUGFLAGS) -shared -o $@ $< -L$(LIBDIR) -lgslam_hip $(LIBRPATH) -lpthread -ldl
 
-$(PLUGDIR)/libgslam_orbhip.so: gslam_amd/plugin/orbhip_app.cpp gslam_amd/plugin/FeatureDetector.h
+$(PLUGDIR)/libgslam_orbhip.so: gslam_amd/plugin/orbhip_app.cpp gslam_amd/plugin/orbhip_types.h gslam_amd/plugin/FeatureDetector.h
 	@mkdir -p $(PLUGDIR)
 	g++ $(PLUGFLAGS) -shared -o $@ $< -lpthread -ldl
 

@@ -136,6 +136,23 @@ def _read_log(path):
     return out
 
 
+def _check_extraction_and_matches(oracle, frames, log):
+    """Extraction + matching of every logged frame: bit-exact against the oracle on the frames the dataset delivered."""
+    prev = None
+    for f in log["frames"]:
+        ek, ed = oracle.orb_extract(frames[f["id"]][1], K)
+        assert len(ek) == len(f["kps"]) and f["kps"].tobytes() == ek.tobytes() and np.array_equal(f["desc"], ed)
+        if prev is not None:
+            fw = oracle.bf_match(ed, prev, threads=4)
+            bw = oracle.bf_match(prev, ed, threads=4)
+            keep = oracle.match_mask(fw[0], fw[1], fw[2], bw[0], len(prev), 100, 0, 1, 1).astype(bool)  # matchMaxDistance 100
+            exp = np.stack([np.nonzero(keep)[0], fw[0][keep]], axis=1).astype(np.int32)
+            assert np.array_equal(f["matches"], exp), f"matches of frame {f['id']}"
+        else:
+            assert len(f["matches"]) == 0
+        prev = ed
+
+
 def test_reference_launcher_runs_orbhip_on_the_synthetic_sequence(tmp_path, oracle):
     _need()
     n_frames = 45
@@ -185,20 +202,7 @@ def test_reference_launcher_runs_orbhip_on_the_synthetic_sequence(tmp_path, orac
     fin = np.loadtxt(tmp_path / "orbhip_traj_final.txt")
     assert fin.shape == (n_frames, 8) and np.allclose(fin[:, 0], vo[:, 0])
 
-    # extraction + matching: bit-exact against the oracle on the frames the dataset delivered
-    prev = None
-    for f in log["frames"]:
-        ek, ed = oracle.orb_extract(frames[f["id"]][1], K)
-        assert len(ek) == len(f["kps"]) and f["kps"].tobytes() == ek.tobytes() and np.array_equal(f["desc"], ed)
-        if prev is not None:
-            fw = oracle.bf_match(ed, prev, threads=4)
-            bw = oracle.bf_match(prev, ed, threads=4)
-            keep = oracle.match_mask(fw[0], fw[1], fw[2], bw[0], len(prev), 100, 0, 1, 1).astype(bool)  # matchMaxDistance 100
-            exp = np.stack([np.nonzero(keep)[0], fw[0][keep]], axis=1).astype(np.int32)
-            assert np.array_equal(f["matches"], exp), f"matches of frame {f['id']}"
-        else:
-            assert len(f["matches"]) == 0
-        prev = ed
+    _check_extraction_and_matches(oracle, frames, log)
 
     # optimizePnP twice on every frame but the first (robust fit, then refit on the inliers), replayed through the oracle
     assert [p["id"] for p in log["pnp"]] == [i for i in range(2, n_frames + 1) for _ in (0, 1)]
@@ -317,3 +321,54 @@ def test_launcher_bow_vectors_loop_candidates_and_connections(tmp_path, oracle):
     # (the procedural texture repeats, so the BoW scores of this sequence barely separate the frames: what is checked above
     #  is the machinery -- transform, batched scoring, ordering, node-consistent verification -- not place recognition)
     assert len([lp for lp in log["loops"] if lp["cands"]]) == n_frames - gap
+
+
+def _launch_six_frames(tmp_path, options):
+    """One launch of `gslam orbhip metric_traj play` on six frames of the synthetic sequence; returns the process, the
+    frames the dataset dumped and the call log."""
+    _need()
+    seq = tmp_path / "seq.synthplane"
+    seq.write_text(f"width {W}\nheight {H}\nframes 6\nfps 200\ntexture 2048\nseed 1592590336\n"
+                   f"dump {tmp_path / 'frames.bin'}\n")
+    os.symlink(os.path.join(PLUGDIR, "libgslamDB_synthplane.so"), tmp_path / "libgslamDB_synthplane.so")
+    cmd = [os.path.join(REFDIR, "gslam"), "orbhip", "metric_traj", "play",
+           "-dataset", str(seq), "-slam", "orbhip", "-playspeed", "1",
+           "-orbhip.nFeatures", str(K), "-orbhip.log", str(tmp_path / "orbhip.bin"), "-orbhip.stop_on_finish", "1",
+           "-orbhip.start_dataset", "1"] + options + [
+           "-FeatureDetectorPlugin", os.path.join(PLUGDIR, "libgslam_featuredetector.so"),
+           "-GSLAM_LIBRARY_PATH", PLUGDIR + ":" + LIBDIR + ":" + REFDIR]
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = LIBDIR + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+    r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return r, _read_dump(tmp_path / "frames.bin"), _read_log(tmp_path / "orbhip.bin")
+
+
+def test_lost_tracking_restarts_from_the_dataset_pose(tmp_path, oracle):
+    """`-orbhip.min_track 100000` makes every frame with a predecessor in the window lose tracking: the window is cleared,
+    the next frame starts again from the dataset's pose, so the window alternates between one frame and none, no
+    optimizePnP and no optimize call is made, and every published frame still carries the dataset's pose."""
+    r, frames, log = _launch_six_frames(tmp_path, [
+        "-orbhip.min_track", "100000", "-orbhip.ba_every", "2", "-orbhip.ba_window", "3",
+        "-OptimizerPlugin", os.path.join(PLUGDIR, "libgslam_optimizer.so")])
+    assert sorted(frames) == list(range(1, 7))
+    assert [f["id"] for f in log["frames"]] == list(range(1, 7))
+    _check_extraction_and_matches(oracle, frames, log)
+    assert log["pnp"] == [] and log["ba"] == []
+    assert "bow" not in log and "loops" not in log
+    vo = np.loadtxt(tmp_path / "orbhip_traj_vo.txt")
+    assert vo.shape == (6, 8)
+    for i in range(1, 7):  # "t tx ty tz qx qy qz qw", printed with 6 significant digits
+        pose = frames[i][0]
+        assert np.abs(vo[i - 1, 1:4] - pose[4:]).max() < 5e-6 and np.abs(vo[i - 1, 4:] - pose[:4]).max() < 5e-6, i
+
+
+def test_track_off_extracts_and_matches_only(tmp_path, oracle):
+    """`-orbhip.track 0`: no Optimizer plugin is loaded (none is even named); the application extracts, matches and
+    publishes, and the log holds nothing but the frame records."""
+    r, frames, log = _launch_six_frames(tmp_path, ["-orbhip.track", "0"])
+    assert r.returncode == 0
+    assert [f["id"] for f in log["frames"]] == list(range(1, 7))
+    _check_extraction_and_matches(oracle, frames, log)
+    assert log["pnp"] == [] and log["ba"] == []
+    assert "bow" not in log and "loops" not in log
