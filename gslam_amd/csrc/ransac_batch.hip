@@ -1,0 +1,355 @@
+// Batched, device-resident RANSAC: many independent problems per launch (gh_ransac_batch_dev) and the frame-pair entry in
+// front of it (gh_ransac_pairs_dev).  Problem p is, bit for bit, one gh_ransac_estimate call on its rows: the sampler, the
+// minimal solvers, the error and the essential projection are the functions of ransac_models.h that the single call runs.
+//
+// One call of gh_ransac_estimate is ~1e8 f64 operations behind four launches, two DMAs and a stream synchronise; verifying
+// the 999 frame pairs of a benchmark step that way is latency, not work.  CDNA4 mapping of the batch:
+//   * norm    (F / E only) Hartley normalisation, ONE LANE per problem, sums taken sequentially in index order as the host
+//             loop of the single call takes them (a tree reduction would round differently);
+//   * score   one LANE per hypothesis, 2048 lanes = eight 256-thread workgroups per problem.  The lane solves its minimal
+//             sample, keeps the model in registers and a private integer count; the problem's correspondences pass through
+//             LDS in tiles of kTileRows rows.  Every lane reads the same LDS address (a broadcast, no bank conflict), the row
+//             goes to registers before model_error sees it, and no reduction is needed.  Any n takes this one path;
+//   * finish  one workgroup per problem: argmax of the 2048 counts (lowest index on ties), the winner's model solved again
+//             from its index (the same function on the same rows: the same bits; 2048 x 12 doubles per problem never travel
+//             through memory), its mask, and for E the projection onto the essential manifold, on the device;
+//   * gather  (pair entry) order-preserving compaction of a pair's kept matches into src / dst rows, one workgroup per pair.
+// A problem with fewer rows than the sample, or a threshold that is negative or NaN, is skipped by every kernel BEFORE the
+// sampler (whose rejection loop does not end for n < s): it is "no model".  Row ranges are clamped to the arrays before
+// they address anything.
+#include "ransac_models.h"
+
+namespace {
+
+using namespace gh_ransac;
+
+constexpr int kTileRows = 512;         // correspondences staged per tile: 512 x (3 + 3) doubles = 24 KB of LDS at the most
+constexpr int kParts = kHyp / 256;     // workgroups per problem in the scoring kernel
+constexpr int kChunk = 8192;           // problems per launch: bounds the counts block (kChunk x 2048 ints = 64 MB)
+
+struct BatchArgs {
+  const double* src;
+  const double* dst;
+  const int32_t* row_begin;   // per problem: first row ...
+  const int32_t* row_end;     // ... and one past the last
+  const int32_t* limit_dev;   // rows the arrays hold (device word), or NULL: `limit`
+  int limit;
+  int nproblems;
+  double threshold;
+  const double* thresholds;   // per problem, or NULL
+  uint64_t seed;
+  const uint64_t* seeds;      // per problem, or NULL
+  Norm* norms;                // scratch, F / E
+  int* counts;                // scratch, nproblems x kHyp
+  const int32_t* row_map;     // pair entry: compacted row -> query row (then `mask` is npairs x map_stride, zeroed already)
+  int map_stride;
+  double* models;
+  uint8_t* mask;
+  int32_t* inliers;
+};
+
+// The rows of problem p.  A range that is empty, reversed or not inside the arrays is 0 rows: nothing of it is addressed.
+__device__ inline int problem_rows(const BatchArgs& a, int p, int* first) {
+  const int limit = a.limit_dev ? *a.limit_dev : a.limit;
+  const int b = a.row_begin[p], e = a.row_end[p];
+  *first = b;
+  if (b < 0 || e > limit || e <= b) return 0;
+  return e - b;
+}
+
+__device__ inline double problem_threshold(const BatchArgs& a, int p) { return a.thresholds ? a.thresholds[p] : a.threshold; }
+__device__ inline uint64_t problem_seed(const BatchArgs& a, int p) { return a.seeds ? a.seeds[p] : a.seed; }
+
+// Hartley normalisation of F / E: the host loop of gh_ransac_estimate_ex, one lane per problem, the same order of additions.
+__global__ __launch_bounds__(64) void ransac_batch_norm_kernel(BatchArgs a) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.nproblems) return;
+  int first;
+  const int n = problem_rows(a, p, &first);
+  Norm nm = {0, 0, 1, 0, 0, 1};
+  if (n >= 8) {
+    const double* src = a.src + (size_t)first * 2;
+    const double* dst = a.dst + (size_t)first * 2;
+    double ax = 0, ay = 0, bx = 0, by = 0;
+    for (int i = 0; i < n; ++i) {
+      ax += src[2 * i]; ay += src[2 * i + 1];
+      bx += dst[2 * i]; by += dst[2 * i + 1];
+    }
+    nm.m1x = ax / n; nm.m1y = ay / n; nm.m2x = bx / n; nm.m2y = by / n;
+    double d1 = 0, d2 = 0;
+    for (int i = 0; i < n; ++i) {
+      const double x = src[2 * i] - nm.m1x, y = src[2 * i + 1] - nm.m1y;
+      const double u = dst[2 * i] - nm.m2x, v = dst[2 * i + 1] - nm.m2y;
+      d1 += sqrt(x * x + y * y);
+      d2 += sqrt(u * u + v * v);
+    }
+    d1 /= n; d2 /= n;
+    nm.s1 = d1 > 0 ? 1.4142135623730951 / d1 : 1.0;
+    nm.s2 = d2 > 0 ? 1.4142135623730951 / d2 : 1.0;
+  }
+  a.norms[p] = nm;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void ransac_batch_score_kernel(BatchArgs a) {
+  constexpr int DP = dim_p(MODEL), DQ = dim_q(MODEL);
+  __shared__ double sp[kTileRows * DP];
+  __shared__ double sq[kTileRows * DQ];
+  const int p = blockIdx.x / kParts, tid = threadIdx.x;
+  const int h = (blockIdx.x % kParts) * 256 + tid;
+  int first;
+  const int n = problem_rows(a, p, &first);
+  const double thr = problem_threshold(a, p);
+  if (n < sample_size(MODEL) || !(thr >= 0)) return;  // no model (the whole workgroup leaves: the finish kernel reads no count)
+  const double thr2 = thr * thr;
+  const double* P = a.src + (size_t)first * DP;
+  const double* Q = a.dst + (size_t)first * DQ;
+  Norm nm = {0, 0, 1, 0, 0, 1};
+  if (MODEL == kModelF || MODEL == kModelE) nm = a.norms[p];
+  double m[12];
+  const bool ok = solve_hypothesis(MODEL, P, Q, n, problem_seed(a, p), nm, h, m);
+  int c = 0;
+  for (int t0 = 0; t0 < n; t0 += kTileRows) {
+    const int rows = n - t0 < kTileRows ? n - t0 : kTileRows;
+    __syncthreads();  // the previous tile has been read by every lane
+    for (int k = tid; k < rows * DP; k += 256) sp[k] = P[(size_t)t0 * DP + k];
+    if (MODEL != kModelPlane)  // (the plane reads src only)
+      for (int k = tid; k < rows * DQ; k += 256) sq[k] = Q[(size_t)t0 * DQ + k];
+    __syncthreads();
+    if (ok)
+      for (int i = 0; i < rows; ++i) {
+        double pr[DP], qr[DQ];  // the row in registers: model_error never sees an LDS address
+        for (int e = 0; e < DP; ++e) pr[e] = sp[i * DP + e];
+        for (int e = 0; e < DQ; ++e) qr[e] = MODEL != kModelPlane ? sq[i * DQ + e] : 0.0;
+        double err;
+        if (model_error(MODEL, m, pr, qr, 0, &err) && err <= thr2) ++c;
+      }
+  }
+  a.counts[(size_t)p * kHyp + h] = ok ? c : -1;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void ransac_batch_finish_kernel(BatchArgs a) {
+  constexpr int DP = dim_p(MODEL), DQ = dim_q(MODEL);
+  __shared__ long long red[256];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  int first;
+  const int n = problem_rows(a, p, &first);
+  const double thr = problem_threshold(a, p);
+  const double thr2 = thr * thr;
+  const double* P = a.src + (size_t)first * DP;
+  const double* Q = a.dst + (size_t)first * DQ;
+  long long best = -1;  // count << 32 | (kHyp - 1 - h): larger count wins, then lower index
+  if (n >= sample_size(MODEL) && thr >= 0) {
+    const int* counts = a.counts + (size_t)p * kHyp;
+    for (int h = tid; h < kHyp; h += 256)
+      if (counts[h] >= 0) {
+        const long long k = ((long long)counts[h] << 32) | (long long)(kHyp - 1 - h);
+        best = k > best ? k : best;
+      }
+    red[tid] = best;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+      if (tid < o) red[tid] = red[tid + o] > red[tid] ? red[tid + o] : red[tid];
+      __syncthreads();
+    }
+    best = red[0];
+  }
+  // every lane solves the winner again: uniform control flow, and the mask below needs the model in each lane's registers
+  double m[12], out[12];
+  bool have = false;
+  if (best >= 0) {
+    Norm nm = {0, 0, 1, 0, 0, 1};
+    if (MODEL == kModelF || MODEL == kModelE) nm = a.norms[p];
+    have = solve_hypothesis(MODEL, P, Q, n, problem_seed(a, p), nm, kHyp - 1 - (int)(best & 0xFFFFFFFFll), m);
+  }
+  const int ms = model_size(MODEL);
+  for (int k = 0; k < 12; ++k) out[k] = have && k < ms ? m[k] : 0.0;
+  // (E: the mask is the scored estimate's, the model its projection; a failed projection is no model, mask included)
+  if (MODEL == kModelE && have) have = project_essential(out);
+  if (tid == 0) {
+    for (int k = 0; k < 12; ++k) a.models[(size_t)p * 12 + k] = have ? out[k] : 0.0;
+    a.inliers[p] = have ? (int)(best >> 32) : 0;
+  }
+  if (!a.mask) return;
+  if (a.row_map) {  // pair entry: the gather kernel has zeroed the pair's row of the mask
+    if (!have) return;
+    uint8_t* mask = a.mask + (size_t)p * a.map_stride;
+    for (int i = tid; i < n; i += 256) {
+      double e;
+      if (model_error(MODEL, m, P, Q, i, &e) && e <= thr2) mask[a.row_map[first + i]] = 1;
+    }
+    return;
+  }
+  for (int i = tid; i < n; i += 256) {
+    double e;
+    a.mask[(size_t)first + i] = (have && model_error(MODEL, m, P, Q, i, &e) && e <= thr2) ? 1 : 0;
+  }
+}
+
+// Pair p's correspondences: the query rows i < counts[pair_q[p]], ascending, with keep[i] (if given) and
+// 0 <= idx1[i] < counts[pair_t[p]].  Written to rows p * cap ... of src / dst (float -> double is exact) with the query row of
+// each in row_map; the pair's row of the inlier mask is cleared here.
+__global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(const gh_keypoint* __restrict__ kps, const int32_t* __restrict__ counts,
+                                                                  int cap, const int32_t* __restrict__ pair_q,
+                                                                  const int32_t* __restrict__ pair_t, const int32_t* __restrict__ idx1,
+                                                                  const uint8_t* __restrict__ keep, double* __restrict__ src,
+                                                                  double* __restrict__ dst, int32_t* __restrict__ row_map,
+                                                                  int32_t* __restrict__ row_begin, int32_t* __restrict__ row_end,
+                                                                  int32_t* __restrict__ n_corr, uint8_t* __restrict__ inlier) {
+  __shared__ int wave_total[4];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fq = pair_q[p], ft = pair_t[p];
+  int cq = counts[fq], ct = counts[ft];
+  cq = cq < 0 ? 0 : (cq > cap ? cap : cq);
+  ct = ct < 0 ? 0 : (ct > cap ? cap : ct);
+  const size_t row0 = (size_t)p * cap;
+  int base = 0;
+  for (int i0 = 0; i0 < cap; i0 += 256) {
+    const int i = i0 + tid;
+    int j = -1;
+    bool take = false;
+    if (i < cap) inlier[row0 + i] = 0;
+    if (i < cq) {
+      j = idx1[row0 + i];
+      take = (!keep || keep[row0 + i]) && j >= 0 && j < ct;
+    }
+    const unsigned long long b = __ballot(take);
+    if (lane == 0) wave_total[w] = __popcll(b);
+    __syncthreads();
+    int at = base + __popcll(b & ((1ull << lane) - 1ull));
+    for (int k = 0; k < w; ++k) at += wave_total[k];
+    if (take) {
+      const gh_keypoint* kq = kps + (size_t)fq * cap + i;
+      const gh_keypoint* kt = kps + (size_t)ft * cap + j;
+      const size_t r = row0 + at;
+      src[2 * r] = (double)kq->x;
+      src[2 * r + 1] = (double)kq->y;
+      dst[2 * r] = (double)kt->x;
+      dst[2 * r + 1] = (double)kt->y;
+      row_map[r] = i;
+    }
+    base += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    row_begin[p] = (int32_t)row0;
+    row_end[p] = (int32_t)row0 + base;
+    n_corr[p] = base;
+  }
+}
+
+size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t batch_scratch_bytes(int nproblems) {
+  const size_t np = nproblems < kChunk ? nproblems : kChunk;
+  return round256(np * sizeof(Norm)) + round256(np * kHyp * sizeof(int));
+}
+
+template <int MODEL>
+gh_status batch_launch(gh_ctx* ctx, const BatchArgs& a) {
+  if (MODEL == kModelF || MODEL == kModelE)
+    GH_LAUNCH(ctx, "ransac_batch_norm", ransac_batch_norm_kernel, dim3(gh_div_up(a.nproblems, 64)), dim3(64), 0, a);
+  GH_LAUNCH(ctx, "ransac_batch_score", ransac_batch_score_kernel<MODEL>, dim3(a.nproblems * kParts), dim3(256), 0, a);
+  GH_LAUNCH(ctx, "ransac_batch_finish", ransac_batch_finish_kernel<MODEL>, dim3(a.nproblems), dim3(256), 0, a);
+  return GH_OK;
+}
+
+// `work`: batch_scratch_bytes(nproblems) bytes of device scratch.  Problems go kChunk at a time (stream order keeps the
+// shared scratch safe); every per-problem array of `all` moves with the chunk, rows stay absolute.
+gh_status batch_run(gh_ctx* ctx, int model, const BatchArgs& all, void* work) {
+  for (int p0 = 0; p0 < all.nproblems; p0 += kChunk) {
+    BatchArgs a = all;
+    a.nproblems = all.nproblems - p0 < kChunk ? all.nproblems - p0 : kChunk;
+    a.row_begin += p0;
+    a.row_end += p0;
+    if (a.thresholds) a.thresholds += p0;
+    if (a.seeds) a.seeds += p0;
+    a.models += (size_t)p0 * 12;
+    a.inliers += p0;
+    if (a.row_map && a.mask) a.mask += (size_t)p0 * a.map_stride;
+    a.norms = (Norm*)work;
+    a.counts = (int*)((uint8_t*)work + round256((size_t)a.nproblems * sizeof(Norm)));
+    switch (model) {
+      case kModelH: GH_TRY(batch_launch<kModelH>(ctx, a)); break;
+      case kModelA2: GH_TRY(batch_launch<kModelA2>(ctx, a)); break;
+      case kModelF: GH_TRY(batch_launch<kModelF>(ctx, a)); break;
+      case kModelA3: GH_TRY(batch_launch<kModelA3>(ctx, a)); break;
+      case kModelE: GH_TRY(batch_launch<kModelE>(ctx, a)); break;
+      case kModelSim3: GH_TRY(batch_launch<kModelSim3>(ctx, a)); break;
+      case kModelPlane: GH_TRY(batch_launch<kModelPlane>(ctx, a)); break;
+      default: GH_TRY(batch_launch<kModelPnP>(ctx, a)); break;
+    }
+  }
+  return GH_OK;
+}
+
+}  // namespace
+
+extern "C" int gh_ransac_batch_tile_rows(int model) { return model >= 0 && model <= 7 ? kTileRows : 0; }
+
+extern "C" gh_status gh_ransac_batch_dev(gh_ctx* ctx, int model, const double* src_dev, const double* dst_dev,
+                                         const int32_t* offsets_dev, int nproblems, double threshold,
+                                         const double* thresholds_dev, uint64_t seed, const uint64_t* seeds_dev,
+                                         double* models_dev, uint8_t* mask_dev, int32_t* inliers_dev) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, model >= 0 && model <= 7 && nproblems >= 0 && nproblems <= (1 << 27));
+  GH_CHECK_ARG(ctx, thresholds_dev || threshold >= 0);
+  if (nproblems == 0) return GH_OK;
+  GH_CHECK_ARG(ctx, src_dev && dst_dev && offsets_dev && models_dev && inliers_dev);
+  void* work = nullptr;
+  GH_TRY(gh_scratch(ctx, batch_scratch_bytes(nproblems), &work));
+  BatchArgs a = {};
+  a.src = src_dev;
+  a.dst = dst_dev;
+  a.row_begin = offsets_dev;
+  a.row_end = offsets_dev + 1;
+  a.limit_dev = offsets_dev + nproblems;  // the arrays hold offsets[nproblems] rows
+  a.nproblems = nproblems;
+  a.threshold = threshold;
+  a.thresholds = thresholds_dev;
+  a.seed = seed;
+  a.seeds = seeds_dev;
+  a.models = models_dev;
+  a.mask = mask_dev;
+  a.inliers = inliers_dev;
+  return batch_run(ctx, model, a, work);
+}
+
+extern "C" gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
+                                         const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs,
+                                         const int32_t* idx1_dev, const uint8_t* keep_dev, double threshold, uint64_t seed,
+                                         double* models_dev, uint8_t* inlier_dev, int32_t* n_corr_dev, int32_t* inliers_dev) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, (model == kModelH || model == kModelA2 || model == kModelF) && cap >= 0 && cap <= 65535 && npairs >= 0);
+  GH_CHECK_ARG(ctx, threshold >= 0 && (long long)npairs * (cap > 0 ? cap : 1) <= 0x7FFFFFFFll && npairs <= (1 << 27));
+  if (npairs == 0) return GH_OK;
+  GH_CHECK_ARG(ctx, kps_dev && counts_dev && pair_q_dev && pair_t_dev && idx1_dev && models_dev && inlier_dev && n_corr_dev &&
+                        inliers_dev);
+  // scratch: src | dst (npairs x cap x 2 doubles each) | row_map | row_begin | row_end | the core's own block
+  const size_t rows = (size_t)npairs * cap;
+  const size_t o_dst = round256(rows * 16), o_map = 2 * o_dst, o_begin = o_map + round256(rows * 4),
+               o_end = o_begin + round256((size_t)npairs * 4), o_work = o_end + round256((size_t)npairs * 4);
+  void* base = nullptr;
+  GH_TRY(gh_scratch(ctx, o_work + batch_scratch_bytes(npairs), &base));
+  uint8_t* b = (uint8_t*)base;
+  GH_LAUNCH(ctx, "ransac_pairs_gather", ransac_pairs_gather_kernel, dim3(npairs), dim3(256), 0, kps_dev, counts_dev, cap,
+            pair_q_dev, pair_t_dev, idx1_dev, keep_dev, (double*)b, (double*)(b + o_dst), (int32_t*)(b + o_map),
+            (int32_t*)(b + o_begin), (int32_t*)(b + o_end), n_corr_dev, inlier_dev);
+  BatchArgs a = {};
+  a.src = (const double*)b;
+  a.dst = (const double*)(b + o_dst);
+  a.row_begin = (const int32_t*)(b + o_begin);
+  a.row_end = (const int32_t*)(b + o_end);
+  a.limit = (int)rows;
+  a.nproblems = npairs;
+  a.threshold = threshold;
+  a.seed = seed;
+  a.row_map = (const int32_t*)(b + o_map);
+  a.map_stride = cap;
+  a.models = models_dev;
+  a.mask = inlier_dev;
+  a.inliers = inliers_dev;
+  return batch_run(ctx, model, a, b + o_work);
+}

@@ -1,6 +1,7 @@
 """Host-side mirror of the Estimator plugin (gslam_amd/plugin/estimator_plugin.cpp): robust model fitting with
 inlier masks through gh_ransac_estimate.  Mirrors GSLAM::Estimator::findHomography / findAffine2D / findFundamental /
-findAffine3D (GSLAM/core/Estimator.h:100-147)."""
+findAffine3D (GSLAM/core/Estimator.h:100-147).  estimate_batch / estimate_pairs are the batched, device-resident entries
+(gh_ransac_batch_dev / gh_ransac_pairs_dev): torch tensors are only the device buffers, as in matcher.py."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +52,82 @@ def estimate(ctx: hip.Context, model, src, dst, threshold, seed=1):
     ctx.check(hip.lib.gh_ransac_estimate(ctx.h, int(model), pv(src), pv(dst), n, C.c_double(threshold), C.c_uint64(seed),
                                          pv(m), pv(mask), C.byref(cnt)))
     return m, mask[:n].copy(), cnt.value
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def batch_tile_rows(model):
+    """gh_ransac_batch_tile_rows: correspondences the batched scoring kernel stages at a time (<= 0: unknown model)."""
+    return int(hip.lib.gh_ransac_batch_tile_rows(int(model)))
+
+
+def estimate_batch(ctx: hip.Context, model, src, dst, offsets, threshold, seed, thresholds=None, seeds=None):
+    """gh_ransac_batch_dev.  src, dst: rows x dim float64 (cuda); offsets: nproblems + 1 int32 (cuda), problem p owns rows
+    offsets[p] .. offsets[p + 1] - 1; thresholds (float64) / seeds (int64 holding the uint64 bits) per problem or None for
+    the scalars.  -> (models nproblems x 12 float64, mask rows uint8, inliers nproblems int32), all on the device; nothing
+    is synchronised.  Problem p equals estimate(ctx, model, src_p, dst_p, threshold_p, seed_p)."""
+    import torch
+    assert src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == torch.float64 and src.is_contiguous() and dst.is_contiguous()
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    assert thresholds is None or (thresholds.is_cuda and thresholds.dtype == torch.float64 and thresholds.is_contiguous())
+    assert seeds is None or (seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous())
+    n = offsets.numel() - 1
+    assert (thresholds is None or thresholds.numel() == n) and (seeds is None or seeds.numel() == n)
+    models = torch.empty((n, 12), dtype=torch.float64, device=src.device)
+    mask = torch.zeros(src.shape[0], dtype=torch.uint8, device=src.device)  # (rows past offsets[n], if any, belong to nobody)
+    inliers = torch.empty(n, dtype=torch.int32, device=src.device)
+    ctx.check(hip.lib.gh_ransac_batch_dev(ctx.h, int(model), _p(src), _p(dst), _p(offsets), n, C.c_double(threshold), _p(thresholds),
+                                          C.c_uint64(seed), _p(seeds), _p(models), _p(mask), _p(inliers)))
+    return models, mask, inliers
+
+
+def estimate_pairs(ctx: hip.Context, model, kps, counts, pair_q, pair_t, idx1, keep, threshold, seed):
+    """gh_ransac_pairs_dev, the call after BFMatcher.match_pairs / mask.  kps: F x cap x 7 float32 view of the KeyPoint
+    records, counts: F int32, pair_q / pair_t: P int32, idx1: P x cap int32, keep: P x cap uint8 or None (all cuda).
+    model: HOMOGRAPHY, AFFINE2D or FUNDAMENTAL.  -> (models P x 12, inlier P x cap uint8, n_corr P int32, inliers P int32)
+    on the device; pair p equals estimate() on the rows correspondences_from_matches lists for it."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
+    P, cap = pair_q.shape[0], kps.shape[1]
+    assert pair_t.shape[0] == P and idx1.numel() == P * cap
+    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
+    models = torch.empty((P, 12), dtype=torch.float64, device=kps.device)
+    inlier = torch.empty((P, cap), dtype=torch.uint8, device=kps.device)
+    n_corr = torch.empty(P, dtype=torch.int32, device=kps.device)
+    inliers = torch.empty(P, dtype=torch.int32, device=kps.device)
+    ctx.check(hip.lib.gh_ransac_pairs_dev(ctx.h, int(model), _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
+                                          C.c_double(threshold), C.c_uint64(seed), _p(models), _p(inlier), _p(n_corr), _p(inliers)))
+    return models, inlier, n_corr, inliers
+
+
+def correspondences_from_matches(kps, counts, pair_q, pair_t, idx1, keep=None):
+    """The gather rule of gh_ransac_pairs_dev restated in numpy (host arrays).  kps: F x cap KeyPoint records (the structured
+    dtype of orb.KP_DTYPE, or F x cap x 7 float32 with x, y first); idx1 / keep: P x cap.  For each pair -> (src n x 2 float64,
+    dst n x 2 float64, rows n): the query rows i < counts[pair_q[p]], ascending, with keep[p, i] (if keep is given) and
+    0 <= idx1[p, i] < counts[pair_t[p]]; src = the query keypoint's (x, y), dst = the matched train keypoint's."""
+    kps = np.asarray(kps)
+    if kps.dtype.names:
+        xy = np.stack([kps["x"], kps["y"]], axis=-1)
+    else:
+        xy = kps[..., :2]
+    xy = xy.astype(np.float64)
+    cap = xy.shape[1]
+    counts = np.clip(np.asarray(counts, dtype=np.int64), 0, cap)
+    idx1 = np.asarray(idx1).reshape(len(pair_q), cap)
+    keep = None if keep is None else np.asarray(keep).reshape(len(pair_q), cap)
+    out = []
+    for p, (fq, ft) in enumerate(zip(np.asarray(pair_q).tolist(), np.asarray(pair_t).tolist())):
+        rows = []
+        for i in range(int(counts[fq])):
+            j = int(idx1[p, i])
+            if (keep is None or keep[p, i]) and 0 <= j < counts[ft]:
+                rows.append(i)
+        rows = np.asarray(rows, dtype=np.int64)
+        out.append((xy[fq, rows].reshape(-1, 2), xy[ft, idx1[p, rows]].reshape(-1, 2), rows))
+    return out
 
 
 def triangulate(ctx: hip.Context, ref2cur_pose, ref_dir, cur_dir):

@@ -467,6 +467,43 @@ gh_status gh_ransac_estimate_conf(gh_ctx* ctx, int model, const double* src, con
 gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double* src, const double* dst, int n, double threshold,
                                 double confidence, uint64_t seed, int sampling, double* model_out, uint8_t* mask_out,
                                 int* inliers_out, int* hypotheses_used_out);
+/* Batched and device-resident: geometric verification of many frame pairs in one call.  Every pointer is a DEVICE pointer,
+ * nothing is copied to the host and the call is asynchronous on the context's stream, like the other _dev entries.
+ * Problem p owns rows offsets[p] .. offsets[p + 1] - 1 of src / dst (row widths per model as above; offsets_dev holds
+ * nproblems + 1 entries, offsets[nproblems] = the rows the arrays hold).  Its result is, bit for bit, what
+ * gh_ransac_estimate(ctx, model, src_p, dst_p, n_p, threshold_p, seed_p, ...) returns: GH_SAMPLE_RANSAC over all 2048
+ * hypotheses, most inliers, lowest index on ties; all eight models (GH_MODEL_ESSENTIAL is projected on the device).
+ *   thresholds_dev  one threshold per problem, or NULL: `threshold` for all.  seeds_dev likewise with `seed`.
+ *   models_dev      nproblems x 12 doubles; inliers_dev nproblems counts; mask_dev offsets[nproblems] bytes or NULL, the
+ *                   mask of problem p at offsets[p].  Every output is written for every problem (dirty buffers never show).
+ * "No model" holds per problem (12 zeros, an all-zero mask segment, 0 inliers): n_p < sample size -- a range that is empty,
+ * reversed (offsets not monotone) or not inside 0 .. offsets[nproblems] counts as 0 rows and nothing of it is addressed --,
+ * no regular hypothesis, a failed essential projection, a per-problem threshold that is negative or NaN.
+ * NOT offered here: `confidence`, GH_SAMPLE_LMEDS and GH_SAMPLE_NONE.  Their selection rules run on the host with libm by
+ * design (the prefix rule, the LMedS radius, the all-point fits); gh_ransac_estimate_ex remains the way to get them.
+ * GH_ERR_ARG: model outside 0..7, nproblems < 0, a NULL among src / dst / offsets / models / inliers, `threshold` negative
+ * or NaN while thresholds_dev is NULL.  nproblems == 0: GH_OK, nothing is launched. */
+gh_status gh_ransac_batch_dev(gh_ctx* ctx, int model, const double* src_dev, const double* dst_dev,
+                              const int32_t* offsets_dev, int nproblems, double threshold, const double* thresholds_dev,
+                              uint64_t seed, const uint64_t* seeds_dev, double* models_dev, uint8_t* mask_dev,
+                              int32_t* inliers_dev);
+/* The call a pipeline makes after gh_bf_match_pairs_dev / gh_match_mask_dev: a gather in front of gh_ransac_batch_dev.
+ * kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, idx1_dev (npairs x cap) as the pair matchers take and return them;
+ * keep_dev (npairs x cap, may be NULL) as gh_match_mask_dev writes it.  The correspondences of pair p are the query rows
+ * i < counts[pair_q[p]], in ascending i, with (keep == NULL || keep[p * cap + i]) and 0 <= idx1[p * cap + i] < counts[pair_t[p]]
+ * (an index outside that range drops the row, it is never dereferenced; counts are clamped to 0 .. cap): src = the query
+ * keypoint's (x, y), dst = the matched train keypoint's (x, y), widened float -> double.  Pair p then equals one
+ * gh_ransac_estimate call with `threshold` and `seed` on those rows: models_dev npairs x 12, inliers_dev npairs,
+ * n_corr_dev npairs (the rows gathered), inlier_dev npairs x cap with 1 exactly at the query rows that are inliers of the
+ * winner and 0 everywhere else.  model: GH_MODEL_HOMOGRAPHY, GH_MODEL_AFFINE2D or GH_MODEL_FUNDAMENTAL only (E needs
+ * intrinsics, PnP 3D points: gather them yourself and call gh_ransac_batch_dev); cap <= 65535.  GH_ERR_ARG otherwise. */
+gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
+                              const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                              const uint8_t* keep_dev, double threshold, uint64_t seed, double* models_dev,
+                              uint8_t* inlier_dev, int32_t* n_corr_dev, int32_t* inliers_dev);
+/* Host only (no GPU needed): the number of correspondences of `model` the batched scoring kernel stages through LDS at a
+ * time; <= 0 for an unknown model.  Exported so that tests can sit exactly on the kernel's own tile boundary. */
+int gh_ransac_batch_tile_rows(int model);
 /* Midpoint triangulation, one correspondence per thread (GSLAM::Estimator::trianglate, Estimator.h:164-168): the point of
  * the REFERENCE frame closest to the two rays ref_dir and cur_dir (camera.UnProject of the two pixels), with
  * X_cur = T_ref2cur X_ref, pose = [qx qy qz qw tx ty tz].  pose_stride = 7: one pose per correspondence; 0: one pose for
