@@ -377,7 +377,13 @@ gh_status gh_bow_vocab_create_f32(gh_ctx* ctx, int k, int L, int weighting, int 
 void gh_bow_vocab_destroy(gh_bow_vocab* vocab);
 /* Batched over images: desc_dev n_images x cap x 32 B, counts_dev (may be NULL = cap rows each).  Per feature:
  * word id, word weight, node id at level L - levelsup (0xFFFFFFFF / 0 / 0xFFFFFFFF for rows >= count).  Per image:
- * bow_word (ascending, 0xFFFFFFFF padded) / bow_val (normalised as the reference does) / bow_n.  cap <= 16384. */
+ * bow_word (ascending, 0xFFFFFFFF padded) / bow_val (normalised as the reference does) / bow_n.  cap <= 16384.
+ * Shallow leaves: a tree may end above level L (childNum == 0 on a higher level).  Where a feature's descent ends above
+ * level L - levelsup (> 0), the node id is 0, the root.  The reference leaves its `nid` unwritten there
+ * (Vocabulary.h:1728 is never reached, the caller's local at :1579 is uninitialised), so 0 is this library's own
+ * contract; word id, weight and the BoW vector are the reference's.  Level L - levelsup <= 0 gives 0 as upstream.
+ * A float descent in which no child compares below FLT_MAX (NaN / inf / overflowing input) stops at the node it is on;
+ * the reference does not terminate on such input.  counts_dev entries are clamped to [.., cap]; <= 0 is an empty image. */
 gh_status gh_bow_transform_dev(gh_bow_vocab* vocab, const uint8_t* desc_dev, const int32_t* counts_dev, int cap,
                                int n_images, int levelsup, uint32_t* word_dev, float* weight_dev, uint32_t* node_dev,
                                uint32_t* bow_word_dev, float* bow_val_dev, int32_t* bow_n_dev);

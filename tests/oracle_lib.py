@@ -517,6 +517,26 @@ class RefVocabulary:
             self.h = None
 
 
+def ref_bow_transform(ref, voc, desc, levelsup):
+    """Vocabulary::load + transform of the reference on a vocabulary dict (gslam_amd/bow_synth.py layout), binary or float
+    -> dict(word, weight, node, bow_ids, bow_vals, fv_nodes, fv_feat); the FeatureVector is None for float descriptors
+    (the shim does not return it)."""
+    from gslam_amd import bow_synth
+    rv = RefVocabulary(ref, bow_synth.to_gbow_bytes(voc))
+    try:
+        assert rv.info() == (int(voc["k"]), int(voc["L"]), len(voc["nodes"]))
+        if voc["desc"].dtype == np.float32:
+            bi, bv, w, wt, nd = rv.transform_f32(np.ascontiguousarray(desc, np.float32).reshape(-1, voc["desc"].shape[1]), levelsup)
+            fn = ff = None
+        else:
+            width = voc["desc"].shape[1]
+            w, wt, nd = rv.words(desc, levelsup, desc_bytes=width)
+            bi, bv, fn, ff = rv.transform(desc, levelsup, desc_bytes=width)
+    finally:
+        rv.close()
+    return dict(word=w.astype(np.uint32), weight=wt, node=nd, bow_ids=bi.astype(np.uint32), bow_vals=bv, fv_nodes=fn, fv_feat=ff)
+
+
 # ---------------------------------------------------------------- Undistorter wrappers
 def _undist_methods(cls):
     def undistort(self, img, tables, fast=False):

@@ -14,6 +14,9 @@ Run in the authoring container only (needs /root/reference); the outputs are com
                      and its undistort / undistortFast outputs on seeded 1- and 3-channel images.
   camera_reference.npz  GSLAM::Camera::Project of a pinhole and two OpenCV cameras on seeded camera-frame points
                      (`gen_golden.py camera`): pins the projection the self-calibrating graph solve differentiates.
+  bow_adversarial.npz  the reference's Vocabulary::transform on the fixture classes of tests/bow_cases.py (shallow leaves
+                     with the mask of features whose node id the reference defines, planted ties, one word, all
+                     stopped) and its score() on one vector pair per scoring type (`gen_golden.py adversarial`).
 """
 import os
 import sys
@@ -55,6 +58,41 @@ def wide_bow(ref, out):
     print("bow_reference_wide.npz written")
 
 
+def adversarial_bow(ref, out):
+    """bow_adversarial.npz: features and the reference's outputs only; the vocabularies are rebuilt by tests/bow_cases.py
+    (a CRC of the .gbow image the reference loaded pins them).  Where a descent ends above level L - levelsup the
+    reference leaves the node id unwritten: those entries are recorded as 0 and marked in defined_<levelsup>."""
+    import zlib
+    from gslam_amd import bow_synth
+    import bow_cases as bc
+    import bow_restate as br
+    rec = {}
+    for name in bc.FIXTURE_CLASSES:
+        voc, desc, levelsups, _ = bc.case(name)
+        rec[f"{name}/gbow_crc"] = zlib.crc32(bow_synth.to_gbow_bytes(voc))
+        rec[f"{name}/desc"] = desc
+        rec[f"{name}/levelsups"] = np.array(levelsups)
+        for levelsup in levelsups:
+            r = oracle_lib.ref_bow_transform(ref, voc, desc, levelsup)
+            defined = br.descend(voc, desc, levelsup)["reached"]
+            keep = defined[r["fv_feat"]]
+            rec.update({f"{name}/word": r["word"], f"{name}/weight": r["weight"], f"{name}/bow_ids": r["bow_ids"],
+                        f"{name}/bow_vals": r["bow_vals"], f"{name}/defined_{levelsup}": defined,
+                        f"{name}/node_{levelsup}": np.where(defined, r["node"], 0).astype(np.uint32),
+                        f"{name}/fv_nodes_{levelsup}": r["fv_nodes"][keep], f"{name}/fv_feat_{levelsup}": r["fv_feat"][keep]})
+    for sc in range(6):
+        _, q, db, _ = bc.score_case(f"lengths_s{sc}")
+        a, b = br.effective(q)[5], br.effective(db)[6]  # 128 words against 129
+        rv = oracle_lib.RefVocabulary(ref, bow_synth.to_gbow_bytes(bc.score_voc(sc)))
+        ra, rb = (a[0].astype(np.uint64), a[1]), (b[0].astype(np.uint64), b[1])
+        rec.update({f"score{sc}/a_ids": a[0], f"score{sc}/a_vals": a[1], f"score{sc}/b_ids": b[0], f"score{sc}/b_vals": b[1],
+                    f"score{sc}/ab": rv.score(ra, rb), f"score{sc}/ba": rv.score(rb, ra)})
+        rv.close()
+    path = os.path.join(out, "bow_adversarial.npz")
+    np.savez_compressed(path, **rec)
+    print("bow_adversarial.npz written,", os.path.getsize(path), "bytes")
+
+
 def camera_golden(ref, out):
     """camera_reference.npz: the reference's Camera::Project (GSLAM/core/Camera.h:213-227,386-407)."""
     rng = np.random.default_rng(20260925)
@@ -93,6 +131,8 @@ def main():
         return bf_bytes_golden(ref, os.path.join(ROOT, "tests", "golden"))
     if len(sys.argv) > 1 and sys.argv[1] == "wide":
         return wide_bow(ref, os.path.join(ROOT, "tests", "golden"))
+    if len(sys.argv) > 1 and sys.argv[1] == "adversarial":
+        return adversarial_bow(ref, os.path.join(ROOT, "tests", "golden"))
     if len(sys.argv) > 1 and sys.argv[1] == "camera":
         return camera_golden(ref, os.path.join(ROOT, "tests", "golden"))
     out = os.path.join(ROOT, "tests", "golden")
@@ -174,6 +214,7 @@ def main():
     ru.close()
     np.savez_compressed(os.path.join(out, "undist_reference.npz"), **rec)
     wide_bow(ref, out)
+    adversarial_bow(ref, out)
     camera_golden(ref, out)
     print("golden vectors written to", out)
 
