@@ -14,6 +14,8 @@
 //             from its index (the same function on the same rows: the same bits; 2048 x 12 doubles per problem never travel
 //             through memory), its mask, and for E the projection onto the essential manifold, on the device;
 //   * gather  (pair entry) order-preserving compaction of a pair's kept matches into src / dst rows, one workgroup per pair.
+// gh_two_view_pairs_dev (the calibrated pair entry: gather with normalisation, the E batch, then two_view.hip's kernel on the
+// inliers) lives here because it is this file's gather and this file's batch_run on one scratch block.
 // A problem with fewer rows than the sample, or a threshold that is negative or NaN, is skipped by every kernel BEFORE the
 // sampler (whose rejection loop does not end for n < s): it is "no model".  Row ranges are clamped to the arrays before
 // they address anything.
@@ -189,8 +191,14 @@ __global__ __launch_bounds__(256) void ransac_batch_finish_kernel(BatchArgs a) {
 
 // Pair p's correspondences: the query rows i < counts[pair_q[p]], ascending, with keep[i] (if given) and
 // 0 <= idx1[i] < counts[pair_t[p]].  Written to rows p * cap ... of src / dst (float -> double is exact) with the query row of
-// each in row_map; the pair's row of the inlier mask is cleared here.
-__global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(const gh_keypoint* __restrict__ kps, const int32_t* __restrict__ counts,
+// each in row_map; the pair's row of the inlier mask is cleared here.  NORMALISE (gh_two_view_pairs_dev): pinhole intrinsics
+// k turn the pixels into normalised coordinates, ((double)x - k.cx) / k.fx, in double.
+struct Pinhole {
+  double fx, fy, cx, cy;
+};
+template <bool NORMALISE>
+__global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, const gh_keypoint* __restrict__ kps,
+                                                                  const int32_t* __restrict__ counts,
                                                                   int cap, const int32_t* __restrict__ pair_q,
                                                                   const int32_t* __restrict__ pair_t, const int32_t* __restrict__ idx1,
                                                                   const uint8_t* __restrict__ keep, double* __restrict__ src,
@@ -223,10 +231,17 @@ __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(const gh_keypo
       const gh_keypoint* kq = kps + (size_t)fq * cap + i;
       const gh_keypoint* kt = kps + (size_t)ft * cap + j;
       const size_t r = row0 + at;
-      src[2 * r] = (double)kq->x;
-      src[2 * r + 1] = (double)kq->y;
-      dst[2 * r] = (double)kt->x;
-      dst[2 * r + 1] = (double)kt->y;
+      if (NORMALISE) {
+        src[2 * r] = ((double)kq->x - k.cx) / k.fx;
+        src[2 * r + 1] = ((double)kq->y - k.cy) / k.fy;
+        dst[2 * r] = ((double)kt->x - k.cx) / k.fx;
+        dst[2 * r + 1] = ((double)kt->y - k.cy) / k.fy;
+      } else {
+        src[2 * r] = (double)kq->x;
+        src[2 * r + 1] = (double)kq->y;
+        dst[2 * r] = (double)kt->x;
+        dst[2 * r + 1] = (double)kt->y;
+      }
       row_map[r] = i;
     }
     base += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
@@ -334,7 +349,8 @@ extern "C" gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoi
   void* base = nullptr;
   GH_TRY(gh_scratch(ctx, o_work + batch_scratch_bytes(npairs), &base));
   uint8_t* b = (uint8_t*)base;
-  GH_LAUNCH(ctx, "ransac_pairs_gather", ransac_pairs_gather_kernel, dim3(npairs), dim3(256), 0, kps_dev, counts_dev, cap,
+  GH_LAUNCH(ctx, "ransac_pairs_gather", ransac_pairs_gather_kernel<false>, dim3(npairs), dim3(256), 0, Pinhole{1, 1, 0, 0},
+            kps_dev, counts_dev, cap,
             pair_q_dev, pair_t_dev, idx1_dev, keep_dev, (double*)b, (double*)(b + o_dst), (int32_t*)(b + o_map),
             (int32_t*)(b + o_begin), (int32_t*)(b + o_end), n_corr_dev, inlier_dev);
   BatchArgs a = {};
@@ -352,4 +368,66 @@ extern "C" gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoi
   a.mask = inlier_dev;
   a.inliers = inliers_dev;
   return batch_run(ctx, model, a, b + o_work);
+}
+
+extern "C" gh_status gh_two_view_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
+                                           const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs,
+                                           const int32_t* idx1_dev, const uint8_t* keep_dev, double fx, double fy, double cx,
+                                           double cy, double threshold, uint64_t seed, const gh_two_view_params* params,
+                                           double* models_dev, uint8_t* inlier_dev, int32_t* n_corr_dev, int32_t* inliers_dev,
+                                           double* poses_dev, double* points_dev, uint8_t* good_dev, int32_t* votes_dev,
+                                           int32_t* status_dev) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, cap >= 0 && cap <= 65535 && npairs >= 0 && fx > 0 && fy > 0 && cx == cx && cy == cy);
+  GH_CHECK_ARG(ctx, threshold >= 0 && (long long)npairs * (cap > 0 ? cap : 1) <= 0x7FFFFFFFll && npairs <= (1 << 27));
+  GH_CHECK_ARG(ctx, two_view_params_ok(params));
+  if (npairs == 0) return GH_OK;
+  GH_CHECK_ARG(ctx, kps_dev && counts_dev && pair_q_dev && pair_t_dev && idx1_dev && models_dev && inlier_dev && n_corr_dev &&
+                        inliers_dev && poses_dev && points_dev && good_dev && votes_dev && status_dev);
+  // ONE scratch block for all three stages (gh_scratch hands out one block per context), laid out as gh_ransac_pairs_dev's:
+  // src | dst | row_map | row_begin | row_end | the core's own block.  The two-view kernel reads the first five again.
+  const size_t rows = (size_t)npairs * cap;
+  const size_t o_dst = round256(rows * 16), o_map = 2 * o_dst, o_begin = o_map + round256(rows * 4),
+               o_end = o_begin + round256((size_t)npairs * 4), o_work = o_end + round256((size_t)npairs * 4);
+  void* base = nullptr;
+  GH_TRY(gh_scratch(ctx, o_work + batch_scratch_bytes(npairs), &base));
+  uint8_t* b = (uint8_t*)base;
+  GH_LAUNCH(ctx, "two_view_pairs_gather", ransac_pairs_gather_kernel<true>, dim3(npairs), dim3(256), 0, Pinhole{fx, fy, cx, cy},
+            kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, idx1_dev, keep_dev, (double*)b, (double*)(b + o_dst),
+            (int32_t*)(b + o_map), (int32_t*)(b + o_begin), (int32_t*)(b + o_end), n_corr_dev, inlier_dev);
+  BatchArgs a = {};
+  a.src = (const double*)b;
+  a.dst = (const double*)(b + o_dst);
+  a.row_begin = (const int32_t*)(b + o_begin);
+  a.row_end = (const int32_t*)(b + o_end);
+  a.limit = (int)rows;
+  a.nproblems = npairs;
+  a.threshold = threshold;
+  a.seed = seed;
+  a.row_map = (const int32_t*)(b + o_map);
+  a.map_stride = cap;
+  a.models = models_dev;
+  a.mask = inlier_dev;
+  a.inliers = inliers_dev;
+  GH_TRY(batch_run(ctx, kModelE, a, b + o_work));
+  TwoViewArgs t = {};
+  t.E = models_dev;
+  t.e_stride = 12;
+  t.src = a.src;
+  t.dst = a.dst;
+  t.row_begin = a.row_begin;
+  t.row_end = a.row_end;
+  t.limit = a.limit;
+  t.nproblems = npairs;
+  t.mask = inlier_dev;
+  t.row_map = a.row_map;
+  t.map_stride = cap;
+  t.prm = *params;
+  t.poses = poses_dev;
+  t.points = points_dev;
+  t.good = good_dev;
+  t.counts = votes_dev;
+  t.status = status_dev;
+  return two_view_launch(ctx, t);
 }

@@ -516,4 +516,139 @@ __host__ __device__ inline bool project_essential(double* E) {
   return true;
 }
 
+// ---- two-view reconstruction (two_view.hip): pose candidates of an essential matrix and the rule for one correspondence.
+// tests/two_view_restate.py restates both in scalar doubles and the device is held to it bit for bit: + - * / sqrt and
+// comparisons only, every sum in the order written here.
+
+// E (row-major, dst^T E src = 0, E ~ [t]x R with X_cur = R X_ref + t) -> the two rotations and the unit baseline of its
+// four candidates (Ra, +th), (Ra, -th), (Rb, +th), (Rb, -th).  Eigenvectors of E^T E ordered as project_essential orders
+// them; u_a = E v_a / s_a, u3 = u1 x u2, v3 = v1 x v2 (det U = det V = +1 by construction), Ra = U W V^T, Rb = U W^T V^T.
+// false: no second singular value (NaN, all zero, rank 1) or no u3.  A matrix that is not exactly essential is decomposed
+// all the same.
+__host__ __device__ inline bool two_view_decompose(const double* E, double* Ra, double* Rb, double* th) {
+  double B[3][3], V[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double acc = 0.0;
+      for (int k = 0; k < 3; ++k) acc = acc + E[3 * k + r] * E[3 * k + c];
+      B[r][c] = acc;
+    }
+  jacobi_eig<3>(B, V);
+  int o[3] = {0, 1, 2};  // eigenvalues in descending order (stable selection)
+  for (int a = 0; a < 2; ++a)
+    for (int b = a + 1; b < 3; ++b)
+      if (B[o[b]][o[b]] > B[o[a]][o[a]]) {
+        const int t = o[a];
+        o[a] = o[b];
+        o[b] = t;
+      }
+  const double l1 = B[o[0]][o[0]], l2 = B[o[1]][o[1]];
+  if (!(l2 > 1e-300)) return false;
+  double u[3][3], v[3][3];
+  for (int a = 0; a < 2; ++a) {
+    const double sv = sqrt(a == 0 ? l1 : l2);
+    for (int r = 0; r < 3; ++r) {
+      double acc = 0.0;
+      for (int k = 0; k < 3; ++k) acc = acc + E[3 * r + k] * V[k][o[a]];
+      u[a][r] = acc / sv;
+      v[a][r] = V[r][o[a]];
+    }
+  }
+  for (int r = 0; r < 3; ++r) {
+    const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
+    u[2][r] = u[0][r1] * u[1][r2] - u[0][r2] * u[1][r1];
+    v[2][r] = v[0][r1] * v[1][r2] - v[0][r2] * v[1][r1];
+  }
+  const double n3 = sqrt(u[2][0] * u[2][0] + u[2][1] * u[2][1] + u[2][2] * u[2][2]);
+  if (!(n3 > 0.0)) return false;
+  for (int r = 0; r < 3; ++r) {
+    th[r] = u[2][r] / n3;
+    for (int c = 0; c < 3; ++c) {
+      Ra[3 * r + c] = (u[1][r] * v[0][c] - u[0][r] * v[1][c]) + u[2][r] * v[2][c];
+      Rb[3 * r + c] = (u[0][r] * v[1][c] - u[1][r] * v[0][c]) + u[2][r] * v[2][c];
+    }
+  }
+  return true;
+}
+
+// One correspondence (x, y) <-> (u, v), normalised coordinates, under the candidate (R, t): the midpoint rule of
+// triangulate_kernel on the rays (x, y, 1) and (u, v, 1), then the tests a map point has to pass -- rays not parallel, both
+// ray parameters positive, parallax (cos^2 of the ray angle below c2), positive depth in both views, squared reprojection
+// error at most r2 in both views.  Every test is written as "not (condition)": a NaN anywhere is never good.  X: the point
+// in the reference frame (defined when the result is true).
+__host__ __device__ inline bool two_view_row(const double* R, const double* t, double x, double y, double u, double v, double c2,
+                                             double r2, double* X) {
+  const double b[3] = {u, v, 1.0};
+  double a[3];
+  for (int r = 0; r < 3; ++r) a[r] = R[3 * r] * x + R[3 * r + 1] * y + R[3 * r + 2] * 1.0;
+  const double aa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2], bb = b[0] * b[0] + b[1] * b[1] + b[2] * b[2];
+  const double ab = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+  const double at = a[0] * t[0] + a[1] * t[1] + a[2] * t[2], bt = b[0] * t[0] + b[1] * t[1] + b[2] * t[2];
+  const double det = aa * bb - ab * ab;
+  if (!(det > 1e-12 * aa * bb)) return false;
+  const double l1 = (ab * bt - bb * at) / det, l2 = (aa * bt - ab * at) / det;
+  if (!(l1 > 0.0) || !(l2 > 0.0)) return false;
+  if (ab > 0.0 && ab * ab >= c2 * aa * bb) return false;
+  double mc[3], xc[3];
+  for (int r = 0; r < 3; ++r) mc[r] = ((l1 * a[r] + t[r]) + l2 * b[r]) / 2.0 - t[r];        // midpoint - t, cur frame
+  for (int r = 0; r < 3; ++r) X[r] = R[r] * mc[0] + R[3 + r] * mc[1] + R[6 + r] * mc[2];    // R^T (.)
+  for (int r = 0; r < 3; ++r) xc[r] = (R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2]) + t[r];
+  if (!(X[2] > 0.0) || !(xc[2] > 0.0)) return false;
+  const double ex = X[0] / X[2] - x, ey = X[1] / X[2] - y, fx = xc[0] / xc[2] - u, fy = xc[1] / xc[2] - v;
+  if (!(ex * ex + ey * ey <= r2) || !(fx * fx + fy * fy <= r2)) return false;
+  return true;
+}
+
+// Unit quaternion [qx qy qz qw], qw >= 0, of a rotation matrix by Shepperd's rule: the largest of (trace, R00, R11, R22),
+// the first on ties, picks the column of the symmetric 4 x 4 form that is built; it is normalised afterwards, so no
+// square root of a pivot is needed.
+__host__ __device__ inline void two_view_quat(const double* R, double* q) {
+  const double tr = R[0] + R[4] + R[8];
+  int pick = 0;
+  double best = tr;
+  if (R[0] > best) { best = R[0]; pick = 1; }
+  if (R[4] > best) { best = R[4]; pick = 2; }
+  if (R[8] > best) { best = R[8]; pick = 3; }
+  double qx, qy, qz, qw;
+  if (pick == 0) {
+    qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = 1.0 + tr;
+  } else if (pick == 1) {
+    qx = ((1.0 + R[0]) - R[4]) - R[8]; qy = R[1] + R[3]; qz = R[2] + R[6]; qw = R[7] - R[5];
+  } else if (pick == 2) {
+    qx = R[1] + R[3]; qy = ((1.0 - R[0]) + R[4]) - R[8]; qz = R[5] + R[7]; qw = R[2] - R[6];
+  } else {
+    qx = R[2] + R[6]; qy = R[5] + R[7]; qz = ((1.0 - R[0]) - R[4]) + R[8]; qw = R[3] - R[1];
+  }
+  const double n = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
+  if (qw < 0.0) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
+  q[0] = qx / n; q[1] = qy / n; q[2] = qz / n; q[3] = qw / n;
+}
+
+// What two_view_kernel works on (two_view.hip).  The batch entry addresses mask / good / points by row; the pair entry
+// (ransac_batch.hip) hands it the compacted rows of its gather with row_map, and then mask / good / points are
+// nproblems x map_stride, addressed by the query row of each compacted row.
+struct TwoViewArgs {
+  const double* E;            // problem p: 9 doubles at p * e_stride
+  int e_stride;
+  const double* src;
+  const double* dst;
+  const int32_t* row_begin;   // per problem: first row ...
+  const int32_t* row_end;     // ... and one past the last
+  const int32_t* limit_dev;   // rows the arrays hold (device word), or NULL: `limit`
+  int limit;
+  int nproblems;
+  const uint8_t* mask;        // rows that take part, or NULL: all
+  const int32_t* row_map;     // pair entry only
+  int map_stride;
+  gh_two_view_params prm;
+  double* poses;
+  double* points;
+  uint8_t* good;
+  int32_t* counts;
+  int32_t* n_used;            // may be NULL
+  int32_t* status;
+};
+bool two_view_params_ok(const gh_two_view_params* prm);
+gh_status two_view_launch(gh_ctx* ctx, const TwoViewArgs& a);
+
 }  // namespace gh_ransac

@@ -1,7 +1,9 @@
 """Host-side mirror of the Estimator plugin (gslam_amd/plugin/estimator_plugin.cpp): robust model fitting with
 inlier masks through gh_ransac_estimate.  Mirrors GSLAM::Estimator::findHomography / findAffine2D / findFundamental /
 findAffine3D (GSLAM/core/Estimator.h:100-147).  estimate_batch / estimate_pairs are the batched, device-resident entries
-(gh_ransac_batch_dev / gh_ransac_pairs_dev): torch tensors are only the device buffers, as in matcher.py."""
+(gh_ransac_batch_dev / gh_ransac_pairs_dev): torch tensors are only the device buffers, as in matcher.py.  two_view_batch /
+two_view_pairs (gh_two_view_batch_dev / gh_two_view_pairs_dev) go on from an essential matrix to the relative pose and the
+3-D points, batched and device-resident in the same way."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +11,7 @@ import numpy as np
 from . import hip
 
 HOMOGRAPHY, AFFINE2D, FUNDAMENTAL, AFFINE3D, ESSENTIAL, SIM3, PLANE, PNP = 0, 1, 2, 3, 4, 5, 6, 7
+TWO_VIEW_OK, TWO_VIEW_NO_MODEL, TWO_VIEW_TOO_FEW, TWO_VIEW_AMBIGUOUS = 0, 1, 2, 3  # GH_TWO_VIEW_*: status per problem
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
@@ -127,6 +130,69 @@ def correspondences_from_matches(kps, counts, pair_q, pair_t, idx1, keep=None):
                 rows.append(i)
         rows = np.asarray(rows, dtype=np.int64)
         out.append((xy[fq, rows].reshape(-1, 2), xy[ft, idx1[p, rows]].reshape(-1, 2), rows))
+    return out
+
+
+def two_view_default_params():
+    """gh_two_view_default_params -> hip.TwoViewParams (min_parallax_cos, max_reproj, min_good, min_good_permille)."""
+    p = hip.TwoViewParams()
+    hip.lib.gh_two_view_default_params(C.byref(p))
+    return p
+
+
+def two_view_batch(ctx: hip.Context, E, src, dst, offsets, mask=None, params=None):
+    """gh_two_view_batch_dev.  E: nproblems x e_stride float64 (cuda, e_stride >= 9: the models of estimate_batch go in as they
+    are), src / dst: rows x 2 float64 normalised coordinates, offsets: nproblems + 1 int32, mask: rows uint8 or None (all rows
+    take part).  -> (poses nproblems x 7 [qx qy qz qw tx ty tz] ref -> cur, points rows x 3 in the reference frame, good rows
+    uint8, counts nproblems x 4 int32, n_used nproblems int32, status nproblems int32: TWO_VIEW_*), all on the device;
+    nothing is synchronised."""
+    import torch
+    assert E.is_cuda and E.dtype == torch.float64 and E.is_contiguous() and E.dim() == 2 and E.shape[1] >= 9
+    assert src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == torch.float64 and src.is_contiguous() and dst.is_contiguous()
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == E.shape[0] + 1
+    rows = src.shape[0]
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == rows)
+    n = E.shape[0]
+    prm = params if params is not None else two_view_default_params()
+    dev = src.device
+    poses = torch.empty((n, 7), dtype=torch.float64, device=dev)
+    points = torch.zeros((rows, 3), dtype=torch.float64, device=dev)  # (rows past offsets[n], if any, belong to nobody)
+    good = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    counts = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    n_used = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    ctx.check(hip.lib.gh_two_view_batch_dev(ctx.h, _p(E), int(E.shape[1]), _p(src), _p(dst), _p(offsets), n, _p(mask), C.byref(prm),
+                                            _p(poses), _p(points), _p(good), _p(counts), _p(n_used), _p(status)))
+    return poses, points, good, counts, n_used, status
+
+
+def two_view_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, intrinsics, threshold, seed, params=None):
+    """gh_two_view_pairs_dev, the call after BFMatcher.match_pairs / mask for a calibrated camera.  kps .. keep as
+    estimate_pairs takes them; intrinsics: (fx, fy, cx, cy); threshold: of the essential fit, in normalised units.
+    -> dict of device tensors: models P x 12, inlier P x cap uint8, n_corr P, inliers P, poses P x 7, points P x cap x 3,
+    good P x cap uint8, votes P x 4 (the four candidate counts), status P.  Pair p equals estimate_batch(ESSENTIAL) and
+    two_view_batch on the normalised rows correspondences_from_matches lists for it, scattered back to query rows."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
+    P, cap = pair_q.shape[0], kps.shape[1]
+    assert pair_t.shape[0] == P and idx1.numel() == P * cap
+    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    prm = params if params is not None else two_view_default_params()
+    dev = kps.device
+    out = {"models": torch.empty((P, 12), dtype=torch.float64, device=dev),
+           "inlier": torch.empty((P, cap), dtype=torch.uint8, device=dev),
+           "n_corr": torch.empty(P, dtype=torch.int32, device=dev),
+           "inliers": torch.empty(P, dtype=torch.int32, device=dev),
+           "poses": torch.empty((P, 7), dtype=torch.float64, device=dev),
+           "points": torch.empty((P, cap, 3), dtype=torch.float64, device=dev),
+           "good": torch.empty((P, cap), dtype=torch.uint8, device=dev),
+           "votes": torch.empty((P, 4), dtype=torch.int32, device=dev),
+           "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    ctx.check(hip.lib.gh_two_view_pairs_dev(ctx.h, _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
+                                            C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(threshold),
+                                            C.c_uint64(seed), C.byref(prm), *(_p(out[k]) for k in out)))
     return out
 
 

@@ -87,6 +87,11 @@ class BaSummary(C.Structure):
                 ("trace_accepted", C.c_uint8 * GH_BA_MAX_TRACE)]
 
 
+class TwoViewParams(C.Structure):
+    _fields_ = [("min_parallax_cos", C.c_double), ("max_reproj", C.c_double), ("min_good", C.c_int32),
+                ("min_good_permille", C.c_int32)]
+
+
 # Every symbol include/gslam_hip.h declares.  tests/test_abi.py checks header <-> this table <-> .so.
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SIGNATURES = {
@@ -182,6 +187,10 @@ SIGNATURES = {
     "gh_ransac_pairs_dev": (C.c_int, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp]),
     "gh_ransac_batch_tile_rows": (C.c_int, [_i]),
     "gh_triangulate": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "gh_two_view_default_params": (None, [C.POINTER(TwoViewParams)]),
+    "gh_two_view_batch_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(TwoViewParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_two_view_pairs_dev": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, C.c_uint64, C.POINTER(TwoViewParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gh_ba_default_options": (None, [C.POINTER(BaOptions)]),
     "gh_ba_solve": (C.c_int, [_vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_ba_graph_create": (C.c_int, [_vp, C.POINTER(BaProblem), C.POINTER(BaOptions), C.POINTER(_vp)]),

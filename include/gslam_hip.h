@@ -516,6 +516,67 @@ int gh_ransac_batch_tile_rows(int model);
  * all.  ok[i] = 0 when the rays are parallel or the point lies behind either camera. */
 gh_status gh_triangulate(gh_ctx* ctx, const double* ref2cur_pose, int pose_stride, const double* ref_dir,
                          const double* cur_dir, int n, double* ref_points, uint8_t* ok);
+/* Two-view reconstruction, batched and device-resident: from an essential matrix and its correspondences to the relative
+ * pose and the 3-D points a bundle adjustment starts from (the step between gh_ransac_batch_dev(GH_MODEL_ESSENTIAL) and
+ * gh_ba_graph_create).  Every pointer is a DEVICE pointer, nothing is copied to the host, the call is asynchronous on
+ * the context's stream.
+ * Problem p reads E = E_dev[p * e_stride .. + 8] (row-major; e_stride >= 9 doubles, 12 reads models_dev of
+ * gh_ransac_batch_dev in place; the estimator's convention dst^T E src = 0, E ~ [t]x R with X_cur = R X_ref + t) and rows
+ * offsets[p] .. offsets[p + 1] - 1 of src (x, y: reference view) and dst (u, v: current view), both in NORMALISED image
+ * coordinates as for GH_MODEL_ESSENTIAL; offsets_dev holds nproblems + 1 entries and a range that is empty, reversed or not
+ * inside 0 .. offsets[nproblems] counts as 0 rows, nothing of it is addressed.  mask_dev (offsets[nproblems] bytes, may be
+ * NULL: all rows) says which rows take part -- the inlier mask of the fit.
+ *   decomposition  eigenvectors v1, v2 of E^T E for its two largest eigenvalues l1 >= l2 (cyclic Jacobi), u_a = E v_a / sqrt(l_a),
+ *                  u3 = u1 x u2, v3 = v1 x v2, t^ = u3 / |u3|, Ra = u2 v1^T - u1 v2^T + u3 v3^T, Rb = u1 v2^T - u2 v1^T + u3 v3^T;
+ *                  candidates 0 (Ra, +t^), 1 (Ra, -t^), 2 (Rb, +t^), 3 (Rb, -t^).  None when l2 > 1e-300 or |u3| > 0 fails.
+ *   one row        midpoint triangulation of the rays (x, y, 1), (u, v, 1) as gh_triangulate does it; the row is GOOD under a
+ *                  candidate when the rays are not parallel, both ray parameters are positive, the cosine of the angle between
+ *                  the rays is below min_parallax_cos, the point has positive depth in both views and its squared reprojection
+ *                  error is at most max_reproj^2 in both views.  A NaN anywhere is never good.
+ *   vote           counts[k] = participating rows good under candidate k; the winner has the largest count, lowest k on ties.
+ *   status         checked in this order:  GH_TWO_VIEW_NO_MODEL   no decomposition, or no participating row;
+ *                                          GH_TWO_VIEW_TOO_FEW    counts[best] < min_good or 1000 counts[best] < min_good_permille n_used;
+ *                                          GH_TWO_VIEW_AMBIGUOUS  some other candidate has 10 counts[j] > 7 counts[best];
+ *                                          GH_TWO_VIEW_OK.
+ * Outputs, ALL written for every problem (dirty buffers never show): status_dev nproblems; counts_dev nproblems x 4 (zeros
+ * for NO_MODEL); n_used_dev nproblems (participating rows); poses_dev nproblems x 7 [qx qy qz qw tx ty tz], ref -> cur, the
+ * layout gh_triangulate takes, |t| = 1, qw >= 0, zeros unless the status is OK; points_dev 3 doubles and good_dev one byte
+ * per row of src: the winner's point in the REFERENCE frame and 1 for its good rows, zeros for every other row of a problem
+ * and for every row of a problem that is not OK.  The scale is the baseline's: |t| = 1.
+ * All counts are integer sums, so the result is the same bits on every run; the arithmetic is + - * / sqrt only and
+ * tests/two_view_restate.py restates it.
+ * GH_ERR_ARG: nproblems < 0, e_stride < 9, params NULL, min_parallax_cos outside (0, 1], max_reproj negative or NaN, a NULL
+ * among the other pointers (mask_dev excepted).  nproblems == 0: GH_OK, nothing is launched. */
+#define GH_TWO_VIEW_OK 0
+#define GH_TWO_VIEW_NO_MODEL 1
+#define GH_TWO_VIEW_TOO_FEW 2
+#define GH_TWO_VIEW_AMBIGUOUS 3
+typedef struct gh_two_view_params {
+  double min_parallax_cos;   /* 0.99998: ORB-SLAM's initialiser asks for a ray angle of about 0.36 degrees */
+  double max_reproj;         /* 0.004 normalised units: 2 px at f = 500 */
+  int32_t min_good;          /* 50 */
+  int32_t min_good_permille; /* 900: ORB-SLAM's 0.9 of the rows */
+} gh_two_view_params;
+void gh_two_view_default_params(gh_two_view_params* p);
+gh_status gh_two_view_batch_dev(gh_ctx* ctx, const double* E_dev, int e_stride, const double* src_dev, const double* dst_dev,
+                                const int32_t* offsets_dev, int nproblems, const uint8_t* mask_dev,
+                                const gh_two_view_params* params, double* poses_dev, double* points_dev, uint8_t* good_dev,
+                                int32_t* counts_dev, int32_t* n_used_dev, int32_t* status_dev);
+/* The call a pipeline makes after the pair matcher when the camera is calibrated: gather, essential fit and two-view
+ * reconstruction of every pair in one call.  kps_dev .. keep_dev as gh_ransac_pairs_dev takes them and the same gather
+ * rule; the rows are normalised with the pinhole intrinsics as ((double)x - cx) / fx, ((double)y - cy) / fy, fitted with
+ * GH_MODEL_ESSENTIAL (`threshold` in normalised units, `seed`) and the two-view kernel runs on the inliers of that fit.
+ * The result equals, bit for bit, the composition of the public pieces: the gather, that normalisation in double,
+ * gh_ransac_batch_dev(GH_MODEL_ESSENTIAL) and gh_two_view_batch_dev with its mask.
+ * Per pair: models_dev npairs x 12, inliers_dev, n_corr_dev, poses_dev npairs x 7, votes_dev npairs x 4 (the four counts),
+ * status_dev.  Per query row, as gh_ransac_pairs_dev indexes its mask: inlier_dev npairs x cap, good_dev npairs x cap,
+ * points_dev npairs x cap x 3 (zeros where good is 0).  Limits as gh_ransac_pairs_dev (cap <= 65535); fx, fy > 0. */
+gh_status gh_two_view_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
+                                const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                                const uint8_t* keep_dev, double fx, double fy, double cx, double cy, double threshold,
+                                uint64_t seed, const gh_two_view_params* params, double* models_dev, uint8_t* inlier_dev,
+                                int32_t* n_corr_dev, int32_t* inliers_dev, double* poses_dev, double* points_dev,
+                                uint8_t* good_dev, int32_t* votes_dev, int32_t* status_dev);
 
 /* ------------------------------------------------------------------ bundle adjustment - */
 /* DOF bits follow GSLAM::KeyFrameEstimzationDOF (GSLAM/core/Optimizer.h:70-84). */
