@@ -23,10 +23,12 @@
 #include <functional>
 #include <thread>
 
+#include "ba_obs.h"
 #include "common.h"
 #include "cr_map.h"
 #include "host_pool.h"
 #include "lm_rule.h"
+#include "pnp_lm.h"
 
 gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_dev, int extra_rows, double* dinv,
                             double* xwork, unsigned* flow_state, bool store_diag, bool state_ready);
@@ -54,114 +56,7 @@ gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, do
 
 namespace {
 
-constexpr double kMinDepth = 1e-9;
-
-struct Obs {
-  double r[2], w, s;
-  double Jc[12], Jp[6];
-};
-
-__device__ __forceinline__ void quat_rotate(const double* q, const double* p, double* o) {
-  double uvx = q[1] * p[2] - q[2] * p[1], uvy = q[2] * p[0] - q[0] * p[2], uvz = q[0] * p[1] - q[1] * p[0];
-  uvx += uvx; uvy += uvy; uvz += uvz;
-  o[0] = p[0] + q[3] * uvx + (q[1] * uvz - q[2] * uvy);
-  o[1] = p[1] + q[3] * uvy + (q[2] * uvx - q[0] * uvz);
-  o[2] = p[2] + q[3] * uvz + (q[0] * uvy - q[1] * uvx);
-}
-
-__device__ __forceinline__ void quat_mul(const double* a, const double* b, double* o) {
-  o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-  o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-  o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
-// T <- T * exp([v, w]) with guarded coefficients (the reference's SE3::exp is NaN at w == 0)
-__device__ void se3_retract(const double* pose, const double* xi, double* out) {
-  const double* v = xi;
-  const double* w = xi + 3;
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double th = sqrt(th2);
-  double imag, real, A, B;
-  if (th < 1e-5) {
-    const double th4 = th2 * th2;
-    imag = 0.5 - th2 / 48.0 + th4 / 3840.0;
-    real = 1.0 - th2 / 8.0 + th4 / 384.0;
-    A = 0.5 - th2 / 24.0 + th4 / 720.0;
-    B = 1.0 / 6.0 - th2 / 120.0 + th4 / 5040.0;
-  } else {
-    imag = sin(0.5 * th) / th;
-    real = cos(0.5 * th);
-    A = (1.0 - cos(th)) / th2;
-    B = (th - sin(th)) / (th2 * th);
-  }
-  double e[7];
-  e[0] = imag * w[0]; e[1] = imag * w[1]; e[2] = imag * w[2]; e[3] = real;
-  const double c1[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
-  const double c2[3] = {w[1] * c1[2] - w[2] * c1[1], w[2] * c1[0] - w[0] * c1[2], w[0] * c1[1] - w[1] * c1[0]};
-  for (int i = 0; i < 3; ++i) e[4 + i] = v[i] + A * c1[i] + B * c2[i];
-  double q[4], t[3];
-  quat_mul(pose, e, q);
-  quat_rotate(pose, e + 4, t);
-  const double nrm = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int i = 0; i < 4; ++i) out[i] = q[i] * nrm;
-  for (int i = 0; i < 3; ++i) out[4 + i] = pose[4 + i] + t[i];
-}
-
-// residual / weight / Jacobians of one observation; false if the point is not in front of the camera
-template <bool WITH_J>
-__device__ __forceinline__ bool linearize(const double* pose, int dof, const double* X, int pfree, const double* m,
-                                          const double* info, double huber, Obs& o) {
-  const double qc[4] = {-pose[0], -pose[1], -pose[2], pose[3]};
-  const double d[3] = {X[0] - pose[4], X[1] - pose[5], X[2] - pose[6]};
-  double Xc[3];
-  quat_rotate(qc, d, Xc);
-  if (!(Xc[2] > kMinDepth)) return false;
-  const double iz = 1.0 / Xc[2];
-  const double u = Xc[0] * iz, v = Xc[1] * iz;
-  o.r[0] = u - m[0];
-  o.r[1] = v - m[1];
-  double L00 = 1, L01 = 0, L10 = 0, L11 = 1;
-  if (info) { L00 = info[0]; L01 = info[1]; L10 = info[2]; L11 = info[3]; }
-  const double s = o.r[0] * (L00 * o.r[0] + L01 * o.r[1]) + o.r[1] * (L10 * o.r[0] + L11 * o.r[1]);
-  double w = 1.0;
-  if (huber > 0 && s > huber * huber) w = huber / sqrt(s);
-  o.w = w;
-  o.s = s;
-  if (!WITH_J) return true;
-  const double P[6] = {iz, 0, -u * iz, 0, iz, -v * iz};
-  const double D[18] = {-1, 0, 0, 0, -Xc[2], Xc[1],
-                        0, -1, 0, Xc[2], 0, -Xc[0],
-                        0, 0, -1, -Xc[1], Xc[0], 0};
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      double acc = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) acc += P[a * 3 + j] * D[j * 6 + k];
-      o.Jc[a * 6 + k] = ((dof >> k) & 1) ? acc : 0.0;
-    }
-  const double x = pose[0], y = pose[1], z = pose[2], qw = pose[3];
-  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - qw * z), 2 * (x * z + qw * y),
-                       2 * (x * y + qw * z), 1 - 2 * (x * x + z * z), 2 * (y * z - qw * x),
-                       2 * (x * z - qw * y), 2 * (y * z + qw * x), 1 - 2 * (x * x + y * y)};
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      double acc = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) acc += P[a * 3 + j] * R[k * 3 + j];  // R^T[j][k] = R[k][j]
-      o.Jp[a * 3 + k] = pfree ? acc : 0.0;
-    }
-  return true;
-}
-
-__device__ __forceinline__ void weighted_info(const double* info, double w, double* L) {
-  L[0] = w; L[1] = 0; L[2] = 0; L[3] = w;
-  if (info) { L[0] = w * info[0]; L[1] = w * info[1]; L[2] = w * info[2]; L[3] = w * info[3]; }
-}
+using namespace gh_ba;
 
 struct Problem {
   int nc, np, no;
@@ -2608,231 +2503,25 @@ struct PnpResult {
   double info[36];
 };
 
-// v[0..N) summed over the 256 threads of the block in a fixed order; the totals land in tot[0..N) (valid after return)
-template <int N>
-__device__ inline void pnp_block_sum(double* v, double (*red)[36], double* tot) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = v[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    if (lane == 0) red[wv][i] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) tot[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-  __syncthreads();
-}
-
+// the LM loop itself is pnp_lm_body (pnp_lm.h), shared with the batched refinement of pnp_batch.hip
 __global__ __launch_bounds__(256) void pnp_lm_kernel(const double* __restrict__ X, const double* __restrict__ M, int n,
                                                      const double* __restrict__ pose_in, int dof, gh_ba_options opt,
                                                      int want_info, PnpResult* __restrict__ out) {
-  __shared__ double s_pose[7], s_dc[6], s_red[4][36], s_tot[36];
-  __shared__ double s_cost, s_radius, s_decrease;
-  __shared__ int s_ctl[4];  // [0] stop, [1] solve ok, [2] need_lin
+  __shared__ PnpLmShared S;
   const int tid = threadIdx.x;
-  const double huber = opt.huber_delta;
-  if (tid < 7) s_pose[tid] = pose_in[tid];
+  if (tid < 7) S.pose[tid] = pose_in[tid];
   __syncthreads();
-  auto rho_of = [&](double s) { return (huber > 0 && s > huber * huber) ? 2.0 * huber * sqrt(s) - huber * huber : s; };
-  // robust cost at `pose` (sum of rho, not yet halved); with `old`: infinite if an observation valid at `old` is lost
-  auto cost_pass = [&](const double* pose, const double* old) {
-    double c = 0;
-    for (int k = tid; k < n; k += 256) {
-      Obs o;
-      const bool in_front = linearize<false>(pose, 0, X + 3 * k, 0, M + 2 * k, nullptr, huber, o);
-      double ck = in_front ? rho_of(o.s) : 0.0;
-      if (old != nullptr && !in_front && linearize<false>(old, 0, X + 3 * k, 0, M + 2 * k, nullptr, huber, o)) ck = __builtin_inf();
-      c += ck;
-    }
-    return c;
-  };
-  double v[36];
-  v[0] = cost_pass(s_pose, nullptr);
-  pnp_block_sum<1>(v, s_red, s_tot);
+  PnpLmResult res;
+  pnp_lm_body<false, true>(S, X, M, nullptr, n, dof, opt, want_info ? out->info : nullptr, &out->sum, res);
   if (tid == 0) {
-    s_cost = 0.5 * s_tot[0];
-    s_radius = opt.initial_radius;
-    s_decrease = 2.0;
-    s_ctl[0] = 0;
-    s_ctl[2] = 1;
-    out->sum.initial_cost = s_cost;
-    out->sum.trace_len = 0;
-    out->sum.accepted = 0;
-  }
-  __syncthreads();
-  double H[21], g[6];  // lower triangle of J^T L J (row a >= column b at a (a + 1) / 2 + b) and J^T L r: thread 0 keeps them
-  int it = 0, term = 0;
-  for (it = 0; it < opt.max_iterations; ++it) {
-    if (s_ctl[2]) {
-      for (int i = 0; i < 27; ++i) v[i] = 0;
-      for (int k = tid; k < n; k += 256) {
-        Obs o;
-        if (!linearize<true>(s_pose, dof, X + 3 * k, 0, M + 2 * k, nullptr, huber, o)) continue;
-        double L[4];
-        weighted_info(nullptr, o.w, L);
-        const double Lr[2] = {L[0] * o.r[0] + L[1] * o.r[1], L[2] * o.r[0] + L[3] * o.r[1]};
-        double LJ[12];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          LJ[j] = L[0] * o.Jc[j] + L[1] * o.Jc[6 + j];
-          LJ[6 + j] = L[2] * o.Jc[j] + L[3] * o.Jc[6 + j];
-        }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          v[21 + a] += o.Jc[a] * Lr[0] + o.Jc[6 + a] * Lr[1];
-#pragma unroll
-          for (int b = 0; b <= a; ++b) v[a * (a + 1) / 2 + b] += o.Jc[a] * LJ[b] + o.Jc[6 + a] * LJ[6 + b];
-        }
-      }
-      pnp_block_sum<27>(v, s_red, s_tot);
-      if (tid == 0) {
-        double gmax = 0;
-        for (int i = 0; i < 21; ++i) H[i] = s_tot[i];
-        for (int a = 0; a < 6; ++a) {
-          g[a] = s_tot[21 + a];
-          gmax = fmax(gmax, fabs(g[a]));
-        }
-        if (gmax <= opt.gradient_tolerance) s_ctl[0] = 2;  // termination 2, nothing recorded for this iteration
-        s_ctl[2] = 0;
-      }
-      __syncthreads();
-      if (s_ctl[0] == 2) {
-        term = 2;
-        break;
-      }
-    }
-    if (tid == 0) {  // damped 6 x 6 system, Cholesky, dc = -(H + D)^-1 g
-      const double radius = s_radius;
-      double Lc[21];
-      bool ok = true;
-      for (int j = 0; j < 6 && ok; ++j) {
-        const double hjj = H[j * (j + 1) / 2 + j];
-        double d = hjj + (hjj < 1e-6 ? 1e-6 : (hjj > 1e32 ? 1e32 : hjj)) / radius;
-        for (int k = 0; k < j; ++k) d -= Lc[j * (j + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-        if (!(d > 0.0)) {
-          ok = false;
-          break;
-        }
-        const double ljj = sqrt(d);
-        Lc[j * (j + 1) / 2 + j] = ljj;
-        for (int i = j + 1; i < 6; ++i) {
-          double x = H[i * (i + 1) / 2 + j];
-          for (int k = 0; k < j; ++k) x -= Lc[i * (i + 1) / 2 + k] * Lc[j * (j + 1) / 2 + k];
-          Lc[i * (i + 1) / 2 + j] = x / ljj;
-        }
-      }
-      if (ok) {
-        double y[6];
-        for (int i = 0; i < 6; ++i) {
-          double x = -g[i];
-          for (int k = 0; k < i; ++k) x -= Lc[i * (i + 1) / 2 + k] * y[k];
-          y[i] = x / Lc[i * (i + 1) / 2 + i];
-        }
-        for (int i = 5; i >= 0; --i) {
-          double x = y[i];
-          for (int k = i + 1; k < 6; ++k) x -= Lc[k * (k + 1) / 2 + i] * y[k];
-          y[i] = x / Lc[i * (i + 1) / 2 + i];
-        }
-        for (int i = 0; i < 6; ++i) s_dc[i] = y[i];
-      }
-      s_ctl[1] = ok ? 1 : 0;
-    }
-    __syncthreads();
-    const bool ok = s_ctl[1] != 0;
-    double pnew[7];
-    if (ok) {
-      double dc[6];
-      for (int a = 0; a < 6; ++a) dc[a] = s_dc[a];
-      if ((dof & 63) == 0) {
-        for (int i = 0; i < 7; ++i) pnew[i] = s_pose[i];
-      } else {
-        double cur[7];
-        for (int i = 0; i < 7; ++i) cur[i] = s_pose[i];
-        se3_retract(cur, dc, pnew);
-      }
-      double model = 0;
-      for (int k = tid; k < n; k += 256) {
-        Obs o;
-        if (!linearize<true>(s_pose, dof, X + 3 * k, 0, M + 2 * k, nullptr, huber, o)) continue;
-        double L[4];
-        weighted_info(nullptr, o.w, L);
-        double Jd[2] = {0, 0};
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          Jd[0] += o.Jc[a] * dc[a];
-          Jd[1] += o.Jc[6 + a] * dc[a];
-        }
-        const double LJd[2] = {L[0] * Jd[0] + L[1] * Jd[1], L[2] * Jd[0] + L[3] * Jd[1]};
-        const double Lr[2] = {L[0] * o.r[0] + L[1] * o.r[1], L[2] * o.r[0] + L[3] * o.r[1]};
-        model -= Jd[0] * Lr[0] + Jd[1] * Lr[1] + 0.5 * (Jd[0] * LJd[0] + Jd[1] * LJd[1]);
-      }
-      v[0] = cost_pass(pnew, s_pose);
-      v[1] = model;
-      pnp_block_sum<2>(v, s_red, s_tot);
-    }
-    if (tid == 0) {  // the step rule of lm_rule.h (LmRule::step), restated for the device: keep the two alike
-      const double cost = s_cost, radius = s_radius;
-      double new_cost = cost, model = 0, rho = -1;
-      if (ok) {
-        new_cost = 0.5 * s_tot[0];
-        model = s_tot[1];
-        rho = model > 0 ? (cost - new_cost) / model : -1;
-        if (!(new_cost == new_cost)) rho = -1;
-      }
-      const bool acc = ok && rho > opt.min_relative_decrease;
-      const int tl = out->sum.trace_len;
-      if (tl < GH_BA_MAX_TRACE) {
-        out->sum.trace_cost[tl] = new_cost;
-        out->sum.trace_radius[tl] = radius;
-        out->sum.trace_accepted[tl] = (uint8_t)acc;
-        out->sum.trace_len = tl + 1;
-      }
-      if (acc) {
-        const double dcost = cost - new_cost;
-        for (int i = 0; i < 7; ++i) s_pose[i] = pnew[i];
-        const double t = 2.0 * rho - 1.0;
-        double r2 = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-        if (r2 > 1e16) r2 = 1e16;
-        s_radius = r2;
-        s_decrease = 2.0;
-        out->sum.accepted = out->sum.accepted + 1;
-        s_ctl[2] = 1;
-        s_cost = new_cost;
-        if (fabs(dcost) <= opt.function_tolerance * cost) s_ctl[0] = 1;
-      } else {
-        s_radius = radius / s_decrease;
-        s_decrease = s_decrease * 2.0;
-        if (s_radius < 1e-32) s_ctl[0] = 3;
-      }
-    }
-    __syncthreads();
-    if (s_ctl[0] != 0) {
-      term = s_ctl[0];
-      ++it;
-      break;
-    }
-  }
-  if (want_info) {  // J^T W J at the solution (columns masked by dof), W = the Huber IRLS weight
-    for (int i = 0; i < 36; ++i) v[i] = 0;
-    for (int k = tid; k < n; k += 256) {
-      Obs o;
-      if (!linearize<true>(s_pose, dof, X + 3 * k, 0, M + 2 * k, nullptr, huber, o)) continue;
-#pragma unroll
-      for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = 0; b < 6; ++b) v[6 * a + b] += o.w * (o.Jc[a] * o.Jc[b] + o.Jc[6 + a] * o.Jc[6 + b]);
-    }
-    pnp_block_sum<36>(v, s_red, s_tot);
-    if (tid < 36) out->info[tid] = s_tot[tid];
-  }
-  if (tid == 0) {
-    out->sum.iterations = it;
-    out->sum.termination = term;
-    out->sum.final_cost = s_cost;
+    out->sum.iterations = res.iterations;
+    out->sum.accepted = res.accepted;
+    out->sum.termination = res.termination;
+    out->sum.initial_cost = res.initial_cost;
+    out->sum.final_cost = res.final_cost;
     out->sum.solve_ms_total = 0;
     out->sum.total_ms = 0;
-    for (int i = 0; i < 7; ++i) out->pose[i] = s_pose[i];
+    for (int i = 0; i < 7; ++i) out->pose[i] = S.pose[i];
   }
 }
 

@@ -16,6 +16,7 @@
 //   * gather  (pair entry) order-preserving compaction of a pair's kept matches into src / dst rows, one workgroup per pair.
 // gh_two_view_pairs_dev (the calibrated pair entry: gather with normalisation, the E batch, then two_view.hip's kernel on the
 // inliers) lives here because it is this file's gather and this file's batch_run on one scratch block.
+// gh_pnp_batch_dev (pnp_batch.hip) chains the GH_MODEL_PNP batch with its own kernels through ransac_batch_ranges below.
 // A problem with fewer rows than the sample, or a threshold that is negative or NaN, is skipped by every kernel BEFORE the
 // sampler (whose rejection loop does not end for n < s): it is "no model".  Row ranges are clamped to the arrays before
 // they address anything.
@@ -299,6 +300,30 @@ gh_status batch_run(gh_ctx* ctx, int model, const BatchArgs& all, void* work) {
 }
 
 }  // namespace
+
+namespace gh_ransac {
+
+size_t ransac_batch_scratch_bytes(int nproblems) { return batch_scratch_bytes(nproblems); }
+
+gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const double* dst, const int32_t* row_begin,
+                              const int32_t* row_end, int limit, int nproblems, double threshold, uint64_t seed,
+                              double* models, uint8_t* mask, int32_t* inliers, void* work) {
+  BatchArgs a = {};
+  a.src = src;
+  a.dst = dst;
+  a.row_begin = row_begin;
+  a.row_end = row_end;
+  a.limit = limit;
+  a.nproblems = nproblems;
+  a.threshold = threshold;
+  a.seed = seed;
+  a.models = models;
+  a.mask = mask;
+  a.inliers = inliers;
+  return batch_run(ctx, model, a, work);
+}
+
+}  // namespace gh_ransac
 
 extern "C" int gh_ransac_batch_tile_rows(int model) { return model >= 0 && model <= 7 ? kTileRows : 0; }
 

@@ -624,6 +624,34 @@ __host__ __device__ inline void two_view_quat(const double* R, double* q) {
   q[0] = qx / n; q[1] = qy / n; q[2] = qz / n; q[3] = qw / n;
 }
 
+// A 7-double T_wc pose [qx qy qz qw tx ty tz] is a usable start of the pose refinement when every value is finite and the
+// quaternion's sum of squares is > 0 (gh_ba_pnp does not renormalise a start, so neither is it done here).
+__host__ __device__ inline bool pnp_start_ok(const double* pose) {
+  for (int k = 0; k < 7; ++k)
+    if (!(pose[k] - pose[k] == 0.0)) return false;  // NaN and +-Inf fail
+  return pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2] + pose[3] * pose[3] > 0.0;
+}
+
+// The model of GH_MODEL_PNP ([R row-major | t], X_cam = R X + t) as the T_wc pose gh_ba_pnp starts from: q = the quaternion
+// of R^T by two_view_quat, t_wc = -R^T t.  false (pose7 all zero) when a value of the model is not finite, when R is all
+// zero (the estimator's "no model" is 12 zeros; Shepperd's column of a zero matrix would be the identity quaternion) or when
+// the converted pose fails pnp_start_ok.
+__host__ __device__ inline bool pnp_pose_from_model(const double* m, double* pose) {
+  bool finite = true, zero = true;
+  for (int k = 0; k < 12; ++k)
+    if (!(m[k] - m[k] == 0.0)) finite = false;
+  for (int k = 0; k < 9; ++k)
+    if (m[k] != 0.0) zero = false;
+  const double Rt[9] = {m[0], m[3], m[6], m[1], m[4], m[7], m[2], m[5], m[8]};
+  const double* t = m + 9;
+  double out[7];
+  two_view_quat(Rt, out);
+  for (int i = 0; i < 3; ++i) out[4 + i] = -((m[i] * t[0] + m[3 + i] * t[1]) + m[6 + i] * t[2]);
+  const bool ok = finite && !zero && pnp_start_ok(out);
+  for (int k = 0; k < 7; ++k) pose[k] = ok ? out[k] : 0.0;
+  return ok;
+}
+
 // What two_view_kernel works on (two_view.hip).  The batch entry addresses mask / good / points by row; the pair entry
 // (ransac_batch.hip) hands it the compacted rows of its gather with row_map, and then mask / good / points are
 // nproblems x map_stride, addressed by the query row of each compacted row.
@@ -650,5 +678,13 @@ struct TwoViewArgs {
 };
 bool two_view_params_ok(const gh_two_view_params* prm);
 gh_status two_view_launch(gh_ctx* ctx, const TwoViewArgs& a);
+
+// gh_ransac_batch_dev on a scratch block the caller owns (ransac_batch.hip), for entries that chain the batch with their
+// own kernels on ONE context scratch block: ransac_batch_scratch_bytes(nproblems) bytes at `work`.  Problem p owns rows
+// row_begin[p] .. row_end[p] - 1, clipped against `limit` rows; one threshold and one seed for all.
+size_t ransac_batch_scratch_bytes(int nproblems);
+gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const double* dst, const int32_t* row_begin,
+                              const int32_t* row_end, int limit, int nproblems, double threshold, uint64_t seed,
+                              double* models, uint8_t* mask, int32_t* inliers, void* work);
 
 }  // namespace gh_ransac

@@ -3,7 +3,8 @@ inlier masks through gh_ransac_estimate.  Mirrors GSLAM::Estimator::findHomograp
 findAffine3D (GSLAM/core/Estimator.h:100-147).  estimate_batch / estimate_pairs are the batched, device-resident entries
 (gh_ransac_batch_dev / gh_ransac_pairs_dev): torch tensors are only the device buffers, as in matcher.py.  two_view_batch /
 two_view_pairs (gh_two_view_batch_dev / gh_two_view_pairs_dev) go on from an essential matrix to the relative pose and the
-3-D points, batched and device-resident in the same way."""
+3-D points, batched and device-resident in the same way.  pnp_refine_batch / pnp_batch (gh_pnp_refine_batch_dev /
+gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba_pnp would on its inliers."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,7 @@ from . import hip
 
 HOMOGRAPHY, AFFINE2D, FUNDAMENTAL, AFFINE3D, ESSENTIAL, SIM3, PLANE, PNP = 0, 1, 2, 3, 4, 5, 6, 7
 TWO_VIEW_OK, TWO_VIEW_NO_MODEL, TWO_VIEW_TOO_FEW, TWO_VIEW_AMBIGUOUS = 0, 1, 2, 3  # GH_TWO_VIEW_*: status per problem
+PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinement next to gh_ba_summary's 0 .. 3
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
@@ -193,6 +195,83 @@ def two_view_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, in
     ctx.check(hip.lib.gh_two_view_pairs_dev(ctx.h, _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
                                             C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(threshold),
                                             C.c_uint64(seed), C.byref(prm), *(_p(out[k]) for k in out)))
+    return out
+
+
+SUMMARY_DTYPE = np.dtype([("iterations", "<i4"), ("accepted", "<i4"), ("termination", "<i4"), ("n_used", "<i4"),
+                          ("initial_cost", "<f8"), ("final_cost", "<f8")])  # hip.PnpBatchSummary as a numpy record
+
+
+def pnp_pose_from_model(model):
+    """gh_pnp_pose_from_model (host only): [R row-major | t], X_cam = R X + t -> (T_wc pose [qx qy qz qw tx ty tz], ok).
+    ok False: no start, the pose is zeros."""
+    m = np.ascontiguousarray(model, dtype=np.float64).reshape(12)
+    pose = np.full(7, np.nan)
+    ok = hip.lib.gh_pnp_pose_from_model(m.ctypes.data_as(C.c_void_p), pose.ctypes.data_as(C.c_void_p))
+    return pose, bool(ok)
+
+
+def _ba_options(options):
+    if options is not None:
+        return options
+    o = hip.BaOptions()
+    hip.lib.gh_ba_default_options(C.byref(o))
+    return o
+
+
+def pnp_refine_batch(ctx: hip.Context, xyz, xy, offsets, start, mask=None, dof=63, options=None, min_rows=0,
+                     inlier_threshold=-1.0, want_information=False):
+    """gh_pnp_refine_batch_dev.  xyz: rows x 3, xy: rows x 2 float64 (cuda); offsets: nproblems + 1 int32; start: nproblems x 7
+    (T_wc poses) or nproblems x 12 (models of estimate_batch(PNP)) float64; mask: rows uint8 or None (all rows take part);
+    options: hip.BaOptions or None for the defaults.  -> dict of device tensors: poses nproblems x 7, info nproblems x 36 or
+    None, summaries nproblems x 32 uint8 (view the host copy as SUMMARY_DTYPE), inlier rows uint8, n_inliers nproblems int32;
+    nothing is synchronised.  A problem that is optimised equals ba.pnp on its participating rows, bit for bit."""
+    import torch
+    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
+    rows = xyz.shape[0]
+    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    n = offsets.numel() - 1
+    assert start.is_cuda and start.dtype == torch.float64 and start.is_contiguous() and start.dim() == 2 and start.shape[0] == n
+    assert start.shape[1] in (7, 12)
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == rows)
+    dev = xyz.device
+    out = {"poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
+           "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
+           "summaries": torch.empty((n, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
+           "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),  # (rows no range owns belong to nobody)
+           "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)}
+    opt = _ba_options(options)
+    ctx.check(hip.lib.gh_pnp_refine_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, _p(mask), _p(start), int(start.shape[1]),
+                                              int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
+                                              *(_p(out[k]) for k in out)))
+    return out
+
+
+def pnp_batch(ctx: hip.Context, xyz, xy, offsets, ransac_threshold, seed, inlier_threshold, dof=63, options=None, min_rows=0,
+              want_information=False):
+    """gh_pnp_batch_dev, the call after a 3D-2D gather: estimate_batch(PNP), pnp_refine_batch on its inliers from its models,
+    pnp_refine_batch again on the rows within inlier_threshold from the first round's poses.  -> dict of device tensors:
+    models nproblems x 12, ransac_inliers nproblems, poses nproblems x 7, info nproblems x 36 or None, summaries
+    nproblems x 2 x 32 uint8 (round 1, round 2), inlier rows uint8, n_inliers nproblems; nothing is synchronised."""
+    import torch
+    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
+    rows = xyz.shape[0]
+    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    n = offsets.numel() - 1
+    dev = xyz.device
+    out = {"models": torch.empty((n, 12), dtype=torch.float64, device=dev),
+           "ransac_inliers": torch.empty(n, dtype=torch.int32, device=dev),
+           "poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
+           "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
+           "summaries": torch.empty((n, 2, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
+           "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),
+           "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)}
+    opt = _ba_options(options)
+    ctx.check(hip.lib.gh_pnp_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, C.c_double(ransac_threshold), C.c_uint64(seed),
+                                       int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
+                                       *(_p(out[k]) for k in out)))
     return out
 
 

@@ -92,6 +92,12 @@ class TwoViewParams(C.Structure):
                 ("min_good_permille", C.c_int32)]
 
 
+class PnpBatchSummary(C.Structure):
+    """gh_pnp_batch_summary (32 bytes), one per problem of gh_pnp_refine_batch_dev."""
+    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("termination", C.c_int32), ("n_used", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
 # Every symbol include/gslam_hip.h declares.  tests/test_abi.py checks header <-> this table <-> .so.
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SIGNATURES = {
@@ -199,6 +205,11 @@ SIGNATURES = {
     "gh_ba_graph_solve": (C.c_int, [_vp, C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_ba_graph_read": (C.c_int, [_vp, _vp, _vp]),
     "gh_ba_pnp": (C.c_int, [_vp, _vp, _vp, _i, _vp, _i, C.POINTER(BaOptions), _vp, C.POINTER(BaSummary)]),
+    "gh_pnp_pose_from_model": (C.c_int, [_vp, _vp]),
+    "gh_pnp_refine_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, C.POINTER(BaOptions), _i, C.c_double,
+                                          _vp, _vp, _vp, _vp, _vp]),
+    "gh_pnp_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _i, C.POINTER(BaOptions), _i, C.c_double,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gh_pg_solve": (C.c_int, [_vp, C.POINTER(PgProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_graph_solve": (C.c_int, [_vp, C.POINTER(GraphProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_align_sim3": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),

@@ -435,7 +435,8 @@ gh_status gh_undistort_host(gh_undist_plan* plan, const uint8_t* img, int channe
  *   6 plane        findPlane           src n x 3 (dst ignored, pass src); model 4 = [nx ny nz d], n . x + d = 0, |n| = 1
  *   7 PnP          findPnP             src n x 3 object points, dst n x 2 normalised image points; 6-point DLT
  *                                      hypotheses (coplanar object points are degenerate); model 12 = [R row-major | t],
- *                                      X_cam = R X + t.  Refine on the inliers with gh_ba_pnp. */
+ *                                      X_cam = R X + t.  Refine on the inliers with gh_ba_pnp (one problem, host arrays)
+ *                                      or gh_pnp_refine_batch_dev / gh_pnp_batch_dev (batched, device-resident). */
 #define GH_MODEL_HOMOGRAPHY 0
 #define GH_MODEL_AFFINE2D 1
 #define GH_MODEL_FUNDAMENTAL 2
@@ -663,6 +664,69 @@ gh_status gh_ba_graph_read(gh_ba_graph* graph, double* cam_pose, double* point_x
  * information_out (36 doubles, row-major 6x6 J^T J at the solution) may be NULL. */
 gh_status gh_ba_pnp(gh_ctx* ctx, const double* points_xyz, const double* obs_xy, int n, double* pose,
                     int dof, const gh_ba_options* options, double* information_out, gh_ba_summary* summary);
+
+/* Pose refinement after the PnP RANSAC, batched and device-resident: many independent gh_ba_pnp problems in one launch.
+ * Every pointer is a DEVICE pointer, nothing is copied to the host, the call is asynchronous on the context's stream.
+ * Problem p owns rows offsets[p] .. offsets[p + 1] - 1 of xyz_dev (3 doubles: world point) and xy_dev (2 doubles: normalised
+ * image point); offsets_dev holds nproblems + 1 entries.  nrows = the rows the arrays hold (what a caller stores in
+ * offsets[nproblems]): the host sizes its index scratch by it, and a range that is empty, reversed or not inside BOTH
+ * 0 .. nrows and 0 .. offsets[nproblems] counts as 0 rows, nothing of it is addressed.  Ranges of different problems must
+ * not overlap (offsets that are not monotone can make them): such problems get unspecified values, still inside the arrays.
+ *   rows         the PARTICIPATING rows of a problem are those of its range with mask_dev == NULL || mask_dev[row] != 0, in
+ *                ascending order (mask_dev: nrows bytes -- the inlier mask of the fit).
+ *   start        start_stride == 7: start_dev[7 p ..] is a T_wc pose [qx qy qz qw tx ty tz], taken as it stands (not
+ *                renormalised: gh_ba_pnp does not either).  start_stride == 12: start_dev[12 p ..] is a model of
+ *                gh_ransac_batch_dev(GH_MODEL_PNP), converted as gh_pnp_pose_from_model does.  No start: a value read that
+ *                is not finite, a quaternion whose sum of squares fails > 0, for stride 12 an all-zero R ("no model").
+ *   refinement   dof, options as gh_ba_pnp takes them (NULL: the defaults; `verbose` is ignored, `deterministic` plays no
+ *                part).  A problem that is optimised equals, BIT FOR BIT, gh_ba_pnp (its default single-launch path) on the
+ *                participating rows with the same start, dof and options: pose, information, iterations, accepted,
+ *                termination, initial_cost and final_cost.
+ *   termination  GH_PNP_NO_START  no start: pose, information, costs, counts and the inlier segment are zero;
+ *                GH_PNP_TOO_FEW   fewer than min_rows participating rows: pose = the (converted) start, costs 0, information
+ *                                 zeros, not optimised;
+ *                0 .. 3           the codes of gh_ba_summary.termination.
+ *   classify     with inlier_threshold >= 0, a last pass over ALL rows of the range, masked or not, at the pose written:
+ *                inlier_dev[row] = 1 when the point's depth in the camera is > 1e-9 and dx * dx + dy * dy <=
+ *                inlier_threshold^2 (the residual of gh_ba_pnp's linearisation), else 0; n_inliers_dev[p] their number (an
+ *                integer sum: the same bits on every run).  Zeros for NO_START; a TOO_FEW problem is classified under its
+ *                start.  With inlier_threshold < 0 nothing is classified: inlier_dev / n_inliers_dev are zero-filled.
+ * Outputs, ALL written for every problem (dirty buffers never show): poses_dev nproblems x 7, summaries_dev nproblems,
+ * info_dev nproblems x 36 (row-major J^T W J, as gh_ba_pnp's information_out), inlier_dev one byte per row of a valid range
+ * (rows no range owns are not touched), n_inliers_dev nproblems.  mask_dev, info_dev, inlier_dev, n_inliers_dev may be NULL.
+ * GH_ERR_ARG: nproblems < 0, nrows < 0, start_stride not 7 or 12, min_rows < 0, inlier_threshold NaN, a NULL among the
+ * other pointers.  nproblems == 0: GH_OK, nothing is launched. */
+#define GH_PNP_NO_START 4
+#define GH_PNP_TOO_FEW 5
+typedef struct gh_pnp_batch_summary { /* 32 bytes */
+  int32_t iterations, accepted, termination, n_used; /* n_used: participating rows */
+  double initial_cost, final_cost;
+} gh_pnp_batch_summary;
+/* Host only (no GPU needed): model12 = [R row-major | t] with X_cam = R X + t  ->  pose7 = T_wc [qx qy qz qw tx ty tz]:
+ * q = the quaternion of R^T by Shepperd's rule (qw >= 0, normalised), t_wc[i] = -((R[i] t[0] + R[3 + i] t[1]) + R[6 + i] t[2]).
+ * Returns 1 with a pose, 0 with pose7 all zero when there is no start (see above).  tests/pnp_restate.py restates it. */
+int gh_pnp_pose_from_model(const double* model12, double* pose7);
+gh_status gh_pnp_refine_batch_dev(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev,
+                                  int nproblems, int nrows, const uint8_t* mask_dev, const double* start_dev, int start_stride,
+                                  int dof, const gh_ba_options* options, int min_rows, double inlier_threshold,
+                                  double* poses_dev, double* info_dev, gh_pnp_batch_summary* summaries_dev,
+                                  uint8_t* inlier_dev, int32_t* n_inliers_dev);
+/* The call after a 3D-2D gather: fit, refine, refit, for every problem in one call.  It equals, bit for bit, the composition
+ * of the public pieces:
+ *   1. gh_ransac_batch_dev(GH_MODEL_PNP, src = xyz, dst = xy, ransac_threshold, seed) -> models_dev (nproblems x 12), its
+ *      mask, ransac_inliers_dev (nproblems);
+ *   2. gh_pnp_refine_batch_dev with that mask, start = the models (stride 12), classification by inlier_threshold;
+ *   3. gh_pnp_refine_batch_dev with mask = the inliers of (2), start = the poses of (2) (stride 7), the same classification.
+ * poses_dev, info_dev, inlier_dev, n_inliers_dev are those of (3); summaries_dev is nproblems x 2: [2 p] round (2),
+ * [2 p + 1] round (3).  A problem whose round-(2) inliers number fewer than min_rows keeps its first fit (TOO_FEW);
+ * NO_START carries through both rounds.  Ranges as above (inside both nrows and offsets[nproblems], for every stage).
+ * GH_ERR_ARG as above, and: ransac_threshold negative or NaN, inlier_threshold negative (round (3) needs the classification),
+ * models_dev or ransac_inliers_dev NULL.  info_dev, inlier_dev, n_inliers_dev may be NULL. */
+gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev,
+                           int nproblems, int nrows, double ransac_threshold, uint64_t seed, int dof,
+                           const gh_ba_options* options, int min_rows, double inlier_threshold, double* models_dev,
+                           int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
+                           gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev);
 
 /* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
