@@ -69,9 +69,12 @@ extern "C" gh_status gh_undist_plan_create(gh_ctx* ctx, int w_in, int h_in, int 
   const size_t n = (size_t)w_out * h_out, n_in = (size_t)w_in * h_in;
   // The reference's own tables step one row / column past the image for source positions in the last row or column
   // (Undistorter.h:184-187; it reads out of bounds there).  Clamp those to the last pixel; reject anything else.
+  // remapFast may be negative (the reference's -1 of an unmapped pixel) only where remapX is not positive: the
+  // 4-channel fast path gathers src[remapFast] wherever remapX > 0 (:260), the 1- and 3-channel ones test remapFast.
   std::vector<int32_t> idx(remapIdx, remapIdx + 4 * n);
   for (size_t i = 0; i < n; ++i) {
     GH_CHECK_ARG(ctx, remapFast[i] < (long long)n_in);
+    GH_CHECK_ARG(ctx, remapFast[i] >= 0 || !(remapX[i] > 0.f));
     for (int t = 0; t < 4; ++t) {
       GH_CHECK_ARG(ctx, idx[4 * i + t] >= 0 && (size_t)idx[4 * i + t] <= n_in + (size_t)w_in);
       if ((size_t)idx[4 * i + t] >= n_in) idx[4 * i + t] = (int32_t)(n_in - 1);

@@ -408,7 +408,9 @@ gh_status gh_bow_score_host(gh_ctx* ctx, int scoring, const uint32_t* q_word, co
 /* ------------------------------------------------------------------ undistortion ----- */
 /* GSLAM::Undistorter::undistort / undistortFast (GSLAM/core/Undistorter.h:206-348) with the remap tables its
  * prepareReMap builds on the host (:120-203): per output pixel remapX, remapFast, remapIdx[4], remapCoef[4].
- * u8 images, 1 / 3 (/ 4 for `fast`) interleaved channels, dense rows.  Pixels the reference leaves unwritten are 0. */
+ * u8 images, 1 / 3 (/ 4 for `fast`) interleaved channels, dense rows.  Pixels the reference leaves unwritten are 0.
+ * Table contract (anything else is GH_ERR_ARG): remapFast < w_in * h_in, and remapFast >= 0 wherever remapX > 0;
+ * 0 <= remapIdx <= w_in * h_in + w_in (the reference's step past the last row / column, clamped to the last pixel). */
 typedef struct gh_undist_plan gh_undist_plan;
 gh_status gh_undist_plan_create(gh_ctx* ctx, int w_in, int h_in, int w_out, int h_out, const float* remapX,
                                 const int32_t* remapFast, const int32_t* remapIdx, const float* remapCoef,

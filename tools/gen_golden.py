@@ -17,6 +17,9 @@ Run in the authoring container only (needs /root/reference); the outputs are com
   bow_adversarial.npz  the reference's Vocabulary::transform on the fixture classes of tests/bow_cases.py (shallow leaves
                      with the mask of features whose node id the reference defines, planted ties, one word, all
                      stopped) and its score() on one vector pair per scoring type (`gen_golden.py adversarial`).
+  undist_adversarial.npz  tables of the reference's prepareReMap and outputs of its undistort / undistortFast for the pinhole
+                     pairs of tests/undist_cases.py (REF_PAIRS: source pixel 0, first / last column, last row, half-pixel
+                     fractions) on 1-, 3- and 4-channel images (`gen_golden.py undist_adversarial`).
 """
 import os
 import sys
@@ -93,6 +96,31 @@ def adversarial_bow(ref, out):
     print("bow_adversarial.npz written,", os.path.getsize(path), "bytes")
 
 
+def adversarial_undist(ref, out):
+    """undist_adversarial.npz: tables, images and outputs only.  The reference leaves some pixels unwritten (uninitialised
+    memory there): they are recorded as 0 and the mask of the pixels it defines is stored beside each output."""
+    import undist_cases as uc
+    orc = oracle_lib.load()
+    rec = {}
+    for name, (cam_in, cam_out) in uc.REF_PAIRS.items():
+        ru = oracle_lib.RefUndistorter(ref, cam_in, cam_out)
+        t = ru.tables()
+        for k in ("remapX", "remapFast", "remapIdx", "remapCoef"):
+            rec[f"{name}/{k}"] = t[k]
+        imgs = uc.ref_images(name)
+        for ch, fast in uc.MODES:
+            rec[f"{name}/img{ch}"] = imgs[ch]
+            written = orc.undistort(imgs[ch], t, fast=fast)[1]
+            res = ru.run(imgs[ch], fast=fast)
+            res[~written] = 0
+            rec[f"{name}/out{ch}_{int(fast)}"] = res
+            rec[f"{name}/written{ch}_{int(fast)}"] = written.astype(np.uint8)
+        ru.close()
+    path = os.path.join(out, "undist_adversarial.npz")
+    np.savez_compressed(path, **rec)
+    print("undist_adversarial.npz written,", os.path.getsize(path), "bytes")
+
+
 def camera_golden(ref, out):
     """camera_reference.npz: the reference's Camera::Project (GSLAM/core/Camera.h:213-227,386-407)."""
     rng = np.random.default_rng(20260925)
@@ -133,6 +161,8 @@ def main():
         return wide_bow(ref, os.path.join(ROOT, "tests", "golden"))
     if len(sys.argv) > 1 and sys.argv[1] == "adversarial":
         return adversarial_bow(ref, os.path.join(ROOT, "tests", "golden"))
+    if len(sys.argv) > 1 and sys.argv[1] == "undist_adversarial":
+        return adversarial_undist(ref, os.path.join(ROOT, "tests", "golden"))
     if len(sys.argv) > 1 and sys.argv[1] == "camera":
         return camera_golden(ref, os.path.join(ROOT, "tests", "golden"))
     out = os.path.join(ROOT, "tests", "golden")
@@ -215,6 +245,7 @@ def main():
     np.savez_compressed(os.path.join(out, "undist_reference.npz"), **rec)
     wide_bow(ref, out)
     adversarial_bow(ref, out)
+    adversarial_undist(ref, out)
     camera_golden(ref, out)
     print("golden vectors written to", out)
 
