@@ -34,11 +34,12 @@ constexpr int kCellRec = 8;                // dwords per compact cell record: co
 // Test-only branch census (gh_orb_plan_debug_counters): which rarely taken paths an extraction went through.
 enum {
   kDbgCells = 0,         // cells processed by fast_cells
-  kDbgDenseCells,        // cells with more than 64 scored pixels (the list-based branch)
+  kDbgDenseCells,        // passes through the list-based branch of the cell stage (more than 64 scored pixels); two-phase: a cell that is dense
+                         // in phase A, keeps nothing there and is dense again in phase B counts twice
   kDbgOverflowCells,     // cells that wrote entries 7.. to their overflow slot
   kDbgCapCells,          // cells that kept exactly kCap entries
   kDbgRankDropped,       // cells with more than kCap candidates: ranks >= kCap dropped
-  kDbgStrongSilenced,    // cells where a strong corner removed weaker candidates
+  kDbgStrongSilenced,    // cells where a strong corner removed weaker candidates (0 where phase A of the two-phase detector ran: it sees none)
   kDbgMaxQueue,          // longest pass-1 queue of a tile
   kDbgMaxNz,             // most scored pixels in one cell
   kDbgSelCut,            // (level, frame) selections where the quota cut something off
@@ -47,7 +48,7 @@ enum {
   kDbgSelStreamed,       // select launches of the streaming (non-cached) variant
   kDbgUnusedSlots,       // zero-filled output rows
   kDbgStarvedLevels,     // (level, frame) selections with fewer candidates than quota
-  kDbgWeakCells,         // cells with candidates but no corner above the initial threshold (a two-phase detector's second pass)
+  kDbgWeakCells,         // cells with candidates but no corner above the initial threshold (two-phase: counted by phase B in orb_select)
   kDbgResizePasses,      // wave-level passes through the fused resize body (one per wave with at least one item, per item block)
   kDbgCount = 16
 };
@@ -381,6 +382,60 @@ __device__ __forceinline__ int fast_score16_pk(const int (&r)[16], int c) {
   const int best_lo = (int)(best & 0xFFFFu), hi_c = (int)(best >> 16);
   return max3i(0, best_lo - c, c - 255 + hi_c);
 }
+// the score of the pixel at p in an LDS image patch of PITCH bytes per row (3 px of margin on every side)
+template <int PITCH>
+__device__ __forceinline__ int fast_ring_score(const uint8_t* p) {
+  const int c = p[0];
+  int r[16];
+  r[0] = p[-3 * PITCH];
+  r[1] = p[-3 * PITCH + 1];
+  r[2] = p[-2 * PITCH + 2];
+  r[3] = p[-1 * PITCH + 3];
+  r[4] = p[3];
+  r[5] = p[1 * PITCH + 3];
+  r[6] = p[2 * PITCH + 2];
+  r[7] = p[3 * PITCH + 1];
+  r[8] = p[3 * PITCH];
+  r[9] = p[3 * PITCH - 1];
+  r[10] = p[2 * PITCH - 2];
+  r[11] = p[1 * PITCH - 3];
+  r[12] = p[-3];
+  r[13] = p[-1 * PITCH - 3];
+  r[14] = p[-2 * PITCH - 2];
+  r[15] = p[-3 * PITCH - 1];
+  return fast_score16_pk(r, c);
+}
+
+// SWAR compass test of pass 1 on the four pixels of one image dword wc (wl / wr: the dwords left and right of it, wu / wd: the
+// dwords three rows up and down; see fast_cells_tile for the arithmetic).  t = the threshold, 0 .. 255.
+struct CompassK {
+  uint32_t ae, de, ao, dko;
+  __device__ __forceinline__ explicit CompassK(uint32_t t)
+      : ae((0x8000u + t) * 0x10001u), de((0x8000u - t - 1u) * 0x10001u), ao((0x4000u + t) * 0x10001u), dko((0x4000u - t - 1u) * 0x10001u) {}
+};
+// -> the flags of pixels 0, 1, 2, 3 at bits 15, 14, 31, 30 (other bits: garbage)
+__device__ __forceinline__ uint32_t fast_compass4(const CompassK& k, uint32_t wc, uint32_t wl, uint32_t wr, uint32_t wu, uint32_t wd) {
+  constexpr uint32_t kF = 0x00FF00FFu;
+  // E(w) by one v_and, O(w) by one v_perm (bytes 1, 3 -> the two fields)
+  constexpr uint32_t kOdd = 0x0c030c01u;
+  const uint2 C{wc & kF, __builtin_amdgcn_perm(0u, wc, kOdd)}, U{wu & kF, __builtin_amdgcn_perm(0u, wu, kOdd)},
+      D{wd & kF, __builtin_amdgcn_perm(0u, wd, kOdd)};
+  // even pixels (cols 4m, 4m+2): left = cols 4m-3, 4m-1 = O(wl); right = cols 4m+3, 4m+5 = {wc.b3, wr.b1}
+  // odd pixels (cols 4m+1, 4m+3): left = cols 4m-2, 4m = {wl.b2, wc.b0}; right = cols 4m+4, 4m+6 = E(wr)
+  // (v_perm_b32 D, S0, S1: selector bytes 0-3 address S1, 4-7 address S0, 0x0c = zero)
+  const uint32_t le = __builtin_amdgcn_perm(0u, wl, kOdd), re = __builtin_amdgcn_perm(wr, wc, 0x0c050c03u);
+  const uint32_t lo = __builtin_amdgcn_perm(wc, wl, 0x0c040c02u), ro = wr & kF;
+  auto half = [](uint32_t A, uint32_t Dk, uint32_t u, uint32_t d, uint32_t l, uint32_t r) {
+    const uint32_t not_bright_lr = (A - l) & (A - r);
+    const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
+    const uint32_t dark_lr = (Dk - l) | (Dk - r);
+    const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
+    return bright | dark;
+  };
+  const uint32_t ye = half(C.x + k.ae, C.x + k.de, U.x, D.x, le, re);
+  const uint32_t yo = half(C.y + k.ao, C.y + k.dko, U.y, D.y, lo, ro);
+  return __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
+}
 
 #ifndef GH_FAST_WAVES
 #define GH_FAST_WAVES 8
@@ -430,15 +485,168 @@ __device__ __forceinline__ const uint4* fast_tile_src(const LevelView& lv, int f
   return reinterpret_cast<const uint4*>(lv.base + (size_t)frame * lv.frame_stride + (__umul24((uint32_t)gy, (uint32_t)lv.pitch) + (uint32_t)gx));
 }
 
+// rec[0] of a cell that phase A of the two-phase detector leaves to phase B (orb_select): outside every valid count
+constexpr uint32_t kWeakCell = 0xFFFFFFFFu;
+
+// The cell stage (oracle steps 3, 4), by one wave: compaction of the cell's scored pixels, 3 x 3 strict NMS, the strong-corner
+// filter, the rank by (score desc, raster asc) and the cap.  sc = the score byte of the cell's first pixel in an LDS score
+// patch of PITCH bytes per row (dword aligned, a 1-px halo around the cell); list2 (1024 entries) and list (256) are wave-private
+// LDS.  Writes entries 0 .. kept - 1 to rec[1 ..] / ovf and returns kept; rec[0] is the caller's.  *nz_out = scored pixels.
+// WEAK = false: every scored pixel is above the initial threshold already (phase A of the two-phase detector), so no filter
+// (and ini_th is not used).
+template <int PITCH, bool WEAK>
+__device__ __forceinline__ int fast_cell_stage(const uint8_t* sc, uint16_t* list2, uint32_t* list, int lane, int ini_th,
+                                               uint32_t* __restrict__ rec, uint32_t* __restrict__ ovf,
+                                               uint32_t* __restrict__ dbg, int* nz_out) {
+  static_assert(PITCH % 4 == 0, "a lane reads its 16 score bytes as dwords");
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  // Stage A: lane l scans 16 consecutive score bytes in raster order (cell row l >> 1, cols 16 (l & 1) ..), so lane
+  // order IS raster order and one wave prefix sum of the per-lane non-zero counts (0..16, five ballots) places
+  // every non-zero pixel; each lane then unpacks its own bits.
+  int nz = 0;
+  {
+    const int row = lane >> 1, cb = 16 * (lane & 1);
+    const uint32_t* sp32 = reinterpret_cast<const uint32_t*>(&sc[row * PITCH + cb]);
+    uint32_t nzb = 0;  // bit k: byte k of the 16 is non-zero
+#pragma unroll
+    for (int dwi = 0; dwi < 4; ++dwi) {
+      const uint32_t w = sp32[dwi];
+      // byte k -> 1 if non-zero, then the four flags are gathered into a nibble by one v_dot4_u32_u8 with weights
+      // 1, 2, 4, 8 (a 32-bit multiply would be quarter rate)
+      const uint32_t f = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u;
+      nzb |= __builtin_amdgcn_udot4(f, 0x08040201u, 0u, false) << (4 * dwi);
+    }
+    const int cnt = __popc(nzb);
+    const int incl = wave_incl_scan_i32(cnt);
+    int pos = incl - cnt;
+    nz = __builtin_amdgcn_readlane(incl, 63);
+    const uint32_t rc0 = (uint32_t)((row << 5) | cb);
+    while (nzb) {
+      const int k = __ffs((int)nzb) - 1;
+      list2[pos++] = (uint16_t)(rc0 + (uint32_t)k);
+      nzb &= nzb - 1u;
+    }
+  }
+  *nz_out = nz;
+  auto put_entry = [&](int idx, uint32_t v) {
+    if (idx < kCellRec - 1) rec[1 + idx] = v;
+    else ovf[idx] = v;
+  };
+  int kept = 0;
+  if (nz <= 64) {
+    // Common case (a cell holds ~25 scored pixels): one candidate per lane, everything stays in registers.  NMS
+    // test, then the strong-corner filter and the rank-in-cell are evaluated over the ballot masks with v_readlane
+    // broadcasts; lane order = raster order, so no list is written or re-read.
+    bool ismax = false;
+    uint32_t e = 0;
+    int sv = 0;
+    if (lane < nz) {
+      const uint32_t rc = list2[lane];
+      const uint8_t* sp = &sc[(int)(rc >> 5) * PITCH + (int)(rc & 31u)];
+      sv = sp[0];
+      e = ((uint32_t)sv << 10) | rc;
+      const int n0 = sp[-PITCH - 1], n1 = sp[-PITCH], n2 = sp[-PITCH + 1], n3 = sp[-1], n4 = sp[1],
+                n5 = sp[PITCH - 1], n6 = sp[PITCH], n7 = sp[PITCH + 1];
+      ismax = max3i(max3i(n0, n1, n2), max3i(n3, n4, n5), max(n6, n7)) < sv;
+    }
+    const uint64_t all_max = __ballot(ismax);
+    uint64_t cand = all_max;
+    if constexpr (WEAK) {
+      const uint64_t strong_mask = __ballot(ismax && sv > ini_th);
+      cand = strong_mask != 0ull ? strong_mask : all_max;  // a strong corner silences the weak ones
+      if (dbg != nullptr && lane == 0) {  // test-only branch census (gh_orb_plan_debug_counters)
+        if (strong_mask != 0ull && strong_mask != all_max) atomicAdd(&dbg[kDbgStrongSilenced], 1u);
+        if (strong_mask == 0ull && all_max != 0ull) atomicAdd(&dbg[kDbgWeakCells], 1u);
+      }
+    }
+    // rank = candidates that come first by (score desc, raster asc).  With the raster bits of e inverted that order is ONE unsigned
+    // comparison (lane order is raster order, rc is unique): v_readlane + v_cmp + v_addc per candidate instead of three compares
+    const uint32_t key = e ^ 0x3FFu;
+    int rank = 0;
+    for (uint64_t mm = cand; mm != 0ull; mm &= mm - 1ull) {
+      const int j = __ffsll((unsigned long long)mm) - 1;
+      rank += (uint32_t)__builtin_amdgcn_readlane((int)key, j) > key ? 1 : 0;
+    }
+    const bool keep = ((cand >> lane) & 1ull) != 0ull && rank < kCap;
+    const uint64_t m = __ballot(keep);
+    if (keep) put_entry(__popcll(m & lt_mask), ((uint32_t)rank << 18) | e);
+    kept = __popcll(m);
+    if (dbg != nullptr && lane == 0 && __popcll(cand) > kCap) atomicAdd(&dbg[kDbgRankDropped], 1u);
+  } else {
+    int n = 0;
+    bool strong = false;
+    for (int base = 0; base < nz; base += 64) {
+      const int i = base + lane;
+      bool ismax = false;
+      uint32_t e = 0;
+      if (i < nz) {
+        const uint32_t rc = list2[i];
+        const uint8_t* sp = &sc[(int)(rc >> 5) * PITCH + (int)(rc & 31u)];
+        const int sv = sp[0];
+        e = ((uint32_t)sv << 10) | rc;
+        // branch-free: all 8 neighbour reads in flight at once, one comparison against their maximum
+        const int n0 = sp[-PITCH - 1], n1 = sp[-PITCH], n2 = sp[-PITCH + 1], n3 = sp[-1], n4 = sp[1],
+                  n5 = sp[PITCH - 1], n6 = sp[PITCH], n7 = sp[PITCH + 1];
+        ismax = max3i(max3i(n0, n1, n2), max3i(n3, n4, n5), max(n6, n7)) < sv;
+      }
+      const uint64_t bm = __ballot(ismax);
+      if (ismax) list[n + __popcll(bm & lt_mask)] = e ^ 0x3FFu;  // (the list holds KEYS: raster bits inverted, see the rank loop)
+      n += __popcll(bm);
+      if constexpr (WEAK) strong = strong || (__ballot(ismax && (int)(e >> 10) > ini_th) != 0ull);
+    }
+    if constexpr (WEAK) {
+      if (strong) {  // keep only candidates above the initial threshold (in place, order preserved)
+        int m2 = 0;
+        for (int base = 0; base < n; base += 64) {
+          const int i = base + lane;
+          const uint32_t e = i < n ? list[i] : 0u;
+          const bool keep = i < n && (int)(e >> 10) > ini_th;
+          const uint64_t m = __ballot(keep);
+          if (keep) list[m2 + __popcll(m & lt_mask)] = e;
+          m2 += __popcll(m);
+        }
+        if (dbg != nullptr && lane == 0 && m2 != n) atomicAdd(&dbg[kDbgStrongSilenced], 1u);
+        n = m2;
+      }
+      if (dbg != nullptr && lane == 0 && !strong && n > 0) atomicAdd(&dbg[kDbgWeakCells], 1u);
+    }
+    if (dbg != nullptr && lane == 0) {
+      atomicAdd(&dbg[kDbgDenseCells], 1u);
+      if (n > kCap) atomicAdd(&dbg[kDbgRankDropped], 1u);
+    }
+    // rank within the cell by (score desc, raster asc) = by key, descending (list order is raster order and the raster position is
+    // unique, so the key order is total): one comparison per pair; keep rank < cap, write in raster order
+    for (int base = 0; base < n; base += 64) {
+      const int i = base + lane;
+      const uint32_t key = i < n ? list[i] : 0xFFFFFFFFu;
+      int rank = 0;
+      for (int j = 0; j < n; ++j) rank += list[j] > key ? 1 : 0;
+      const bool keep = i < n && rank < kCap;
+      const uint64_t m = __ballot(keep);
+      if (keep) put_entry(kept + __popcll(m & lt_mask), ((uint32_t)rank << 18) | (key ^ 0x3FFu));
+      kept += __popcll(m);
+    }
+  }
+  return kept;
+}
+
 // One 64 x 64 tile (2 x 2 cells) of one level of one frame, by one 256-thread workgroup; tile_id in [0, nbx nby n_frames).
 // Pass 1 is SWAR on 16-bit fields (full-rate and / or / sub / v_bitop3), fields split in registers.  (A variant that read the
 // fields pre-split from LDS planes lost 22 %: 38 KB of LDS leave 4 workgroups per CU; profiles/orb_pass1_ab_r04.txt.)
 // PLANE: no cell stage; the tile's scores go to the level's score plane instead (the quadtree mode).
-template <bool PLANE>
-__device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th,
+// TWO_PHASE with `two` set (uniform; the host sets it only where ini_th > min_th): phase A of the two-phase detector.  The
+// tile is scored at ini_th instead of min_th: a candidate above ini_th is a strict 3 x 3 maximum of the scores above ini_th
+// exactly when it is one of all scores, and a cell that holds one keeps only those (oracle step 4), so such a cell's record
+// comes out as before from far fewer scored pixels.  A cell without any such maximum is marked kWeakCell and redone at
+// min_th by orb_select (select_weak_cells), which reads every record anyway; a tile in which nothing passes the compass test
+// at ini_th is redone at min_th on the spot, while its image is still in LDS.
+template <bool PLANE, bool TWO_PHASE>
+__device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th, bool two,
                                                 uint32_t* __restrict__ cell_cnt, uint32_t* __restrict__ cell_ent,
                                                 int cells_per_frame, int cell_off, int n_frames, const NextLevel& nx,
                                                 uint32_t* __restrict__ dbg, int tile_id) {
+  bool phase_a = TWO_PHASE && two;
+  int score_th = phase_a ? ini_th : min_th;  // scores at or below it are stored as 0
   // Pass 1 covers a window row with 17 aligned dwords (window cols -2 .. 65) and the score tile is FLAT with 68 bytes
   // per row: byte 68 sy + 3 + sx, so (item, pixel k) lands at 4 item + 1 + k.  Cols -2 / -1 of a row share their bytes with
   // cols 66 / 67 of the row above; nothing ever reads them (NMS looks at cols 0 .. 65 only).
@@ -526,45 +734,25 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   constexpr int kItemsPerRow = 17, kItems = kScoreH * kItemsPerRow;
   constexpr int kTrips = (kItems + 255) / 256;  // 5
   static_assert(2 * kTrips <= 14 && kScoreW == 4 * kItemsPerRow, "candidate bits of all trips share one dword");
-  constexpr uint32_t kF = 0x00FF00FFu;
-  const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(min_th, 0), 255));  // (scalar: the constants below are s_mul)
-  const uint32_t kAe = (0x8000u + t) * 0x10001u, kDe = (0x8000u - t - 1u) * 0x10001u;
-  const uint32_t kAo = (0x4000u + t) * 0x10001u, kDo = (0x4000u - t - 1u) * 0x10001u;
   const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-  const uint32_t tid3856 = (uint32_t)tid * 3856u;  // (item * 3856) >> 16 == item / 17 for item < 3855
-  uint32_t allbits = 0;
+  auto pass1 = [&](int th) {
+    const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(th, 0), 255));  // (scalar: the constants below are s_mul)
+    const CompassK ck(t);
+    const uint32_t tid3856 = (uint32_t)tid * 3856u;  // (item * 3856) >> 16 == item / 17 for item < 3855
+    uint32_t allbits = 0;
 #pragma unroll
-  for (int trip = 0; trip < kTrips; ++trip) {
-    const int item = 256 * trip + tid;
-    if (item < kItems) {
-      const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
-      const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
-      const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
-      const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
-      // E(w) by one v_and, O(w) by one v_perm (bytes 1, 3 -> the two fields)
-      constexpr uint32_t kOdd = 0x0c030c01u;
-      const uint2 C{wc & kF, __builtin_amdgcn_perm(0u, wc, kOdd)}, U{wu & kF, __builtin_amdgcn_perm(0u, wu, kOdd)},
-          D{wd & kF, __builtin_amdgcn_perm(0u, wd, kOdd)};
-      // even pixels (cols 4m, 4m+2): left = cols 4m-3, 4m-1 = O(wl); right = cols 4m+3, 4m+5 = {wc.b3, wr.b1}
-      // odd pixels (cols 4m+1, 4m+3): left = cols 4m-2, 4m = {wl.b2, wc.b0}; right = cols 4m+4, 4m+6 = E(wr)
-      // (v_perm_b32 D, S0, S1: selector bytes 0-3 address S1, 4-7 address S0, 0x0c = zero)
-      const uint32_t le = __builtin_amdgcn_perm(0u, wl, kOdd), re = __builtin_amdgcn_perm(wr, wc, 0x0c050c03u);
-      const uint32_t lo = __builtin_amdgcn_perm(wc, wl, 0x0c040c02u), ro = wr & kF;
-      auto half = [](uint32_t A, uint32_t Dk, uint32_t u, uint32_t d, uint32_t l, uint32_t r) {
-        const uint32_t not_bright_lr = (A - l) & (A - r);
-        const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
-        const uint32_t dark_lr = (Dk - l) | (Dk - r);
-        const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
-        return bright | dark;
-      };
-      const uint32_t ye = half(C.x + kAe, C.x + kDe, U.x, D.x, le, re);
-      const uint32_t yo = half(C.y + kAo, C.y + kDo, U.y, D.y, lo, ro);
-      const uint32_t w = __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
-      allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * trip), 0xC000C000u >> (2 * trip), 0xF8);  // a | (b & c)
+    for (int trip = 0; trip < kTrips; ++trip) {
+      const int item = 256 * trip + tid;
+      if (item < kItems) {
+        const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
+        const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
+        const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
+        const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
+        const uint32_t w = fast_compass4(ck, wc, wl, wr, wu, wd);
+        allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * trip), 0xC000C000u >> (2 * trip), 0xF8);  // a | (b & c)
+      }
     }
-  }
-  // ONE queue reservation per wave for all trips; an entry is (bit << 8 | tid), decoded in pass 2 where every lane is busy
-  {
+    // ONE queue reservation per wave for all trips; an entry is (bit << 8 | tid), decoded in pass 2 where every lane is busy
     const int cnt = __popc(allbits);
     const int incl = wave_incl_scan_i32(cnt);
     const int wave_total = __builtin_amdgcn_readlane(incl, 63);
@@ -578,10 +766,24 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
         allbits &= allbits - 1u;
       }
     }
-  }
+  };
+  pass1(score_th);
   __syncthreads();
   GH_PHASE(1);
-  const int nq = q_count;
+  int nq = q_count;
+  if constexpr (TWO_PHASE) {
+    // A flat tile: nothing passes the compass test at ini_th, so all four cells would be marked.  The image tile is still intact:
+    // pass 1 again at min_th and the tile is finished single-phase, without markers (low-texture input then costs one more
+    // pass 1 on tiles that have no pass 2, instead of a second phase for every cell).  nq is block-uniform.
+    if (phase_a && nq == 0) {
+      phase_a = false;
+      score_th = min_th;
+      __syncthreads();  // (every thread has read q_count == 0 before a wave adds to it again)
+      pass1(score_th);
+      __syncthreads();
+      nq = q_count;
+    }
+  }
   for (int i = tid; i < nq; i += 256) {
     const int e = queue[i];
     const int pos = 4 * (e & 255) + bit_pos[e >> 8];
@@ -593,27 +795,8 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
     const int sx = pos - sy * kScoreW - kScoreOff;
     // border tiles: pass 1 did not trim -- pixels outside the valid region [kEdge, dim - kEdge) keep S = 0 (oracle step 2)
     if (!interior && (sx < sx_lo || sx >= sx_hi || y0 - 1 + sy < kEdge || y0 - 1 + sy >= lv.h - kEdge)) continue;
-    const uint8_t* p = &tile[(sy + 3) * kTileW + sx + 18];
-    const int c = p[0];
-    int r[16];
-    r[0] = p[-3 * kTileW];
-    r[1] = p[-3 * kTileW + 1];
-    r[2] = p[-2 * kTileW + 2];
-    r[3] = p[-1 * kTileW + 3];
-    r[4] = p[3];
-    r[5] = p[1 * kTileW + 3];
-    r[6] = p[2 * kTileW + 2];
-    r[7] = p[3 * kTileW + 1];
-    r[8] = p[3 * kTileW];
-    r[9] = p[3 * kTileW - 1];
-    r[10] = p[2 * kTileW - 2];
-    r[11] = p[1 * kTileW - 3];
-    r[12] = p[-3];
-    r[13] = p[-1 * kTileW - 3];
-    r[14] = p[-2 * kTileW - 2];
-    r[15] = p[-3 * kTileW - 1];
-    const int s = fast_score16_pk(r, c);
-    if (s > min_th) score[pos] = (uint8_t)s;
+    const int s = fast_ring_score<kTileW>(&tile[(sy + 3) * kTileW + sx + 18]);
+    if (s > score_th) score[pos] = (uint8_t)s;
   }
   __syncthreads();
   GH_PHASE(2);
@@ -661,143 +844,24 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   const int wv = tid >> 6, lane = tid & 63;
   const int cx = 2 * bx + (wv & 1), cy = 2 * by + (wv >> 1);
   if (cx >= ncx || cy >= ncy) return;  // no block-wide sync below
-  uint32_t* list = lists[wv];
-  // 3x3 strict NMS over the cell.  Stage A compacts the few non-zero pixels of the cell, in raster order, into
-  // list2; stage B tests only those against their 8 neighbours with every lane busy.  Both keep raster order.
-  const int sy0 = 1 + 32 * (wv >> 1);
-  const int col0 = kScoreOff + 1 + 32 * (wv & 1);  // byte column of the cell's first pixel: 4 or 36
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  // the cell's first pixel in the score tile: row 1 or 33, byte column 4 or 36
+  const uint8_t* sc = &score[(1 + 32 * (wv >> 1)) * kScoreW + kScoreOff + 1 + 32 * (wv & 1)];
   uint16_t* list2 = queue + wv * 1024;  // the pass-1 queue is dead after pass 2: reuse it (row << 5 | col per entry)
-  // Stage A: lane l scans 16 consecutive score bytes in raster order (cell row l >> 1, cols 16 (l & 1) ..), so lane
-  // order IS raster order and one wave prefix sum of the per-lane non-zero counts (0..16, five ballots) places
-  // every non-zero pixel; each lane then unpacks its own bits.
-  int nz = 0;
-  {
-    const int row = lane >> 1, cb = 16 * (lane & 1);
-    const uint32_t* sp32 = reinterpret_cast<const uint32_t*>(&score[(sy0 + row) * kScoreW + col0 + cb]);
-    uint32_t nzb = 0;  // bit k: byte k of the 16 is non-zero
-#pragma unroll
-    for (int dwi = 0; dwi < 4; ++dwi) {
-      const uint32_t w = sp32[dwi];
-      // byte k -> 1 if non-zero, then the four flags are gathered into a nibble by one v_dot4_u32_u8 with weights
-      // 1, 2, 4, 8 (a 32-bit multiply would be quarter rate)
-      const uint32_t f = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u;
-      nzb |= __builtin_amdgcn_udot4(f, 0x08040201u, 0u, false) << (4 * dwi);
-    }
-    const int cnt = __popc(nzb);
-    const int incl = wave_incl_scan_i32(cnt);
-    int pos = incl - cnt;
-    nz = __builtin_amdgcn_readlane(incl, 63);
-    const uint32_t rc0 = (uint32_t)((row << 5) | cb);
-    while (nzb) {
-      const int k = __ffs((int)nzb) - 1;
-      list2[pos++] = (uint16_t)(rc0 + (uint32_t)k);
-      nzb &= nzb - 1u;
-    }
-  }
   // (cy * ncx + cx < 2^24: the per-wave part on the 24-bit multiplier, the per-frame part is scalar)
   const size_t cell = (size_t)frame * cells_per_frame + cell_off + (size_t)(__umul24((uint32_t)cy, (uint32_t)ncx) + (uint32_t)cx);
   // cell record: {count, entries 0..6} in one 32-byte line of cell_cnt (a cell holds ~5 entries: orb_select reads ONE
   // 32-byte record per cell instead of a count plus a 128-byte slot); entries 7.. go to the cell's slot in cell_ent
   uint32_t* rec = cell_cnt + cell * kCellRec;
   uint32_t* ovf = cell_ent + cell * kCap;
-  auto put_entry = [&](int idx, uint32_t v) {
-    if (idx < kCellRec - 1) rec[1 + idx] = v;
-    else ovf[idx] = v;
-  };
-  int kept = 0;
-  if (nz <= 64) {
-    // Common case (a cell holds ~25 scored pixels): one candidate per lane, everything stays in registers.  NMS
-    // test, then the strong-corner filter and the rank-in-cell are evaluated over the ballot masks with v_readlane
-    // broadcasts; lane order = raster order, so no list is written or re-read.
-    bool ismax = false;
-    uint32_t e = 0;
-    int sv = 0;
-    if (lane < nz) {
-      const uint32_t rc = list2[lane];
-      const uint8_t* sp = &score[(sy0 + (int)(rc >> 5)) * kScoreW + col0 + (int)(rc & 31u)];
-      sv = sp[0];
-      e = ((uint32_t)sv << 10) | rc;
-      const int n0 = sp[-kScoreW - 1], n1 = sp[-kScoreW], n2 = sp[-kScoreW + 1], n3 = sp[-1], n4 = sp[1],
-                n5 = sp[kScoreW - 1], n6 = sp[kScoreW], n7 = sp[kScoreW + 1];
-      ismax = max3i(max3i(n0, n1, n2), max3i(n3, n4, n5), max(n6, n7)) < sv;
-    }
-    const uint64_t strong_mask = __ballot(ismax && sv > ini_th);
-    const uint64_t cand = strong_mask != 0ull ? strong_mask : __ballot(ismax);  // a strong corner silences the weak ones
-    // rank = candidates that come first by (score desc, raster asc).  With the raster bits of e inverted that order is ONE unsigned
-    // comparison (lane order is raster order, rc is unique): v_readlane + v_cmp + v_addc per candidate instead of three compares
-    const uint32_t key = e ^ 0x3FFu;
-    int rank = 0;
-    for (uint64_t mm = cand; mm != 0ull; mm &= mm - 1ull) {
-      const int j = __ffsll((unsigned long long)mm) - 1;
-      rank += (uint32_t)__builtin_amdgcn_readlane((int)key, j) > key ? 1 : 0;
-    }
-    const bool keep = ((cand >> lane) & 1ull) != 0ull && rank < kCap;
-    const uint64_t m = __ballot(keep);
-    if (keep) put_entry(__popcll(m & lt_mask), ((uint32_t)rank << 18) | e);
-    kept = __popcll(m);
-    if (dbg != nullptr) {  // test-only branch census (gh_orb_plan_debug_counters)
-      const uint64_t all_max = __ballot(ismax);
-      if (lane == 0) {
-        if (__popcll(cand) > kCap) atomicAdd(&dbg[kDbgRankDropped], 1u);
-        if (strong_mask != 0ull && strong_mask != all_max) atomicAdd(&dbg[kDbgStrongSilenced], 1u);
-        if (strong_mask == 0ull && all_max != 0ull) atomicAdd(&dbg[kDbgWeakCells], 1u);
-      }
-    }
+  int nz, kept;
+  if (phase_a) {
+    kept = fast_cell_stage<kScoreW, false>(sc, list2, lists[wv], lane, ini_th, rec, ovf, dbg, &nz);
+    // no maximum above ini_th in the cell: its record needs the scores down to min_th (orb_select, select_weak_cells)
+    if (lane == 0) rec[0] = kept == 0 ? kWeakCell : (uint32_t)kept;
   } else {
-    int n = 0;
-    bool strong = false;
-    for (int base = 0; base < nz; base += 64) {
-      const int i = base + lane;
-      bool ismax = false;
-      uint32_t e = 0;
-      if (i < nz) {
-        const uint32_t rc = list2[i];
-        const uint8_t* sp = &score[(sy0 + (int)(rc >> 5)) * kScoreW + col0 + (int)(rc & 31u)];
-        const int sv = sp[0];
-        e = ((uint32_t)sv << 10) | rc;
-        // branch-free: all 8 neighbour reads in flight at once, one comparison against their maximum
-        const int n0 = sp[-kScoreW - 1], n1 = sp[-kScoreW], n2 = sp[-kScoreW + 1], n3 = sp[-1], n4 = sp[1],
-                  n5 = sp[kScoreW - 1], n6 = sp[kScoreW], n7 = sp[kScoreW + 1];
-        ismax = max3i(max3i(n0, n1, n2), max3i(n3, n4, n5), max(n6, n7)) < sv;
-      }
-      const uint64_t bm = __ballot(ismax);
-      if (ismax) list[n + __popcll(bm & lt_mask)] = e ^ 0x3FFu;  // (the list holds KEYS: raster bits inverted, see the rank loop)
-      n += __popcll(bm);
-      strong = strong || (__ballot(ismax && (int)(e >> 10) > ini_th) != 0ull);
-    }
-    if (strong) {  // keep only candidates above the initial threshold (in place, order preserved)
-      int m2 = 0;
-      for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const uint32_t e = i < n ? list[i] : 0u;
-        const bool keep = i < n && (int)(e >> 10) > ini_th;
-        const uint64_t m = __ballot(keep);
-        if (keep) list[m2 + __popcll(m & lt_mask)] = e;
-        m2 += __popcll(m);
-      }
-      if (dbg != nullptr && lane == 0 && m2 != n) atomicAdd(&dbg[kDbgStrongSilenced], 1u);
-      n = m2;
-    }
-    if (dbg != nullptr && lane == 0) {
-      if (!strong && n > 0) atomicAdd(&dbg[kDbgWeakCells], 1u);
-      atomicAdd(&dbg[kDbgDenseCells], 1u);
-      if (n > kCap) atomicAdd(&dbg[kDbgRankDropped], 1u);
-    }
-    // rank within the cell by (score desc, raster asc) = by key, descending (list order is raster order and the raster position is
-    // unique, so the key order is total): one comparison per pair; keep rank < cap, write in raster order
-    for (int base = 0; base < n; base += 64) {
-      const int i = base + lane;
-      const uint32_t key = i < n ? list[i] : 0xFFFFFFFFu;
-      int rank = 0;
-      for (int j = 0; j < n; ++j) rank += list[j] > key ? 1 : 0;
-      const bool keep = i < n && rank < kCap;
-      const uint64_t m = __ballot(keep);
-      if (keep) put_entry(kept + __popcll(m & lt_mask), ((uint32_t)rank << 18) | (key ^ 0x3FFu));
-      kept += __popcll(m);
-    }
+    kept = fast_cell_stage<kScoreW, true>(sc, list2, lists[wv], lane, ini_th, rec, ovf, dbg, &nz);
+    if (lane == 0) rec[0] = (uint32_t)kept;
   }
-  if (lane == 0) rec[0] = (uint32_t)kept;
   GH_PHASE(3);
   if (dbg != nullptr && lane == 0) {
     atomicAdd(&dbg[kDbgCells], 1u);
@@ -814,11 +878,13 @@ __global__ __launch_bounds__(256, GH_FAST_WAVES) void fast_cells_kernel(LevelVie
                                                          uint32_t* __restrict__ cell_cnt,
                                                          uint32_t* __restrict__ cell_ent, int cells_per_frame,
                                                          int cell_off, int n_frames, NextLevel nx,
-                                                         uint32_t* __restrict__ dbg) {
+                                                         uint32_t* __restrict__ dbg, int two_phase) {
   const int total = ((ncx + 1) >> 1) * ((ncy + 1) >> 1) * n_frames;
   const int tile_id = xcd_strip_tile(blockIdx.x, total);
   if (tile_id >= total) return;
-  fast_cells_tile<PLANE>(lv, ncx, ncy, min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, cell_off, n_frames, nx, dbg, tile_id);
+  // (the score plane of the quadtree mode wants S itself: single-phase)
+  fast_cells_tile<PLANE, !PLANE>(lv, ncx, ncy, min_th, ini_th, two_phase != 0, cell_cnt, cell_ent, cells_per_frame, cell_off, n_frames, nx,
+                                 dbg, tile_id);
 }
 
 // Every level in ONE launch, over a pyramid that exists already (stand-alone resize launches): what a small call wants --
@@ -837,8 +903,8 @@ __global__ __launch_bounds__(256) void fast_cells_all_kernel(AllLevels A, int mi
   for (int k = 1; k < A.n_levels; ++k)
     if ((int)blockIdx.x >= A.tile_start[k]) l = k;
   const NextLevel none{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-  fast_cells_tile<false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l], n_frames, none,
-                         dbg, (int)blockIdx.x - A.tile_start[l]);
+  fast_cells_tile<false, false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, false, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l],
+                                n_frames, none, dbg, (int)blockIdx.x - A.tile_start[l]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -906,19 +972,132 @@ struct SelectArgs {
   int ncells[kMaxL], cell_off[kMaxL], ncx[kMaxL], quota[kMaxL], quota_off[kMaxL];
 };
 
+// Phase B of the two-phase detector (see fast_cells_tile): the level views and thresholds that orb_select needs to redo the
+// cells that phase A marked kWeakCell.  two_phase == 0 (the small path, the quadtree mode, ini_th <= min_th): none of it runs.
+struct SelectWeak {
+  LevelView lv[kMaxL];
+  int min_th, ini_th, two_phase;
+};
+constexpr int kWeakImgW = 64, kWeakImgH = 40;  // image patch: rows y0 - 4 .. y0 + 35, four aligned 16-byte columns from x0 - 19
+constexpr int kWeakScoreW = 40, kWeakWin = 34; // score patch: window col sx (cell + 1 px halo) at byte sx + 3, 34 rows
+constexpr int kWeakImgBytes = kWeakImgW * kWeakImgH, kWeakScoreBytes = kWeakWin * kWeakScoreW + 16;
+constexpr int kWeakQueueBytes = (kWeakWin * kWeakWin * 2 + 15) & ~15;
+constexpr int kWeakWaveBytes = kWeakImgBytes + kWeakScoreBytes + kWeakQueueBytes;
+constexpr int kWeakRound = 2048;  // cells per gathering round (one round at every level the cached select takes)
+
+// One marked cell (cx, cy) of level view lv, frame b, by one wave: the cell's 34 x 34 window scored at min_th out of a
+// wave-private image patch, then the cell stage with the strong-corner filter -- what the single-phase kernel computes.
+__device__ __forceinline__ void select_weak_cell(const LevelView& lv, int b, int cx, int cy, int min_th, int ini_th, uint8_t* wlds,
+                                                 int lane, uint32_t* rec, uint32_t* ovf, uint32_t* dbg) {
+  uint8_t* img = wlds;
+  uint8_t* score = wlds + kWeakImgBytes;
+  uint16_t* queue = reinterpret_cast<uint16_t*>(wlds + kWeakImgBytes + kWeakScoreBytes);
+  const int x0 = kEdge + kCell * cx, y0 = kEdge + kCell * cy, ax = kCell * cx;  // x0 - 4 == ax + 15
+  const uint8_t* src = lv.base + (size_t)b * lv.frame_stride;
+  for (int i = lane; i < kWeakImgH * (kWeakImgW / 16); i += 64) {
+    const int row = i >> 2, c = i & 3;
+    int gy = y0 - 4 + row;
+    gy = gy < 0 ? 0 : (gy > lv.h - 1 ? lv.h - 1 : gy);
+    int gx = ax + 16 * c;
+    gx = gx > lv.pitch - 16 ? lv.pitch - 16 : gx;
+    *reinterpret_cast<uint4*>(&img[16 * i]) = *reinterpret_cast<const uint4*>(src + (__umul24((uint32_t)gy, (uint32_t)lv.pitch) + (uint32_t)gx));
+  }
+  static_assert(kWeakScoreBytes % 16 == 0 && kWeakImgBytes % 16 == 0 && kWeakWaveBytes % 16 == 0, "16-byte stores");
+  for (int i = lane; i < kWeakScoreBytes / 16; i += 64) reinterpret_cast<uint4*>(score)[i] = make_uint4(0u, 0u, 0u, 0u);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // pass 1: image dwords 4 .. 12 of patch rows 3 .. 36 hold window cols -2 .. 33 of the 34 window rows
+  constexpr int kPerRow = 9, kItems = kWeakWin * kPerRow;
+  const CompassK ck((uint32_t)min(max(min_th, 0), 255));
+  const uint32_t* img32 = reinterpret_cast<const uint32_t*>(img);
+  int nq = 0;
+  for (int base = 0; base < kItems; base += 64) {
+    const int item = base + lane;
+    uint32_t bits = 0;
+    int sy = 0, m = 0;
+    if (item < kItems) {
+      sy = (int)(__umul24((uint32_t)item, 7282u) >> 16);  // item / 9, exact for item < 306
+      m = item - kPerRow * sy;
+      const int ix = (sy + 3) * (kWeakImgW / 4) + 4 + m;
+      bits = fast_compass4(ck, img32[ix], img32[ix - 1], img32[ix + 1], img32[ix - 3 * (kWeakImgW / 4)], img32[ix + 3 * (kWeakImgW / 4)]) &
+             (m == 0 ? 0xC0000000u : 0xC000C000u);  // (the first dword of a row starts at window col -2)
+    }
+    const int cnt = __popc(bits);
+    const int incl = wave_incl_scan_i32(cnt);
+    int pos = nq + incl - cnt;
+    nq += __builtin_amdgcn_readlane(incl, 63);
+    while (bits) {
+      const int bt = __ffs((int)bits) - 1;  // bits 15, 14, 31, 30 = pixels 0, 1, 2, 3
+      const int sx = 4 * m - 2 + 2 * (bt >> 4) + ((bt & 1) ^ 1);
+      queue[pos++] = (uint16_t)((sy << 6) | sx);
+      bits &= bits - 1u;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // pass 2: the arc score of every survivor; pixels outside the valid region [kEdge, dim - kEdge) keep S = 0 (oracle step 2)
+  for (int i = lane; i < nq; i += 64) {
+    const int e = queue[i], sy = e >> 6, sx = e & 63;
+    const int gx = x0 - 1 + sx, gy = y0 - 1 + sy;
+    if (gx < kEdge || gx >= lv.w - kEdge || gy < kEdge || gy >= lv.h - kEdge) continue;
+    const int s = fast_ring_score<kWeakImgW>(&img[(sy + 3) * kWeakImgW + sx + 18]);
+    if (s > min_th) score[sy * kWeakScoreW + kScoreOff + sx] = (uint8_t)s;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // the cell stage: list2 over the queue, the candidate list over the image patch (both dead now)
+  static_assert(kWeakQueueBytes >= 1024 * 2 && kWeakImgBytes >= 256 * 4, "the cell stage's lists fit what they alias");
+  int nz;
+  const int kept = fast_cell_stage<kWeakScoreW, true>(&score[kWeakScoreW + kScoreOff + 1], queue, reinterpret_cast<uint32_t*>(img), lane, ini_th,
+                                                      rec, ovf, dbg, &nz);
+  if (lane == 0) rec[0] = (uint32_t)kept;
+  if (dbg != nullptr && lane == 0) {  // (the cell itself was counted by phase A)
+    if (kept > kCellRec - 1) atomicAdd(&dbg[kDbgOverflowCells], 1u);
+    if (kept == kCap) atomicAdd(&dbg[kDbgCapCells], 1u);
+    atomicMax(&dbg[kDbgMaxNz], (uint32_t)nz);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Phase B at the head of orb_select: the workgroup gathers the cells of its (level, frame) that phase A marked into an LDS list
+// (one LDS counter; kWeakRound cells per round), its four waves take them in a stride, one wave per cell, and a barrier makes the
+// rewritten records visible to the passes that follow.  lds = at least 4 kWeakWaveBytes + 2 kWeakRound + 16 bytes, 16-byte aligned.
+__device__ __forceinline__ void select_weak_cells(const SelectWeak& w, int l, int b, int ncells, int ncx, uint32_t* rec, uint32_t* ent,
+                                                  uint8_t* lds, uint32_t* dbg) {
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  uint16_t* marked = reinterpret_cast<uint16_t*>(lds + 4 * kWeakWaveBytes);
+  int* n_marked = reinterpret_cast<int*>(lds + 4 * kWeakWaveBytes + 2 * kWeakRound);
+  const LevelView lv = w.lv[l];
+  for (int c0 = 0; c0 < ncells; c0 += kWeakRound) {
+    if (tid == 0) *n_marked = 0;
+    __syncthreads();
+    const int c1 = min(ncells, c0 + kWeakRound);
+    for (int c = c0 + tid; c < c1; c += 256)
+      if (rec[(size_t)c * kCellRec] == kWeakCell) marked[atomicAdd(n_marked, 1)] = (uint16_t)(c - c0);
+    __syncthreads();
+    const int n = *n_marked;
+    for (int i = wv; i < n; i += 4) {
+      const int c = c0 + marked[i];
+      const int cy = c / ncx, cx = c - cy * ncx;
+      select_weak_cell(lv, b, cx, cy, w.min_th, w.ini_th, lds + wv * kWeakWaveBytes, lane, rec + (size_t)c * kCellRec, ent + (size_t)c * kCap, dbg);
+    }
+    __syncthreads();
+  }
+}
+
 // CACHED (levels of at most kSelCached * 256 cells): every thread fetches the records of ALL its cells up front -- one
 // memory round trip with up to kSelCached loads in flight -- and the three passes below (histogram, counts, output) read
 // them from registers.  Streaming them three times made the kernel a chain of ~24 dependent round trips per thread at
 // 1080p (the workgroup does little else: it was latency, not bandwidth).
 constexpr int kSelCached = 8;
 template <bool CACHED>
-__global__ __launch_bounds__(256) void select_kernel(SelectArgs a, const uint32_t* __restrict__ cell_cnt,
-                                                     const uint32_t* __restrict__ cell_ent, int cells_per_frame,
+__global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cell_cnt, uint32_t* cell_ent, int cells_per_frame,
                                                      int K, SelKp* __restrict__ sel, int32_t* __restrict__ level_cnt,
-                                                     uint32_t* __restrict__ dbg, int level0) {
+                                                     uint32_t* __restrict__ dbg, int level0, SelectWeak weak) {
   // bin k lives at k + (k >> 5): a thread's 32 consecutive bins (tid * 32 + i) then fall into different banks for
   // different threads (unpadded, all 64 lanes of a wave hit bank i)
-  __shared__ uint32_t hist[kHistBins + kHistBins / 32];
+  __shared__ __attribute__((aligned(16))) uint32_t hist[kHistBins + kHistBins / 32];
   __shared__ int wave_tot[4];
   __shared__ int s_cut, s_m;
   const int l = level0 + blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -929,6 +1108,11 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, const uint32_
     if (tid == 0) level_cnt[b * kMaxL + l] = 0;
     return;
   }
+  // phase B of the two-phase detector first: its patches and queues alias hist[], which is cleared only after it
+  static_assert(sizeof(hist) >= 4 * kWeakWaveBytes + 2 * kWeakRound + 16, "phase B fits the histogram");
+  if (weak.two_phase != 0)
+    select_weak_cells(weak, l, b, ncells, a.ncx[l], cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec,
+                      cell_ent + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCap, reinterpret_cast<uint8_t*>(hist), dbg);
   uint4 ra[kSelCached], rb[kSelCached];
   if (CACHED) {
 #pragma unroll
@@ -2169,6 +2353,7 @@ struct OrbSchedule {
   bool overlap;     // kPerLevel: select(l) on the side stream beside fast_cells(l + 1 ..) instead of one select at the end
   bool sel_cached;  // select_kernel<true>: no level has more cells than its registers hold
   bool zero_copy0;  // level 0 is read from the caller's buffer, not staged through the plan's slab
+  bool two_phase;   // kPerLevel: fast_cells scores at ini_th and marks the cells without a strong corner, select redoes those at min_th
 };
 
 // The side stream of the select overlap and its events, created at the first call that wants them.  *ok = false when the
@@ -2208,6 +2393,9 @@ static gh_status orb_schedule(gh_orb_plan* p, int batch, const uint8_t* gray_dev
   // view whose allocation ends at (h-1) * row_stride + w) is staged through the plan's own level-0 slab instead
   s->zero_copy0 = ((uintptr_t)gray_dev & 15) == 0 && (row_stride & 15) == 0 && (frame_stride & 15) == 0 &&
                   frame_stride >= (size_t)row_stride * p->h;
+  // (at ini_th <= min_th the scores above ini_th would hold some that the specification zeroes: single-phase.  plan_check_params
+  // refuses ini_th < min_th, so equality is the only such case that reaches this point)
+  s->two_phase = s->kind == OrbSchedule::kPerLevel && p->prm.ini_th_fast > p->prm.min_th_fast;
   return GH_OK;
 }
 
@@ -2282,12 +2470,17 @@ static SelectArgs select_args(const gh_orb_plan* p) {
 static gh_status launch_select(const OrbCall& c, const SelectArgs& sa, int l0, int nl) {
   const gh_orb_plan* p = c.p;
   gh_ctx* ctx = p->ctx;
+  SelectWeak weak;
+  for (int l = 0; l < kMaxL; ++l) weak.lv[l] = c.lv[l < p->L ? l : 0];
+  weak.min_th = p->prm.min_th_fast;
+  weak.ini_th = p->prm.ini_th_fast;
+  weak.two_phase = c.s.two_phase ? 1 : 0;
   if (c.s.sel_cached)
     GH_LAUNCH(ctx, "orb_select", select_kernel<true>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0);
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak);
   else
     GH_LAUNCH(ctx, "orb_select", select_kernel<false>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0);
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak);
   return GH_OK;
 }
 
@@ -2319,10 +2512,10 @@ static gh_status fast_level(const OrbCall& c, int l, bool plane) {
     nx.plane_frame_stride = p->plane_slab;
     nx.plane_pitch = p->plane_pitch[l];
     GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg);
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, 0);
   } else {
     GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg);
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, c.s.two_phase ? 1 : 0);
   }
   return GH_OK;
 }
