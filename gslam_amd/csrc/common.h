@@ -125,3 +125,5 @@ void gh_prof_end(gh_ctx* ctx, int pending);
   } while (0)
 
 static inline int gh_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
+// Segments of a scratch block start on 256-byte boundaries.
+static inline size_t gh_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }

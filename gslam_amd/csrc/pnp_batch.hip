@@ -16,7 +16,7 @@
 //   * classify a last pass over ALL rows of the range at the final pose, counts by ballot (integer sums).
 // Row ranges are clamped to the arrays before they address anything; every list entry is a row of the problem's own range.
 #include "pnp_lm.h"
-#include "ransac_models.h"
+#include "estimate_batch.h"
 
 namespace {
 
@@ -26,10 +26,7 @@ using namespace gh_ransac;
 struct PnpBatchArgs {
   const double* xyz;
   const double* xy;
-  const int32_t* row_begin;   // per problem: first row ...
-  const int32_t* row_end;     // ... and one past the last
-  const int32_t* limit_dev;   // rows the arrays hold (device word) or NULL; a range lies inside this AND `limit`
-  int limit;
+  RowRanges range;
   int nproblems;
   const uint8_t* mask;        // rows that take part, or NULL: all
   const double* start;        // per problem: start_stride doubles
@@ -54,10 +51,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   __shared__ PnpLmShared S;
   __shared__ int wave_cnt[4];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // the rows of the problem: a range that is empty, reversed or not inside the arrays is 0 rows
-  int limit = a.limit;
-  if (a.limit_dev && *a.limit_dev < limit) limit = *a.limit_dev;
-  const int first = a.row_begin[p], end = a.row_end[p];
+  // problem_rows (estimate_batch.h), spelled out: through the call the compiler settles on another polarity of the test, and
+  // under the two-wave register bound below that costs 8 more spilled registers (36 instead of 20 bytes of scratch)
+  int limit = a.range.limit;
+  if (a.range.limit_dev && *a.range.limit_dev < limit) limit = *a.range.limit_dev;
+  const int first = a.range.row_begin[p], end = a.range.row_end[p];
   const int n = (first < 0 || end > limit || end <= first) ? 0 : end - first;
 
   double pose[7];
@@ -80,14 +78,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i0 = 0; i0 < n; i0 += 256) {
       const int i = i0 + tid;
       const bool use = i < n && (!a.mask || a.mask[(size_t)first + i] != 0);
-      const unsigned long long b = __ballot(use);
-      if (lane == 0) wave_cnt[w] = __popcll(b);
-      __syncthreads();
-      int at = n_used + __popcll(b & ((1ull << lane) - 1ull));
-      for (int k = 0; k < w; ++k) at += wave_cnt[k];
-      if (use) list[at] = first + i;
-      n_used += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-      __syncthreads();  // (wave_cnt is free again; after the last trip: the list is visible to the whole workgroup)
+      compact_trip(use, &n_used, wave_cnt, [&](int at) { list[at] = first + i; });
     }
   }
 
@@ -145,21 +136,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-// The chain's ranges: problem p's (offsets[p], offsets[p + 1]) when it lies inside both offsets[nproblems] and nrows,
-// else (0, 0) -- every stage of the chain then sees the same rows, and the masks of nrows bytes hold them.
-__global__ __launch_bounds__(256) void pnp_batch_ranges_kernel(const int32_t* __restrict__ offsets, int nproblems, int nrows,
-                                                               int32_t* __restrict__ row_begin, int32_t* __restrict__ row_end) {
+// The chain's ranges: problem p's own when it has rows, else (0, 0) -- every stage of the chain then sees the same rows,
+// and the masks of nrows bytes hold them.
+__global__ __launch_bounds__(256) void pnp_batch_ranges_kernel(RowRanges offsets, int nproblems, int32_t* __restrict__ row_begin,
+                                                               int32_t* __restrict__ row_end) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= nproblems) return;
-  int limit = offsets[nproblems];
-  if (nrows < limit) limit = nrows;
-  const int b = offsets[p], e = offsets[p + 1];
-  const bool ok = !(b < 0 || e > limit || e <= b);
-  row_begin[p] = ok ? b : 0;
-  row_end[p] = ok ? e : 0;
+  int first;
+  const int n = problem_rows(offsets, p, &first);
+  if (n == 0) first = 0;
+  row_begin[p] = first;
+  row_end[p] = first + n;
 }
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 gh_status refine_launch(gh_ctx* ctx, const PnpBatchArgs& a) {
   GH_LAUNCH(ctx, "pnp_refine_batch", pnp_refine_batch_kernel, dim3(a.nproblems), dim3(256), 0, a);
@@ -192,14 +180,11 @@ extern "C" gh_status gh_pnp_refine_batch_dev(gh_ctx* ctx, const double* xyz_dev,
   if (nproblems == 0) return GH_OK;
   GH_CHECK_ARG(ctx, xyz_dev && xy_dev && offsets_dev && start_dev && poses_dev && summaries_dev);
   void* rows = nullptr;
-  GH_TRY(gh_scratch(ctx, round256((size_t)nrows * 4), &rows));
+  GH_TRY(gh_scratch(ctx, gh_round256((size_t)nrows * 4), &rows));
   PnpBatchArgs a = {};
   a.xyz = xyz_dev;
   a.xy = xy_dev;
-  a.row_begin = offsets_dev;
-  a.row_end = offsets_dev + 1;
-  a.limit_dev = offsets_dev + nproblems;
-  a.limit = nrows;
+  a.range = {offsets_dev, offsets_dev + 1, offsets_dev + nproblems, nrows};
   a.nproblems = nproblems;
   a.mask = mask_dev;
   a.start = start_dev;
@@ -232,23 +217,22 @@ extern "C" gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const 
   // ONE scratch block for all stages (gh_scratch hands out one block per context):
   // row list | RANSAC mask | round-1 inliers | round-1 poses | row_begin | row_end | the RANSAC core's own block
   const size_t np = (size_t)nproblems;
-  const size_t o_mask = round256((size_t)nrows * 4), o_in1 = o_mask + round256((size_t)nrows), o_pose1 = o_in1 + round256((size_t)nrows),
-               o_begin = o_pose1 + round256(np * 56), o_end = o_begin + round256(np * 4), o_work = o_end + round256(np * 4);
+  const size_t o_mask = gh_round256((size_t)nrows * 4), o_in1 = o_mask + gh_round256((size_t)nrows), o_pose1 = o_in1 + gh_round256((size_t)nrows),
+               o_begin = o_pose1 + gh_round256(np * 56), o_end = o_begin + gh_round256(np * 4), o_work = o_end + gh_round256(np * 4);
   void* base = nullptr;
   GH_TRY(gh_scratch(ctx, o_work + ransac_batch_scratch_bytes(nproblems), &base));
   uint8_t* b = (uint8_t*)base;
   int32_t* row_begin = (int32_t*)(b + o_begin);
   int32_t* row_end = (int32_t*)(b + o_end);
-  GH_LAUNCH(ctx, "pnp_batch_ranges", pnp_batch_ranges_kernel, dim3(gh_div_up(nproblems, 256)), dim3(256), 0, offsets_dev, nproblems,
-            nrows, row_begin, row_end);
-  GH_TRY(ransac_batch_ranges(ctx, kModelPnP, xyz_dev, xy_dev, row_begin, row_end, nrows, nproblems, ransac_threshold, seed,
-                             models_dev, b + o_mask, ransac_inliers_dev, b + o_work));
+  GH_LAUNCH(ctx, "pnp_batch_ranges", pnp_batch_ranges_kernel, dim3(gh_div_up(nproblems, 256)), dim3(256), 0,
+            RowRanges{offsets_dev, offsets_dev + 1, offsets_dev + nproblems, nrows}, nproblems, row_begin, row_end);
+  const RowRanges range = {row_begin, row_end, nullptr, nrows};
+  GH_TRY(ransac_batch_ranges(ctx, kModelPnP, xyz_dev, xy_dev, range, nproblems, ransac_threshold, nullptr, seed, nullptr, models_dev,
+                             b + o_mask, ransac_inliers_dev, b + o_work));
   PnpBatchArgs a = {};
   a.xyz = xyz_dev;
   a.xy = xy_dev;
-  a.row_begin = row_begin;
-  a.row_end = row_end;
-  a.limit = nrows;
+  a.range = range;
   a.nproblems = nproblems;
   a.dof = dof;
   a.opt = options_or_default(options);

@@ -15,7 +15,7 @@
 // normalised 8x9 nullspace by full pivoting, Sampson error; rank 2 is not enforced), A3 (4 pairs, 3x4 affine, 3D).
 // CDNA4 mapping: one lane per hypothesis for the tiny dense solves, one workgroup per hypothesis for scoring
 // (coalesced point reads, integer block reduction), everything in one stream; the work is small and latency-bound.
-#include "ransac_models.h"
+#include "estimate_batch.h"
 
 namespace {
 
@@ -56,21 +56,10 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(int model, const doub
 
 __global__ __launch_bounds__(256) void ransac_best_kernel(const int* __restrict__ counts, int* __restrict__ best) {
   __shared__ long long red[256];
-  long long key = -1;  // count << 32 | (kHyp - 1 - h): larger count wins, then lower index
-  for (int h = threadIdx.x; h < kHyp; h += 256)
-    if (counts[h] >= 0) {
-      const long long k = ((long long)counts[h] << 32) | (long long)(kHyp - 1 - h);
-      key = k > key ? k : key;
-    }
-  red[threadIdx.x] = key;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x + o] > red[threadIdx.x] ? red[threadIdx.x + o] : red[threadIdx.x];
-    __syncthreads();
-  }
+  const long long key = winner_key(counts, red);
   if (threadIdx.x == 0) {
-    best[0] = red[0] < 0 ? -1 : kHyp - 1 - (int)(red[0] & 0xFFFFFFFFll);
-    best[1] = red[0] < 0 ? 0 : (int)(red[0] >> 32);
+    best[0] = key < 0 ? -1 : winner_index(key);
+    best[1] = key < 0 ? 0 : winner_count(key);
   }
 }
 
@@ -312,150 +301,152 @@ extern "C" gh_status gh_ransac_estimate_conf(gh_ctx* ctx, int model, const doubl
                                inliers_out, hypotheses_used_out);
 }
 
-extern "C" gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double* src, const double* dst, int n,
-                                           double threshold, double confidence, uint64_t seed, int sampling, double* model_out,
-                                           uint8_t* mask_out, int* inliers_out, int* hypotheses_used_out) {
-  if (!ctx) return GH_ERR_ARG;
-  GH_ENTER(ctx);
-  GH_CHECK_ARG(ctx, model >= 0 && model <= 7 && src && dst && model_out && inliers_out && threshold >= 0);
-  GH_CHECK_ARG(ctx, sampling == GH_SAMPLE_RANSAC || sampling == GH_SAMPLE_LMEDS || sampling == GH_SAMPLE_NONE);
-  const int dim = dim_p(model), dimq = dim_q(model);
-  const int s = sample_size(model);
-  *inliers_out = 0;
-  if (hypotheses_used_out) *hypotheses_used_out = 0;
-  for (int k = 0; k < 12; ++k) model_out[k] = 0.0;
-  if (mask_out)
-    for (int i = 0; i < n; ++i) mask_out[i] = 0;
-  if (n < s) return GH_OK;  // not enough correspondences: no model (inliers 0)
-  GH_HIP(ctx, hipSetDevice(ctx->device));
-  Norm nm = {0, 0, 1, 0, 0, 1};
-  if (model == kModelF || model == kModelE) {  // Hartley normalisation, sequential sums in index order (the oracle does the same)
-    double ax = 0, ay = 0, bx = 0, by = 0;
-    for (int i = 0; i < n; ++i) {
-      ax += src[2 * i]; ay += src[2 * i + 1];
-      bx += dst[2 * i]; by += dst[2 * i + 1];
-    }
-    nm.m1x = ax / n; nm.m1y = ay / n; nm.m2x = bx / n; nm.m2y = by / n;
-    double d1 = 0, d2 = 0;
-    for (int i = 0; i < n; ++i) {
-      const double x = src[2 * i] - nm.m1x, y = src[2 * i + 1] - nm.m1y;
-      const double u = dst[2 * i] - nm.m2x, v = dst[2 * i + 1] - nm.m2y;
-      d1 += sqrt(x * x + y * y);
-      d2 += sqrt(u * u + v * v);
-    }
-    d1 /= n; d2 /= n;
-    nm.s1 = d1 > 0 ? 1.4142135623730951 / d1 : 1.0;
-    nm.s2 = d2 > 0 ? 1.4142135623730951 / d2 : 1.0;
-  }
-  const size_t pb = (((size_t)n * 3 * 8) + 255) & ~(size_t)255;  // sized for the wider of the two point sets
-  // (the counts slot holds 8 bytes per hypothesis: LMedS stores its medians there as 64-bit keys)
-  const size_t off_q = pb, off_models = 2 * pb, off_valid = off_models + (size_t)kHyp * 12 * 8,
-               off_counts = off_valid + kHyp * 4, off_best = off_counts + kHyp * 8, off_mout = off_best + 256,
-               off_mask = off_mout + 256, total = off_mask + (((size_t)n + 255) & ~(size_t)255);
-  void *base = nullptr, *hbase = nullptr;
-  GH_TRY(gh_scratch(ctx, total, &base));
-  GH_TRY(gh_pinned(ctx, total, &hbase));  // host mirror of the same layout: one DMA per direction and phase
-  uint8_t *b = (uint8_t*)base, *hb = (uint8_t*)hbase;
-  double* d_p = (double*)b;
-  double* d_q = (double*)(b + off_q);
-  double* d_models = (double*)(b + off_models);
-  int* d_valid = (int*)(b + off_valid);
-  int* d_counts = (int*)(b + off_counts);
-  int* d_best = (int*)(b + off_best);
-  double* d_mout = (double*)(b + off_mout);
-  uint8_t* d_mask = b + off_mask;
-  // (a per-frame caller -- Estimator::findFundamental / findHomography / findPnPRansac -- paid two pageable uploads and
-  // three to five pageable downloads of ~30-50 us each around ~100 us of kernels)
-  memcpy(hb, src, (size_t)n * dim * 8);
-  memcpy(hb + off_q, dst, (size_t)n * dimq * 8);
-  GH_HIP(ctx, hipMemcpyAsync(b, hb, off_q + (size_t)n * dimq * 8, hipMemcpyHostToDevice, ctx->stream));
-  double thr2 = threshold * threshold;
-  int best[2] = {-1, 0};
-  if (sampling == GH_SAMPLE_NONE) {
-    // the all-point fit is hypothesis 0; the device evaluates it against every correspondence (mask + inlier count)
-    double m[12];
-    // (the eigenvector fits never refuse; on NaN / Inf input they hand back a model that is not finite, whose NaN payloads
-    // are the compiler's choice of operand order: such a fit is no model)
-    bool ok = fit_all(model, src, dst, n, nm, m);
-    for (int k = 0; k < 12; ++k) ok = ok && fabs(m[k]) <= 1.7976931348623157e308;
-    if (hypotheses_used_out) *hypotheses_used_out = ok ? 1 : 0;
-    if (!ok) {  // degenerate fit: outputs stay zero (cleared at entry); the upload from the pinned block must not outlive the call
-      GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return GH_OK;
-    }
-    memcpy(hb + off_models, m, sizeof(m));
-    best[0] = 0;
-    memcpy(hb + off_best, best, 8);
-    GH_HIP(ctx, hipMemcpyAsync(d_models, hb + off_models, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
-    GH_HIP(ctx, hipMemcpyAsync(d_best, hb + off_best, 8, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    GH_LAUNCH(ctx, "ransac_solve", ransac_solve_kernel, dim3(kHyp / 64), dim3(64), 0, model, d_p, d_q, n, seed, nm,
-              d_models, d_valid);
-  }
-  if (sampling == GH_SAMPLE_LMEDS) {
-    // least median of squares (Rousseeuw; OpenCV's LMEDS): the hypothesis with the smallest median squared error wins
-    // (lowest index on ties); inlier radius = max(threshold, 2.5 * 1.4826 * (1 + 5 / (n - s)) * sqrt(median))
-    unsigned long long* d_med = (unsigned long long*)d_counts;
-    GH_LAUNCH(ctx, "ransac_median", ransac_median_kernel, dim3(kHyp), dim3(256), 0, model, d_p, d_q, n, d_models, d_valid, d_med);
-    const unsigned long long* h_med = (const unsigned long long*)(hb + off_counts);
-    GH_HIP(ctx, hipMemcpyAsync(hb + off_counts, d_med, kHyp * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+namespace {
+
+// The device scratch of one gh_ransac_estimate_ex call: p | q | models | valid | counts | best | model | mask.  The pinned
+// host block mirrors it offset for offset, so that every phase moves its data with one DMA per direction.
+struct EstimateLayout {
+  // (p is at 0; q: sized for the wider of the two point sets; counts: 8 bytes per hypothesis, LMedS stores its medians there
+  // as 64-bit keys; best | model | mask lie back to back: one download)
+  size_t q, models, valid, counts, best, mout, mask, total;
+  explicit EstimateLayout(int n)
+      : q(gh_round256((size_t)n * 3 * 8)), models(2 * q), valid(models + (size_t)kHyp * 12 * 8), counts(valid + kHyp * 4),
+        best(counts + kHyp * 8), mout(best + 256), mask(mout + 256), total(mask + gh_round256((size_t)n)) {}
+};
+
+// One call on its way through the phases below.
+struct EstimateRun {
+  int model, n, s;
+  double threshold, thr2;   // thr2: the squared inlier radius of the mask (LMedS replaces it with its own)
+  uint64_t seed;
+  Norm nm;
+  EstimateLayout at;
+  uint8_t *b, *hb;          // the device block and its pinned mirror
+  int best[2];              // the winner as the host knows it: hypothesis (-1: none), inlier count
+  int used;                 // hypotheses looked at: what hypotheses_used_out reports
+  bool count_from_mask;     // the inlier count is the population of the mask (no device count: NOSAMPLE, LMedS)
+  double* p() const { return (double*)b; }
+  double* q() const { return (double*)(b + at.q); }
+  double* models() const { return (double*)(b + at.models); }
+  int* valid() const { return (int*)(b + at.valid); }
+  int* counts() const { return (int*)(b + at.counts); }
+  int* d_best() const { return (int*)(b + at.best); }
+};
+
+// Both point sets to the device through the pinned mirror.
+// (a per-frame caller -- Estimator::findFundamental / findHomography / findPnPRansac -- paid two pageable uploads and
+// three to five pageable downloads of ~30-50 us each around ~100 us of kernels)
+gh_status estimate_upload_points(gh_ctx* ctx, const EstimateRun& R, const double* src, const double* dst) {
+  const size_t qbytes = (size_t)R.n * dim_q(R.model) * 8;
+  memcpy(R.hb, src, (size_t)R.n * dim_p(R.model) * 8);
+  memcpy(R.hb + R.at.q, dst, qbytes);
+  GH_HIP(ctx, hipMemcpyAsync(R.b, R.hb, R.at.q + qbytes, hipMemcpyHostToDevice, ctx->stream));
+  return GH_OK;
+}
+
+// The host's choice of the winner (two ints) to the device; the download at the end into the same words of the pinned mirror
+// is ordered behind it by the stream.
+gh_status estimate_send_best(gh_ctx* ctx, const EstimateRun& R) {
+  memcpy(R.hb + R.at.best, R.best, 8);
+  GH_HIP(ctx, hipMemcpyAsync(R.d_best(), R.hb + R.at.best, 8, hipMemcpyHostToDevice, ctx->stream));
+  return GH_OK;
+}
+
+// NOSAMPLE: the all-point fit is hypothesis 0; the device evaluates it against every correspondence (mask + inlier count).
+// *have = false: a degenerate fit, the outputs stay as they were cleared.
+gh_status estimate_choose_fit_all(gh_ctx* ctx, EstimateRun& R, const double* src, const double* dst, bool* have) {
+  double m[12];
+  // (the eigenvector fits never refuse; on NaN / Inf input they hand back a model that is not finite, whose NaN payloads
+  // are the compiler's choice of operand order: such a fit is no model)
+  bool ok = fit_all(R.model, src, dst, R.n, R.nm, m);
+  for (int k = 0; k < 12; ++k) ok = ok && fabs(m[k]) <= 1.7976931348623157e308;
+  R.used = ok ? 1 : 0;
+  R.count_from_mask = true;
+  *have = ok;
+  if (!ok) {  // the upload from the pinned block must not outlive the call
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    unsigned long long bm = ~0ull;
-    for (int h = 0; h < kHyp; ++h)
-      if (h_med[h] < bm) {
-        bm = h_med[h];
-        best[0] = h;
-      }
-    if (hypotheses_used_out) *hypotheses_used_out = kHyp;
-    if (best[0] < 0 || bm >= 0x7FF0000000000000ull) return GH_OK;  // no hypothesis explains half of the correspondences
-    double med;
-    memcpy(&med, &bm, 8);
-    const double sigma = 2.5 * 1.4826 * (1.0 + 5.0 / (double)(n - s > 0 ? n - s : 1)) * sqrt(med);
-    const double radius = sigma > threshold ? sigma : threshold;
-    thr2 = radius * radius;
-    memcpy(hb + off_best, best, 8);
-    GH_HIP(ctx, hipMemcpyAsync(d_best, hb + off_best, 8, hipMemcpyHostToDevice, ctx->stream));
-  } else if (sampling == GH_SAMPLE_RANSAC) {
-    GH_LAUNCH(ctx, "ransac_score", ransac_score_kernel, dim3(kHyp), dim3(256), 0, model, d_p, d_q, n, thr2, d_models,
-              d_valid, d_counts);
+    return GH_OK;
   }
-  if (sampling != GH_SAMPLE_RANSAC) {
-    // (the winner is known on the host already)
-  } else if (confidence > 0.0 && confidence < 1.0) {
-    // the prefix rule needs the counts on the host: 8 KB back, the choice (two ints) forth
-    const int* h_counts = (const int*)(hb + off_counts);
-    GH_HIP(ctx, hipMemcpyAsync(hb + off_counts, d_counts, kHyp * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  memcpy(R.hb + R.at.models, m, sizeof(m));
+  GH_HIP(ctx, hipMemcpyAsync(R.models(), R.hb + R.at.models, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+  R.best[0] = 0;
+  return estimate_send_best(ctx, R);
+}
+
+// Least median of squares (Rousseeuw; OpenCV's LMEDS): the hypothesis with the smallest median squared error wins
+// (lowest index on ties); inlier radius = max(threshold, 2.5 * 1.4826 * (1 + 5 / (n - s)) * sqrt(median)).
+// *have = false: no hypothesis explains half of the correspondences.
+gh_status estimate_choose_lmeds(gh_ctx* ctx, EstimateRun& R, bool* have) {
+  GH_LAUNCH(ctx, "ransac_solve", ransac_solve_kernel, dim3(kHyp / 64), dim3(64), 0, R.model, R.p(), R.q(), R.n, R.seed, R.nm,
+            R.models(), R.valid());
+  unsigned long long* d_med = (unsigned long long*)R.counts();
+  GH_LAUNCH(ctx, "ransac_median", ransac_median_kernel, dim3(kHyp), dim3(256), 0, R.model, R.p(), R.q(), R.n, R.models(), R.valid(),
+            d_med);
+  const unsigned long long* h_med = (const unsigned long long*)(R.hb + R.at.counts);
+  GH_HIP(ctx, hipMemcpyAsync(R.hb + R.at.counts, d_med, kHyp * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  unsigned long long bm = ~0ull;
+  for (int h = 0; h < kHyp; ++h)
+    if (h_med[h] < bm) {
+      bm = h_med[h];
+      R.best[0] = h;
+    }
+  R.used = kHyp;
+  R.count_from_mask = true;
+  *have = R.best[0] >= 0 && bm < 0x7FF0000000000000ull;
+  if (!*have) return GH_OK;
+  double med;
+  memcpy(&med, &bm, 8);
+  const double sigma = 2.5 * 1.4826 * (1.0 + 5.0 / (double)(R.n - R.s > 0 ? R.n - R.s : 1)) * sqrt(med);
+  const double radius = sigma > R.threshold ? sigma : R.threshold;
+  R.thr2 = radius * radius;
+  return estimate_send_best(ctx, R);
+}
+
+// RANSAC: every hypothesis scored on the device; the winner by the adaptive prefix rule on the host (confidence inside
+// (0, 1)) or by the device's argmax.  Either way the device holds winner and count afterwards ("none" included).
+gh_status estimate_choose_ransac(gh_ctx* ctx, EstimateRun& R, double confidence) {
+  GH_LAUNCH(ctx, "ransac_solve", ransac_solve_kernel, dim3(kHyp / 64), dim3(64), 0, R.model, R.p(), R.q(), R.n, R.seed, R.nm,
+            R.models(), R.valid());
+  GH_LAUNCH(ctx, "ransac_score", ransac_score_kernel, dim3(kHyp), dim3(256), 0, R.model, R.p(), R.q(), R.n, R.thr2, R.models(),
+            R.valid(), R.counts());
+  R.count_from_mask = false;
+  if (confidence > 0.0 && confidence < 1.0) {
+    // the prefix rule needs the counts on the host: 8 KB back, the choice forth
+    const int* h_counts = (const int*)(R.hb + R.at.counts);
+    GH_HIP(ctx, hipMemcpyAsync(R.hb + R.at.counts, R.counts(), kHyp * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int used = 0;
-    best[0] = adaptive_prefix_best(h_counts, n, s, confidence, &best[1], &used);
-    if (hypotheses_used_out) *hypotheses_used_out = used;
-    // sent from the pinned mirror; the download below into the same words is ordered behind it by the stream
-    memcpy(hb + off_best, best, 8);
-    GH_HIP(ctx, hipMemcpyAsync(d_best, hb + off_best, 8, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    GH_LAUNCH(ctx, "ransac_best", ransac_best_kernel, dim3(1), dim3(256), 0, d_counts, d_best);
-    if (hypotheses_used_out) *hypotheses_used_out = kHyp;
+    R.best[0] = adaptive_prefix_best(h_counts, R.n, R.s, confidence, &R.best[1], &R.used);
+    return estimate_send_best(ctx, R);
   }
-  GH_LAUNCH(ctx, "ransac_mask", ransac_mask_kernel, dim3(gh_div_up(n > 12 ? n : 12, 256)), dim3(256), 0, model, d_p, d_q,
-            n, thr2, d_models, d_best, d_mask, d_mout);
-  // best | model | mask lie back to back: one download
-  GH_HIP(ctx, hipMemcpyAsync(hb + off_best, d_best, (off_mask - off_best) + ((mask_out || sampling != GH_SAMPLE_RANSAC) ? (size_t)n : 0),
+  GH_LAUNCH(ctx, "ransac_best", ransac_best_kernel, dim3(1), dim3(256), 0, R.counts(), R.d_best());
+  R.used = kHyp;
+  return GH_OK;
+}
+
+// The winner's mask and model on the device, ONE download, and the outputs.  No winner: the cleared outputs stay.
+gh_status estimate_finish(gh_ctx* ctx, EstimateRun& R, double* model_out, uint8_t* mask_out, int* inliers_out) {
+  const int n = R.n;
+  const EstimateLayout& at = R.at;
+  GH_LAUNCH(ctx, "ransac_mask", ransac_mask_kernel, dim3(gh_div_up(n > 12 ? n : 12, 256)), dim3(256), 0, R.model, R.p(), R.q(), n,
+            R.thr2, R.models(), R.d_best(), R.b + at.mask, (double*)(R.b + at.mout));
+  GH_HIP(ctx, hipMemcpyAsync(R.hb + at.best, R.d_best(), (at.mask - at.best) + ((mask_out || R.count_from_mask) ? (size_t)n : 0),
                              hipMemcpyDeviceToHost, ctx->stream));
   GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (sampling == GH_SAMPLE_RANSAC) memcpy(best, hb + off_best, 8);
-  memcpy(model_out, hb + off_mout, 12 * 8);
-  if (mask_out) memcpy(mask_out, hb + off_mask, (size_t)n);
-  if (best[0] < 0) {
+  if (!R.count_from_mask) memcpy(R.best, R.hb + at.best, 8);
+  memcpy(model_out, R.hb + at.mout, 12 * 8);
+  if (mask_out) memcpy(mask_out, R.hb + at.mask, (size_t)n);
+  if (R.best[0] < 0) {
     for (int k = 0; k < 12; ++k) model_out[k] = 0.0;
     return GH_OK;
   }
-  if (sampling != GH_SAMPLE_RANSAC) {  // the inlier count of the chosen model is the population of its mask
-    best[1] = 0;
-    const uint8_t* hm = hb + off_mask;
-    for (int i = 0; i < n; ++i) best[1] += hm[i] ? 1 : 0;
+  if (R.count_from_mask) {
+    R.best[1] = 0;
+    const uint8_t* hm = R.hb + at.mask;
+    for (int i = 0; i < n; ++i) R.best[1] += hm[i] ? 1 : 0;
   }
-  *inliers_out = best[1];
-  if (model == kModelE && !project_essential(model_out)) {
+  *inliers_out = R.best[1];
+  if (R.model == kModelE && !project_essential(model_out)) {
     // the scored 8-point estimate has no essential matrix near it (rank 1, or not finite): no model, and like every
     // other no-model exit neither an inlier count nor a mask (the one copied out above belonged to the rejected estimate)
     for (int k = 0; k < 12; ++k) model_out[k] = 0.0;
@@ -464,6 +455,40 @@ extern "C" gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double*
     *inliers_out = 0;
   }
   return GH_OK;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_ransac_estimate_ex(gh_ctx* ctx, int model, const double* src, const double* dst, int n,
+                                           double threshold, double confidence, uint64_t seed, int sampling, double* model_out,
+                                           uint8_t* mask_out, int* inliers_out, int* hypotheses_used_out) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, model >= 0 && model <= 7 && src && dst && model_out && inliers_out && threshold >= 0);
+  GH_CHECK_ARG(ctx, sampling == GH_SAMPLE_RANSAC || sampling == GH_SAMPLE_LMEDS || sampling == GH_SAMPLE_NONE);
+  *inliers_out = 0;
+  if (hypotheses_used_out) *hypotheses_used_out = 0;
+  for (int k = 0; k < 12; ++k) model_out[k] = 0.0;
+  if (mask_out)
+    for (int i = 0; i < n; ++i) mask_out[i] = 0;
+  if (n < sample_size(model)) return GH_OK;  // not enough correspondences: no model (inliers 0)
+  GH_HIP(ctx, hipSetDevice(ctx->device));
+  EstimateRun R = {model, n, sample_size(model), threshold, threshold * threshold, seed, {0, 0, 1, 0, 0, 1}, EstimateLayout(n)};
+  if (model == kModelF || model == kModelE) R.nm = hartley_norm(src, dst, n);
+  R.best[0] = -1;
+  void *base = nullptr, *hbase = nullptr;
+  GH_TRY(gh_scratch(ctx, R.at.total, &base));
+  GH_TRY(gh_pinned(ctx, R.at.total, &hbase));
+  R.b = (uint8_t*)base;
+  R.hb = (uint8_t*)hbase;
+  GH_TRY(estimate_upload_points(ctx, R, src, dst));
+  bool have = true;
+  if (sampling == GH_SAMPLE_NONE) GH_TRY(estimate_choose_fit_all(ctx, R, src, dst, &have));
+  else if (sampling == GH_SAMPLE_LMEDS) GH_TRY(estimate_choose_lmeds(ctx, R, &have));
+  else GH_TRY(estimate_choose_ransac(ctx, R, confidence));
+  if (hypotheses_used_out) *hypotheses_used_out = R.used;
+  if (!have) return GH_OK;
+  return estimate_finish(ctx, R, model_out, mask_out, inliers_out);
 }
 
 namespace {

@@ -20,7 +20,7 @@
 // A problem with fewer rows than the sample, or a threshold that is negative or NaN, is skipped by every kernel BEFORE the
 // sampler (whose rejection loop does not end for n < s): it is "no model".  Row ranges are clamped to the arrays before
 // they address anything.
-#include "ransac_models.h"
+#include "estimate_batch.h"
 
 namespace {
 
@@ -33,10 +33,7 @@ constexpr int kChunk = 8192;           // problems per launch: bounds the counts
 struct BatchArgs {
   const double* src;
   const double* dst;
-  const int32_t* row_begin;   // per problem: first row ...
-  const int32_t* row_end;     // ... and one past the last
-  const int32_t* limit_dev;   // rows the arrays hold (device word), or NULL: `limit`
-  int limit;
+  RowRanges range;
   int nproblems;
   double threshold;
   const double* thresholds;   // per problem, or NULL
@@ -51,45 +48,17 @@ struct BatchArgs {
   int32_t* inliers;
 };
 
-// The rows of problem p.  A range that is empty, reversed or not inside the arrays is 0 rows: nothing of it is addressed.
-__device__ inline int problem_rows(const BatchArgs& a, int p, int* first) {
-  const int limit = a.limit_dev ? *a.limit_dev : a.limit;
-  const int b = a.row_begin[p], e = a.row_end[p];
-  *first = b;
-  if (b < 0 || e > limit || e <= b) return 0;
-  return e - b;
-}
-
 __device__ inline double problem_threshold(const BatchArgs& a, int p) { return a.thresholds ? a.thresholds[p] : a.threshold; }
 __device__ inline uint64_t problem_seed(const BatchArgs& a, int p) { return a.seeds ? a.seeds[p] : a.seed; }
 
-// Hartley normalisation of F / E: the host loop of gh_ransac_estimate_ex, one lane per problem, the same order of additions.
+// Hartley normalisation of F / E, one lane per problem: hartley_norm is what the single call runs on the host.
 __global__ __launch_bounds__(64) void ransac_batch_norm_kernel(BatchArgs a) {
   const int p = blockIdx.x * 64 + threadIdx.x;
   if (p >= a.nproblems) return;
   int first;
-  const int n = problem_rows(a, p, &first);
+  const int n = problem_rows(a.range, p, &first);
   Norm nm = {0, 0, 1, 0, 0, 1};
-  if (n >= 8) {
-    const double* src = a.src + (size_t)first * 2;
-    const double* dst = a.dst + (size_t)first * 2;
-    double ax = 0, ay = 0, bx = 0, by = 0;
-    for (int i = 0; i < n; ++i) {
-      ax += src[2 * i]; ay += src[2 * i + 1];
-      bx += dst[2 * i]; by += dst[2 * i + 1];
-    }
-    nm.m1x = ax / n; nm.m1y = ay / n; nm.m2x = bx / n; nm.m2y = by / n;
-    double d1 = 0, d2 = 0;
-    for (int i = 0; i < n; ++i) {
-      const double x = src[2 * i] - nm.m1x, y = src[2 * i + 1] - nm.m1y;
-      const double u = dst[2 * i] - nm.m2x, v = dst[2 * i + 1] - nm.m2y;
-      d1 += sqrt(x * x + y * y);
-      d2 += sqrt(u * u + v * v);
-    }
-    d1 /= n; d2 /= n;
-    nm.s1 = d1 > 0 ? 1.4142135623730951 / d1 : 1.0;
-    nm.s2 = d2 > 0 ? 1.4142135623730951 / d2 : 1.0;
-  }
+  if (n >= 8) nm = hartley_norm(a.src + (size_t)first * 2, a.dst + (size_t)first * 2, n);  // (fewer rows: no model, nothing reads it)
   a.norms[p] = nm;
 }
 
@@ -101,7 +70,7 @@ __global__ __launch_bounds__(256) void ransac_batch_score_kernel(BatchArgs a) {
   const int p = blockIdx.x / kParts, tid = threadIdx.x;
   const int h = (blockIdx.x % kParts) * 256 + tid;
   int first;
-  const int n = problem_rows(a, p, &first);
+  const int n = problem_rows(a.range, p, &first);
   const double thr = problem_threshold(a, p);
   if (n < sample_size(MODEL) || !(thr >= 0)) return;  // no model (the whole workgroup leaves: the finish kernel reads no count)
   const double thr2 = thr * thr;
@@ -137,34 +106,20 @@ __global__ __launch_bounds__(256) void ransac_batch_finish_kernel(BatchArgs a) {
   __shared__ long long red[256];
   const int p = blockIdx.x, tid = threadIdx.x;
   int first;
-  const int n = problem_rows(a, p, &first);
+  const int n = problem_rows(a.range, p, &first);
   const double thr = problem_threshold(a, p);
   const double thr2 = thr * thr;
   const double* P = a.src + (size_t)first * DP;
   const double* Q = a.dst + (size_t)first * DQ;
-  long long best = -1;  // count << 32 | (kHyp - 1 - h): larger count wins, then lower index
-  if (n >= sample_size(MODEL) && thr >= 0) {
-    const int* counts = a.counts + (size_t)p * kHyp;
-    for (int h = tid; h < kHyp; h += 256)
-      if (counts[h] >= 0) {
-        const long long k = ((long long)counts[h] << 32) | (long long)(kHyp - 1 - h);
-        best = k > best ? k : best;
-      }
-    red[tid] = best;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-      if (tid < o) red[tid] = red[tid + o] > red[tid] ? red[tid + o] : red[tid];
-      __syncthreads();
-    }
-    best = red[0];
-  }
+  long long best = -1;
+  if (n >= sample_size(MODEL) && thr >= 0) best = winner_key(a.counts + (size_t)p * kHyp, red);
   // every lane solves the winner again: uniform control flow, and the mask below needs the model in each lane's registers
   double m[12], out[12];
   bool have = false;
   if (best >= 0) {
     Norm nm = {0, 0, 1, 0, 0, 1};
     if (MODEL == kModelF || MODEL == kModelE) nm = a.norms[p];
-    have = solve_hypothesis(MODEL, P, Q, n, problem_seed(a, p), nm, kHyp - 1 - (int)(best & 0xFFFFFFFFll), m);
+    have = solve_hypothesis(MODEL, P, Q, n, problem_seed(a, p), nm, winner_index(best), m);
   }
   const int ms = model_size(MODEL);
   for (int k = 0; k < 12; ++k) out[k] = have && k < ms ? m[k] : 0.0;
@@ -172,7 +127,7 @@ __global__ __launch_bounds__(256) void ransac_batch_finish_kernel(BatchArgs a) {
   if (MODEL == kModelE && have) have = project_essential(out);
   if (tid == 0) {
     for (int k = 0; k < 12; ++k) a.models[(size_t)p * 12 + k] = have ? out[k] : 0.0;
-    a.inliers[p] = have ? (int)(best >> 32) : 0;
+    a.inliers[p] = have ? winner_count(best) : 0;
   }
   if (!a.mask) return;
   if (a.row_map) {  // pair entry: the gather kernel has zeroed the pair's row of the mask
@@ -207,7 +162,7 @@ __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, con
                                                                   int32_t* __restrict__ row_begin, int32_t* __restrict__ row_end,
                                                                   int32_t* __restrict__ n_corr, uint8_t* __restrict__ inlier) {
   __shared__ int wave_total[4];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int p = blockIdx.x, tid = threadIdx.x;
   const int fq = pair_q[p], ft = pair_t[p];
   int cq = counts[fq], ct = counts[ft];
   cq = cq < 0 ? 0 : (cq > cap ? cap : cq);
@@ -223,12 +178,7 @@ __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, con
       j = idx1[row0 + i];
       take = (!keep || keep[row0 + i]) && j >= 0 && j < ct;
     }
-    const unsigned long long b = __ballot(take);
-    if (lane == 0) wave_total[w] = __popcll(b);
-    __syncthreads();
-    int at = base + __popcll(b & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) at += wave_total[k];
-    if (take) {
+    compact_trip(take, &base, wave_total, [&](int at) {
       const gh_keypoint* kq = kps + (size_t)fq * cap + i;
       const gh_keypoint* kt = kps + (size_t)ft * cap + j;
       const size_t r = row0 + at;
@@ -244,21 +194,13 @@ __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, con
         dst[2 * r + 1] = (double)kt->y;
       }
       row_map[r] = i;
-    }
-    base += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
-    __syncthreads();
+    });
   }
   if (tid == 0) {
     row_begin[p] = (int32_t)row0;
     row_end[p] = (int32_t)row0 + base;
     n_corr[p] = base;
   }
-}
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t batch_scratch_bytes(int nproblems) {
-  const size_t np = nproblems < kChunk ? nproblems : kChunk;
-  return round256(np * sizeof(Norm)) + round256(np * kHyp * sizeof(int));
 }
 
 template <int MODEL>
@@ -270,21 +212,21 @@ gh_status batch_launch(gh_ctx* ctx, const BatchArgs& a) {
   return GH_OK;
 }
 
-// `work`: batch_scratch_bytes(nproblems) bytes of device scratch.  Problems go kChunk at a time (stream order keeps the
+// `work`: ransac_batch_scratch_bytes(nproblems) bytes of device scratch.  Problems go kChunk at a time (stream order keeps the
 // shared scratch safe); every per-problem array of `all` moves with the chunk, rows stay absolute.
 gh_status batch_run(gh_ctx* ctx, int model, const BatchArgs& all, void* work) {
   for (int p0 = 0; p0 < all.nproblems; p0 += kChunk) {
     BatchArgs a = all;
     a.nproblems = all.nproblems - p0 < kChunk ? all.nproblems - p0 : kChunk;
-    a.row_begin += p0;
-    a.row_end += p0;
+    a.range.row_begin += p0;
+    a.range.row_end += p0;
     if (a.thresholds) a.thresholds += p0;
     if (a.seeds) a.seeds += p0;
     a.models += (size_t)p0 * 12;
     a.inliers += p0;
     if (a.row_map && a.mask) a.mask += (size_t)p0 * a.map_stride;
     a.norms = (Norm*)work;
-    a.counts = (int*)((uint8_t*)work + round256((size_t)a.nproblems * sizeof(Norm)));
+    a.counts = (int*)((uint8_t*)work + gh_round256((size_t)a.nproblems * sizeof(Norm)));
     switch (model) {
       case kModelH: GH_TRY(batch_launch<kModelH>(ctx, a)); break;
       case kModelA2: GH_TRY(batch_launch<kModelA2>(ctx, a)); break;
@@ -299,24 +241,75 @@ gh_status batch_run(gh_ctx* ctx, int model, const BatchArgs& all, void* work) {
   return GH_OK;
 }
 
+// The scratch block of a pair entry: src | dst (npairs x cap x 2 doubles each) | row_map | row_begin | row_end | the core's
+// own block.  ONE block for every stage of the call (gh_scratch hands out one block per context).
+struct PairScratch {
+  size_t rows, dst, map, begin, end, work, total;  // (src is at 0)
+  PairScratch(int npairs, int cap)
+      : rows((size_t)npairs * cap), dst(gh_round256(rows * 16)), map(2 * dst), begin(map + gh_round256(rows * 4)),
+        end(begin + gh_round256((size_t)npairs * 4)), work(end + gh_round256((size_t)npairs * 4)),
+        total(work + ransac_batch_scratch_bytes(npairs)) {}
+};
+
+// What both pair entries do once their own arguments are in order: refuse a bad shape or a NULL array, take the scratch,
+// gather every pair's correspondences (NORMALISE: to the normalised coordinates of pinhole k) and describe them to the core.
+// *a and *work are what batch_run takes; a->nproblems = 0 (and nothing launched) when there are no pairs.
+template <bool NORMALISE>
+gh_status pairs_front(gh_ctx* ctx, Pinhole k, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
+                      const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                      const uint8_t* keep_dev, double threshold, uint64_t seed, double* models_dev, uint8_t* inlier_dev,
+                      int32_t* n_corr_dev, int32_t* inliers_dev, BatchArgs* a, void** work) {
+  *a = {};
+  GH_CHECK_ARG(ctx, cap >= 0 && cap <= 65535 && npairs >= 0);
+  GH_CHECK_ARG(ctx, threshold >= 0 && (long long)npairs * (cap > 0 ? cap : 1) <= 0x7FFFFFFFll && npairs <= (1 << 27));
+  if (npairs == 0) return GH_OK;
+  GH_CHECK_ARG(ctx, kps_dev && counts_dev && pair_q_dev && pair_t_dev && idx1_dev && models_dev && inlier_dev && n_corr_dev &&
+                        inliers_dev);
+  const PairScratch at(npairs, cap);
+  void* base = nullptr;
+  GH_TRY(gh_scratch(ctx, at.total, &base));
+  uint8_t* b = (uint8_t*)base;
+  double *src = (double*)b, *dst = (double*)(b + at.dst);
+  int32_t *row_map = (int32_t*)(b + at.map), *row_begin = (int32_t*)(b + at.begin), *row_end = (int32_t*)(b + at.end);
+  GH_LAUNCH(ctx, NORMALISE ? "two_view_pairs_gather" : "ransac_pairs_gather", ransac_pairs_gather_kernel<NORMALISE>, dim3(npairs),
+            dim3(256), 0, k, kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, idx1_dev, keep_dev, src, dst, row_map, row_begin,
+            row_end, n_corr_dev, inlier_dev);
+  a->src = src;
+  a->dst = dst;
+  a->range = {row_begin, row_end, nullptr, (int)at.rows};
+  a->nproblems = npairs;
+  a->threshold = threshold;
+  a->seed = seed;
+  a->row_map = row_map;
+  a->map_stride = cap;
+  a->models = models_dev;
+  a->mask = inlier_dev;
+  a->inliers = inliers_dev;
+  *work = b + at.work;
+  return GH_OK;
+}
+
 }  // namespace
 
 namespace gh_ransac {
 
-size_t ransac_batch_scratch_bytes(int nproblems) { return batch_scratch_bytes(nproblems); }
+size_t ransac_batch_scratch_bytes(int nproblems) {
+  const size_t np = nproblems < kChunk ? nproblems : kChunk;
+  return gh_round256(np * sizeof(Norm)) + gh_round256(np * kHyp * sizeof(int));
+}
 
-gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const double* dst, const int32_t* row_begin,
-                              const int32_t* row_end, int limit, int nproblems, double threshold, uint64_t seed,
+gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const double* dst, const RowRanges& range,
+                              int nproblems, double threshold, const double* thresholds, uint64_t seed, const uint64_t* seeds,
                               double* models, uint8_t* mask, int32_t* inliers, void* work) {
   BatchArgs a = {};
   a.src = src;
   a.dst = dst;
-  a.row_begin = row_begin;
-  a.row_end = row_end;
-  a.limit = limit;
+  a.range = range;
   a.nproblems = nproblems;
   a.threshold = threshold;
+  a.thresholds = thresholds;
   a.seed = seed;
+  a.seeds = seeds;
   a.models = models;
   a.mask = mask;
   a.inliers = inliers;
@@ -338,22 +331,10 @@ extern "C" gh_status gh_ransac_batch_dev(gh_ctx* ctx, int model, const double* s
   if (nproblems == 0) return GH_OK;
   GH_CHECK_ARG(ctx, src_dev && dst_dev && offsets_dev && models_dev && inliers_dev);
   void* work = nullptr;
-  GH_TRY(gh_scratch(ctx, batch_scratch_bytes(nproblems), &work));
-  BatchArgs a = {};
-  a.src = src_dev;
-  a.dst = dst_dev;
-  a.row_begin = offsets_dev;
-  a.row_end = offsets_dev + 1;
-  a.limit_dev = offsets_dev + nproblems;  // the arrays hold offsets[nproblems] rows
-  a.nproblems = nproblems;
-  a.threshold = threshold;
-  a.thresholds = thresholds_dev;
-  a.seed = seed;
-  a.seeds = seeds_dev;
-  a.models = models_dev;
-  a.mask = mask_dev;
-  a.inliers = inliers_dev;
-  return batch_run(ctx, model, a, work);
+  GH_TRY(gh_scratch(ctx, ransac_batch_scratch_bytes(nproblems), &work));
+  const RowRanges range = {offsets_dev, offsets_dev + 1, offsets_dev + nproblems, INT_MAX};  // the arrays hold offsets[nproblems] rows
+  return ransac_batch_ranges(ctx, model, src_dev, dst_dev, range, nproblems, threshold, thresholds_dev, seed, seeds_dev, models_dev,
+                             mask_dev, inliers_dev, work);
 }
 
 extern "C" gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
@@ -362,37 +343,12 @@ extern "C" gh_status gh_ransac_pairs_dev(gh_ctx* ctx, int model, const gh_keypoi
                                          double* models_dev, uint8_t* inlier_dev, int32_t* n_corr_dev, int32_t* inliers_dev) {
   if (!ctx) return GH_ERR_ARG;
   GH_ENTER(ctx);
-  GH_CHECK_ARG(ctx, (model == kModelH || model == kModelA2 || model == kModelF) && cap >= 0 && cap <= 65535 && npairs >= 0);
-  GH_CHECK_ARG(ctx, threshold >= 0 && (long long)npairs * (cap > 0 ? cap : 1) <= 0x7FFFFFFFll && npairs <= (1 << 27));
-  if (npairs == 0) return GH_OK;
-  GH_CHECK_ARG(ctx, kps_dev && counts_dev && pair_q_dev && pair_t_dev && idx1_dev && models_dev && inlier_dev && n_corr_dev &&
-                        inliers_dev);
-  // scratch: src | dst (npairs x cap x 2 doubles each) | row_map | row_begin | row_end | the core's own block
-  const size_t rows = (size_t)npairs * cap;
-  const size_t o_dst = round256(rows * 16), o_map = 2 * o_dst, o_begin = o_map + round256(rows * 4),
-               o_end = o_begin + round256((size_t)npairs * 4), o_work = o_end + round256((size_t)npairs * 4);
-  void* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_work + batch_scratch_bytes(npairs), &base));
-  uint8_t* b = (uint8_t*)base;
-  GH_LAUNCH(ctx, "ransac_pairs_gather", ransac_pairs_gather_kernel<false>, dim3(npairs), dim3(256), 0, Pinhole{1, 1, 0, 0},
-            kps_dev, counts_dev, cap,
-            pair_q_dev, pair_t_dev, idx1_dev, keep_dev, (double*)b, (double*)(b + o_dst), (int32_t*)(b + o_map),
-            (int32_t*)(b + o_begin), (int32_t*)(b + o_end), n_corr_dev, inlier_dev);
-  BatchArgs a = {};
-  a.src = (const double*)b;
-  a.dst = (const double*)(b + o_dst);
-  a.row_begin = (const int32_t*)(b + o_begin);
-  a.row_end = (const int32_t*)(b + o_end);
-  a.limit = (int)rows;
-  a.nproblems = npairs;
-  a.threshold = threshold;
-  a.seed = seed;
-  a.row_map = (const int32_t*)(b + o_map);
-  a.map_stride = cap;
-  a.models = models_dev;
-  a.mask = inlier_dev;
-  a.inliers = inliers_dev;
-  return batch_run(ctx, model, a, b + o_work);
+  GH_CHECK_ARG(ctx, model == kModelH || model == kModelA2 || model == kModelF);
+  BatchArgs a;
+  void* work = nullptr;
+  GH_TRY(pairs_front<false>(ctx, Pinhole{1, 1, 0, 0}, kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, npairs, idx1_dev, keep_dev,
+                            threshold, seed, models_dev, inlier_dev, n_corr_dev, inliers_dev, &a, &work));
+  return batch_run(ctx, model, a, work);
 }
 
 extern "C" gh_status gh_two_view_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int cap,
@@ -404,46 +360,22 @@ extern "C" gh_status gh_two_view_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_d
                                            int32_t* status_dev) {
   if (!ctx) return GH_ERR_ARG;
   GH_ENTER(ctx);
-  GH_CHECK_ARG(ctx, cap >= 0 && cap <= 65535 && npairs >= 0 && fx > 0 && fy > 0 && cx == cx && cy == cy);
-  GH_CHECK_ARG(ctx, threshold >= 0 && (long long)npairs * (cap > 0 ? cap : 1) <= 0x7FFFFFFFll && npairs <= (1 << 27));
+  GH_CHECK_ARG(ctx, fx > 0 && fy > 0 && cx == cx && cy == cy);
   GH_CHECK_ARG(ctx, two_view_params_ok(params));
+  // (every refusal comes before the first launch; no pairs is nothing to do, whatever the pointers)
+  GH_CHECK_ARG(ctx, npairs <= 0 || (poses_dev && points_dev && good_dev && votes_dev && status_dev));
+  BatchArgs a;
+  void* work = nullptr;
+  GH_TRY(pairs_front<true>(ctx, Pinhole{fx, fy, cx, cy}, kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, npairs, idx1_dev,
+                           keep_dev, threshold, seed, models_dev, inlier_dev, n_corr_dev, inliers_dev, &a, &work));
   if (npairs == 0) return GH_OK;
-  GH_CHECK_ARG(ctx, kps_dev && counts_dev && pair_q_dev && pair_t_dev && idx1_dev && models_dev && inlier_dev && n_corr_dev &&
-                        inliers_dev && poses_dev && points_dev && good_dev && votes_dev && status_dev);
-  // ONE scratch block for all three stages (gh_scratch hands out one block per context), laid out as gh_ransac_pairs_dev's:
-  // src | dst | row_map | row_begin | row_end | the core's own block.  The two-view kernel reads the first five again.
-  const size_t rows = (size_t)npairs * cap;
-  const size_t o_dst = round256(rows * 16), o_map = 2 * o_dst, o_begin = o_map + round256(rows * 4),
-               o_end = o_begin + round256((size_t)npairs * 4), o_work = o_end + round256((size_t)npairs * 4);
-  void* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_work + batch_scratch_bytes(npairs), &base));
-  uint8_t* b = (uint8_t*)base;
-  GH_LAUNCH(ctx, "two_view_pairs_gather", ransac_pairs_gather_kernel<true>, dim3(npairs), dim3(256), 0, Pinhole{fx, fy, cx, cy},
-            kps_dev, counts_dev, cap, pair_q_dev, pair_t_dev, idx1_dev, keep_dev, (double*)b, (double*)(b + o_dst),
-            (int32_t*)(b + o_map), (int32_t*)(b + o_begin), (int32_t*)(b + o_end), n_corr_dev, inlier_dev);
-  BatchArgs a = {};
-  a.src = (const double*)b;
-  a.dst = (const double*)(b + o_dst);
-  a.row_begin = (const int32_t*)(b + o_begin);
-  a.row_end = (const int32_t*)(b + o_end);
-  a.limit = (int)rows;
-  a.nproblems = npairs;
-  a.threshold = threshold;
-  a.seed = seed;
-  a.row_map = (const int32_t*)(b + o_map);
-  a.map_stride = cap;
-  a.models = models_dev;
-  a.mask = inlier_dev;
-  a.inliers = inliers_dev;
-  GH_TRY(batch_run(ctx, kModelE, a, b + o_work));
-  TwoViewArgs t = {};
+  GH_TRY(batch_run(ctx, kModelE, a, work));
+  TwoViewArgs t = {};  // the two-view kernel reads the gathered rows and the row map again
   t.E = models_dev;
   t.e_stride = 12;
   t.src = a.src;
   t.dst = a.dst;
-  t.row_begin = a.row_begin;
-  t.row_end = a.row_end;
-  t.limit = a.limit;
+  t.range = a.range;
   t.nproblems = npairs;
   t.mask = inlier_dev;
   t.row_map = a.row_map;

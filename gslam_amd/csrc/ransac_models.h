@@ -270,10 +270,33 @@ __host__ __device__ inline bool ge_solve(double (*a)[12], int n, int nrhs) {
   return true;
 }
 
-struct Norm {  // Hartley normalisation of both point sets (computed on the host over ALL points)
+struct Norm {  // Hartley normalisation of both point sets, over ALL points of a problem
   double m1x, m1y, s1, m2x, m2y, s2;
 };
 
+// The normalisation of n >= 1 correspondences (F / E): centroid, and sqrt(2) over the mean distance from it.  The sums are
+// taken sequentially in index order, on the host (gh_ransac_estimate_ex) and on the device (one lane per problem of the
+// batch) alike, as the oracle takes them: a tree reduction would round differently.
+__host__ __device__ inline Norm hartley_norm(const double* src, const double* dst, int n) {
+  Norm nm;
+  double ax = 0, ay = 0, bx = 0, by = 0;
+  for (int i = 0; i < n; ++i) {
+    ax += src[2 * i]; ay += src[2 * i + 1];
+    bx += dst[2 * i]; by += dst[2 * i + 1];
+  }
+  nm.m1x = ax / n; nm.m1y = ay / n; nm.m2x = bx / n; nm.m2y = by / n;
+  double d1 = 0, d2 = 0;
+  for (int i = 0; i < n; ++i) {
+    const double x = src[2 * i] - nm.m1x, y = src[2 * i + 1] - nm.m1y;
+    const double u = dst[2 * i] - nm.m2x, v = dst[2 * i + 1] - nm.m2y;
+    d1 += sqrt(x * x + y * y);
+    d2 += sqrt(u * u + v * v);
+  }
+  d1 /= n; d2 /= n;
+  nm.s1 = d1 > 0 ? 1.4142135623730951 / d1 : 1.0;
+  nm.s2 = d2 > 0 ? 1.4142135623730951 / d2 : 1.0;
+  return nm;
+}
 
 // Hypothesis h of a problem: draws its minimal sample with splitmix64(seed, h) (duplicates rejected; n >= sample_size(model)
 // is the caller's business: the rejection loop does not end otherwise) and solves it into out (model_size(model) doubles).
@@ -651,40 +674,5 @@ __host__ __device__ inline bool pnp_pose_from_model(const double* m, double* pos
   for (int k = 0; k < 7; ++k) pose[k] = ok ? out[k] : 0.0;
   return ok;
 }
-
-// What two_view_kernel works on (two_view.hip).  The batch entry addresses mask / good / points by row; the pair entry
-// (ransac_batch.hip) hands it the compacted rows of its gather with row_map, and then mask / good / points are
-// nproblems x map_stride, addressed by the query row of each compacted row.
-struct TwoViewArgs {
-  const double* E;            // problem p: 9 doubles at p * e_stride
-  int e_stride;
-  const double* src;
-  const double* dst;
-  const int32_t* row_begin;   // per problem: first row ...
-  const int32_t* row_end;     // ... and one past the last
-  const int32_t* limit_dev;   // rows the arrays hold (device word), or NULL: `limit`
-  int limit;
-  int nproblems;
-  const uint8_t* mask;        // rows that take part, or NULL: all
-  const int32_t* row_map;     // pair entry only
-  int map_stride;
-  gh_two_view_params prm;
-  double* poses;
-  double* points;
-  uint8_t* good;
-  int32_t* counts;
-  int32_t* n_used;            // may be NULL
-  int32_t* status;
-};
-bool two_view_params_ok(const gh_two_view_params* prm);
-gh_status two_view_launch(gh_ctx* ctx, const TwoViewArgs& a);
-
-// gh_ransac_batch_dev on a scratch block the caller owns (ransac_batch.hip), for entries that chain the batch with their
-// own kernels on ONE context scratch block: ransac_batch_scratch_bytes(nproblems) bytes at `work`.  Problem p owns rows
-// row_begin[p] .. row_end[p] - 1, clipped against `limit` rows; one threshold and one seed for all.
-size_t ransac_batch_scratch_bytes(int nproblems);
-gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const double* dst, const int32_t* row_begin,
-                              const int32_t* row_end, int limit, int nproblems, double threshold, uint64_t seed,
-                              double* models, uint8_t* mask, int32_t* inliers, void* work);
 
 }  // namespace gh_ransac

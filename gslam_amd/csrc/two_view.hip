@@ -14,7 +14,7 @@
 //   * after the vote a second pass over the rows computes the winner's points again with the same function (the same
 //     bits) and writes point and good for every row, the zeros included.
 // Any n takes this one path.  Row ranges are clamped to the arrays before they address anything.
-#include "ransac_models.h"
+#include "estimate_batch.h"
 
 namespace gh_ransac {
 
@@ -23,10 +23,8 @@ namespace {
 __global__ __launch_bounds__(256) void two_view_kernel(TwoViewArgs a) {
   __shared__ int wave_sum[4][5];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // the rows of the problem: a range that is empty, reversed or not inside the arrays is 0 rows
-  const int limit = a.limit_dev ? *a.limit_dev : a.limit;
-  const int first = a.row_begin[p], end = a.row_end[p];
-  const int n = (first < 0 || end > limit || end <= first) ? 0 : end - first;
+  int first;
+  const int n = problem_rows(a.range, p, &first);
   const double* P = a.src + (size_t)first * 2;   // (not dereferenced when n = 0)
   const double* Q = a.dst + (size_t)first * 2;
   // pair entry: mask / good / points of the problem start at its row of the npairs x map_stride arrays
@@ -151,9 +149,7 @@ extern "C" gh_status gh_two_view_batch_dev(gh_ctx* ctx, const double* E_dev, int
   a.e_stride = e_stride;
   a.src = src_dev;
   a.dst = dst_dev;
-  a.row_begin = offsets_dev;
-  a.row_end = offsets_dev + 1;
-  a.limit_dev = offsets_dev + nproblems;  // the arrays hold offsets[nproblems] rows
+  a.range = {offsets_dev, offsets_dev + 1, offsets_dev + nproblems, INT_MAX};  // the arrays hold offsets[nproblems] rows
   a.nproblems = nproblems;
   a.mask = mask_dev;
   a.prm = *params;

@@ -17,46 +17,35 @@ PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinemen
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
-def estimate_ex(ctx: hip.Context, model, src, dst, threshold, sampling, confidence=1.0, seed=1):
-    """gh_ransac_estimate_ex -> (model, mask, inliers, hypotheses_used)."""
+def _estimate_host(ctx, fn, model, src, dst, scalars, with_used=True):
+    """One host-array call of the gh_ransac_estimate family: fn(ctx, model, src, dst, n, *scalars, model, mask, &inliers
+    [, &hypotheses_used]) -> (model, mask, inliers[, hypotheses_used])."""
     src = np.ascontiguousarray(src, dtype=np.float64)
     dst = np.ascontiguousarray(dst, dtype=np.float64)
     n = src.shape[0]
     m = np.zeros(12)
     mask = np.zeros(max(n, 1), np.uint8)
-    cnt, used = C.c_int(), C.c_int()
+    outs = [C.c_int() for _ in range(2 if with_used else 1)]
     pv = lambda a: a.ctypes.data_as(C.c_void_p)
-    ctx.check(hip.lib.gh_ransac_estimate_ex(ctx.h, int(model), pv(src), pv(dst), n, C.c_double(threshold), C.c_double(confidence),
-                                            C.c_uint64(seed), int(sampling), pv(m), pv(mask), C.byref(cnt), C.byref(used)))
-    return m, mask[:n].copy(), cnt.value, used.value
+    ctx.check(fn(ctx.h, int(model), pv(src), pv(dst), n, *scalars, pv(m), pv(mask), *(C.byref(o) for o in outs)))
+    return (m, mask[:n].copy()) + tuple(o.value for o in outs)
+
+
+def estimate_ex(ctx: hip.Context, model, src, dst, threshold, sampling, confidence=1.0, seed=1):
+    """gh_ransac_estimate_ex -> (model, mask, inliers, hypotheses_used)."""
+    return _estimate_host(ctx, hip.lib.gh_ransac_estimate_ex, model, src, dst,
+                          (C.c_double(threshold), C.c_double(confidence), C.c_uint64(seed), int(sampling)))
 
 
 def estimate_conf(ctx: hip.Context, model, src, dst, threshold, confidence, seed=1):
     """gh_ransac_estimate_conf -> (model, mask, inliers, hypotheses_used)."""
-    src = np.ascontiguousarray(src, dtype=np.float64)
-    dst = np.ascontiguousarray(dst, dtype=np.float64)
-    n = src.shape[0]
-    m = np.zeros(12)
-    mask = np.zeros(max(n, 1), np.uint8)
-    cnt, used = C.c_int(), C.c_int()
-    pv = lambda a: a.ctypes.data_as(C.c_void_p)
-    ctx.check(hip.lib.gh_ransac_estimate_conf(ctx.h, int(model), pv(src), pv(dst), n, C.c_double(threshold),
-                                              C.c_double(confidence), C.c_uint64(seed), pv(m), pv(mask), C.byref(cnt),
-                                              C.byref(used)))
-    return m, mask[:n].copy(), cnt.value, used.value
+    return _estimate_host(ctx, hip.lib.gh_ransac_estimate_conf, model, src, dst,
+                          (C.c_double(threshold), C.c_double(confidence), C.c_uint64(seed)))
 
 
 def estimate(ctx: hip.Context, model, src, dst, threshold, seed=1):
-    src = np.ascontiguousarray(src, dtype=np.float64)
-    dst = np.ascontiguousarray(dst, dtype=np.float64)
-    n = src.shape[0]
-    m = np.zeros(12)
-    mask = np.zeros(max(n, 1), np.uint8)
-    cnt = C.c_int()
-    pv = lambda a: a.ctypes.data_as(C.c_void_p)
-    ctx.check(hip.lib.gh_ransac_estimate(ctx.h, int(model), pv(src), pv(dst), n, C.c_double(threshold), C.c_uint64(seed),
-                                         pv(m), pv(mask), C.byref(cnt)))
-    return m, mask[:n].copy(), cnt.value
+    return _estimate_host(ctx, hip.lib.gh_ransac_estimate, model, src, dst, (C.c_double(threshold), C.c_uint64(seed)),
+                          with_used=False)
 
 
 def _p(t):
@@ -88,24 +77,31 @@ def estimate_batch(ctx: hip.Context, model, src, dst, offsets, threshold, seed, 
     return models, mask, inliers
 
 
-def estimate_pairs(ctx: hip.Context, model, kps, counts, pair_q, pair_t, idx1, keep, threshold, seed):
-    """gh_ransac_pairs_dev, the call after BFMatcher.match_pairs / mask.  kps: F x cap x 7 float32 view of the KeyPoint
-    records, counts: F int32, pair_q / pair_t: P int32, idx1: P x cap int32, keep: P x cap uint8 or None (all cuda).
-    model: HOMOGRAPHY, AFFINE2D or FUNDAMENTAL.  -> (models P x 12, inlier P x cap uint8, n_corr P int32, inliers P int32)
-    on the device; pair p equals estimate() on the rows correspondences_from_matches lists for it."""
+def _pair_io(kps, counts, pair_q, pair_t, idx1, keep):
+    """The inputs of the pair entries, checked, and the output tensors both have, in the order of the C arguments
+    -> (P, cap, out)."""
     import torch
     assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
     assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
     P, cap = pair_q.shape[0], kps.shape[1]
     assert pair_t.shape[0] == P and idx1.numel() == P * cap
     assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
-    models = torch.empty((P, 12), dtype=torch.float64, device=kps.device)
-    inlier = torch.empty((P, cap), dtype=torch.uint8, device=kps.device)
-    n_corr = torch.empty(P, dtype=torch.int32, device=kps.device)
-    inliers = torch.empty(P, dtype=torch.int32, device=kps.device)
+    out = {"models": torch.empty((P, 12), dtype=torch.float64, device=kps.device),
+           "inlier": torch.empty((P, cap), dtype=torch.uint8, device=kps.device),
+           "n_corr": torch.empty(P, dtype=torch.int32, device=kps.device),
+           "inliers": torch.empty(P, dtype=torch.int32, device=kps.device)}
+    return P, cap, out
+
+
+def estimate_pairs(ctx: hip.Context, model, kps, counts, pair_q, pair_t, idx1, keep, threshold, seed):
+    """gh_ransac_pairs_dev, the call after BFMatcher.match_pairs / mask.  kps: F x cap x 7 float32 view of the KeyPoint
+    records, counts: F int32, pair_q / pair_t: P int32, idx1: P x cap int32, keep: P x cap uint8 or None (all cuda).
+    model: HOMOGRAPHY, AFFINE2D or FUNDAMENTAL.  -> (models P x 12, inlier P x cap uint8, n_corr P int32, inliers P int32)
+    on the device; pair p equals estimate() on the rows correspondences_from_matches lists for it."""
+    P, cap, out = _pair_io(kps, counts, pair_q, pair_t, idx1, keep)
     ctx.check(hip.lib.gh_ransac_pairs_dev(ctx.h, int(model), _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
-                                          C.c_double(threshold), C.c_uint64(seed), _p(models), _p(inlier), _p(n_corr), _p(inliers)))
-    return models, inlier, n_corr, inliers
+                                          C.c_double(threshold), C.c_uint64(seed), *(_p(out[k]) for k in out)))
+    return tuple(out.values())
 
 
 def correspondences_from_matches(kps, counts, pair_q, pair_t, idx1, keep=None):
@@ -175,23 +171,15 @@ def two_view_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, in
     good P x cap uint8, votes P x 4 (the four candidate counts), status P.  Pair p equals estimate_batch(ESSENTIAL) and
     two_view_batch on the normalised rows correspondences_from_matches lists for it, scattered back to query rows."""
     import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
-    P, cap = pair_q.shape[0], kps.shape[1]
-    assert pair_t.shape[0] == P and idx1.numel() == P * cap
-    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
+    P, cap, out = _pair_io(kps, counts, pair_q, pair_t, idx1, keep)
     fx, fy, cx, cy = (float(v) for v in intrinsics)
     prm = params if params is not None else two_view_default_params()
     dev = kps.device
-    out = {"models": torch.empty((P, 12), dtype=torch.float64, device=dev),
-           "inlier": torch.empty((P, cap), dtype=torch.uint8, device=dev),
-           "n_corr": torch.empty(P, dtype=torch.int32, device=dev),
-           "inliers": torch.empty(P, dtype=torch.int32, device=dev),
-           "poses": torch.empty((P, 7), dtype=torch.float64, device=dev),
-           "points": torch.empty((P, cap, 3), dtype=torch.float64, device=dev),
-           "good": torch.empty((P, cap), dtype=torch.uint8, device=dev),
-           "votes": torch.empty((P, 4), dtype=torch.int32, device=dev),
-           "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    out.update({"poses": torch.empty((P, 7), dtype=torch.float64, device=dev),
+                "points": torch.empty((P, cap, 3), dtype=torch.float64, device=dev),
+                "good": torch.empty((P, cap), dtype=torch.uint8, device=dev),
+                "votes": torch.empty((P, 4), dtype=torch.int32, device=dev),
+                "status": torch.empty(P, dtype=torch.int32, device=dev)})
     ctx.check(hip.lib.gh_two_view_pairs_dev(ctx.h, _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
                                             C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(threshold),
                                             C.c_uint64(seed), C.byref(prm), *(_p(out[k]) for k in out)))
@@ -219,6 +207,29 @@ def _ba_options(options):
     return o
 
 
+def _pnp_io(xyz, xy, offsets, want_information, chain=False):
+    """The inputs both PnP batch entries share, checked, and their output tensors in the order of the C arguments (chain: with
+    the fit's outputs in front and a summary per round) -> (nproblems, rows, out)."""
+    import torch
+    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
+    rows = xyz.shape[0]
+    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    n = offsets.numel() - 1
+    dev = xyz.device
+    out = {}
+    if chain:
+        out["models"] = torch.empty((n, 12), dtype=torch.float64, device=dev)
+        out["ransac_inliers"] = torch.empty(n, dtype=torch.int32, device=dev)
+    size = C.sizeof(hip.PnpBatchSummary)
+    out.update({"poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
+                "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
+                "summaries": torch.empty((n, 2, size) if chain else (n, size), dtype=torch.uint8, device=dev),
+                "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),  # (rows no range owns belong to nobody)
+                "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)})
+    return n, rows, out
+
+
 def pnp_refine_batch(ctx: hip.Context, xyz, xy, offsets, start, mask=None, dof=63, options=None, min_rows=0,
                      inlier_threshold=-1.0, want_information=False):
     """gh_pnp_refine_batch_dev.  xyz: rows x 3, xy: rows x 2 float64 (cuda); offsets: nproblems + 1 int32; start: nproblems x 7
@@ -227,20 +238,10 @@ def pnp_refine_batch(ctx: hip.Context, xyz, xy, offsets, start, mask=None, dof=6
     None, summaries nproblems x 32 uint8 (view the host copy as SUMMARY_DTYPE), inlier rows uint8, n_inliers nproblems int32;
     nothing is synchronised.  A problem that is optimised equals ba.pnp on its participating rows, bit for bit."""
     import torch
-    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
-    rows = xyz.shape[0]
-    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
-    n = offsets.numel() - 1
+    n, rows, out = _pnp_io(xyz, xy, offsets, want_information)
     assert start.is_cuda and start.dtype == torch.float64 and start.is_contiguous() and start.dim() == 2 and start.shape[0] == n
     assert start.shape[1] in (7, 12)
     assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == rows)
-    dev = xyz.device
-    out = {"poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
-           "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
-           "summaries": torch.empty((n, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
-           "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),  # (rows no range owns belong to nobody)
-           "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)}
     opt = _ba_options(options)
     ctx.check(hip.lib.gh_pnp_refine_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, _p(mask), _p(start), int(start.shape[1]),
                                               int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
@@ -254,20 +255,7 @@ def pnp_batch(ctx: hip.Context, xyz, xy, offsets, ransac_threshold, seed, inlier
     pnp_refine_batch again on the rows within inlier_threshold from the first round's poses.  -> dict of device tensors:
     models nproblems x 12, ransac_inliers nproblems, poses nproblems x 7, info nproblems x 36 or None, summaries
     nproblems x 2 x 32 uint8 (round 1, round 2), inlier rows uint8, n_inliers nproblems; nothing is synchronised."""
-    import torch
-    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
-    rows = xyz.shape[0]
-    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
-    n = offsets.numel() - 1
-    dev = xyz.device
-    out = {"models": torch.empty((n, 12), dtype=torch.float64, device=dev),
-           "ransac_inliers": torch.empty(n, dtype=torch.int32, device=dev),
-           "poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
-           "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
-           "summaries": torch.empty((n, 2, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
-           "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),
-           "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)}
+    n, rows, out = _pnp_io(xyz, xy, offsets, want_information, chain=True)
     opt = _ba_options(options)
     ctx.check(hip.lib.gh_pnp_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, C.c_double(ransac_threshold), C.c_uint64(seed),
                                        int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
