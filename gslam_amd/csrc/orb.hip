@@ -48,7 +48,7 @@ enum {
   kDbgSelStreamed,       // select launches of the streaming (non-cached) variant
   kDbgUnusedSlots,       // zero-filled output rows
   kDbgStarvedLevels,     // (level, frame) selections with fewer candidates than quota
-  kDbgWeakCells,         // cells with candidates but no corner above the initial threshold (two-phase: counted by phase B in orb_select)
+  kDbgWeakCells,         // cells with candidates but no corner above the initial threshold (two-phase: counted by phase B in orb_select, so not where it is skipped)
   kDbgResizePasses,      // wave-level passes through the fused resize body (one per wave with at least one item, per item block)
   kDbgCount = 16
 };
@@ -485,7 +485,9 @@ __device__ __forceinline__ const uint4* fast_tile_src(const LevelView& lv, int f
   return reinterpret_cast<const uint4*>(lv.base + (size_t)frame * lv.frame_stride + (__umul24((uint32_t)gy, (uint32_t)lv.pitch) + (uint32_t)gx));
 }
 
-// rec[0] of a cell that phase A of the two-phase detector leaves to phase B (orb_select): outside every valid count
+// rec[0] of a cell that phase A of the two-phase detector leaves to phase B (orb_select): outside every valid count.  A marked
+// record may survive orb_select: where the strong cells of a (level, frame) alone fill its quota, phase B is skipped
+// (select_weak_cells) and every reader takes the mark for an empty cell (cell_entries).
 constexpr uint32_t kWeakCell = 0xFFFFFFFFu;
 
 // The cell stage (oracle steps 3, 4), by one wave: compaction of the cell's scored pixels, 3 x 3 strict NMS, the strong-corner
@@ -941,13 +943,17 @@ __device__ __forceinline__ void for_each_overflow(const uint32_t* __restrict__ o
   }
 }
 
+// Entries of a cell whose record starts with `count`: a count outside 0 .. kCap -- kWeakCell, which a (level, frame) that
+// skipped phase B leaves in place (select_weak_cells) -- means no entries.
+__device__ __forceinline__ int cell_entries(uint32_t count) { return count <= (uint32_t)kCap ? (int)count : 0; }
+
 // Visit the entries of one cell.  rec = the cell's 32-byte record {count, entries 0..6} (two 16-byte loads issued
 // together: one memory round trip for the common case), ovf = its 128-byte slot holding entries 7.. at their index.
 template <typename F>
 __device__ __forceinline__ int for_each_entry(const uint32_t* __restrict__ rec, const uint32_t* __restrict__ ovf, F f) {
   const uint4 a = reinterpret_cast<const uint4*>(rec)[0];
   const uint4 b = reinterpret_cast<const uint4*>(rec)[1];
-  const int n = (int)a.x;
+  const int n = cell_entries(a.x);
   const uint32_t first[kCellRec - 1] = {a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
   for (int e = 0; e < kCellRec - 1; ++e)
@@ -959,13 +965,25 @@ __device__ __forceinline__ int for_each_entry(const uint32_t* __restrict__ rec, 
 // The same on a record that is already in registers
 template <typename F>
 __device__ __forceinline__ int for_each_entry_reg(const uint4& a, const uint4& b, const uint32_t* __restrict__ ovf, F f) {
-  const int n = (int)a.x;
+  const int n = cell_entries(a.x);
   const uint32_t first[kCellRec - 1] = {a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
   for (int e = 0; e < kCellRec - 1; ++e)
     if (e < n) f(first[e]);
   for_each_overflow(ovf, n, f);
   return n;
+}
+
+// Sum of one int per lane over the wave, returned in every lane: four DPP adds give each 16-lane row its row sum
+// (quad_perm xor 1, xor 2, row_half_mirror, row_mirror), the four row sums meet through v_readlane / SALU adds.
+// (A __shfl_xor butterfly is 6 x 2 ds_bpermute plus the index arithmetic.)
+__device__ __forceinline__ int wave_sum_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);  // row_half_mirror
+  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);  // row_mirror
+  return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+         __builtin_amdgcn_readlane(v, 48);
 }
 
 struct SelectArgs {
@@ -1063,19 +1081,50 @@ __device__ __forceinline__ void select_weak_cell(const LevelView& lv, int b, int
 // Phase B at the head of orb_select: the workgroup gathers the cells of its (level, frame) that phase A marked into an LDS list
 // (one LDS counter; kWeakRound cells per round), its four waves take them in a stride, one wave per cell, and a barrier makes the
 // rewritten records visible to the passes that follow.  lds = at least 4 kWeakWaveBytes + 2 kWeakRound + 16 bytes, 16-byte aligned.
-__device__ __forceinline__ void select_weak_cells(const SelectWeak& w, int l, int b, int ncells, int ncx, uint32_t* rec, uint32_t* ent,
-                                                  uint8_t* lds, uint32_t* dbg) {
+//
+// None of it runs where the result cannot see it.  The level's output is the first `quota` entries under (rank asc, S desc,
+// cell asc, raster asc) (oracle step 5).  Every rank-0 entry comes before every entry of rank >= 1, and among the rank-0
+// entries those with S > ini_th come before the others.  A cell has a rank-0 entry with S > ini_th exactly when it is STRONG --
+// it holds a strict 3 x 3 maximum above ini_th -- while a marked cell is empty or holds entries with S <= ini_th only.  So with
+// strong >= quota the first `quota` entries are rank-0 entries of strong cells: the cut-off bin is (rank 0, s*) with
+// s* > ini_th, its ties are split by cell index among strong cells, and no record of a marked cell reaches one output byte.
+// Then phase B is skipped and the marks stay (cell_entries reads them as empty cells).  With strong < quota every marked
+// cell is redone, as before: how many of them the quota needs depends on the order of their scores.
+// The workgroup counts its strong cells over ALL cells of the level before the first round: in the gathering loop where one
+// round covers the level, in a pass of its own in front of the rounds otherwise.  A strong cell's count is 1 .. kCap and its
+// first entry scores above ini_th; a cell with any entry above ini_th holds only such entries (oracle step 4), so the first
+// one decides.  The score test is needed: the cells of a tile that the flat-tile shortcut of orb_fast_cells finished single-phase
+// carry ordinary counts and scores <= ini_th.
+template <bool ONE_ROUND>
+__device__ __forceinline__ void select_weak_cells(const SelectWeak& w, int l, int b, int ncells, int ncx, int quota, uint32_t* rec,
+                                                  uint32_t* ent, uint8_t* lds, int* wave_tot, uint32_t* dbg) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   uint16_t* marked = reinterpret_cast<uint16_t*>(lds + 4 * kWeakWaveBytes);
   int* n_marked = reinterpret_cast<int*>(lds + 4 * kWeakWaveBytes + 2 * kWeakRound);
   const LevelView lv = w.lv[l];
+  const bool one_round = ONE_ROUND || ncells <= kWeakRound;
+  // {count, first entry} of a cell -> 1 if the cell is strong
+  auto strong_cell = [&](uint2 r) { return r.x - 1u < (uint32_t)kCap && (int)((r.y >> 10) & 255u) > w.ini_th ? 1 : 0; };
+  int strong = 0;
+  if (!one_round)
+    for (int c = tid; c < ncells; c += 256) strong += strong_cell(*reinterpret_cast<const uint2*>(rec + (size_t)c * kCellRec));
   for (int c0 = 0; c0 < ncells; c0 += kWeakRound) {
     if (tid == 0) *n_marked = 0;
     __syncthreads();
     const int c1 = min(ncells, c0 + kWeakRound);
-    for (int c = c0 + tid; c < c1; c += 256)
-      if (rec[(size_t)c * kCellRec] == kWeakCell) marked[atomicAdd(n_marked, 1)] = (uint16_t)(c - c0);
+    for (int c = c0 + tid; c < c1; c += 256) {
+      const uint2 r = *reinterpret_cast<const uint2*>(rec + (size_t)c * kCellRec);
+      if (r.x == kWeakCell) marked[atomicAdd(n_marked, 1)] = (uint16_t)(c - c0);
+      if (one_round) strong += strong_cell(r);
+    }
+    if (c0 == 0) {  // (the count covers the whole level here in either case)
+      strong = wave_sum_i32(strong);
+      if (lane == 0) wave_tot[wv] = strong;
+    }
     __syncthreads();
+    // workgroup-uniform, and nothing of phase B has touched a record yet.  (wave_tot lies outside lds: the caller may clear the
+    // histogram at once; its next writer, block_excl_scan, comes after two more barriers.)
+    if (c0 == 0 && wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3] >= quota) return;
     const int n = *n_marked;
     for (int i = wv; i < n; i += 4) {
       const int c = c0 + marked[i];
@@ -1108,11 +1157,12 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cel
     if (tid == 0) level_cnt[b * kMaxL + l] = 0;
     return;
   }
-  // phase B of the two-phase detector first: its patches and queues alias hist[], which is cleared only after it
+  // phase B of the two-phase detector first (or the count that shows it is not needed): its patches and queues alias hist[], which is
+  // cleared only after it
   static_assert(sizeof(hist) >= 4 * kWeakWaveBytes + 2 * kWeakRound + 16, "phase B fits the histogram");
   if (weak.two_phase != 0)
-    select_weak_cells(weak, l, b, ncells, a.ncx[l], cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec,
-                      cell_ent + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCap, reinterpret_cast<uint8_t*>(hist), dbg);
+    select_weak_cells<CACHED>(weak, l, b, ncells, a.ncx[l], quota, cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec,
+                              cell_ent + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCap, reinterpret_cast<uint8_t*>(hist), wave_tot, dbg);
   uint4 ra[kSelCached], rb[kSelCached];
   if (CACHED) {
 #pragma unroll
@@ -1247,18 +1297,6 @@ struct DescribeArgs {
   // workgroups per frame; a workgroup = 4 kDescPipe slots of ONE level's quota)
   int blk_off[kMaxL + 1];
 };
-
-// Sum of one int per lane over the wave, returned in every lane: four DPP adds give each 16-lane row its row sum
-// (quad_perm xor 1, xor 2, row_half_mirror, row_mirror), the four row sums meet through v_readlane / SALU adds.
-// (A __shfl_xor butterfly is 6 x 2 ds_bpermute plus the index arithmetic.)
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);  // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);  // row_mirror
-  return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-         __builtin_amdgcn_readlane(v, 48);
-}
 
 // Patch geometry of orb_describe for a test pattern of radius BR (blurred region = (2 BR + 1)^2, raw patch 3 px wider for
 // the 7x7 Gaussian): BR = 13 is the 30-bin table mode (33 x 33 patch: also covers the radius-15 centroid disc), BR = 19 the
