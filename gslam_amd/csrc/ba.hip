@@ -24,35 +24,11 @@
 #include <thread>
 
 #include "ba_obs.h"
-#include "common.h"
 #include "cr_map.h"
+#include "dense_solve.h"
 #include "host_pool.h"
 #include "lm_rule.h"
 #include "pnp_lm.h"
-
-gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_dev, int extra_rows, double* dinv,
-                            double* xwork, unsigned* flow_state, bool store_diag, bool state_ready);
-size_t gh_potrf_flow_words(const gh_ctx* ctx, int n, int extra_rows);
-size_t gh_potrf_flow_flag_words(int n, int extra_rows);
-std::mutex& gh_potrf_flow_mutex(int device);
-// chol_cr.hip: band solver (block cyclic reduction)
-int gh_cr_tiles(int n, int hbw);
-size_t gh_cr_dinv_doubles(int n, int T);
-size_t gh_cr_panel_doubles(int n, int T);
-gh_status gh_cr_solve_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int T, double* dinv, double* W, double* x_dev,
-                               int* info_dev, bool info_ready);
-size_t gh_arrow_ws_doubles(const gh_ctx* ctx, int n_band, int T, int nbr);
-int gh_cr_compact_lda(int n_band, int T, int nbr, int* brow);
-gh_status gh_arrow_solve_dev_impl(gh_ctx* ctx, double* A, int n_band, int nbr, int lda, int T, double* dinv, double* W, double* bws,
-                                  double* x_dev, int* info_dev, bool info_ready, bool allow_flow, const uint8_t* border_nz, bool compact);
-int gh_ba_order_cameras(const gh_ba_problem* pr, std::vector<int32_t>& perm, int* reordered, bool allow_reorder, int* band_span,
-                        std::vector<int32_t>* border_points);  // ba_order.hip
-size_t gh_cr_border_symbolic_bytes(int n_band, int T, int nbr);
-void gh_cr_border_symbolic(int n_band, int T, int nbr, const uint8_t* init, uint8_t* out);
-gh_status gh_csr_build_dev(gh_ctx* ctx, const int32_t* keys_host, int n_items, int n_keys, int32_t* start_host, int32_t* list_host);
-gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, double* b, double* work,
-                                const double* dinv, const double* yv, long long ystride, double* xh, int* info_dev,
-                                bool xh_ready);
 
 namespace {
 
@@ -869,23 +845,13 @@ __global__ __launch_bounds__(256) void pair_segments_kernel(int nblocks, const i
 // 64 threads per block: thread t < 42 adds element t of the block's segment totals in segment order, then
 // S[block] -= total (this thread is the element's only writer), rhs += total for the diagonal blocks
 // (the right-hand side is also kept as row `rhs_row` of S, where the factorisation picks it up)
-// what the two single-launch kernels behind the Schur product need cleared / filled before they start: done by the tail
-// workgroups of schur_reduce_kernel instead of three memset nodes in the stream
-struct SolveState {
-  unsigned* flow_flags;  // zero
-  unsigned n_flow;
-  unsigned* xh_words;    // the sentinel of bwd_chain_kernel in every 32-bit word
-  unsigned n_xh;
-  int* info;             // zero
-};
+// the tail workgroups run the ready protocol of the dense solve behind the Schur product (dense_solve.h)
 __global__ __launch_bounds__(256) void schur_reduce_kernel(SchurBlocks B, const double* __restrict__ partial,
                                                            double* __restrict__ S, int n, double* __restrict__ rhs,
-                                                           int rhs_row, int n_reduce_blocks, SolveState st, CrMap map) {
+                                                           int rhs_row, int n_reduce_blocks, DenseReady st, CrMap map) {
   if ((int)blockIdx.x >= n_reduce_blocks) {
     const unsigned i = ((unsigned)blockIdx.x - (unsigned)n_reduce_blocks) * 256u + threadIdx.x;
-    if (i < st.n_flow) st.flow_flags[i] = 0u;
-    if (i < st.n_xh) st.xh_words[i] = 0xFFF8BEEFu;
-    if (i == 0 && st.info) *st.info = 0;
+    dense_ready_word(st, i);
     return;
   }
   const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), t = threadIdx.x & 63;
@@ -1489,13 +1455,14 @@ struct BaSession {
   int nchunks = 0, nsegs = 0, nblocks = 0;
   bool device_pairs = false;
   double *d_Hcc = nullptr, *d_gc = nullptr, *d_Hpi = nullptr, *d_S = nullptr, *d_dc = nullptr, *d_dp = nullptr, *d_partial = nullptr,
-         *d_out = nullptr, *d_work = nullptr, *d_dinv = nullptr, *d_spart = nullptr, *d_xwork = nullptr;
+         *d_out = nullptr, *d_spart = nullptr;
   LinSet lin[2];  // [0]: the linearisation of the current state; [1]: the speculative one (swapped in when its step is accepted)
   unsigned long long* d_keep = nullptr;  // {gradient maximum, damping flag} of the iteration, saved by backsub_update before it clears them
   unsigned long long* d_gmax = nullptr;
-  int *d_bad = nullptr, *d_info = nullptr;
-  unsigned* d_flow = nullptr;  // state of the single-launch factorisation (null when the shape does not fit it, or after a time-out: ba_run)
-  double* d_xh = nullptr;      // ... and of the single-launch back-substitution
+  int* d_bad = nullptr;
+  // workspace of the dense solve of n() unknowns + the right-hand-side row; its info word is the solve's, whichever solver runs.
+  // flow_state: null when the shape does not fit the single-launch factorisation, or after a time-out (ba_run); xh likewise
+  DenseWork dense{};
   size_t n_pairs = 0;
   // band solver (chol_cr.hip): tiles per superblock (0 = the dense factorisation), its inverted diagonal tiles and panels
   int cr_T = 0, cam_span = 0;
@@ -1624,12 +1591,13 @@ size_t ba_arena_need(const gh_ctx* ctx, const BaSession& S, const BaSwitches& sw
                  gh_arrow_ws_doubles(ctx, n_band, T_plan, n - n_band) + gh_cr_border_symbolic_bytes(n_band, T_plan, n - n_band) / 8 + 4 * 64;
   }
   return
-      // ba_raw_arrays: d_poses + d_poses_new, d_pts + d_pts_new, d_oxy, d_oinfo;  ba_alloc_work: d_Hcc; d_gc, d_dc, d_work; Hpp and d_Hpi;
-      // gp and d_dp; S with its workspaces; d_dinv, d_xwork and d_xh; W; d_partial; d_out, d_keep, d_gmax (the second LinSet and d_flow
-      // have no term: they live on the slack of the upper bounds and the eighth DevBuf::reserve adds)
-      8 * (2 * NC * 7 + 2 * NP * 3 + NO * 2 + (S.has_info ? NO * 4 : 0) + NC * 36 + N * 3 + NP * 9 * 2 + NP * 3 * 2 + s_doubles +
-           (N + 64) * 64 * 3 + NO * 18 + (NO / 256 + 2) * 2 + 8) +
-      // d_dof, d_ocam, d_opt;  ba_upload_tables: d_plist, d_clist, d_pstart, d_cstart; d_bad, d_info; the host-built pair_a / pair_b and
+      // ba_raw_arrays: d_poses + d_poses_new, d_pts + d_pts_new, d_oxy, d_oinfo;  ba_alloc_work: d_Hcc; d_gc, d_dc; Hpp and d_Hpi;
+      // gp and d_dp; S with its workspaces; W; d_partial; d_out, d_keep, d_gmax (the second LinSet has no term: it lives on the
+      // slack of the upper bounds and the eighth DevBuf::reserve adds); the workspace of the dense solve
+      8 * (2 * NC * 7 + 2 * NP * 3 + NO * 2 + (S.has_info ? NO * 4 : 0) + NC * 36 + N * 2 + NP * 9 * 2 + NP * 3 * 2 + s_doubles +
+           NO * 18 + (NO / 256 + 2) * 2 + 8) +
+      dense_layout(n, 1, ctx->cu_count).bytes +
+      // d_dof, d_ocam, d_opt;  ba_upload_tables: d_plist, d_clist, d_pstart, d_cstart; d_bad; the host-built pair_a / pair_b and
       // bstart / bci / bcj;  d_pfree;  the 256-byte rounding of 64 allocations
       4 * (NC + NO * 4 + NP + NC + 4 + host_pairs * 2 + host_blocks * 3) + NP + 64 * 256 +
       // ba_upload_tables, point border: d_pbslot, d_bpts
@@ -1831,12 +1799,11 @@ gh_status ba_alloc_work(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, con
   GH_TRY(db.alloc(&S.d_Hpi, (size_t)np * 9));
   GH_TRY(db.alloc(&S.d_dc, (size_t)n));
   GH_TRY(db.alloc(&S.d_dp, (size_t)np * 3));
-  GH_TRY(db.alloc(&S.d_work, (size_t)n));
-  GH_TRY(db.alloc(&S.d_dinv, (size_t)gh_div_up(n, 64) * 4096));
+  const DenseLayout dl = dense_layout(n, 1, ctx->cu_count);
+  char* dense_base = nullptr;
+  GH_TRY(db.alloc(&dense_base, dl.bytes));
+  S.dense = dense_carve(dense_base, dl);
   GH_TRY(db.alloc(&S.lin[0].W, (size_t)no * 18));
-  GH_TRY(db.alloc(&S.d_xwork, (size_t)2 * 64 * (n + 1)));
-  GH_TRY(db.alloc(&S.d_xh, (size_t)gh_div_up(n, 64) * 64));
-  if (const size_t words = gh_potrf_flow_words(ctx, n, 1)) GH_TRY(db.alloc(&S.d_flow, words));
   S.cr_T = sw.band_tiles(n_band, S.cam_span);
   if (S.n_bpts() > 0 && S.cr_T == 0)  // (ba_order.hip only proposes a point border to the band solver: the dense assembly has camera columns only)
     return gh_set_error(ctx, GH_ERR_ARG, "gh_ba_solve: a point border without the band solver (internal)");
@@ -1896,7 +1863,6 @@ gh_status ba_alloc_work(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, con
   GH_TRY(db.alloc(&S.d_out, 4));
   GH_TRY(db.alloc(&S.d_gmax, 1));
   GH_TRY(db.alloc(&S.d_bad, 1));
-  GH_TRY(db.alloc(&S.d_info, 1));
   return GH_OK;
 }
 
@@ -2056,7 +2022,7 @@ gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, L
   }
   L.PB.Hpp = lin.Hpp;  // (the linearisation's buffer sets swap when a speculative linearisation is adopted)
   L.PB.gp = lin.gp;
-  const bool slim_init = S.d_flow != nullptr || cr_T != 0;  // both solvers read the lower tiles only
+  const bool slim_init = S.dense.flow_state != nullptr || cr_T != 0;  // both solvers read the lower tiles only
   const bool fused_seed = slim_init && no > 0 && opt.deterministic;  // then the seed rides with the segment sums below
   const int gx = cr_T ? 1 : gh_div_up(n + 1, 2048);  // workgroups per column of the seed (the band solver's: one)
   bool solve_state_ready = false;  // set when schur_reduce_kernel has cleared what the single-launch solve kernels need
@@ -2083,17 +2049,8 @@ gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, L
                   (const double*)lin.W, S.d_spart);
       }
       const int nred = gh_div_up(S.nblocks, 4);
-      SolveState st{nullptr, 0u, nullptr, 0u, S.d_info};
-      if (S.d_flow) {
-        st.flow_flags = S.d_flow;
-        st.n_flow = (unsigned)gh_potrf_flow_flag_words(n, 1);
-      }
-      if (S.d_xh) {
-        st.xh_words = reinterpret_cast<unsigned*>(S.d_xh);
-        st.n_xh = (unsigned)gh_div_up(n, 64) * 64u * 2u;
-      }
-      const unsigned words = st.n_flow > st.n_xh ? st.n_flow : st.n_xh;
-      GH_LAUNCH(ctx, "ba_schur_reduce", schur_reduce_kernel, dim3(nred + gh_div_up((int)(words ? words : 1u), 256)),
+      const DenseReady st = dense_ready(S.dense);
+      GH_LAUNCH(ctx, "ba_schur_reduce", schur_reduce_kernel, dim3(nred + gh_div_up((int)(st.words() ? st.words() : 1u), 256)),
                 dim3(256), 0, S.SB, (const double*)S.d_spart, S.d_S, lda, S.d_dc, n, nred, st, S.map);
       solve_state_ready = true;
     } else {
@@ -2105,7 +2062,7 @@ gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, L
     GH_LAUNCH(ctx, "ba_border_points", border_points_kernel, dim3(n_bpts), dim3(64), 0, L.P, L.PB, (const double*)lin.W, S.d_S, lda,
               n_band, S.map);
   step.t_solve0 = now_ms();
-  if (S.d_flow || cr_T)  // (band / arrowhead: the dense top may run as the single-launch factorisation)
+  if (S.dense.flow_state || cr_T)  // (band / arrowhead: the dense top may run as the single-launch factorisation)
     step.flow_lock = std::unique_lock<std::mutex>(gh_potrf_flow_mutex(ctx->device));
   // The whole candidate step is enqueued without waiting for the factorisation flags (the kernels have no
   // data-dependent control flow, so a failed factorisation only produces numbers that are then ignored): one host
@@ -2114,15 +2071,15 @@ gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, L
   if (!(slim_init && opt.deterministic))
     GH_LAUNCH(ctx, "ba_rhs_row", rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, S.d_dc, S.d_S, lda, n, S.map);
   if (cr_T) {  // (n_band == n: a band without a border)
-    GH_TRY(gh_arrow_solve_dev_impl(ctx, S.d_S, n_band, n - n_band, lda, cr_T, S.d_cr_dinv, S.d_cr_W, S.d_arrow_ws, S.d_dc, S.d_info,
+    GH_TRY(gh_arrow_solve_dev_impl(ctx, S.d_S, n_band, n - n_band, lda, cr_T, S.d_cr_dinv, S.d_cr_W, S.d_arrow_ws, S.d_dc, S.dense.info,
                                    solve_state_ready, L.cr_flow_ok, S.d_border_nz, S.map.m != 0));
   } else {
-    GH_TRY(gh_potrf_dev_impl(ctx, S.d_S, n, lda, S.d_info, 1, S.d_dinv, S.d_xwork, S.d_flow, false, solve_state_ready));
+    GH_TRY(gh_potrf_dev_impl(ctx, S.d_S, n, lda, 1, S.dense, false, solve_state_ready));
     // y = L^-1 b is row n of the factored matrix; the back-substitution reads it in place
-    GH_TRY(gh_potrs_bwd_dev_impl(ctx, S.d_S, n, lda, S.d_dc, S.d_work, S.d_dinv, S.d_S + n, lda, S.d_xh, S.d_info, solve_state_ready));
+    GH_TRY(gh_potrs_bwd_dev_impl(ctx, S.d_S, n, lda, S.dense, S.d_dc, S.d_S + n, lda, solve_state_ready));
   }
   if (!step.publish) {
-    GH_HIP(ctx, hipMemcpyAsync(&L.rb->info, S.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GH_HIP(ctx, hipMemcpyAsync(&L.rb->info, S.dense.info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GH_HIP(ctx, hipMemcpyAsync(&L.rb->bad, S.d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   }
   GH_LAUNCH(ctx, "ba_backsub", backsub_update_kernel, dim3(gh_div_up(nc > np ? nc : np, 256)), dim3(256), 0, L.P, S.d_Hpi, lin.gp,
@@ -2133,7 +2090,7 @@ gh_status ba_enqueue_step(gh_ctx* ctx, BaSession& S, const gh_ba_options& opt, L
     GH_LAUNCH(ctx, "ba_eval", eval_kernel, dim3(L.eval_blocks), dim3(256), 0, L.P, (const double*)S.d_poses_new,
               (const double*)S.d_pts_new, S.d_dc, S.d_dp, 1, S.d_partial);
     GH_LAUNCH(ctx, "ba_reduce", reduce_publish_kernel, dim3(1), dim3(256), 0, (const double*)S.d_partial, L.eval_blocks,
-              (const unsigned long long*)S.d_keep, (const int*)S.d_info, L.rb, want);
+              (const unsigned long long*)S.d_keep, (const int*)S.dense.info, L.rb, want);
     Problem Pn = L.P;
     Pn.poses = S.d_poses_new;
     Pn.pts = S.d_pts_new;
@@ -2177,10 +2134,10 @@ gh_status ba_wait_verdict(gh_ctx* ctx, const HostVerdict* rb, unsigned want) {
 
 // A bounded wait inside one of the single-launch kernels expired (chol.hip: the launch could not get all its workgroups resident,
 // e.g. another process holds part of the GPU): the iteration is repeated on the launch-per-step path, and the solve stays on it.
-// d_flow and d_xh are SESSION fields: a resident graph stays on that path for the rest of its life (cr_flow_ok is per solve).
+// dense.flow_state and dense.xh are SESSION fields: a resident graph stays on that path for the rest of its life (cr_flow_ok is per solve).
 gh_status ba_leave_single_launch(gh_ctx* ctx, BaSession& S, LmLoop& L, const LmStep& step) {
-  S.d_flow = nullptr;
-  S.d_xh = nullptr;
+  S.dense.flow_state = nullptr;
+  S.dense.xh = nullptr;
   L.cr_flow_ok = false;  // (band / arrowhead: the dense top stays off the single-launch kernels)
   if (step.fresh_lin) L.need_lin = true;  // (cheap, and keeps the gradient read-back of this iteration in place)
   if (step.spec_launched)  // the speculation wrote the gradient maximum the repeated linearisation accumulates into
@@ -2275,7 +2232,7 @@ gh_status ba_run(gh_ctx* ctx, BaSession& S, gh_ba_problem* pr, const BaSwitches&
         break;
       }
     }
-    if (L.rb->info > n && (S.cr_T ? L.cr_flow_ok : (S.d_flow || S.d_xh))) {  // nothing was decided yet: repeat this iteration
+    if (L.rb->info > n && (S.cr_T ? L.cr_flow_ok : (S.dense.flow_state || S.dense.xh))) {  // nothing was decided yet: repeat this iteration
       if (opt.verbose) fprintf(stderr, "[gh_ba] it %3d: single-launch solve timed out (info %d), repeating on the launch path\n", it, L.rb->info);
       GH_TRY(ba_leave_single_launch(ctx, S, L, step));
       --it;

@@ -27,7 +27,7 @@
 //   * up to eight barycentre sweeps (a camera moves to the mean position of its sampled points, a point sits at the mean position of
 //     its observers; points whose observers are more than 4 * kBandSpan apart -- loop closures -- do not vote) iron out what
 //     sampling noise scrambled locally.
-#include "common.h"
+#include "dense_solve.h"
 #include "host_pool.h"
 
 #include <algorithm>
@@ -446,9 +446,7 @@ bool covis_order(const gh_ba_problem* pr, std::vector<int32_t>& order) {
 
 }  // namespace
 
-// perm[new] = old camera (empty: the caller's order stands), returns the number of border cameras at the end of the order.
-// *reordered (may be null): 1 when the bandwidth-reducing order was applied.  `allow_reorder` = false: rounds 4-5 (A/B runs).
-// The border of an arrowhead system can be made of the far CAMERAS of the long-range points (6 unknowns each; the cameras move to
+// gh_ba_order_cameras (contract: dense_solve.h).  The border of an arrowhead system can be made of the far CAMERAS of the long-range points (6 unknowns each; the cameras move to
 // the end of the order) or of the long-range POINTS themselves (3 unknowns each: they are kept OUT of the Schur complement and
 // solved for together with the cameras; no camera moves).  A revisit seen by a handful of cameras through hundreds of points wants
 // the first, a handful of points seen from many far cameras the second: the smaller border wins.
@@ -463,8 +461,6 @@ static bool points_make_the_smaller_border(int nb_cams, const std::vector<int32_
 
 int gh_ba_order_cameras(const gh_ba_problem* pr, std::vector<int32_t>& perm, int* reordered, bool allow_reorder, int* band_span,
                         std::vector<int32_t>* border_points) {
-  // *band_span (may be null): the camera span of the order that results when this function has measured it (no camera border), else -1
-  // *border_points (may be null = never): filled when the long-range POINTS form the border (the return value is then 0)
   perm.clear();
   if (reordered) *reordered = 0;
   if (band_span) *band_span = -1;

@@ -14,7 +14,7 @@
 //   the rank-256 trailing update keeps C traffic (the HBM-bound part) at ~1/4 of a rank-64 update.
 // Solve: the right-hand side rides through the factorisation as an extra row (forward substitution for free);
 // backward substitution = one launch per 64-block step: x_k = M_kk^T y_k, then a coalesced panel mat-vec.
-#include "common.h"
+#include "dense_solve.h"
 
 namespace {
 
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(256) void bwd_step2_inv_kernel(const double* __rest
 // to the tile's word; consuming = relaxed poll of that ONE word until all waves have arrived, then sc1 loads.  Every wait
 // is bounded and watches a common abort word: an expired wait raises `info`, sets the abort word and the launch runs out
 // (with garbage) instead of hanging.
-constexpr int FL_MAXT = 6;                       // tiles per worker: 3 per half of the workgroup, 16 accumulator doubles per lane each
+constexpr int FL_MAXT = kFlowMaxT;               // tiles per worker: 3 per half of the workgroup, 16 accumulator doubles per lane each
 constexpr unsigned kFlowSpinLimit = 1u << 22;
 constexpr int kFlowLdsBytes = 4 * NBI * LP * (int)sizeof(double) + 1024;  // four tile buffers (or Potf2Lds + extras)
 
@@ -1549,7 +1549,6 @@ __global__ void gather_strided_kernel(const double* __restrict__ src, long long 
 // consumer re-reads its 16 values with agent-scope relaxed loads until none is the sentinel.  No flag, no fence.
 // Workgroup c only waits for workgroups with a LOWER blockIdx (block 0 owns the last column block); every spin is bounded:
 // on expiry the workgroup raises `info`, publishes NaN so that nobody behind it waits, and the launch ends.
-constexpr unsigned long long kXSentinel = 0xFFF8BEEFFFF8BEEFull;  // a NaN no computation produces; two equal 32-bit halves
 constexpr int kBwdChainMaxN = 8192;                                // 128 workgroups; workgroup 0 streams <= 4 MB of L
 constexpr unsigned kBwdSpinLimit = 1u << 21;
 
@@ -1642,102 +1641,89 @@ __global__ __launch_bounds__(256) void bwd_chain_kernel(const double* __restrict
 
 }  // namespace
 
-// The dataflow launch needs every workgroup resident: one per CU (its LDS request admits no second one).  Returns the
-// number of worker workgroups, or -1 when the shape does not fit (then the launch-per-step path below is taken).
-static int flow_groups(const gh_ctx* ctx, int n, int extra_rows) {
-  if (extra_rows < 0 || extra_rows > 1 || n < 1) return -1;
-  const int nb = gh_div_up(n, NBI), ntr = gh_div_up(n + extra_rows, NBI);
-  int groups = 0;
-  for (int i = 2; i < ntr; ++i) groups += gh_div_up(i - 1, FL_MAXT);
-  const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-  (void)nb;
-  return 1 + (ntr > 1 ? ntr - 1 : 0) + groups <= cus ? groups : -1;  // chain + accumulator workgroups + workers
-}
-
-// Two dataflow launches in flight on one GPU could each hold part of the CUs and wait for the rest for ever (until their
-// bounded waits expire): callers in this process take this lock from the launch to their next stream synchronisation.
-// The hazard is per device: solves on different GPUs of one process do not serialise on each other.  (Across PROCESSES
-// that share a GPU nothing protects; there the bounded waits expire, info > n comes back and the caller stays on the
-// launch-per-step path for the rest of its solve: gh_ba_solve.)
+// (What the lock is for: dense_solve.h.)  The hazard is per device: solves on different GPUs of one process do not serialise
+// on each other.  (Across PROCESSES that share a GPU nothing protects; there the bounded waits expire, info > n comes back
+// and the caller stays on the launch-per-step path for the rest of its solve: gh_ba_solve.)
 std::mutex& gh_potrf_flow_mutex(int device) {
   static std::mutex mu[64];
   return mu[(unsigned)device & 63u];
 }
 
-static size_t flow_flag_words(size_t nb, size_t ntr) { return (ntr * nb + nb + ntr + 16 + 31) & ~(size_t)31; }
-// u32 words at the start of the dataflow state that have to be ZERO when the launch starts (flags, abort word)
-size_t gh_potrf_flow_flag_words(int n, int extra_rows) {
-  return flow_flag_words((size_t)gh_div_up(n, NBI), (size_t)gh_div_up(n + extra_rows, NBI));
+// Worker workgroups of the single dataflow launch for this call, or -1: then the launch-per-step path is taken.
+static int flow_eligible(const gh_ctx* ctx, const double* A, int n, int lda, int extra_rows, const DenseWork& w) {
+  const char* env = getenv("GSLAM_HIP_CHOL_FLOW");  // "0" keeps the launch-per-step path (A/B measurements, tests)
+  // tiles must not share 128-byte lines: a line is only ever touched with plain loads by the one workgroup that owns it
+  const bool aligned = lda % 16 == 0 && (reinterpret_cast<uintptr_t>(A) & 127u) == 0;
+  if (!w.flow_state || !aligned || (env && env[0] == '0')) return -1;
+  return dense_layout(n, extra_rows, ctx->cu_count).flow_workers;
 }
 
-// u32 words of device state the dataflow launch needs (tile flags, block flags, abort word), 0 = shape not eligible
-size_t gh_potrf_flow_words(const gh_ctx* ctx, int n, int extra_rows) {
-  if (flow_groups(ctx, n, extra_rows) < 0) return 0;
-  const size_t nb = (size_t)gh_div_up(n, NBI), ntr = (size_t)gh_div_up(n + extra_rows, NBI);
-  return flow_flag_words(nb, ntr) + ntr * 8192 * 2;  // flags, then the hand-over tiles (doubles)
-}
-
-// Factor (lower, in place) and optionally solve.  info_dev: device int (0 = ok, else first bad block column + 1).
-// `extra_rows` rows below the n x n matrix (lda >= n + extra_rows) ride along through trsm / syrk: with the
-// right-hand side stored as row n, the factorisation leaves y = L^-1 b there (forward substitution for free).
-// `dinv`: ceil(n / 64) * 4096 doubles of device workspace that receives the inverted diagonal blocks.
-// `xwork`: optional 2 * 64 * (n + extra_rows) doubles; when given, full panel steps of the small-matrix regime run as one
-// launch each (panel_step_kernel) with their X rows parked there until a later launch copies them home.
-// `flow_state`: optional gh_potrf_flow_words() u32 words; when given (and GSLAM_HIP_CHOL_FLOW != 0) the whole factorisation
-// is the single dataflow launch (potrf_flow_kernel); `store_diag` = false lets it leave the diagonal blocks of L unwritten
-// (a caller that only solves never reads them: the triangular solves use `dinv`).
-// `dinv`: only the lower triangle of each block is defined -- every reader masks the rest.
-// `state_ready`: the caller's previous kernel has already cleared `info_dev` and the flag words of `flow_state`
-// (gh_potrf_flow_flag_words): two memset nodes less in front of the launch.
-gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_dev, int extra_rows, double* dinv,
-                            double* xwork, unsigned* flow_state, bool store_diag, bool state_ready) {
-  const int nr = n + extra_rows;  // row bound of every panel / trailing operation
-  if (!state_ready) GH_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
-  {
-    const char* env = getenv("GSLAM_HIP_CHOL_FLOW");  // "0" keeps the launch-per-step path (A/B measurements, tests)
-    // tiles must not share 128-byte lines: a line is only ever touched with plain loads by the one workgroup that owns it
-    const bool aligned = lda % 16 == 0 && (reinterpret_cast<uintptr_t>(A) & 127u) == 0;
-    const int groups = flow_state && aligned && !(env && env[0] == '0') ? flow_groups(ctx, n, extra_rows) : -1;
-    if (groups >= 0) {
-      static bool lds_attr_set[64] = {};  // per device: the attribute belongs to the code object loaded there
-      const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-      if (!lds_attr_set[dev] || ctx->device != dev) {
-        GH_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(potrf_flow_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kFlowLdsBytes));
-        lds_attr_set[dev] = true;
-      }
-      FlowArgs fa;
-      fa.A = A;
-      fa.lda = lda;
-      fa.n = n;
-      fa.nr = nr;
-      fa.nb = gh_div_up(n, NBI);
-      fa.ntr = gh_div_up(nr, NBI);
-      fa.n_groups = groups;
-      fa.store_diag = store_diag ? 1 : 0;
-      fa.dinv = dinv;
-      fa.tf = flow_state;
-      fa.mf = flow_state + (size_t)fa.ntr * fa.nb;
-      fa.hf = fa.mf + fa.nb;
-      fa.abort_word = fa.hf + fa.ntr;
-      const size_t flag_words = flow_flag_words((size_t)fa.nb, (size_t)fa.ntr);
-      fa.hand = reinterpret_cast<double*>(flow_state + flag_words);
-      fa.info = info_dev;
-      fa.spin_limit = kFlowSpinLimit;
-      if (const char* e = getenv("GSLAM_HIP_FLOW_SPIN_LIMIT")) fa.spin_limit = (unsigned)strtoul(e, nullptr, 10);
-#ifdef GH_FLOW_WHATIF
-      {
-        const char* w = getenv("GSLAM_HIP_FLOW_WHATIF");
-        const unsigned mask = w ? (unsigned)strtoul(w, nullptr, 0) : 0u;
-        GH_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_flow_whatif), &mask, sizeof(mask)));
-      }
-#endif
-      if (!state_ready) GH_HIP(ctx, hipMemsetAsync(flow_state, 0, flag_words * sizeof(unsigned), ctx->stream));
-      GH_LAUNCH(ctx, "ba_potrf_flow", potrf_flow_kernel, dim3(1 + (fa.ntr > 1 ? fa.ntr - 1 : 0) + groups), dim3(512),
-                kFlowLdsBytes, fa);
-      return GH_OK;
-    }
+static gh_status potrf_flow_launch(gh_ctx* ctx, double* A, int n, int lda, int extra_rows, const DenseWork& w, bool store_diag,
+                                   bool ready, int groups) {
+  static bool lds_attr_set[64] = {};  // per device: the attribute belongs to the code object loaded there
+  const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
+  if (!lds_attr_set[dev] || ctx->device != dev) {
+    GH_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(potrf_flow_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFlowLdsBytes));
+    lds_attr_set[dev] = true;
   }
+  const int nr = n + extra_rows, nb = gh_div_up(n, NBI), ntr = gh_div_up(nr, NBI);
+  unsigned* const tf = w.flow_state;  // the flag words: tile flags, block flags, hand-over flags, the abort word; then the tiles
+  unsigned* const mf = tf + (size_t)ntr * nb;
+  FlowArgs fa{A, lda, n, nr, nb, ntr, groups, store_diag ? 1 : 0, w.dinv, tf, mf, /*hf*/ mf + nb,
+              /*hand*/ reinterpret_cast<double*>(tf + w.n_flow_flag_words), /*abort_word*/ mf + nb + ntr, w.info, kFlowSpinLimit};
+  if (const char* e = getenv("GSLAM_HIP_FLOW_SPIN_LIMIT")) fa.spin_limit = (unsigned)strtoul(e, nullptr, 10);
+#ifdef GH_FLOW_WHATIF
+  {
+    const char* wi = getenv("GSLAM_HIP_FLOW_WHATIF");
+    const unsigned mask = wi ? (unsigned)strtoul(wi, nullptr, 0) : 0u;
+    GH_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_flow_whatif), &mask, sizeof(mask)));
+  }
+#endif
+  if (!ready) GH_HIP(ctx, hipMemsetAsync(w.flow_state, 0, w.n_flow_flag_words * sizeof(unsigned), ctx->stream));
+  GH_LAUNCH(ctx, "ba_potrf_flow", potrf_flow_kernel, dim3(1 + (fa.ntr > 1 ? fa.ntr - 1 : 0) + groups), dim3(512),
+            kFlowLdsBytes, fa);
+  return GH_OK;
+}
+
+static int lower_tiles(int ti, int tj) { return tj * (tj + 1) / 2 + (ti - tj) * tj; }
+
+// what every rank-k update of one factorisation has in common
+struct SyrkCall { gh_ctx* ctx; double* A; int lda, nr; int* info_dev; int syrk8, syrk_prio; };
+// rank-kdim update of rows [cb, nr) x columns [cb, ce) + factorisation of the diagonal block at cb
+// The eight-wave tile is worth 4.5 % on the reduced camera system of C5 (1175 -> 1124 ms per LM iteration, same box) and
+// nothing on a dense random matrix of the same size (1154 ms for either tile shape, and for every other variant tried).
+// (Rounds 3-4 put that down to the board's power limit.  The round-5 counters say otherwise: SQ_VALU_MFMA_BUSY_CYCLES against
+// GRBM_GUI_ACTIVE has the matrix pipe 85 % busy inside this kernel at 2.2-2.3 GHz effective -- most of the gap to the peak is
+// waiting inside the kernel: profiles/c5_dense_solve_r05.txt.)
+// (Tried and dropped: look-ahead -- the bulk of a trailing update on a low-priority side stream while the next panel is
+// factored on this one.  Bit-identical, but the two streams' kernels do not overlap on this part: 1155 ms against
+// 1152 ms for the n = 60 000 factorisation, tools/c5_solve_probe.py.)
+static gh_status syrk_update(const SyrkCall& u, const char* name, int cb, int ce, int kc0, int kdim, int kbn, double* minv_next) {
+  gh_ctx* ctx = u.ctx;
+  // grid = the lower tiles (see the decode in the kernel), rounded up to the 8 XCD strips, + the potf2 workgroup
+  if ((long long)gh_div_up(u.nr - cb, TM) * gh_div_up(ce - cb, TM) >= 1024) {  // enough 128-tiles for 256 CUs x 2 workgroups
+    const int tiles_j = gh_div_up(ce - cb, TM), tiles_i = gh_div_up(u.nr - cb, TM);
+    const dim3 grid(8 * gh_div_up(lower_tiles(tiles_i, tiles_j), 8) + 1);
+    if (u.syrk8)  // eight waves per tile: four waves per SIMD keep the f64 matrix core busier (GSLAM_HIP_SYRK8=0: four)
+      GH_LAUNCH(ctx, name, syrk_mfma8_kernel<TM>, grid, dim3(512), 0, u.A, u.lda, u.nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb,
+                kbn, u.info_dev, minv_next, u.syrk_prio);
+    else
+      GH_LAUNCH(ctx, name, syrk_mfma_kernel<TM>, grid, dim3(256), 0, u.A, u.lda, u.nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb,
+                kbn, u.info_dev, minv_next);
+  } else {
+    const int tiles_j = gh_div_up(ce - cb, TM / 2), tiles_i = gh_div_up(u.nr - cb, TM / 2);
+    GH_LAUNCH(ctx, name, syrk_mfma_kernel<TM / 2>, dim3(8 * gh_div_up(lower_tiles(tiles_i, tiles_j), 8) + 1), dim3(256), 0, u.A,
+              u.lda, u.nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb, kbn, u.info_dev, minv_next);
+  }
+  return GH_OK;
+}
+
+// The launch-per-step path: a loop over outer panels, blocks of 64 columns inside them.
+static gh_status potrf_stepwise(gh_ctx* ctx, double* A, int n, int lda, int extra_rows, const DenseWork& w) {
+  const int nr = n + extra_rows;  // row bound of every panel / trailing operation
+  int* const info_dev = w.info;
+  double *const dinv = w.dinv, *const xwork = w.xwork;
   // outer panel width: wider for large systems (each doubling halves the passes over the trailing matrix, whose C-tile
   // read-modify-write is what keeps the rank-k update below the MFMA rate, at the price of more in-panel rank-64
   // updates; measured at n = 60 000: 512 -> 58.0, 1024 -> 60.1 TFLOP/s), 256 for small, latency-bound ones
@@ -1746,38 +1732,12 @@ gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_de
   // rank-k update that precedes it (potf2_fused), so a panel step is two launches: trsm, then update + next potf2
   // -- or one (panel_step_kernel) for full steps of small matrices.
   GH_LAUNCH(ctx, "ba_potf2", potf2_inv_kernel, dim3(1), dim3(256), 0, A, lda, 0, n < NBI ? n : NBI, info_dev, dinv);
-  auto lower_tiles = [](int ti, int tj) { return tj * (tj + 1) / 2 + (ti - tj) * tj; };
-  auto t128_of = [&](int cb, int ce) { return (long long)gh_div_up(nr - cb, TM) * gh_div_up(ce - cb, TM); };
-  // rank-kdim update of rows [cb, nr) x columns [cb, ce) + factorisation of the diagonal block at cb
-  // The eight-wave tile is worth 4.5 % on the reduced camera system of C5 (1175 -> 1124 ms per LM iteration, same box) and
-  // nothing on a dense random matrix of the same size (1154 ms for either tile shape, and for every other variant tried).
-  // (Rounds 3-4 put that down to the board's power limit.  The round-5 counters say otherwise: SQ_VALU_MFMA_BUSY_CYCLES against
-  // GRBM_GUI_ACTIVE has the matrix pipe 85 % busy inside this kernel at 2.2-2.3 GHz effective -- most of the gap to the peak is
-  // waiting inside the kernel: profiles/c5_dense_solve_r05.txt.)
-  // (Tried and dropped: look-ahead -- the bulk of a trailing update on a low-priority side stream while the next panel is
-  // factored on this one.  Bit-identical, but the two streams' kernels do not overlap on this part: 1155 ms against
-  // 1152 ms for the n = 60 000 factorisation, tools/c5_solve_probe.py.)
   const int syrk8 = [] { const char* e = getenv("GSLAM_HIP_SYRK8"); return e ? atoi(e) : 1; }();
   const int syrk_prio = [] { const char* e = getenv("GSLAM_HIP_SYRK_PRIO"); return e ? atoi(e) : 0; }();
-  auto update = [&](const char* name, int cb, int ce, int kc0, int kdim, int kbn, double* minv_next) -> gh_status {
-    // grid = the lower tiles (see the decode in the kernel), rounded up to the 8 XCD strips, + the potf2 workgroup
-    if (t128_of(cb, ce) >= 1024) {  // enough 128-tiles for 256 CUs x 2 workgroups
-      const int tiles_j = gh_div_up(ce - cb, TM), tiles_i = gh_div_up(nr - cb, TM);
-      const dim3 grid(8 * gh_div_up(lower_tiles(tiles_i, tiles_j), 8) + 1);
-      if (syrk8)  // eight waves per tile: four waves per SIMD keep the f64 matrix core busier (GSLAM_HIP_SYRK8=0: four)
-        GH_LAUNCH(ctx, name, syrk_mfma8_kernel<TM>, grid, dim3(512), 0, A, lda, nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb,
-                  kbn, info_dev, minv_next, syrk_prio);
-      else
-        GH_LAUNCH(ctx, name, syrk_mfma_kernel<TM>, grid, dim3(256), 0, A, lda, nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb, kbn,
-                  info_dev, minv_next);
-    } else {
-      const int tiles_j = gh_div_up(ce - cb, TM / 2), tiles_i = gh_div_up(nr - cb, TM / 2);
-      GH_LAUNCH(ctx, name, syrk_mfma_kernel<TM / 2>, dim3(8 * gh_div_up(lower_tiles(tiles_i, tiles_j), 8) + 1), dim3(256),
-                0, A, lda, nr, cb, cb, ce, kc0, kdim, tiles_i, tiles_j, cb, kbn, info_dev, minv_next);
-    }
-    return GH_OK;
-  };
-  XCopy pend{nullptr, nr, 0, 0, 0};  // X of the last fused step, not yet in place
+  const SyrkCall upd{ctx, A, lda, nr, info_dev, syrk8, syrk_prio};
+  // X of the last fused step, not yet in place.  Two buffers of 64 * nr doubles in xwork, used in turn: a step's launch copies
+  // the previous step's X home while it parks its own (rows cb .. nr - 1 of 64 columns, column pitch nr).
+  XCopy pend{nullptr, nr, 0, 0, 0};
   int xsel = 0;
   // In-panel updates two blocks at a time (large systems): after block k only the NEXT 64 columns get its rank-64 update
   // (a narrow strip, so that block k + 64 can be factored and solved), the rest of the panel then takes blocks k and k + 64
@@ -1799,7 +1759,7 @@ gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_de
         GH_LAUNCH(ctx, "ba_trsm", trsm_inv_kernel, dim3(ntrsm + ncopy), dim3(256), 0, A, lda, nr, k, kb, r0,
                   (const double*)minv, ntrsm, pend);
         pend.src = nullptr;
-        if (cb < ce) GH_TRY(update("ba_syrk_panel", cb, ce, deferred_k, 2 * NBI, ce - cb < NBI ? ce - cb : NBI, minv + NBI * NBI));
+        if (cb < ce) GH_TRY(syrk_update(upd, "ba_syrk_panel", cb, ce, deferred_k, 2 * NBI, ce - cb < NBI ? ce - cb : NBI, minv + NBI * NBI));
         deferred_k = -1;
         continue;
       }
@@ -1826,11 +1786,11 @@ gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_de
                           !(xwork && lower_tiles(gh_div_up(nr - cb2, 64), gh_div_up(ce - cb2, 64)) <= 256);
         if (pair) {
           // the next block's 64 columns only (+ its factorisation); the rest waits for the pair's rank-128 update
-          GH_TRY(update("ba_syrk_panel", cb, cb2, k, kb, NBI, minv + NBI * NBI));
+          GH_TRY(syrk_update(upd, "ba_syrk_panel", cb, cb2, k, kb, NBI, minv + NBI * NBI));
           deferred_k = k;
         } else if (cb < ce) {
           // update the rest of this panel with the fresh 64 columns (+ factor the next diagonal block)
-          GH_TRY(update("ba_syrk_panel", cb, ce, k, kb, ce - cb < NBI ? ce - cb : NBI, minv + NBI * NBI));
+          GH_TRY(syrk_update(upd, "ba_syrk_panel", cb, ce, k, kb, ce - cb < NBI ? ce - cb : NBI, minv + NBI * NBI));
         }
       }
     }
@@ -1840,32 +1800,34 @@ gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_de
     }
     const int t0 = c0 + pw;
     if (t0 < n)
-      GH_TRY(update("ba_syrk_trailing", t0, n, c0, pw, n - t0 < NBI ? n - t0 : NBI, dinv + (size_t)(t0 / NBI) * (NBI * NBI)));
+      GH_TRY(syrk_update(upd, "ba_syrk_trailing", t0, n, c0, pw, n - t0 < NBI ? n - t0 : NBI, dinv + (size_t)(t0 / NBI) * (NBI * NBI)));
   }
   return GH_OK;
 }
 
-// backward substitution only: y[i] = yv[i * ystride] on entry, x is written to b.  `work`: n doubles (the launch-per-step
-// path keeps its running right-hand side there); `xh`: ceil(n / 64) * 64 doubles for the single-launch path (n <=
-// kBwdChainMaxN, GSLAM_HIP_BWD_CHAIN != 0) or nullptr; `info_dev` receives n + 1 + block if a hand-off wait expired.
-// `xh_ready`: the caller has already filled `xh` with the sentinel (every 32-bit word 0xFFF8BEEF).
-gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, double* b, double* work,
-                                const double* dinv, const double* yv, long long ystride, double* xh, int* info_dev,
-                                bool xh_ready) {
+gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int extra_rows, const DenseWork& w, bool store_diag, bool ready) {
+  if (!ready) GH_HIP(ctx, hipMemsetAsync(w.info, 0, sizeof(int), ctx->stream));
+  const int groups = flow_eligible(ctx, A, n, lda, extra_rows, w);
+  if (groups >= 0) return potrf_flow_launch(ctx, A, n, lda, extra_rows, w, store_diag, ready, groups);
+  return potrf_stepwise(ctx, A, n, lda, extra_rows, w);
+}
+
+gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, const DenseWork& w, double* b, const double* yv,
+                                long long ystride, bool ready) {
+  double *const work = w.work, *const dinv = w.dinv;
   const char* env = getenv("GSLAM_HIP_BWD_CHAIN");  // "0" keeps the launch-per-step path (A/B measurements, tests)
   const bool chain_ok = !(env && env[0] == '0');
-  if (xh && info_dev && chain_ok) {
+  if (w.xh && w.info && chain_ok) {
     const int nb = gh_div_up(n, NBI);
-    if (!xh_ready)
-      GH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)xh, (int)0xFFF8BEEFu, (size_t)nb * NBI * 2, ctx->stream));
+    if (!ready) GH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)w.xh, (int)kXSentinelWord, w.n_xh_words, ctx->stream));
     unsigned spin_limit = kBwdSpinLimit;
     if (const char* e = getenv("GSLAM_HIP_FLOW_SPIN_LIMIT")) spin_limit = (unsigned)strtoul(e, nullptr, 10);
     // segments of at most 128 column blocks from the bottom right up: a workgroup only ever waits for workgroups of its own
     // launch with a lower index, everything older is final (n = 60 000: 8 launches instead of 938)
     for (int first = 0; first < nb; first += kBwdChainMaxN / NBI) {
       const int cnt = nb - first < kBwdChainMaxN / NBI ? nb - first : kBwdChainMaxN / NBI;
-      GH_LAUNCH(ctx, "ba_trsv_bwd", bwd_chain_kernel, dim3(cnt), dim3(256), 0, L, lda, n, nb, first, yv, ystride, dinv, xh, b,
-                info_dev, spin_limit);
+      GH_LAUNCH(ctx, "ba_trsv_bwd", bwd_chain_kernel, dim3(cnt), dim3(256), 0, L, lda, n, nb, first, yv, ystride, dinv, w.xh, b,
+                w.info, spin_limit);
     }
     return GH_OK;
   }
@@ -1890,16 +1852,16 @@ gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, do
   return GH_OK;
 }
 
-// work: n doubles of device scratch
-gh_status gh_potrs_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, double* b, double* work, const double* dinv,
-                            double* xh, int* info_dev) {
+// forward substitution launch per step, then the backward substitution above
+static gh_status potrs_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, double* b, const DenseWork& w) {
+  double* const work = w.work;
   for (int k = 0; k < n; k += NBI) {
     const int kb = n - k < NBI ? n - k : NBI;
     const int rows = n - (k + kb);
     GH_LAUNCH(ctx, "ba_trsv_fwd", fwd_step_kernel, dim3(rows > 0 ? gh_div_up(rows, 256) : 1), dim3(256), 0, L, lda, n,
               k, kb, b, work);
   }
-  return gh_potrs_bwd_dev_impl(ctx, L, n, lda, b, work, dinv, work, 1, xh, info_dev, false);
+  return gh_potrs_bwd_dev_impl(ctx, L, n, lda, w, b, work, 1, false);
 }
 
 namespace {
@@ -1918,29 +1880,22 @@ extern "C" gh_status gh_potrf_solve_dev(gh_ctx* ctx, double* A_dev, int n, int l
   GH_CHECK_ARG(ctx, A_dev && n > 0 && lda >= n && info);
   const int extra = (b_dev && lda > n) ? 1 : 0;
   void* scratch = nullptr;
-  const size_t nblk = (size_t)gh_div_up(n, NBI);
-  const size_t flow_words = gh_potrf_flow_words(ctx, n, extra);
-  GH_TRY(gh_scratch(ctx, 256 + ((size_t)n + nblk * NBI * NBI + 2 * (size_t)NBI * n + nblk * NBI) * sizeof(double) +
-                             flow_words * sizeof(unsigned), &scratch));
-  int* info_dev = (int*)scratch;
-  double* dinv = (double*)((char*)scratch + 256);
-  double* work = dinv + nblk * NBI * NBI;
-  double* xwork = work + n;
-  double* xh = xwork + 2 * (size_t)NBI * n;
-  unsigned* flow_state = flow_words ? (unsigned*)(xh + nblk * NBI) : nullptr;
+  const DenseLayout layout = dense_layout(n, extra, ctx->cu_count);
+  GH_TRY(gh_scratch(ctx, layout.bytes, &scratch));
+  const DenseWork w = dense_carve(scratch, layout);
   {
     std::unique_lock<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device), std::defer_lock);
-    if (flow_state) flow_lock.lock();
+    if (w.flow_state) flow_lock.lock();
     if (extra)
       GH_LAUNCH(ctx, "ba_rhs_row", solve_rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, (const double*)b_dev, A_dev, lda, n);
-    GH_TRY(gh_potrf_dev_impl(ctx, A_dev, n, lda, info_dev, extra, dinv, xwork, flow_state, true, false));
-    if (extra) GH_TRY(gh_potrs_bwd_dev_impl(ctx, A_dev, n, lda, b_dev, work, dinv, A_dev + n, lda, xh, info_dev, false));
-    GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GH_TRY(gh_potrf_dev_impl(ctx, A_dev, n, lda, extra, w, true, false));
+    if (extra) GH_TRY(gh_potrs_bwd_dev_impl(ctx, A_dev, n, lda, w, b_dev, A_dev + n, lda, false));
+    GH_HIP(ctx, hipMemcpyAsync(info, w.info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (*info == 0 && b_dev && !extra) {
-    GH_TRY(gh_potrs_dev_impl(ctx, A_dev, n, lda, b_dev, work, dinv, xh, info_dev));
-    GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GH_TRY(potrs_dev_impl(ctx, A_dev, n, lda, b_dev, w));
+    GH_HIP(ctx, hipMemcpyAsync(info, w.info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return GH_OK;

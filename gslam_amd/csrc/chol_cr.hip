@@ -24,21 +24,10 @@
 // then backwards, one launch per level:  x_i = (y_i - x_u W_u - x_d W_d) L_i^-1   (ba_cr_back).
 // Storage: A is the dense column-major lower triangle chol.hip uses (n x n, lda > n, rhs in row n); L_i overwrites D_i, the
 // W panels go to a workspace (2 N m^2 doubles), the inverted diagonal tiles to `dinv` (N T tiles).
-#include "common.h"
 #include "cr_map.h"
+#include "dense_solve.h"  // (chol.hip's dense factorisation / back-substitution take the surviving superblocks + the border)
 
 #include <type_traits>
-
-// chol.hip: the dense factorisation / back-substitution (the arrowhead solver hands them superblock 0 + the border)
-gh_status gh_potrf_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int* info_dev, int extra_rows, double* dinv,
-                            double* xwork, unsigned* flow_state, bool store_diag, bool state_ready);
-gh_status gh_potrs_bwd_dev_impl(gh_ctx* ctx, const double* L, int n, int lda, double* b, double* work,
-                                const double* dinv, const double* yv, long long ystride, double* xh, int* info_dev,
-                                bool xh_ready);
-size_t gh_potrf_flow_words(const gh_ctx* ctx, int n, int extra_rows);
-size_t gh_potrf_flow_flag_words(int n, int extra_rows);
-std::mutex& gh_potrf_flow_mutex(int device);
-int gh_cr_top(int nbr);
 
 namespace {
 
@@ -1049,15 +1038,12 @@ __global__ __launch_bounds__(256) void cr_border_syrk_reduce_kernel(CrArgs a, in
 // then the border, with the right-hand side as row qn.  qb = band unknowns that survive (only the last survivor can be partial).
 // M is qn x qn column-major with pitch ldq; element (r, c), r >= c.
 template <int T>
-__global__ void cr_border_gather_kernel(CrArgs a, int qb, double* __restrict__ M, int ldq, unsigned* __restrict__ flow_flags, unsigned n_flow,
-                                        unsigned* __restrict__ xh_words, unsigned n_xh, int* __restrict__ info_q) {
+__global__ void cr_border_gather_kernel(CrArgs a, int qb, double* __restrict__ M, int ldq, DenseReady ready) {
   constexpr int m_ = NBI * T;
   const int c = (int)blockIdx.x, qn = qb + a.nbr, n = a.n;
   if (c >= qn) {  // the workgroups behind the columns clear what the single-launch solve kernels need (as ba.hip's schur_reduce does)
     const unsigned i0 = (unsigned)(c - qn) * blockDim.x + threadIdx.x, step = (gridDim.x - (unsigned)qn) * blockDim.x;
-    if (i0 == 0) *info_q = 0;
-    for (unsigned i = i0; i < n_flow; i += step) flow_flags[i] = 0u;
-    for (unsigned i = i0; i < n_xh; i += step) xh_words[i] = 0xFFF8BEEFu;
+    for (unsigned i = i0; i < ready.words(); i += step) dense_ready_word(ready, i);
     return;
   }
   const size_t lda = (size_t)a.lda;
@@ -1126,14 +1112,47 @@ __global__ __launch_bounds__(256) void cr_border_yh_kernel(CrArgs a, const doubl
 // their number and the band unknowns qb they hold (only the last survivor can be partial).  ONE function for the solver and for the
 // size of its workspace (gh_arrow_ws_doubles): the two used to disagree on qn when the last survivor is partial or fewer than `top`
 // superblocks survive, and the single-launch factorisation's state then lay past the reserved block.
-struct TopShape { int S, nsv, qb; };
+struct TopShape { int S, nsv, qb, levels; };  // (S = 2^levels)
 inline TopShape top_shape(int n, int m, int top) {
   const int N = gh_div_up(n, m);
-  int S = 1;
-  while (gh_div_up(N, S) > top) S *= 2;
+  int S = 1, levels = 0;
+  for (; gh_div_up(N, S) > top; S *= 2) ++levels;
   const int nsv = gh_div_up(N, S);
   const int last = n - (nsv - 1) * S * m;
-  return TopShape{S, nsv, (nsv - 1) * m + (last < m ? last : m)};
+  return TopShape{S, nsv, (nsv - 1) * m + (last < m ? last : m), levels};
+}
+
+// The border workspace of a system reduced down to its dense top (offsets in doubles from a 128-byte aligned `bws`, every
+// segment on a 128-byte line): the corner update's partial tiles, the dense system M of the surviving superblocks + border
+// (qn unknowns, pitch ldq, right-hand side as row qn), the workspace of its dense solve -- whose info word is the dense top's own:
+// the reduction's factor kernels use *info_dev with THEIR column numbers --, its solution, the backward pass's t vector.
+// ONE function for cr_solve_t's carve and for gh_arrow_ws_doubles.  (qn of THIS system: the DenseLayout's flow state is not
+// monotonic in qn -- it is empty once the shape exceeds the CU count -- so a bound from the largest possible qn may reserve
+// nothing where the real qn needs megabytes.)
+struct BorderLayout {
+  int qb, qn, ldq, ntiles;
+  BorderChunks chunks;
+  DenseLayout dense;
+  size_t part, Mq, dense_at, xq, tvec, doubles;
+};
+inline BorderLayout border_layout(const gh_ctx* ctx, int n_band, int T, int nbr) {
+  BorderLayout B{};
+  const int m = NBI * T, ntr = gh_div_up(nbr + 1, 64);
+  B.qb = top_shape(n_band, m, gh_cr_top(nbr)).qb;
+  B.qn = B.qb + nbr;
+  B.ldq = (B.qn + 1 + 15) & ~15;
+  B.ntiles = ntr * (ntr + 1) / 2;
+  B.chunks = border_chunks(n_band, m, nbr);
+  B.dense = dense_layout(B.qn, 1, ctx->cu_count);
+  size_t at = 0;
+  auto segment = [&at](size_t doubles) { const size_t off = at; at += (doubles + 15) & ~(size_t)15; return off; };
+  B.part = segment((size_t)B.chunks.n * B.ntiles * (NBI * NBI));
+  B.Mq = segment((size_t)B.ldq * B.qn);
+  B.dense_at = segment(B.dense.bytes / sizeof(double));
+  B.xq = segment((size_t)B.qn);
+  B.tvec = segment((size_t)n_band);
+  B.doubles = at;
+  return B;
 }
 
 // a launch on `stream` through the context's profiler (GH_LAUNCH times on ctx->stream)
@@ -1200,8 +1219,7 @@ gh_status cr_solve_t(gh_ctx* ctx, double* A, int n, int lda, double* dinv, doubl
   const int S = ts.S, nsv = ts.nsv;  // stride and number of the survivors
   a.keep = S;
   if (compact) {  // (cr_map.h; lda = gh_cr_compact_lda of the same system)
-    int levels = 0;
-    while ((1 << levels) < S) ++levels;
+    const int levels = ts.levels;
     a.map.m = m_;
     a.map.n_band = n;
     a.map.brow = (2 + levels) * m_;
@@ -1242,35 +1260,23 @@ gh_status cr_solve_t(gh_ctx* ctx, double* A, int n, int lda, double* dinv, doubl
   a.count = 1;
   if (nbr > 0 || nsv > 1) {
     // the survivors are not factored on their own: they join the border in the dense system that is left
-    const int qb = ts.qb;
-    const int qn = qb + nbr, ldq = (qn + 1 + 15) & ~15;
-    const int ntr = gh_div_up(nbr + 1, 64), ntiles = ntr * (ntr + 1) / 2;
-    const BorderChunks bc = border_chunks(n, m_, nbr);
-    const int nchunks = bc.n;
-    double* part = bws;
-    double* Mq = part + (size_t)nchunks * ntiles * 4096;
-    double* dinv_q = Mq + (size_t)ldq * qn;
-    double* xwork_q = dinv_q + (size_t)gh_div_up(qn, NBI) * (NBI * NBI);
-    double* work_q = xwork_q + (size_t)2 * 64 * (qn + 1);
-    double* xq = work_q + (((size_t)qn + 15) & ~(size_t)15);
-    double* xh_q = xq + (((size_t)qn + 15) & ~(size_t)15);
-    double* tvec = xh_q + (size_t)gh_div_up(qn, NBI) * NBI;
+    const BorderLayout B = border_layout(ctx, n, T, nbr);
+    const int qb = B.qb, qn = B.qn, ldq = B.ldq, ntiles = B.ntiles, nchunks = B.chunks.n;
+    double *part = bws + B.part, *Mq = bws + B.Mq, *xq = bws + B.xq, *tvec = bws + B.tvec;
     // the corner through the single-launch factorisation when its shape fits (the caller holds gh_potrf_flow_mutex)
-    const size_t flow_words = allow_flow ? gh_potrf_flow_words(ctx, qn, 1) : 0;
-    // the dense top reports into a word of its own (the reduction's factor kernels use *info_dev with THEIR column numbers)
-    int* info_q = reinterpret_cast<int*>(tvec + (((size_t)n + 15) & ~(size_t)15));
-    unsigned* flow_q = flow_words ? reinterpret_cast<unsigned*>(tvec + (((size_t)n + 15) & ~(size_t)15) + 16) : nullptr;
-    const unsigned n_flow = flow_words ? (unsigned)gh_potrf_flow_flag_words(qn, 1) : 0u;
-    const unsigned n_xh = (unsigned)gh_div_up(qn, NBI) * NBI * 2u;
+    DenseWork dw = dense_carve(bws + B.dense_at, B.dense);
+    if (!allow_flow) dw.flow_state = nullptr;
+    const DenseReady ready = dense_ready(dw);  // (the gather kernel writes xh's sentinel either way)
+    if (!allow_flow) dw.xh = nullptr;
+    int* info_q = dw.info;
     if (nchunks > 0) {
-      GH_LAUNCH(ctx, "ba_cr_border_syrk", cr_border_syrk_kernel<T>, dim3(nchunks * ntiles), dim3(256), 0, a, bc.kc, ntiles, part);
+      GH_LAUNCH(ctx, "ba_cr_border_syrk", cr_border_syrk_kernel<T>, dim3(nchunks * ntiles), dim3(256), 0, a, B.chunks.kc, ntiles, part);
       GH_LAUNCH(ctx, "ba_cr_border_reduce", cr_border_syrk_reduce_kernel<T>, dim3(16 * ntiles), dim3(256), 0, a, ntiles, nchunks,
                 (const double*)part);
     }
-    GH_LAUNCH(ctx, "ba_cr_border_gather", cr_border_gather_kernel<T>, dim3(qn + 8), dim3(256), 0, a, qb, Mq, ldq, flow_q, n_flow,
-              reinterpret_cast<unsigned*>(xh_q), n_xh, info_q);
-    GH_TRY(gh_potrf_dev_impl(ctx, Mq, qn, ldq, info_q, 1, dinv_q, xwork_q, flow_q, false, true));
-    GH_TRY(gh_potrs_bwd_dev_impl(ctx, Mq, qn, ldq, xq, work_q, dinv_q, Mq + qn, ldq, allow_flow ? xh_q : nullptr, info_q, true));
+    GH_LAUNCH(ctx, "ba_cr_border_gather", cr_border_gather_kernel<T>, dim3(qn + 8), dim3(256), 0, a, qb, Mq, ldq, ready);
+    GH_TRY(gh_potrf_dev_impl(ctx, Mq, qn, ldq, 1, dw, false, true));
+    GH_TRY(gh_potrs_bwd_dev_impl(ctx, Mq, qn, ldq, dw, xq, Mq + qn, ldq, true));
     if (S > 1) GH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->cr_events[1], 0));
     GH_LAUNCH(ctx, "ba_cr_border_back", cr_border_back_kernel<T>, dim3(gh_div_up(n + nbr, 4)), dim3(256), 0, a, qb, (const double*)xq, tvec, (const int*)info_q);
     if (S > 1 && nbr > 0) GH_LAUNCH(ctx, "ba_cr_border_yh", cr_border_yh_kernel<T>, dim3(N - 1), dim3(256), 0, a, (const double*)tvec);
@@ -1303,36 +1309,16 @@ int gh_cr_top_env() {
 }
 int gh_cr_top(int nbr) { return gh_cr_top_env() ? gh_cr_top_env() : (nbr > 0 ? 4 : 2); }
 
-// Rows of a column of the COMPACT layout (cr_map.h) for this system as cr_solve_t will reduce it; *brow = local row of the first
-// border row / of the right-hand side when there is no border.  Only systems solved WITH the border workspace (dense top).
 int gh_cr_compact_lda(int n_band, int T, int nbr, int* brow) {
   const int m = NBI * T;
   const TopShape ts = top_shape(n_band, m, gh_cr_top(nbr));
-  int levels = 0;
-  while ((1 << levels) < ts.S) ++levels;
-  if (brow) *brow = (2 + levels) * m;
-  return cr_compact_lda(m, levels, nbr);
+  if (brow) *brow = (2 + ts.levels) * m;
+  return cr_compact_lda(m, ts.levels, nbr);
 }
 
-// border workspace of an arrowhead solve (doubles): the corner update's partial tiles, the dense system of superblock 0 + border
-// and what chol.hip's dense path needs for it, the backward pass's t vector
-size_t gh_arrow_ws_doubles(const gh_ctx* ctx, int n_band, int T, int nbr) {
-  // (qn of THIS system, as cr_solve_t computes it: gh_potrf_flow_words is not monotonic in qn -- it is 0 once the shape exceeds the
-  //  CU count -- so a bound from the largest possible qn may reserve nothing where the real qn needs megabytes)
-  const size_t m = (size_t)NBI * T, qn = (size_t)top_shape(n_band, NBI * T, gh_cr_top(nbr)).qb + (size_t)nbr, ldq = (qn + 1 + 15) & ~(size_t)15;
-  const size_t ntr = ((size_t)nbr + 1 + 63) / 64, ntiles = ntr * (ntr + 1) / 2;
-  const size_t nchunks = (size_t)border_chunks(n_band, (int)m, nbr).n;
-  const size_t qb = (qn + NBI - 1) / NBI;
-  return nchunks * ntiles * 4096 + ldq * qn + qb * (NBI * NBI) + 2 * 64 * (qn + 1) + 2 * ((qn + 15) & ~(size_t)15) + qb * NBI +
-         (((size_t)n_band + 15) & ~(size_t)15) + gh_potrf_flow_words(ctx, (int)qn, 1) / 2 + 64;
-}
+size_t gh_arrow_ws_doubles(const gh_ctx* ctx, int n_band, int T, int nbr) { return border_layout(ctx, n_band, T, nbr).doubles; }
 
-// Structure of the border through the reduction (host, once per topology).  init[i * nbs + strip] != 0 iff the 16-row strip
-// of the border rows has a structural non-zero among the band columns of superblock i (a border camera and a band camera that
-// see a common point).  Eliminating i at level s fills the strips of i into i - s and i + s (E_u -= Y_i W_u^T); out receives
-// nzY [N][nbs] -- the strips of E_i when i is eliminated, all set for the survivors of the dense top -- then nzT [N][ntr]: per
-// 64-row tile of the corner, with the tile that holds the right-hand-side row (it rides along as row nbr) always set.
-// Conservative by construction: a block marked zero is never written by any kernel and was cleared by the assembly.
+// Structure of the border through the reduction (contract: dense_solve.h)
 size_t gh_cr_border_symbolic_bytes(int n_band, int T, int nbr) {
   const size_t N = (size_t)gh_div_up(n_band, NBI * T);
   return N * ((size_t)gh_div_up(nbr, 16) + (size_t)gh_div_up(nbr + 1, 64));
@@ -1343,9 +1329,7 @@ void gh_cr_border_symbolic(int n_band, int T, int nbr, const uint8_t* init, uint
   uint8_t* nzY = out;
   uint8_t* nzT = out + (size_t)N * nbs;
   memset(nzY, 1, (size_t)N * nbs);
-  const int top = gh_cr_top(nbr);
-  int S = 1;
-  while (gh_div_up(N, S) > top) S *= 2;
+  const int S = top_shape(n_band, m, gh_cr_top(nbr)).S;
   for (int s = 1; s < S; s *= 2)
     for (int i = s; i < N; i += 2 * s) {
       memcpy(nzY + (size_t)i * nbs, &cur[(size_t)i * nbs], (size_t)nbs);
@@ -1373,8 +1357,6 @@ extern "C" size_t gh_cr_border_structure(int n_band, int tiles, int nbr, const u
   return need;
 }
 
-// Tiles per superblock for a half-bandwidth of `hbw` scalars (A[r][c] = 0 for r - c > hbw), 0 = the band is too wide for
-// this solver (or the matrix too small to gain from it): the caller stays on the dense factorisation.
 int gh_cr_tiles(int n, int hbw) {
   if (hbw < 0 || n < 1) return 0;
   const int T = hbw <= NBI ? 1 : (hbw <= 2 * NBI ? 2 : (hbw <= 3 * NBI ? 3 : 0));
@@ -1383,32 +1365,11 @@ int gh_cr_tiles(int n, int hbw) {
   return T;
 }
 size_t gh_cr_dinv_doubles(int n, int T) { return (size_t)gh_div_up(n, NBI * T) * T * (NBI * NBI); }
-// workspace of the panels: W and G (two sides each), W3, yh
 size_t gh_cr_panel_doubles(int n, int T) {
   const size_t N = (size_t)gh_div_up(n, NBI * T), m = (size_t)NBI * T;
   return N * (5 * m * m + m);
 }
 
-// Solve A x = b for a band matrix: A n x n column-major lower triangle (overwritten), b in row n of A (lda > n), T from
-// gh_cr_tiles; everything outside the band must be ZERO in the lower triangle (the fill lands there).  x_dev: n doubles.
-// *info_dev: 0 or the first column + 1 of a diagonal tile that is not positive definite.  Asynchronous on the ctx stream.
-gh_status gh_cr_solve_dev_impl(gh_ctx* ctx, double* A, int n, int lda, int T, double* dinv, double* W, double* x_dev,
-                               int* info_dev, bool info_ready) {
-  // (no border workspace: the reduction runs down to superblock 0 -- the form of rounds 4 / 5a, kept for A/B runs and tests)
-  if (!info_ready) GH_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
-  switch (T) {
-    case 1: return cr_solve_t<1>(ctx, A, n, lda, dinv, W, x_dev, info_dev);
-    case 2: return cr_solve_t<2>(ctx, A, n, lda, dinv, W, x_dev, info_dev);
-    case 3: return cr_solve_t<3>(ctx, A, n, lda, dinv, W, x_dev, info_dev);
-    default: return gh_set_error(ctx, GH_ERR_ARG, "gh_cr_solve: %d tiles per superblock", T);
-  }
-}
-
-// Arrowhead solve: A holds n_band + nbr unknowns (band first, border last) and the right-hand side in row n_band + nbr; the
-// lower triangle of the band part must be zero outside the band, the border rows are dense.  x_dev: n_band + nbr doubles.
-// border_nz (device, may be null = E dense): the structure gh_cr_border_symbolic computed for this system, N * (nbs + ntr) bytes.
-// allow_flow = false: the dense top stays off chol.hip's single-launch kernels (the caller saw one of their bounded waits expire:
-// *info_dev > n_band + nbr).
 gh_status gh_arrow_solve_dev_impl(gh_ctx* ctx, double* A, int n_band, int nbr, int lda, int T, double* dinv, double* W, double* bws,
                                   double* x_dev, int* info_dev, bool info_ready, bool allow_flow, const uint8_t* border_nz, bool compact) {
   if (!info_ready) GH_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
@@ -1425,6 +1386,29 @@ __global__ void cr_rhs_to_row_kernel(const double* __restrict__ rhs, double* __r
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j < n) A[(size_t)j * lda + row] = rhs[j];
 }
+
+// The body of the three test / tool entries below: scratch for the reduction and the border workspace, the right-hand side into
+// local row `rhs_row` of every column, the solve (the dense top may run as the single-launch factorisation: the lock), x and
+// info back.
+gh_status arrow_solve_entry(gh_ctx* ctx, double* A_dev, int n, int lda, int n_band, int T, int rhs_row, bool compact, double* b_dev,
+                            int* info) {
+  const int nbr = n - n_band;
+  void* scratch = nullptr;
+  const size_t nd = gh_cr_dinv_doubles(n_band, T), nw = gh_cr_panel_doubles(n_band, T), nbw = gh_arrow_ws_doubles(ctx, n_band, T, nbr);
+  std::lock_guard<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device));
+  GH_TRY(gh_scratch(ctx, 256 + (nd + nw + nbw + (size_t)n) * sizeof(double), &scratch));
+  int* info_dev = (int*)scratch;
+  double* dinv = (double*)((char*)scratch + 256);
+  double* W = dinv + nd;
+  double* bws = W + nw;
+  double* x = bws + nbw;
+  GH_LAUNCH(ctx, "ba_rhs_row", cr_rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, (const double*)b_dev, A_dev, lda, rhs_row, n);
+  GH_TRY(gh_arrow_solve_dev_impl(ctx, A_dev, n_band, nbr, lda, T, dinv, W, bws, x, info_dev, false, true, nullptr, compact));
+  GH_HIP(ctx, hipMemcpyAsync(b_dev, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return GH_OK;
+}
 }  // namespace
 
 extern "C" gh_status gh_band_solve_dev(gh_ctx* ctx, double* A_dev, int n, int lda, int half_bandwidth, double* b_dev,
@@ -1436,21 +1420,7 @@ extern "C" gh_status gh_band_solve_dev(gh_ctx* ctx, double* A_dev, int n, int ld
   if (T == 0)
     return gh_set_error(ctx, GH_ERR_ARG, "gh_band_solve_dev: half-bandwidth %d of n = %d does not fit (<= %d, >= 4 superblocks)",
                         half_bandwidth, n, 3 * NBI);
-  void* scratch = nullptr;
-  const size_t nd = gh_cr_dinv_doubles(n, T), nw = gh_cr_panel_doubles(n, T), nbw = gh_arrow_ws_doubles(ctx, n, T, 0);
-  std::lock_guard<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device));  // (the dense top may run as the single-launch factorisation)
-  GH_TRY(gh_scratch(ctx, 256 + (nd + nw + nbw + (size_t)n) * sizeof(double), &scratch));
-  int* info_dev = (int*)scratch;
-  double* dinv = (double*)((char*)scratch + 256);
-  double* W = dinv + nd;
-  double* bws = W + nw;
-  double* x = bws + nbw;
-  GH_LAUNCH(ctx, "ba_rhs_row", cr_rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, (const double*)b_dev, A_dev, lda, n, n);
-  GH_TRY(gh_arrow_solve_dev_impl(ctx, A_dev, n, 0, lda, T, dinv, W, bws, x, info_dev, false, true, nullptr, false));
-  GH_HIP(ctx, hipMemcpyAsync(b_dev, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GH_OK;
+  return arrow_solve_entry(ctx, A_dev, n, lda, n, T, n, false, b_dev, info);
 }
 
 // Arrowhead SPD solve (test / tool entry, like gh_band_solve_dev): A_dev n x n column-major lower triangle (lda > n, overwritten),
@@ -1460,25 +1430,11 @@ extern "C" gh_status gh_arrow_solve_dev(gh_ctx* ctx, double* A_dev, int n, int l
   if (!ctx) return GH_ERR_ARG;
   GH_ENTER(ctx);
   GH_CHECK_ARG(ctx, A_dev && b_dev && info && n > 0 && lda > n && half_bandwidth >= 0 && n_band > 0 && n_band < n);
-  const int T = gh_cr_tiles(n_band, half_bandwidth), nbr = n - n_band;
+  const int T = gh_cr_tiles(n_band, half_bandwidth);
   if (T == 0)
     return gh_set_error(ctx, GH_ERR_ARG, "gh_arrow_solve_dev: half-bandwidth %d of n_band = %d does not fit (<= %d, >= 4 superblocks)",
                         half_bandwidth, n_band, 3 * NBI);
-  void* scratch = nullptr;
-  const size_t nd = gh_cr_dinv_doubles(n_band, T), nw = gh_cr_panel_doubles(n_band, T), nbw = gh_arrow_ws_doubles(ctx, n_band, T, nbr);
-  std::lock_guard<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device));  // (the dense corner may run as the single-launch factorisation)
-  GH_TRY(gh_scratch(ctx, 256 + (nd + nw + nbw + (size_t)n) * sizeof(double), &scratch));
-  int* info_dev = (int*)scratch;
-  double* dinv = (double*)((char*)scratch + 256);
-  double* W = dinv + nd;
-  double* bws = W + nw;
-  double* x = bws + nbw;
-  GH_LAUNCH(ctx, "ba_rhs_row", cr_rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, (const double*)b_dev, A_dev, lda, n, n);
-  GH_TRY(gh_arrow_solve_dev_impl(ctx, A_dev, n_band, nbr, lda, T, dinv, W, bws, x, info_dev, false, true, nullptr, false));
-  GH_HIP(ctx, hipMemcpyAsync(b_dev, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GH_OK;
+  return arrow_solve_entry(ctx, A_dev, n, lda, n_band, T, n, false, b_dev, info);
 }
 
 // ---------------------------------------------------------------- the compact layout through the C ABI (tests, tools)
@@ -1513,20 +1469,6 @@ extern "C" gh_status gh_arrow_solve_compact_dev(gh_ctx* ctx, double* A_dev, int 
                         half_bandwidth, n_band, 3 * NBI);
   int brow = 0;
   GH_CHECK_ARG(ctx, lda >= gh_cr_compact_lda(n_band, T, nbr, &brow));
-  void* scratch = nullptr;
-  const size_t nd = gh_cr_dinv_doubles(n_band, T), nw = gh_cr_panel_doubles(n_band, T), nbw = gh_arrow_ws_doubles(ctx, n_band, T, nbr);
-  std::lock_guard<std::mutex> flow_lock(gh_potrf_flow_mutex(ctx->device));
-  GH_TRY(gh_scratch(ctx, 256 + (nd + nw + nbw + (size_t)n) * sizeof(double), &scratch));
-  int* info_dev = (int*)scratch;
-  double* dinv = (double*)((char*)scratch + 256);
-  double* W = dinv + nd;
-  double* bws = W + nw;
-  double* x = bws + nbw;
   // the right-hand side into its row: local row brow + nbr of every column
-  GH_LAUNCH(ctx, "ba_rhs_row", cr_rhs_to_row_kernel, dim3(gh_div_up(n, 256)), dim3(256), 0, (const double*)b_dev, A_dev, lda, brow + nbr, n);
-  GH_TRY(gh_arrow_solve_dev_impl(ctx, A_dev, n_band, nbr, lda, T, dinv, W, bws, x, info_dev, false, true, nullptr, true));
-  GH_HIP(ctx, hipMemcpyAsync(b_dev, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  GH_HIP(ctx, hipMemcpyAsync(info, info_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GH_OK;
+  return arrow_solve_entry(ctx, A_dev, n, lda, n_band, T, brow + nbr, true, b_dev, info);
 }

@@ -7,7 +7,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.h"
+#include "dense_solve.h"
 
 namespace {
 
@@ -26,8 +26,6 @@ __global__ __launch_bounds__(256) void csr_prepare_kernel(const int32_t* __restr
 
 }  // namespace
 
-// keys_host: n_items keys in [0, n_keys); start_host: n_keys + 1 offsets; list_host: n_items item indices, grouped by key in
-// ascending key order, ascending inside a key.  Device memory comes from (and goes back to) hipMalloc: a setup-time call.
 gh_status gh_csr_build_dev(gh_ctx* ctx, const int32_t* keys_host, int n_items, int n_keys, int32_t* start_host, int32_t* list_host) {
   if (n_items <= 0 || n_keys <= 0) return gh_set_error(ctx, GH_ERR_ARG, "gh_csr_build_dev: empty input");
   int bits = 1;

@@ -161,6 +161,40 @@ def test_single_launch_factorisation_matches_the_launch_per_step_path(ctx, n, mo
     assert np.linalg.norm(A @ x1 - b) <= 1e-12 * np.linalg.norm(b)
 
 
+@pytest.mark.parametrize("n", [65, 130, 321])
+def test_potrf_solve_with_the_rhs_row_at_sizes_off_the_16_grid(ctx, n, monkeypatch):
+    """gh_potrf_solve_dev called directly with lda > n (the right-hand side rides as row n: extra_rows = 1) at n that are no
+    multiple of 16, two to six diagonal blocks: every buffer of the solve's workspace then starts where the shared layout
+    (dense_solve.h) puts it, on a 128-byte line.  Single-launch kernels on and off, each reproducible bit for bit, right by
+    the residual, and the paths agree."""
+    import ctypes as C
+    import torch
+    from gslam_amd import hip
+    rng = np.random.default_rng(n)
+    M = rng.standard_normal((n, 96))
+    A = M @ M.T / 96.0 + 2.0 * np.eye(n)
+    b = rng.standard_normal(n)
+    lda = (n + 1 + 15) // 16 * 16
+    cols = np.zeros((n, lda))  # row c = column c of the column-major device matrix; the rows n .. lda - 1 are scratch
+    cols[:, :n] = A
+
+    def solve(flow, chain):
+        monkeypatch.setenv("GSLAM_HIP_CHOL_FLOW", flow)
+        monkeypatch.setenv("GSLAM_HIP_BWD_CHAIN", chain)
+        dA, x, info = torch.from_numpy(cols).cuda(), torch.from_numpy(b).cuda(), C.c_int(-1)
+        ctx.check(hip.lib.gh_potrf_solve_dev(ctx.h, C.c_void_p(dA.data_ptr()), n, lda, C.c_void_p(x.data_ptr()), C.byref(info)))
+        ctx.sync()
+        assert info.value == 0
+        return x.cpu().numpy()
+
+    x_step = solve("0", "0")
+    for flow, chain in (("1", "1"), ("1", "0"), ("0", "1"), ("0", "0")):
+        x = solve(flow, chain)
+        assert x.tobytes() == solve(flow, chain).tobytes()
+        assert np.linalg.norm(A @ x - b) <= 1e-12 * np.linalg.norm(b)
+        assert np.abs(x - x_step).max() <= 1e-13 * np.abs(x_step).max()
+
+
 @pytest.mark.parametrize("cams", [3, 11, 32, 50, 64, 100])
 def test_ba_single_launch_factorisation_against_the_launch_path(ctx, cams, monkeypatch):
     """The right-hand-side row rides through the factorisation: inside the last diagonal tile (6 * cams not a multiple of

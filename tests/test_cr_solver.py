@@ -332,7 +332,7 @@ def test_arrow_solve_border_around_the_single_launch_threshold(ctx):
     from gslam_amd import ba
     cus = ctx.device_info()["cu_count"]
 
-    def fits(qn):  # chol.hip flow_groups, FL_MAXT = 6
+    def fits(qn):  # dense_solve.h dense_layout, kFlowMaxT = 6
         ntr = -(-(qn + 1) // 64)
         return 1 + max(ntr - 1, 0) + sum(-(-(i - 1) // 6) for i in range(2, ntr)) <= cus
     qn_last = max(q for q in range(64, 8192) if fits(q))

@@ -1,5 +1,6 @@
 // Wall-clock stamps inside the level-0 launches of the band solver (perf probe, not part of the product).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude tools/cr_stamp_probe.hip -o build/cr_stamp_probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -munsafe-fp-atomics -Iinclude tools/cr_stamp_probe.hip gslam_amd/csrc/chol.hip -o build/cr_stamp_probe
+// (chol.hip rides along as a second source: the band solver hands its dense top to the dense factorisation there)
 #define GH_CR_PROBE 1
 #include "../gslam_amd/csrc/chol_cr.hip"
 #include "../gslam_amd/csrc/ctx.hip"

@@ -17,16 +17,13 @@ int main(int argc, char** argv) {
   }
   gh_ctx* ctx = nullptr;
   if (gh_ctx_create(0, &ctx) != GH_OK) return 1;
-  double *dA, *dM, *dX;
-  int* dinfo;
-  unsigned* dflow;
-  const size_t words = gh_potrf_flow_words(ctx, n, 1);
-  if (!words) { printf("shape not eligible\n"); return 1; }
+  double* dA;
+  void* dwork;
+  const DenseLayout layout = dense_layout(n, 1, ctx->cu_count);
+  if (layout.flow_workers < 0) { printf("shape not eligible\n"); return 1; }
   hipMalloc(&dA, A.size() * 8);
-  hipMalloc(&dM, (size_t)((n + 63) / 64) * 4096 * 8);
-  hipMalloc(&dX, (size_t)2 * 64 * (n + 1) * 8);
-  hipMalloc(&dinfo, 4);
-  hipMalloc(&dflow, words * 4);
+  hipMalloc(&dwork, layout.bytes);
+  const DenseWork w = dense_carve(dwork, layout);
   const int nb = (n + 63) / 64;
   for (int rep = 0; rep < 3; ++rep) {
     hipMemcpy(dA, A.data(), A.size() * 8, hipMemcpyHostToDevice);
@@ -35,13 +32,13 @@ int main(int argc, char** argv) {
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     hipEventRecord(e0, ctx->stream);
-    if (gh_potrf_dev_impl(ctx, dA, n, lda, dinfo, 1, dM, dX, dflow, false, false) != GH_OK) { printf("launch failed: %s\n", ctx->last_error.c_str()); return 1; }
+    if (gh_potrf_dev_impl(ctx, dA, n, lda, 1, w, false, false) != GH_OK) { printf("launch failed: %s\n", ctx->last_error.c_str()); return 1; }
     hipEventRecord(e1, ctx->stream);
     hipDeviceSynchronize();
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);
     int info = -1;
-    hipMemcpy(&info, dinfo, 4, hipMemcpyDeviceToHost);
+    hipMemcpy(&info, w.info, 4, hipMemcpyDeviceToHost);
     std::vector<long long> st(128 * 8);
     hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_flow_trace), st.size() * 8);
     std::vector<long long> cy(128 * 8);
