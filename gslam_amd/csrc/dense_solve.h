@@ -150,3 +150,10 @@ int gh_ba_order_cameras(const gh_ba_problem* pr, std::vector<int32_t>& perm, int
 // keys_host: n_items keys in [0, n_keys); start_host: n_keys + 1 offsets; list_host: n_items item indices, grouped by key in
 // ascending key order, ascending inside a key.  Device memory comes from (and goes back to) hipMalloc: a setup-time call.
 gh_status gh_csr_build_dev(gh_ctx* ctx, const int32_t* keys_host, int n_items, int n_keys, int32_t* start_host, int32_t* list_host);
+// The device-side core of it, asynchronous on the context's stream: keys_dev as above but on the device (left unchanged);
+// *start_dev / *list_dev point into `work` (256-byte aligned, at least gh_csr_index_bytes(ctx, n_items, n_keys) bytes; 0 = the
+// size query failed), valid until the work space is reused.  *bad_dev (may be null): an int on the device, non-zero when a key
+// was outside [0, n_keys) -- start and list are then unspecified.  No allocation, no synchronisation.
+size_t gh_csr_index_bytes(gh_ctx* ctx, int n_items, int n_keys);
+gh_status gh_csr_index_dev(gh_ctx* ctx, const int32_t* keys_dev, int n_items, int n_keys, void* work, size_t work_bytes,
+                           const int32_t** start_dev, const int32_t** list_dev, const int** bad_dev);

@@ -4,7 +4,8 @@ findAffine3D (GSLAM/core/Estimator.h:100-147).  estimate_batch / estimate_pairs 
 (gh_ransac_batch_dev / gh_ransac_pairs_dev): torch tensors are only the device buffers, as in matcher.py.  two_view_batch /
 two_view_pairs (gh_two_view_batch_dev / gh_two_view_pairs_dev) go on from an essential matrix to the relative pose and the
 3-D points, batched and device-resident in the same way.  pnp_refine_batch / pnp_batch (gh_pnp_refine_batch_dev /
-gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba_pnp would on its inliers."""
+gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba_pnp would on its inliers.
+triangulate_tracks (gh_triangulate_tracks_dev) gives every map point of a gh_ba_problem its start from all of its observations."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,8 @@ from . import hip
 HOMOGRAPHY, AFFINE2D, FUNDAMENTAL, AFFINE3D, ESSENTIAL, SIM3, PLANE, PNP = 0, 1, 2, 3, 4, 5, 6, 7
 TWO_VIEW_OK, TWO_VIEW_NO_MODEL, TWO_VIEW_TOO_FEW, TWO_VIEW_AMBIGUOUS = 0, 1, 2, 3  # GH_TWO_VIEW_*: status per problem
 PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinement next to gh_ba_summary's 0 .. 3
+# GH_TRACK_*: status per point of triangulate_tracks
+TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_INCONSISTENT, TRACK_LOW_PARALLAX, TRACK_SKIPPED = 0, 1, 2, 3, 4, 5
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
@@ -260,6 +263,51 @@ def pnp_batch(ctx: hip.Context, xyz, xy, offsets, ransac_threshold, seed, inlier
     ctx.check(hip.lib.gh_pnp_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, C.c_double(ransac_threshold), C.c_uint64(seed),
                                        int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
                                        *(_p(out[k]) for k in out)))
+    return out
+
+
+def track_default_params():
+    """gh_track_default_params -> hip.TrackParams (min_parallax_cos, max_reproj, min_views, max_drops)."""
+    p = hip.TrackParams()
+    hip.lib.gh_track_default_params(C.byref(p))
+    return p
+
+
+def track_group_lanes():
+    """gh_track_group_lanes: the number of partial sums of gh_triangulate_tracks_dev (8)."""
+    return int(hip.lib.gh_track_group_lanes())
+
+
+def triangulate_tracks(ctx: hip.Context, cam_pose, obs_cam, obs_point, obs_xy, n_points, obs_use=None, point_select=None,
+                       params=None, point_xyz=None):
+    """gh_triangulate_tracks_dev, the call between pnp_batch and a BA graph.  cam_pose: n_cams x 7 float64 T_wc, obs_cam /
+    obs_point: n_obs int32, obs_xy: n_obs x 2 float64 (all cuda, laid out as in a gh_ba_problem); obs_use: n_obs uint8 or None
+    (all observations), point_select: n_points uint8 or None (all points); point_xyz: n_points x 3 float64 to be updated in
+    place (the points that are not selected keep their values) or None for a zeroed one.  -> dict of device tensors:
+    point_xyz n_points x 3, status n_points int32 (TRACK_*), n_good n_points int32, obs_good n_obs uint8; nothing is
+    synchronised."""
+    import torch
+    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() % 7 == 0
+    assert obs_xy.is_cuda and obs_xy.dtype == torch.float64 and obs_xy.is_contiguous()
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (obs_cam, obs_point))
+    n_cams, n_obs, n_points = cam_pose.numel() // 7, obs_cam.numel(), int(n_points)
+    assert obs_point.numel() == n_obs and obs_xy.numel() == 2 * n_obs and n_points >= 0
+    assert obs_use is None or (obs_use.is_cuda and obs_use.dtype == torch.uint8 and obs_use.is_contiguous() and obs_use.numel() == n_obs)
+    assert point_select is None or (point_select.is_cuda and point_select.dtype == torch.uint8 and point_select.is_contiguous() and
+                                    point_select.numel() == n_points)
+    dev = cam_pose.device
+    if point_xyz is None:
+        point_xyz = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
+    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
+    prm = params if params is not None else track_default_params()
+    out = {"point_xyz": point_xyz,
+           "status": torch.empty(n_points, dtype=torch.int32, device=dev),
+           "n_good": torch.empty(n_points, dtype=torch.int32, device=dev),
+           "obs_good": torch.empty(n_obs, dtype=torch.uint8, device=dev)}
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_triangulate_tracks_dev(ctx.h, p(cam_pose), n_cams, p(obs_cam), p(obs_point), p(obs_xy), n_obs, n_points,
+                                                _p(obs_use), _p(point_select), C.byref(prm), *(p(out[k]) for k in out)))
     return out
 
 

@@ -98,6 +98,12 @@ class PnpBatchSummary(C.Structure):
                 ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class TrackParams(C.Structure):
+    """gh_track_params (24 bytes) of gh_triangulate_tracks_dev."""
+    _fields_ = [("min_parallax_cos", C.c_double), ("max_reproj", C.c_double), ("min_views", C.c_int32),
+                ("max_drops", C.c_int32)]
+
+
 # Every symbol include/gslam_hip.h declares.  tests/test_abi.py checks header <-> this table <-> .so.
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SIGNATURES = {
@@ -210,6 +216,9 @@ SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _vp]),
     "gh_pnp_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _i, C.POINTER(BaOptions), _i, C.c_double,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_track_default_params": (None, [C.POINTER(TrackParams)]),
+    "gh_track_group_lanes": (C.c_int, []),
+    "gh_triangulate_tracks_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(TrackParams), _vp, _vp, _vp, _vp]),
     "gh_pg_solve": (C.c_int, [_vp, C.POINTER(PgProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_graph_solve": (C.c_int, [_vp, C.POINTER(GraphProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_align_sim3": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),

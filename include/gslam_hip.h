@@ -730,6 +730,68 @@ gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const double* xy_
                            int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
                            gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev);
 
+/* Map points from multi-view tracks, batched and device-resident: the step between gh_pnp_batch_dev (cameras registered) and
+ * gh_ba_graph_create (gh_ba_problem.point_xyz needs a start for every point).  Every pointer is a DEVICE pointer, the call is
+ * asynchronous on the context's stream, nothing is synchronised or allocated per call (scratch comes from the context).
+ * Inputs are laid out as in gh_ba_problem: cam_pose_dev n_cams x 7 T_wc [qx qy qz qw tx ty tz], taken as it stands (not
+ * renormalised); obs_cam_dev / obs_point_dev n_obs; obs_xy_dev n_obs x 2 on the z = 1 plane; obs_use_dev n_obs bytes or NULL = all
+ * observations; point_select_dev n_points bytes or NULL = all points.
+ *   track      of point p: the observations with obs_point == p in ascending observation index (the caller need not group or
+ *              sort them); the RANK of an observation is its position in that list.  Only USABLE observations are listed:
+ *              obs_use NULL or non-zero, 0 <= obs_cam < n_cams, 0 <= obs_point < n_points.  An index outside its range drops the
+ *              observation; it is never dereferenced.
+ *   arithmetic + - * / and sqrt in IEEE doubles, nothing fused, in the order written here.
+ *   ray        w = quat_rotate(q, (x, y, 1)):  uv = q.xyz X p, uv += uv, w_i = (p_i + qw * uv_i) + (q.xyz X uv)_i, with
+ *              (a X b)_0 = a1 * b2 - a2 * b1, (a X b)_1 = a2 * b0 - a0 * b2, (a X b)_2 = a0 * b1 - a1 * b0;
+ *              d = w * (1 / sqrt((w0 * w0 + w1 * w1) + w2 * w2));  P = I - d d^T: Pii = 1 - di * di, Pij = -(di * dj);
+ *              g_i = (Pi0 * t0 + Pi1 * t1) + Pi2 * t2.
+ *   sums       gh_track_group_lanes() = 8 partial sums, each from +0.0: partial j adds the (P, g) of the LIVE observations with
+ *              rank % 8 == j in ascending rank; total = ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)) entry by entry: A (the
+ *              sum of P, six entries) and b (the sum of g).  Every round sums anew over the live set; nothing is subtracted.
+ *   solve      A X = b by LDL^T without pivoting: D0 = A00; L10 = A01 / D0; L20 = A02 / D0; D1 = A11 - L10 * A01;
+ *              u = A12 - L20 * A01; L21 = u / D1; D2 = (A22 - L20 * A02) - L21 * u; every pivot must satisfy D > 1e-12 (a NaN does
+ *              not), else DEGENERATE; z0 = b0; z1 = b1 - L10 * z0; z2 = (b2 - L20 * z0) - L21 * z1; y_i = z_i / D_i; X2 = y2;
+ *              X1 = y1 - L21 * X2; X0 = (y0 - L10 * X1) - L20 * X2.
+ *   classify   a live observation at X, with the residual of gh_ba_solve's linearisation: Xc = quat_rotate((-qx, -qy, -qz, qw),
+ *              X - t); not good unless Xc[2] > 1e-9; iz = 1 / Xc[2]; r = (Xc[0] * iz - x, Xc[1] * iz - y); e = r0 * r0 + r1 * r1;
+ *              good when e <= max_reproj * max_reproj.  Drop key: e when the depth test passed and e is not a NaN, else +inf.
+ *              (A NaN that reaches only b, from a camera translation, leaves the pivots regular: X is NaN, no observation is
+ *              good, every key is +inf and the drop rule removes the lowest rank.)
+ *   per point  (selected)  1. live = its usable observations; fewer than min_views: TOO_FEW.
+ *              2. loop: sum and solve (failure: DEGENERATE); classify; all live observations good: leave the loop; drops ==
+ *                 max_drops or the live set has min_views members: INCONSISTENT; else drop the live observation with the largest
+ *                 key (lowest rank on ties), ++drops.
+ *              3. parallax on the final live set: f = the live observation of lowest rank; cos_k = (df0 * dk0 + df1 * dk1) +
+ *                 df2 * dk2 for every other live k; no cos_k < min_parallax_cos: LOW_PARALLAX (all rays within theta of the
+ *                 first: every pair within 2 theta).  4. else OK.
+ * Outputs, ALL written for every point and observation (dirty buffers never show): status_dev n_points (GH_TRACK_*);
+ * point_xyz_dev n_points x 3: X for OK points, zeros for every other selected point, NOT written for SKIPPED points (in/out:
+ * existing map points survive); n_good_dev n_points: the size of the final live set for OK points, else 0; obs_good_dev n_obs
+ * bytes: 1 exactly at the final live observations of OK points, 0 everywhere else (a bad index included).  Counts are integer
+ * and the floating-point order is fixed: the same bits on every run.  tests/tracks_restate.py restates all of it.
+ * GH_ERR_ARG: ctx or params NULL; n_cams, n_obs or n_points negative; min_parallax_cos outside (0, 1]; max_reproj negative or
+ * NaN; min_views < 2; max_drops < 0; a NULL among cam_pose, obs_cam, obs_point, obs_xy or the four outputs.  n_points == 0:
+ * GH_OK, nothing is launched.  n_obs == 0 with n_points > 0: every selected point is TOO_FEW. */
+#define GH_TRACK_OK 0
+#define GH_TRACK_TOO_FEW 1        /* fewer than min_views usable observations */
+#define GH_TRACK_DEGENERATE 2     /* the 3 x 3 system has no regular solution (parallel rays, a NaN) */
+#define GH_TRACK_INCONSISTENT 3   /* some live observation still fails after the allowed drops */
+#define GH_TRACK_LOW_PARALLAX 4
+#define GH_TRACK_SKIPPED 5        /* point_select says: not this point */
+typedef struct gh_track_params {  /* 24 bytes */
+  double min_parallax_cos;  /* 0.9998: ORB-SLAM's bound when it creates map points */
+  double max_reproj;        /* 0.004 normalised units, as gh_two_view_params */
+  int32_t min_views;        /* 2 */
+  int32_t max_drops;        /* 2 */
+} gh_track_params;
+void gh_track_default_params(gh_track_params* p);
+int gh_track_group_lanes(void);   /* host only: 8, the number of partial sums (above); lets tests sit on the boundary */
+gh_status gh_triangulate_tracks_dev(gh_ctx* ctx, const double* cam_pose_dev, int n_cams, const int32_t* obs_cam_dev,
+                                    const int32_t* obs_point_dev, const double* obs_xy_dev, int n_obs, int n_points,
+                                    const uint8_t* obs_use_dev, const uint8_t* point_select_dev,
+                                    const gh_track_params* params, double* point_xyz_dev, int32_t* status_dev,
+                                    int32_t* n_good_dev, uint8_t* obs_good_dev);
+
 /* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
  * information (row-major, [v, w] order of SE3::exp) of the second camera's pose relative to the first held fixed -- the
