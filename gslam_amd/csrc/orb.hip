@@ -490,6 +490,13 @@ __device__ __forceinline__ const uint4* fast_tile_src(const LevelView& lv, int f
 // (select_weak_cells) and every reader takes the mark for an empty cell (cell_entries).
 constexpr uint32_t kWeakCell = 0xFFFFFFFFu;
 
+// The threshold phase A runs a (level, slot) at in the adaptive call number `epoch`, from the slot's advice word (hint_next:
+// T | hold << 8 | penalty << 16).  A slot with a penalty is cautious: it goes above ini_th in calls of even epoch only, so
+// that the call in between, at ini_th, learns whether any slot of the plan mispredicted before the next attempt.
+__device__ __forceinline__ int hint_threshold(uint32_t word, uint32_t epoch, int ini_th) {
+  return ((word >> 16) & 255u) != 0u && (epoch & 1u) != 0u ? ini_th : (int)(word & 255u);
+}
+
 // The cell stage (oracle steps 3, 4), by one wave: compaction of the cell's scored pixels, 3 x 3 strict NMS, the strong-corner
 // filter, the rank by (score desc, raster asc) and the cap.  sc = the score byte of the cell's first pixel in an LDS score
 // patch of PITCH bytes per row (dword aligned, a 1-px halo around the cell); list2 (1024 entries) and list (256) are wave-private
@@ -642,13 +649,18 @@ __device__ __forceinline__ int fast_cell_stage(const uint8_t* sc, uint16_t* list
 // comes out as before from far fewer scored pixels.  A cell without any such maximum is marked kWeakCell and redone at
 // min_th by orb_select (select_weak_cells), which reads every record anyway; a tile in which nothing passes the compass test
 // at ini_th is redone at min_th on the spot, while its image is still in LDS.
+// The threshold hint: phase A may run at any T with ini_th <= T <= 255 in place of ini_th -- hint_threshold of hint[frame * kMaxL] (the
+// plan's advice for this level and batch slot, written by orb_select of the previous call) or, hint == null, th_a.  The same
+// argument holds with T for ini_th; what a record then lacks, its entries in (ini_th, T], orb_select either proves invisible
+// or redoes (select_weak_cells).  The flat-tile shortcut needs a complete record: T == ini_th only.
 template <bool PLANE, bool TWO_PHASE>
 __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th, bool two,
+                                                const uint32_t* __restrict__ hint, int th_a, uint32_t epoch,
                                                 uint32_t* __restrict__ cell_cnt, uint32_t* __restrict__ cell_ent,
                                                 int cells_per_frame, int cell_off, int n_frames, const NextLevel& nx,
                                                 uint32_t* __restrict__ dbg, int tile_id) {
   bool phase_a = TWO_PHASE && two;
-  int score_th = phase_a ? ini_th : min_th;  // scores at or below it are stored as 0
+  int score_th = min_th;  // scores at or below it are stored as 0 (phase A: T, once the frame is known)
   // Pass 1 covers a window row with 17 aligned dwords (window cols -2 .. 65) and the score tile is FLAT with 68 bytes
   // per row: byte 68 sy + 3 + sx, so (item, pixel k) lands at 4 item + 1 + k.  Cols -2 / -1 of a row share their bytes with
   // cols 66 / 67 of the row above; nothing ever reads them (NMS looks at cols 0 .. 65 only).
@@ -671,6 +683,12 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   const int nbx = (ncx + 1) >> 1, nby = (ncy + 1) >> 1;
   int frame, bx, by;
   fast_tile_coords(nx, nbx, nby, tile_id, frame, bx, by);
+  if constexpr (TWO_PHASE) {
+    if (phase_a) {  // (frame is workgroup-uniform: one scalar load)
+      if (hint != nullptr) th_a = hint_threshold(hint[__builtin_amdgcn_readfirstlane(frame) * kMaxL], epoch, ini_th);
+      score_th = th_a;
+    }
+  }
 #ifdef GH_ORB_PHASES
   if (threadIdx.x == 0) {
     const unsigned int slot_ = (unsigned int)(frame * cells_per_frame + cell_off + by * nbx + bx);
@@ -776,8 +794,9 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   if constexpr (TWO_PHASE) {
     // A flat tile: nothing passes the compass test at ini_th, so all four cells would be marked.  The image tile is still intact:
     // pass 1 again at min_th and the tile is finished single-phase, without markers (low-texture input then costs one more
-    // pass 1 on tiles that have no pass 2, instead of a second phase for every cell).  nq is block-uniform.
-    if (phase_a && nq == 0) {
+    // pass 1 on tiles that have no pass 2, instead of a second phase for every cell).  nq is block-uniform.  (Above ini_th an
+    // empty queue says nothing about the scores in (ini_th, T]: the four cells are marked, as the cell stage does on its own.)
+    if (phase_a && nq == 0 && th_a == ini_th) {
       phase_a = false;
       score_th = min_th;
       __syncthreads();  // (every thread has read q_count == 0 before a wave adds to it again)
@@ -858,7 +877,7 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   int nz, kept;
   if (phase_a) {
     kept = fast_cell_stage<kScoreW, false>(sc, list2, lists[wv], lane, ini_th, rec, ovf, dbg, &nz);
-    // no maximum above ini_th in the cell: its record needs the scores down to min_th (orb_select, select_weak_cells)
+    // no maximum above T in the cell: its record needs the scores down to min_th (orb_select, select_weak_cells)
     if (lane == 0) rec[0] = kept == 0 ? kWeakCell : (uint32_t)kept;
   } else {
     kept = fast_cell_stage<kScoreW, true>(sc, list2, lists[wv], lane, ini_th, rec, ovf, dbg, &nz);
@@ -880,13 +899,14 @@ __global__ __launch_bounds__(256, GH_FAST_WAVES) void fast_cells_kernel(LevelVie
                                                          uint32_t* __restrict__ cell_cnt,
                                                          uint32_t* __restrict__ cell_ent, int cells_per_frame,
                                                          int cell_off, int n_frames, NextLevel nx,
-                                                         uint32_t* __restrict__ dbg, int two_phase) {
+                                                         uint32_t* __restrict__ dbg, int two_phase,
+                                                         const uint32_t* __restrict__ hint, int th_a, uint32_t epoch) {
   const int total = ((ncx + 1) >> 1) * ((ncy + 1) >> 1) * n_frames;
   const int tile_id = xcd_strip_tile(blockIdx.x, total);
   if (tile_id >= total) return;
   // (the score plane of the quadtree mode wants S itself: single-phase)
-  fast_cells_tile<PLANE, !PLANE>(lv, ncx, ncy, min_th, ini_th, two_phase != 0, cell_cnt, cell_ent, cells_per_frame, cell_off, n_frames, nx,
-                                 dbg, tile_id);
+  fast_cells_tile<PLANE, !PLANE>(lv, ncx, ncy, min_th, ini_th, two_phase != 0, hint, th_a, epoch, cell_cnt, cell_ent, cells_per_frame, cell_off,
+                                 n_frames, nx, dbg, tile_id);
 }
 
 // Every level in ONE launch, over a pyramid that exists already (stand-alone resize launches): what a small call wants --
@@ -905,7 +925,7 @@ __global__ __launch_bounds__(256) void fast_cells_all_kernel(AllLevels A, int mi
   for (int k = 1; k < A.n_levels; ++k)
     if ((int)blockIdx.x >= A.tile_start[k]) l = k;
   const NextLevel none{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-  fast_cells_tile<false, false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, false, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l],
+  fast_cells_tile<false, false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, false, nullptr, ini_th, 0u, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l],
                                 n_frames, none, dbg, (int)blockIdx.x - A.tile_start[l]);
 }
 
@@ -996,6 +1016,48 @@ struct SelectWeak {
   LevelView lv[kMaxL];
   int min_th, ini_th, two_phase;
 };
+
+// The threshold advice of one (level, batch slot): what phase A of the NEXT call on the slot runs at, and the hold-off.
+//   bits 0 .. 7    T, ini_th <= T <= 255
+//   bits 8 .. 15   hold: calls that stay at ini_th whatever the cut says
+//   bits 16 .. 23  penalty: the hold that the next misprediction earns is twice this (at least 2, at most kHintMaxHold)
+// A misprediction is a call at T > ini_th whose (level, frame) had fewer T-strong cells than its quota: the whole level was
+// redone by its select workgroup.  Each one doubles the penalty; each call that ran above ini_th and held takes 1 off.
+// While it has a penalty a slot goes above ini_th in every other call only (hint_threshold).
+// The redo is one workgroup's work, so ONE misprediction anywhere in a call sets the time of the whole call: slots that
+// mispredict at different calls would keep every call slow.  Hence the plan-wide signal: two more words behind the advice,
+// word (epoch & 1) = the epoch (the plan's count of adaptive calls) of the last call of that parity in which some workgroup
+// mispredicted.  A call reads the OTHER word -- complete since the previous call ended, written by nobody during this one -- and
+// every (level, slot) that is not holding takes a misprediction of the previous call for its own, with a hold one call
+// shorter, since it learns of it one call later; one that is holding keeps at least that hold, without a new penalty.  So
+// the holds of a plan end in the same call, and slots that went wrong at different calls fall into step.
+constexpr int kHintMaxHold = 64;
+constexpr uint32_t kHintFirstEpoch = 256;  // (above every ini_th, which is what the memset at plan creation leaves in the two words)
+// T for the next call from the bin of this call's entry number `quota` (select_kernel: rank * 256 + 255 - score; kHistBins =
+// fewer entries exist): with that entry in rank 0 at s* > ini_th every threshold below s* leaves `quota` strong cells on the
+// same image; kHintNum / kHintDen of the way there.
+constexpr int kHintNum = 2, kHintDen = 3;
+__host__ __device__ inline int hint_from_cut(int cut, int ini_th) {
+  const int s = 255 - cut;
+  return cut < 256 && s > ini_th ? ini_th + (s - ini_th) * kHintNum / kHintDen : ini_th;
+}
+// (t_used: what this call ran at, hint_threshold)
+__host__ __device__ inline uint32_t hint_next(uint32_t word, int t_used, int cut, bool mispredicted, bool others, int ini_th) {
+  int t = t_used, hold = (int)((word >> 8) & 255u), pen = (int)((word >> 16) & 255u);
+  if (mispredicted || (others && hold == 0)) {
+    pen = pen == 0 ? 2 : (2 * pen > kHintMaxHold ? kHintMaxHold : 2 * pen);
+    hold = mispredicted ? pen : pen - 1;
+    t = ini_th;
+  } else if (hold > 0) {
+    --hold;
+    if (others && hold < pen - 1) hold = pen - 1;
+    t = ini_th;
+  } else {
+    if (t > ini_th && pen > 0) --pen;
+    t = hint_from_cut(cut, ini_th);
+  }
+  return (uint32_t)t | ((uint32_t)hold << 8) | ((uint32_t)pen << 16);
+}
 constexpr int kWeakImgW = 64, kWeakImgH = 40;  // image patch: rows y0 - 4 .. y0 + 35, four aligned 16-byte columns from x0 - 19
 constexpr int kWeakScoreW = 40, kWeakWin = 34; // score patch: window col sx (cell + 1 px halo) at byte sx + 3, 34 rows
 constexpr int kWeakImgBytes = kWeakImgW * kWeakImgH, kWeakScoreBytes = kWeakWin * kWeakScoreW + 16;
@@ -1095,16 +1157,21 @@ __device__ __forceinline__ void select_weak_cell(const LevelView& lv, int b, int
 // first entry scores above ini_th; a cell with any entry above ini_th holds only such entries (oracle step 4), so the first
 // one decides.  The score test is needed: the cells of a tile that the flat-tile shortcut of orb_fast_cells finished single-phase
 // carry ordinary counts and scores <= ini_th.
+// Phase A at T > ini_th (th_a; the threshold hint, fast_cells_tile): all of the above holds with T for ini_th -- with at least
+// `quota` T-strong cells the first `quota` entries are rank-0 entries above T, which every record holds with their true ranks.
+// With fewer, nothing can be said cell by cell: an unmarked record lacks its entries in (ini_th, T].  Then EVERY cell of the
+// level is redone, marked or not, and the function returns true (a misprediction: select_kernel, hint_next).
 template <bool ONE_ROUND>
-__device__ __forceinline__ void select_weak_cells(const SelectWeak& w, int l, int b, int ncells, int ncx, int quota, uint32_t* rec,
+__device__ __forceinline__ bool select_weak_cells(const SelectWeak& w, int th_a, int l, int b, int ncells, int ncx, int quota, uint32_t* rec,
                                                   uint32_t* ent, uint8_t* lds, int* wave_tot, uint32_t* dbg) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   uint16_t* marked = reinterpret_cast<uint16_t*>(lds + 4 * kWeakWaveBytes);
   int* n_marked = reinterpret_cast<int*>(lds + 4 * kWeakWaveBytes + 2 * kWeakRound);
   const LevelView lv = w.lv[l];
   const bool one_round = ONE_ROUND || ncells <= kWeakRound;
+  const bool redo_all = th_a > w.ini_th;  // (once the count below has come out short)
   // {count, first entry} of a cell -> 1 if the cell is strong
-  auto strong_cell = [&](uint2 r) { return r.x - 1u < (uint32_t)kCap && (int)((r.y >> 10) & 255u) > w.ini_th ? 1 : 0; };
+  auto strong_cell = [&](uint2 r) { return r.x - 1u < (uint32_t)kCap && (int)((r.y >> 10) & 255u) > th_a ? 1 : 0; };
   int strong = 0;
   if (!one_round)
     for (int c = tid; c < ncells; c += 256) strong += strong_cell(*reinterpret_cast<const uint2*>(rec + (size_t)c * kCellRec));
@@ -1124,15 +1191,16 @@ __device__ __forceinline__ void select_weak_cells(const SelectWeak& w, int l, in
     __syncthreads();
     // workgroup-uniform, and nothing of phase B has touched a record yet.  (wave_tot lies outside lds: the caller may clear the
     // histogram at once; its next writer, block_excl_scan, comes after two more barriers.)
-    if (c0 == 0 && wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3] >= quota) return;
-    const int n = *n_marked;
+    if (c0 == 0 && wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3] >= quota) return false;
+    const int n = redo_all ? c1 - c0 : *n_marked;
     for (int i = wv; i < n; i += 4) {
-      const int c = c0 + marked[i];
+      const int c = c0 + (redo_all ? i : (int)marked[i]);
       const int cy = c / ncx, cx = c - cy * ncx;
       select_weak_cell(lv, b, cx, cy, w.min_th, w.ini_th, lds + wv * kWeakWaveBytes, lane, rec + (size_t)c * kCellRec, ent + (size_t)c * kCap, dbg);
     }
     __syncthreads();
   }
+  return redo_all;
 }
 
 // CACHED (levels of at most kSelCached * 256 cells): every thread fetches the records of ALL its cells up front -- one
@@ -1143,12 +1211,13 @@ constexpr int kSelCached = 8;
 template <bool CACHED>
 __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cell_cnt, uint32_t* cell_ent, int cells_per_frame,
                                                      int K, SelKp* __restrict__ sel, int32_t* __restrict__ level_cnt,
-                                                     uint32_t* __restrict__ dbg, int level0, SelectWeak weak) {
+                                                     uint32_t* __restrict__ dbg, int level0, SelectWeak weak, uint32_t* hints, int th_a,
+                                                     uint32_t* plan_mis, uint32_t epoch) {
   // bin k lives at k + (k >> 5): a thread's 32 consecutive bins (tid * 32 + i) then fall into different banks for
   // different threads (unpadded, all 64 lanes of a wave hit bank i)
   __shared__ __attribute__((aligned(16))) uint32_t hist[kHistBins + kHistBins / 32];
   __shared__ int wave_tot[4];
-  __shared__ int s_cut, s_m;
+  __shared__ int s_cut, s_m, s_qbin;
   const int l = level0 + blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int ncells = a.ncells[l], quota = a.quota[l];
   const uint32_t* rec = cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec;
@@ -1160,9 +1229,16 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cel
   // phase B of the two-phase detector first (or the count that shows it is not needed): its patches and queues alias hist[], which is
   // cleared only after it
   static_assert(sizeof(hist) >= 4 * kWeakWaveBytes + 2 * kWeakRound + 16, "phase B fits the histogram");
+  // (the threshold phase A ran at: fast_cells(l) of this call read the same word, and nobody has written it since)
+  // hints: the plan's threshold advice, one word per (batch slot, level); null: every (level, frame) ran at th_a
+  uint32_t* const hint = weak.two_phase != 0 && hints != nullptr ? hints + (b * kMaxL + l) : nullptr;
+  const uint32_t hint_word = hint != nullptr ? *hint : (uint32_t)th_a;
+  bool mispredicted = false;
   if (weak.two_phase != 0)
-    select_weak_cells<CACHED>(weak, l, b, ncells, a.ncx[l], quota, cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec,
-                              cell_ent + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCap, reinterpret_cast<uint8_t*>(hist), wave_tot, dbg);
+    mispredicted = select_weak_cells<CACHED>(weak, hint != nullptr ? hint_threshold(hint_word, epoch, weak.ini_th) : th_a, l, b, ncells, a.ncx[l], quota,
+                                             cell_cnt + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCellRec,
+                                             cell_ent + ((size_t)b * cells_per_frame + a.cell_off[l]) * kCap, reinterpret_cast<uint8_t*>(hist),
+                                             wave_tot, dbg);
   uint4 ra[kSelCached], rb[kSelCached];
   if (CACHED) {
 #pragma unroll
@@ -1202,18 +1278,22 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cel
   if (tid == 0) {
     s_cut = kHistBins;  // everything selected
     s_m = 0;
+    s_qbin = kHistBins;  // fewer than `quota` entries
   }
   __syncthreads();
-  if (total > quota && excl < quota && excl + mine >= quota) {
+  if (excl < quota && excl + mine >= quota) {
     int run = excl;
     for (int i = 0; i < kPer; ++i) {
       const int hv = (int)hist[tid * (kPer + 1) + i];
       if (run + hv >= quota) {
-        s_cut = tid * kPer + i;
-        s_m = quota - run;
-        if (dbg != nullptr) {
-          atomicAdd(&dbg[kDbgSelCut], 1u);
-          if (quota - run < hv) atomicAdd(&dbg[kDbgSelTieSplit], 1u);
+        s_qbin = tid * kPer + i;  // the bin of entry number `quota`
+        if (total > quota) {
+          s_cut = tid * kPer + i;
+          s_m = quota - run;
+          if (dbg != nullptr) {
+            atomicAdd(&dbg[kDbgSelCut], 1u);
+            if (quota - run < hv) atomicAdd(&dbg[kDbgSelTieSplit], 1u);
+          }
         }
         break;
       }
@@ -1222,6 +1302,15 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a, uint32_t* cel
   }
   __syncthreads();
   const int cut = s_cut, m = s_m;
+  // The advice for the next call on this (level, slot), from the bin of entry number `quota`.  In place: fast_cells(l) of this
+  // call has finished, and a plan's workspace admits one call at a time.  That entry does not depend on the T the records were
+  // cut at: above ini_th this point is reached with at least `quota` T-strong cells or with every record redone, and in both
+  // cases the first `quota` entries are exact.  (Whether MORE than `quota` entries exist does depend on it, so it is not asked.)
+  if (hint != nullptr && tid == 0) {
+    if (mispredicted) plan_mis[epoch & 1u] = epoch;  // (every writer of this call stores the same value)
+    const bool others = plan_mis[(epoch - 1u) & 1u] == epoch - 1u;  // some (level, slot) of the previous call
+    *hint = hint_next(hint_word, hint_threshold(hint_word, epoch, weak.ini_th), s_qbin, mispredicted, others, weak.ini_th);
+  }
   // slots: traverse cells in order, chunks of 256 with carries
   int tie_carry = 0, out_carry = 0;
   SelKp* out = sel + (size_t)b * K + a.quota_off[l];
@@ -1887,6 +1976,9 @@ struct gh_orb_plan {
   uint32_t* tabs = nullptr;
   uint32_t* dbg = nullptr;  // kDbgCount counters, allocated by gh_orb_plan_debug_counters(enable)
   bool dbg_on = false;
+  uint32_t* hint = nullptr;  // max_batch x kMaxL words of threshold advice (hint_word), every T = ini_th at creation
+  int hint_mode = GH_ORB_HINT_ADAPTIVE, hint_value = 0;  // gh_orb_plan_set_threshold_hint
+  uint32_t hint_epoch = kHintFirstEpoch;  // adaptive calls so far (+ kHintFirstEpoch): the plan-wide misprediction signal (hint_next)
   // host staging for gh_orb_extract_host
   // single-frame host entry point: device staging (image; count | keypoints | descriptors in ONE block so that the
   // results come back in one copy) and a pinned host mirror of the result block
@@ -1940,7 +2032,7 @@ extern "C" void gh_orb_plan_destroy(gh_orb_plan* p) {
   GH_ENTER(c);
   hipStreamSynchronize(c->stream);
   void* ptrs[] = {p->pyr, p->cell_cnt, p->cell_ent, p->sel, p->level_cnt, p->d_pattern, p->d_base_pattern, p->d_dir, p->tabs,
-                  p->stage_img, p->stage_out, p->dbg, p->score_plane};
+                  p->stage_img, p->stage_out, p->dbg, p->score_plane, p->hint};
   for (void* q : ptrs)
     if (q) hipFree(q);
   if (p->stage_host) hipHostFree(p->stage_host);
@@ -2159,6 +2251,7 @@ static gh_status plan_allocate(gh_orb_plan* p, size_t tab_words) {
   GH_TRY(plan_alloc(p, sizeof(GH_ORB_PATTERN), (void**)&p->d_pattern));
   GH_TRY(plan_alloc(p, 256 * 4, (void**)&p->d_base_pattern));
   GH_TRY(plan_alloc(p, sizeof(GH_ORB_DIR), (void**)&p->d_dir));
+  GH_TRY(plan_alloc(p, (B * kMaxL + 2) * sizeof(uint32_t), (void**)&p->hint));  // (+ the two words of the plan-wide signal)
   return plan_alloc(p, tab_words * sizeof(uint32_t), (void**)&p->tabs);
 }
 
@@ -2308,6 +2401,8 @@ static gh_status plan_upload(gh_orb_plan* p, const std::vector<uint32_t>& htab) 
   GH_TRY(upload_pattern(p, &GH_ORB_PATTERN[0][0][0]));
   memcpy(p->base_pattern, &GH_ORB_PATTERN[0][0][0], sizeof(p->base_pattern));  // bin 0 = the unrotated tests
   GH_TRY(gh_dev_upload(ctx, p->d_base_pattern, p->base_pattern, sizeof(p->base_pattern)));
+  // no advice yet: T = ini_th, no hold, no penalty -- the first call on a slot does what a plan without hints does
+  GH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)p->hint, p->prm.ini_th_fast, (size_t)p->max_batch * kMaxL + 2, ctx->stream));
   return gh_dev_upload(ctx, p->d_dir, GH_ORB_DIR, sizeof(GH_ORB_DIR));
 }
 
@@ -2371,13 +2466,14 @@ struct OrbEnv {
   bool all_levels;     // GSLAM_HIP_ORB_ALL_LEVELS=0: small calls take the per-level schedule too
   int select_overlap;  // GSLAM_HIP_ORB_SELECT_OVERLAP=0 / 1 forces the select overlap off / on; -1 (unset): by size
   bool select_cached;  // GSLAM_HIP_ORB_SELECT_CACHED=0: stream the cell records
+  bool hint;           // GSLAM_HIP_ORB_HINT=0: no plan applies or updates adaptive threshold advice (gh_orb_plan_set_threshold_hint)
 };
 static const OrbEnv& orb_env() {
   static const OrbEnv env = [] {
     auto is0 = [](const char* e) { return e && e[0] == '0'; };
     const char* ov = getenv("GSLAM_HIP_ORB_SELECT_OVERLAP");
     return OrbEnv{!is0(getenv("GSLAM_HIP_ORB_GRAPH")), !is0(getenv("GSLAM_HIP_ORB_ALL_LEVELS")), ov ? (ov[0] == '0' ? 0 : 1) : -1,
-                  !is0(getenv("GSLAM_HIP_ORB_SELECT_CACHED"))};
+                  !is0(getenv("GSLAM_HIP_ORB_SELECT_CACHED")), !is0(getenv("GSLAM_HIP_ORB_HINT"))};
   }();
   return env;
 }
@@ -2392,6 +2488,12 @@ struct OrbSchedule {
   bool sel_cached;  // select_kernel<true>: no level has more cells than its registers hold
   bool zero_copy0;  // level 0 is read from the caller's buffer, not staged through the plan's slab
   bool two_phase;   // kPerLevel: fast_cells scores at ini_th and marks the cells without a strong corner, select redoes those at min_th
+  // two_phase: the threshold of phase A is the plan's advice per (level, slot), which orb_select updates (hint_adaptive), or th_a
+  // for all of them (ini_th, or the forced value).  The branch census of the debug counters describes the call at ini_th: while
+  // it is on, adaptive advice is neither applied nor updated.
+  bool hint_adaptive;
+  int th_a;
+  uint32_t hint_epoch;  // hint_adaptive: this call's number among the plan's adaptive calls
 };
 
 // The side stream of the select overlap and its events, created at the first call that wants them.  *ok = false when the
@@ -2434,6 +2536,9 @@ static gh_status orb_schedule(gh_orb_plan* p, int batch, const uint8_t* gray_dev
   // (at ini_th <= min_th the scores above ini_th would hold some that the specification zeroes: single-phase.  plan_check_params
   // refuses ini_th < min_th, so equality is the only such case that reaches this point)
   s->two_phase = s->kind == OrbSchedule::kPerLevel && p->prm.ini_th_fast > p->prm.min_th_fast;
+  s->hint_adaptive = s->two_phase && p->hint_mode == GH_ORB_HINT_ADAPTIVE && env.hint && !p->dbg_on;
+  s->hint_epoch = s->hint_adaptive ? ++p->hint_epoch : 0u;
+  s->th_a = s->two_phase && p->hint_mode == GH_ORB_HINT_FORCED && p->hint_value > p->prm.ini_th_fast ? p->hint_value : p->prm.ini_th_fast;
   return GH_OK;
 }
 
@@ -2513,12 +2618,15 @@ static gh_status launch_select(const OrbCall& c, const SelectArgs& sa, int l0, i
   weak.min_th = p->prm.min_th_fast;
   weak.ini_th = p->prm.ini_th_fast;
   weak.two_phase = c.s.two_phase ? 1 : 0;
+  uint32_t* const hints = c.s.hint_adaptive ? p->hint : nullptr;
   if (c.s.sel_cached)
     GH_LAUNCH(ctx, "orb_select", select_kernel<true>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak);
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak, hints, c.s.th_a,
+              p->hint + (size_t)p->max_batch * kMaxL, c.s.hint_epoch);
   else
     GH_LAUNCH(ctx, "orb_select", select_kernel<false>, dim3(nl, c.batch), dim3(256), 0, sa, p->cell_cnt, p->cell_ent,
-              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak);
+              p->cells_per_frame, p->prm.n_features, p->sel, p->level_cnt, c.dbg, l0, weak, hints, c.s.th_a,
+              p->hint + (size_t)p->max_batch * kMaxL, c.s.hint_epoch);
   return GH_OK;
 }
 
@@ -2550,10 +2658,11 @@ static gh_status fast_level(const OrbCall& c, int l, bool plane) {
     nx.plane_frame_stride = p->plane_slab;
     nx.plane_pitch = p->plane_pitch[l];
     GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, 0);
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, 0, nullptr, 0, 0u);
   } else {
     GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, c.s.two_phase ? 1 : 0);
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, c.s.two_phase ? 1 : 0,
+              c.s.hint_adaptive ? p->hint + l : nullptr, c.s.th_a, c.s.hint_epoch);
   }
   return GH_OK;
 }
@@ -2904,6 +3013,29 @@ extern "C" gh_status gh_orb_plan_debug_counters(gh_orb_plan* p, int enable, uint
     GH_HIP(ctx, hipMemsetAsync(p->dbg, 0, kDbgCount * sizeof(uint32_t), ctx->stream));
   }
   p->dbg_on = enable != 0;
+  return GH_OK;
+}
+
+extern "C" gh_status gh_orb_plan_set_threshold_hint(gh_orb_plan* p, int mode, int value) {
+  if (!p) return GH_ERR_ARG;
+  gh_ctx* ctx = p->ctx;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, mode == GH_ORB_HINT_ADAPTIVE || mode == GH_ORB_HINT_OFF || mode == GH_ORB_HINT_FORCED);
+  GH_CHECK_ARG(ctx, value >= 0 && value <= 255);
+  p->hint_mode = mode;
+  p->hint_value = mode == GH_ORB_HINT_FORCED ? value : 0;
+  return GH_OK;
+}
+
+extern "C" gh_status gh_orb_plan_debug_hints(gh_orb_plan* p, uint8_t* out_host) {
+  if (!p) return GH_ERR_ARG;
+  gh_ctx* ctx = p->ctx;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, out_host != nullptr);
+  std::vector<uint32_t> words((size_t)p->max_batch * kMaxL);
+  GH_HIP(ctx, hipMemcpyAsync(words.data(), p->hint, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  GH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < words.size(); ++i) out_host[i] = (uint8_t)(words[i] & 255u);
   return GH_OK;
 }
 

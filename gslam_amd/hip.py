@@ -148,6 +148,8 @@ SIGNATURES = {
     "gh_orb_plan_set_pattern": (C.c_int, [_vp, _vp]),
     "gh_orb_plan_set_steering": (C.c_int, [_vp, _i]),
     "gh_orb_plan_set_distribution": (C.c_int, [_vp, _i]),
+    "gh_orb_plan_set_threshold_hint": (C.c_int, [_vp, _i, _i]),
+    "gh_orb_plan_debug_hints": (C.c_int, [_vp, _vp]),
     "gh_orb_stream_plan": (_vp, [_vp]),
     "gh_orb_plan_level": (C.c_int, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "gh_orb_plan_device_bytes": (_sz, [_vp]),

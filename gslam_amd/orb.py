@@ -66,6 +66,20 @@ class OrbExtractor:
         """0: 32 x 32 cells + rank order (default); 1: ORB-SLAM's cells + quadtree.  See gh_orb_plan_set_distribution."""
         self.ctx.check(hip.lib.gh_orb_plan_set_distribution(self.plan, int(mode)))
 
+    HINT_MODES = {"adaptive": 0, "off": 1, "forced": 2}
+
+    def threshold_hint(self, mode, value=0):
+        """'adaptive' (default): large calls detect each (level, batch slot) at a threshold learnt from the previous call's
+        quota cut; 'off': always ini_th; 'forced': max(value, ini_th) everywhere.  Outputs never depend on it.  See
+        gh_orb_plan_set_threshold_hint."""
+        self.ctx.check(hip.lib.gh_orb_plan_set_threshold_hint(self.plan, self.HINT_MODES[mode], int(value)))
+
+    def debug_hints(self):
+        """max_batch x 8 uint8: the adaptive threshold of every (batch slot, level) (gh_orb_plan_debug_hints)."""
+        out = np.zeros((self.max_batch, 8), np.uint8)
+        self.ctx.check(hip.lib.gh_orb_plan_debug_hints(self.plan, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def level(self, l):
         w, h, q = C.c_int(), C.c_int(), C.c_int()
         self.ctx.check(hip.lib.gh_orb_plan_level(self.plan, l, C.byref(w), C.byref(h), C.byref(q)))

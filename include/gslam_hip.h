@@ -239,6 +239,23 @@ gh_status gh_orb_plan_set_steering(gh_orb_plan* plan, int mode);
  * Together with gh_orb_plan_set_steering(plan, 1) and the canonical pattern this is the ORB-SLAM extraction up to the image
  * arithmetic (integer pyramid and blur here, float resize there; KeyPoint.response = FAST score, OpenCV's is score - 1). */
 gh_status gh_orb_plan_set_distribution(gh_orb_plan* plan, int mode);
+/* The threshold hint of large calls (the per-level schedule with ini_th_fast > min_th_fast; every other call ignores it).
+ * The detector may score a (level, frame) at any threshold T >= ini_th_fast first: where at least `quota` cells hold a
+ * corner above T the output does not depend on T, and where they do not the level is redone from min_th_fast.  So T is
+ * advice: it changes the time a call takes and not one output byte.
+ *   GH_ORB_HINT_ADAPTIVE (default)  per (level, batch slot) the plan keeps a T that every call derives from the score at
+ *                                   its quota cut, for the next call on that slot: good while a slot sees similar images
+ *                                   call after call (a camera).  A redo is slow (one workgroup per level and frame), so
+ *                                   after one the whole plan stays at ini_th_fast for 2, 4, .. 64 calls, and then goes
+ *                                   above it in every other call only until calls that hold have worked the penalty off
+ *   GH_ORB_HINT_OFF                 always ini_th_fast (also: GSLAM_HIP_ORB_HINT=0 in the environment)
+ *   GH_ORB_HINT_FORCED              every level and slot at max(value, ini_th_fast), value <= 255; nothing is updated */
+#define GH_ORB_HINT_ADAPTIVE 0
+#define GH_ORB_HINT_OFF 1
+#define GH_ORB_HINT_FORCED 2
+gh_status gh_orb_plan_set_threshold_hint(gh_orb_plan* plan, int mode, int value);
+/* Test access: the adaptive T of every (batch slot, level), max_batch x 8 bytes to host; waits for the plan's stream. */
+gh_status gh_orb_plan_debug_hints(gh_orb_plan* plan, uint8_t* out_host);
 /* Level geometry of the plan, for tests. */
 gh_status gh_orb_plan_level(const gh_orb_plan* plan, int level, int* w, int* h, int* quota);
 size_t gh_orb_plan_device_bytes(const gh_orb_plan* plan);
