@@ -1,7 +1,8 @@
 // Index lists (CSR) of a large graph built on the GPU: items sorted by key, ascending item index inside a key -- what
 // build_csr (ba.hip) does on the host with a counting sort.  For the 6 M observations of BASELINE configs[2] (C5) the host
 // teams take ~60 ms per solve, a stable LSD radix sort of (key, item) pairs on the device ~1 ms plus the transfers.
-// rocPRIM is the sort (plumbing, like the runtime's memcpy); everything that touches it is in this file.
+// rocPRIM is the sort (plumbing, like the runtime's memcpy); what this index needs of it is in this file (track_link.hip sorts
+// and scans for itself: its keys have one hot bin, which the histogram below would serialise).
 // gh_csr_index_dev is the device-side core (keys on the device in, start and list on the device out, work space passed in, nothing
 // synchronised); gh_csr_build_dev wraps it for host arrays, tracks.hip calls it on the stream with context scratch.
 #include <cstring>

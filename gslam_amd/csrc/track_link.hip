@@ -1,0 +1,358 @@
+// Multi-view tracks from pair matches, device-resident: gh_link_tracks_dev.  The inlier rows of every matched frame pair are the
+// edges of a graph on the keypoint rows (node = frame * cap + row); its connected components are the tracks.  The contract is in
+// include/gslam_hip.h; tests/track_link_restate.py restates it with a textbook union-find and the device is held to it byte for
+// byte.  Everything is integer work except the two divisions per observation, so the result is the same bits on every run.
+//
+// THE INVARIANT.  parent[] is written by link_init (parent[n] = n) and, after that launch, ONLY by atomic operations that lower
+// the value: the compare-and-swap that hooks a root under a smaller node and the atomic minimum of the halving step.  Hence
+// parent[x] <= x at every moment, every parent chain strictly descends, the structure is acyclic under any interleaving and find
+// terminates on whatever mix of fresh and stale values it reads.  Both writes put an ancestor (or a node of the tree that is
+// being joined) in the place of an ancestor, so a tree never splits; a root is the smallest node of its tree because every other
+// node of the tree has a chain that descends to it.  When link_union has returned every edge joins two nodes of one tree, so the
+// root of a node is the smallest id of its connected component: the label, whatever the order of the pairs, the launch geometry
+// or the outcome of any race.  A stale root only makes a compare-and-swap fail (then somebody else's succeeded: global progress)
+// or hooks under an ancestor of the true root; no lane ever waits for another lane's store, there is no lock.
+// Every read of parent[] while it changes is an agent-scope relaxed atomic load: a CU's L1 is never refreshed by another CU's
+// stores and the L2s of the XCDs are not coherent with each other, the atomics are served past both.
+//
+// CDNA4 mapping (this is the Jayanti-Tarjan / ECL-CC scheme; linking by index is what makes the root the minimum):
+//   * link_init     parent[n] = n;
+//   * link_union    one lane per (pair, query row), grid-stride; the gather rule of gh_ransac_pairs_dev decides whether the row is
+//                   an edge; find with path halving on both ends, hook the larger root under the smaller, retry from the new roots
+//                   when the compare-and-swap fails (the larger root strictly descends: the loop ends);
+//   * link_label    a launch of its own: key[n] = find(n) without any write for an existing node, the extra bin N otherwise.  The
+//                   labels do not depend on how far link_union compressed the paths;
+//   * sort          rocPRIM's stable radix sort of (key, node) pairs lists a component in ascending node id, so two nodes of one
+//                   frame are neighbours in the list.  Not gh_csr_index_dev (csr_sort.hip), which was measured here first: its
+//                   histogram is one atomic add per item on the item's bin, and wrong matches chain tracks into very large
+//                   components -- one hot word: 2.4 / 9.7 / 15.2 ms of a 2.9 / 10.5 / 16.2 ms call at 2 M nodes;
+//   * link_runs     over the sorted list: a position whose left neighbour has another key stores begin[label], one whose right
+//                   neighbour has another key end[label] (so end - begin is the size of the component, without any atomic);
+//                   neighbours with one label and one frame store the byte 1 to the label's flag (the same value from every writer);
+//   * link_flags    per node: observation? (low word) and, at the label itself, track? (high word) packed into one uint64, so that
+//                   ONE rocPRIM exclusive scan numbers the observations and the points; grid-stride over at most 1024 workgroups,
+//                   the CONFLICT and SHORT components counted in registers, then LDS, then one integer atomic per workgroup;
+//   * link_emit     writes every entry of every output: node_point, the observation of a track node at its rank, the padding past
+//                   n_obs, point_len at the labels and zeros past n_points, totals.
+// rocPRIM (one sort, one scan) is plumbing here as in csr_sort.hip; the work space comes from the context's scratch.
+#include <climits>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "dense_solve.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxUnionBlocks = 1 << 16;  // grid-stride beyond this many workgroups
+constexpr int kMaxFlagBlocks = 1024;
+
+struct LinkArgs {
+  const gh_keypoint* kps;
+  int cap, N;
+  int min_views;
+  double fx, fy, cx, cy;
+  const int32_t* key;        // N: label, or N for a node that does not exist
+  const int32_t* begin;      // N, by label: the component's range in the sorted list
+  const int32_t* end;
+  const uint8_t* conflict;   // N, by label
+  const uint64_t* rank;      // N + 1: exclusive scan of the flags; [N] = the totals
+  const int32_t* counters;   // CONFLICT components, SHORT components of two nodes or more
+  int32_t* node_point;
+  int32_t* obs_cam;
+  int32_t* obs_point;
+  double* obs_xy;
+  int32_t* obs_node;
+  int32_t* point_len;
+  int32_t* totals;
+};
+
+__device__ __forceinline__ int link_count(const int32_t* __restrict__ counts, int f, int cap) {
+  const int c = counts[f];
+  return c < 0 ? 0 : (c > cap ? cap : c);
+}
+
+__device__ __forceinline__ int link_load(const int32_t* parent, int x) {
+  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x as far as this lane can see it, p = parent[x] as just read; every step taken also lowers parent[x] to its
+// grandparent (path halving)
+__device__ __forceinline__ int link_find_halve(int32_t* parent, int x, int p) {
+  while (p != x) {  // p < x
+    const int g = link_load(parent, p);
+    if (g != p) (void)__hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = p;
+    p = g;
+  }
+  return x;
+}
+
+__device__ __forceinline__ int link_find(const int32_t* parent, int x) {
+  int p = link_load(parent, x);
+  while (p != x) {
+    x = p;
+    p = link_load(parent, x);
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(kBlock) void link_init_kernel(int32_t* __restrict__ parent, int N) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (g < N) parent[g] = (int32_t)g;
+}
+
+__global__ __launch_bounds__(kBlock) void link_union_kernel(const int32_t* __restrict__ counts, int n_frames, int cap,
+                                                            const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_t,
+                                                            long long rows, const int32_t* __restrict__ idx1,
+                                                            const uint8_t* __restrict__ inlier, int32_t* parent) {
+  const long long step = (long long)gridDim.x * kBlock;
+  for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += step) {
+    const int p = (int)(r / cap), i = (int)(r - (long long)p * cap);
+    const int fq = pair_q[p], ft = pair_t[p];
+    if (fq < 0 || fq >= n_frames || ft < 0 || ft >= n_frames || fq == ft) continue;
+    if (i >= link_count(counts, fq, cap)) continue;
+    if (inlier && inlier[r] == 0) continue;
+    const int j = idx1[r];
+    if (j < 0 || j >= link_count(counts, ft, cap)) continue;
+    const int u = fq * cap + i, v = ft * cap + j;
+    const int pu = link_load(parent, u), pv = link_load(parent, v);
+    if (pu == pv) continue;  // one tree already: in a flat component this spares the root's hot word two reads per edge
+    int a = link_find_halve(parent, u, pu), b = link_find_halve(parent, v, pv);
+    while (a != b) {
+      const int hi = a > b ? a : b, lo = a > b ? b : a;
+      const int old = atomicCAS(parent + hi, hi, lo);
+      if (old == hi) break;
+      a = link_find_halve(parent, old, link_load(parent, old));  // < hi
+      b = link_find_halve(parent, lo, link_load(parent, lo));
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void link_label_kernel(const int32_t* __restrict__ counts, int cap, int N,
+                                                            const int32_t* parent, int32_t* __restrict__ key,
+                                                            int32_t* __restrict__ item) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= N) return;
+  const int n = (int)g;
+  const int f = n / cap, i = n - f * cap;
+  key[n] = i < link_count(counts, f, cap) ? link_find(parent, n) : N;
+  item[n] = n;
+}
+
+__global__ __launch_bounds__(kBlock) void link_runs_kernel(const int32_t* __restrict__ skey, const int32_t* __restrict__ list, int cap,
+                                                           int N, int32_t* __restrict__ begin, int32_t* __restrict__ end,
+                                                           uint8_t* __restrict__ conflict) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= N) return;
+  const int s = (int)g;
+  const int l = skey[s];
+  if (l == N) return;  // (the nodes that do not exist come last)
+  const int prev = s > 0 ? skey[s - 1] : -1, next = s + 1 < N ? skey[s + 1] : N;
+  if (prev != l) begin[l] = s;
+  if (next != l) end[l] = s + 1;
+  else if (list[s] / cap == list[s + 1] / cap) conflict[l] = 1;
+}
+
+__global__ __launch_bounds__(kBlock) void link_flags_kernel(const int32_t* __restrict__ key, const int32_t* __restrict__ begin,
+                                                            const int32_t* __restrict__ end, const uint8_t* __restrict__ conflict, int N,
+                                                            int min_views, uint64_t* __restrict__ flags, int32_t* __restrict__ counters) {
+  __shared__ int s_count[2];
+  if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
+  __syncthreads();
+  int nc = 0, ns = 0;  // the same in every lane of a wave
+  const long long step = (long long)gridDim.x * kBlock;
+  for (long long base = (long long)blockIdx.x * kBlock; base <= N; base += step) {  // (entry N is the scan's room for the totals)
+    const long long g = base + threadIdx.x;
+    bool is_conflict = false, is_short = false;
+    if (g <= N) {
+      const int n = (int)g;
+      uint64_t f = 0;
+      const int l = n < N ? key[n] : N;
+      if (l != N) {
+        const int size = end[l] - begin[l];
+        const bool bad = conflict[l] != 0;
+        const bool track = !bad && size >= min_views;
+        f = track ? 1u : 0u;
+        if (n == l) {
+          if (track) f |= 1ull << 32;
+          is_conflict = bad;
+          is_short = !bad && !track && size >= 2;
+        }
+      }
+      flags[n] = f;
+    }
+    nc += __popcll(__ballot(is_conflict));
+    ns += __popcll(__ballot(is_short));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (nc) atomicAdd(&s_count[0], nc);
+    if (ns) atomicAdd(&s_count[1], ns);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_count[threadIdx.x]) atomicAdd(counters + threadIdx.x, s_count[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(kBlock) void link_emit_kernel(LinkArgs a) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= a.N) return;
+  const int n = (int)g;
+  const uint64_t total = a.rank[a.N];
+  const int n_obs = (int)(uint32_t)total, n_points = (int)(total >> 32);
+  if (n == 0) {
+    a.totals[0] = n_obs;
+    a.totals[1] = n_points;
+    a.totals[2] = a.counters[0];
+    a.totals[3] = a.counters[1];
+  }
+  if (n >= n_obs) {  // the padding; the entries below n_obs are written by the nodes that own them
+    a.obs_cam[n] = -1;
+    a.obs_point[n] = -1;
+    a.obs_node[n] = -1;
+    a.obs_xy[2 * (size_t)n] = 0.0;
+    a.obs_xy[2 * (size_t)n + 1] = 0.0;
+  }
+  if (n >= n_points && n < a.N / 2) a.point_len[n] = 0;
+  const int l = a.key[n];
+  int code = GH_LINK_NO_ROW;
+  if (l != a.N) {
+    const int size = a.end[l] - a.begin[l];
+    if (a.conflict[l]) {
+      code = GH_LINK_CONFLICT;
+    } else if (size < a.min_views) {
+      code = GH_LINK_SHORT;
+    } else {
+      code = (int)(a.rank[l] >> 32);
+      const int k = (int)(uint32_t)a.rank[n];
+      const int f = n / a.cap;
+      const float x = a.kps[n].x, y = a.kps[n].y;
+      a.obs_cam[k] = f;
+      a.obs_point[k] = code;
+      a.obs_node[k] = n;
+      a.obs_xy[2 * (size_t)k] = ((double)x - a.cx) / a.fx;
+      a.obs_xy[2 * (size_t)k + 1] = ((double)y - a.cy) / a.fy;
+      if (n == l) a.point_len[code] = size;
+    }
+  }
+  a.node_point[n] = code;
+}
+
+int link_key_bits(int N) {  // the keys are 0 .. N
+  int bits = 1;
+  while (bits < 31 && (1ll << bits) <= N) ++bits;
+  return bits;
+}
+
+// temporary storage that serves both the sort of N pairs and the scan of N + 1 flags
+bool link_rocprim_bytes(hipStream_t stream, int N, size_t* bytes) {
+  uint64_t* null_u = nullptr;
+  int32_t* null_i = nullptr;
+  size_t scan = 0, sort = 0;
+  if (rocprim::exclusive_scan(nullptr, scan, null_u, null_u, (uint64_t)0, (size_t)N + 1, rocprim::plus<uint64_t>(), stream) != hipSuccess ||
+      rocprim::radix_sort_pairs(nullptr, sort, null_i, null_i, null_i, null_i, (size_t)N, 0, link_key_bits(N), stream) != hipSuccess)
+    return false;
+  *bytes = gh_round256(std::max(std::max(scan, sort), (size_t)1));
+  return true;
+}
+
+}  // namespace
+
+extern "C" gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int n_frames, int cap,
+                                        const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                                        const uint8_t* inlier_dev, double fx, double fy, double cx, double cy, int min_views,
+                                        int32_t* node_point_dev, int32_t* obs_cam_dev, int32_t* obs_point_dev, double* obs_xy_dev,
+                                        int32_t* obs_node_dev, int32_t* point_len_dev, int32_t* totals_dev) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, n_frames >= 0 && cap >= 0 && npairs >= 0 && cap <= 65535);
+  GH_CHECK_ARG(ctx, (long long)n_frames * cap <= (long long)INT32_MAX - 1);
+  GH_CHECK_ARG(ctx, min_views >= 2);
+  GH_CHECK_ARG(ctx, fx > 0.0 && fy > 0.0);  // (a NaN fails)
+  GH_CHECK_ARG(ctx, kps_dev && counts_dev);
+  GH_CHECK_ARG(ctx, node_point_dev && obs_cam_dev && obs_point_dev && obs_xy_dev && obs_node_dev && point_len_dev && totals_dev);
+  GH_CHECK_ARG(ctx, npairs == 0 || (pair_q_dev && pair_t_dev && idx1_dev));
+  const int N = n_frames * cap;
+  if (N == 0) {
+    GH_HIP(ctx, hipMemsetAsync(totals_dev, 0, 4 * sizeof(int32_t), ctx->stream));
+    return GH_OK;
+  }
+
+  // scratch: parent | key | sorted keys | item | list | conflict bytes, two counters (one memset) | flags | rank | rocPRIM storage.
+  // begin lives in parent's place (dead after link_label), end in item's (the sort's input, dead after the sort).
+  const size_t n = (size_t)N;
+  size_t tmp_bytes = 0;
+  if (!link_rocprim_bytes(ctx->stream, N, &tmp_bytes)) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: rocPRIM size query failed");
+  const size_t ints = gh_round256(n * 4);
+  const size_t o_key = ints, o_skey = 2 * ints, o_item = 3 * ints, o_list = 4 * ints, o_conflict = 5 * ints;
+  const size_t o_counters = o_conflict + gh_round256(n);
+  const size_t o_flags = o_counters + 256;
+  const size_t o_rank = o_flags + gh_round256((n + 1) * 8);
+  const size_t o_tmp = o_rank + gh_round256((n + 1) * 8);
+  char* base = nullptr;
+  GH_TRY(gh_scratch(ctx, o_tmp + tmp_bytes, (void**)&base));
+  int32_t* parent = (int32_t*)base;
+  int32_t* key = (int32_t*)(base + o_key);
+  int32_t* skey = (int32_t*)(base + o_skey);
+  int32_t* item = (int32_t*)(base + o_item);
+  int32_t* list = (int32_t*)(base + o_list);
+  int32_t *begin = parent, *end = item;
+  uint8_t* conflict = (uint8_t*)(base + o_conflict);
+  int32_t* counters = (int32_t*)(base + o_counters);
+  uint64_t* flags = (uint64_t*)(base + o_flags);
+  uint64_t* rank = (uint64_t*)(base + o_rank);
+
+  const dim3 grid(gh_div_up(N, kBlock)), block(kBlock);
+  GH_HIP(ctx, hipMemsetAsync(conflict, 0, o_flags - o_conflict, ctx->stream));
+  GH_LAUNCH(ctx, "link_init", link_init_kernel, grid, block, 0, parent, N);
+  const long long rows = (long long)npairs * cap;
+  if (rows > 0) {
+    const long long want = (rows + kBlock - 1) / kBlock;
+    GH_LAUNCH(ctx, "link_union", link_union_kernel, dim3((unsigned)(want < kMaxUnionBlocks ? want : kMaxUnionBlocks)), block, 0,
+              counts_dev, n_frames, cap, pair_q_dev, pair_t_dev, rows, idx1_dev, inlier_dev, parent);
+  }
+  GH_LAUNCH(ctx, "link_label", link_label_kernel, grid, block, 0, counts_dev, cap, N, parent, key, item);
+  {
+    const int prof = gh_prof_begin(ctx, "link_sort");
+    size_t tb = tmp_bytes;
+    const hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tb, key, skey, item, list, n, 0, link_key_bits(N), ctx->stream);
+    gh_prof_end(ctx, prof);
+    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: sort");
+  }
+  GH_LAUNCH(ctx, "link_runs", link_runs_kernel, grid, block, 0, skey, list, cap, N, begin, end, conflict);
+  const int flag_blocks = gh_div_up((long long)N + 1, kBlock);
+  GH_LAUNCH(ctx, "link_flags", link_flags_kernel, dim3(flag_blocks < kMaxFlagBlocks ? flag_blocks : kMaxFlagBlocks), block, 0, key, begin,
+            end, conflict, N, min_views, flags, counters);
+  {
+    const int prof = gh_prof_begin(ctx, "link_scan");
+    size_t tb = tmp_bytes;
+    const hipError_t e = rocprim::exclusive_scan(base + o_tmp, tb, flags, rank, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream);
+    gh_prof_end(ctx, prof);
+    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: scan");
+  }
+
+  LinkArgs a = {};
+  a.kps = kps_dev;
+  a.cap = cap;
+  a.N = N;
+  a.min_views = min_views;
+  a.fx = fx;
+  a.fy = fy;
+  a.cx = cx;
+  a.cy = cy;
+  a.key = key;
+  a.begin = begin;
+  a.end = end;
+  a.conflict = conflict;
+  a.rank = rank;
+  a.counters = counters;
+  a.node_point = node_point_dev;
+  a.obs_cam = obs_cam_dev;
+  a.obs_point = obs_point_dev;
+  a.obs_xy = obs_xy_dev;
+  a.obs_node = obs_node_dev;
+  a.point_len = point_len_dev;
+  a.totals = totals_dev;
+  GH_LAUNCH(ctx, "link_emit", link_emit_kernel, grid, block, 0, a);
+  return GH_OK;
+}

@@ -5,7 +5,8 @@ findAffine3D (GSLAM/core/Estimator.h:100-147).  estimate_batch / estimate_pairs 
 two_view_pairs (gh_two_view_batch_dev / gh_two_view_pairs_dev) go on from an essential matrix to the relative pose and the
 3-D points, batched and device-resident in the same way.  pnp_refine_batch / pnp_batch (gh_pnp_refine_batch_dev /
 gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba_pnp would on its inliers.
-triangulate_tracks (gh_triangulate_tracks_dev) gives every map point of a gh_ba_problem its start from all of its observations."""
+triangulate_tracks (gh_triangulate_tracks_dev) gives every map point of a gh_ba_problem its start from all of its observations;
+link_tracks (gh_link_tracks_dev) builds those per-point arrays from the inlier rows of the pair entries."""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +18,7 @@ TWO_VIEW_OK, TWO_VIEW_NO_MODEL, TWO_VIEW_TOO_FEW, TWO_VIEW_AMBIGUOUS = 0, 1, 2, 
 PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinement next to gh_ba_summary's 0 .. 3
 # GH_TRACK_*: status per point of triangulate_tracks
 TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_INCONSISTENT, TRACK_LOW_PARALLAX, TRACK_SKIPPED = 0, 1, 2, 3, 4, 5
+LINK_SHORT, LINK_CONFLICT, LINK_NO_ROW = -1, -2, -3  # GH_LINK_*: what node_point of link_tracks holds where there is no point id
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
@@ -308,6 +310,38 @@ def triangulate_tracks(ctx: hip.Context, cam_pose, obs_cam, obs_point, obs_xy, n
     p = lambda t: C.c_void_p(t.data_ptr() or 256)
     ctx.check(hip.lib.gh_triangulate_tracks_dev(ctx.h, p(cam_pose), n_cams, p(obs_cam), p(obs_point), p(obs_xy), n_obs, n_points,
                                                 _p(obs_use), _p(point_select), C.byref(prm), *(p(out[k]) for k in out)))
+    return out
+
+
+def link_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, intrinsics, min_views=2):
+    """gh_link_tracks_dev, the call between the pair entries and triangulate_tracks.  kps: F x cap x 7 float32 view of the
+    KeyPoint records, counts: F int32, pair_q / pair_t: P int32, idx1: P x cap int32, inlier: P x cap uint8 or None (all rows):
+    keep of BFMatcher.mask, inlier of estimate_pairs, inlier / good of two_view_pairs (all cuda); intrinsics: (fx, fy, cx, cy).
+    With N = F * cap -> dict of device tensors: node_point N int32 (a point id, LINK_SHORT, LINK_CONFLICT or LINK_NO_ROW),
+    obs_cam / obs_point / obs_node N int32 and obs_xy N x 2 float64 (padded past n_obs with -1 and zeros), point_len N // 2
+    int32, totals 4 int32 (n_obs, n_points, CONFLICT components, SHORT components of two nodes or more); nothing is
+    synchronised and nothing is read back: obs_cam, obs_point, obs_xy go to triangulate_tracks as they are, with
+    n_points = N // 2."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
+    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
+    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap
+    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    N, dev = F * cap, kps.device
+    out = {"node_point": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_cam": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_point": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
+           "obs_node": torch.empty(N, dtype=torch.int32, device=dev),
+           "point_len": torch.empty(N // 2, dtype=torch.int32, device=dev),
+           "totals": torch.empty(4, dtype=torch.int32, device=dev)}
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_link_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
+                                         C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(min_views),
+                                         *(p(out[k]) for k in out)))
     return out
 
 

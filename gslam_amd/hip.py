@@ -221,6 +221,8 @@ SIGNATURES = {
     "gh_track_default_params": (None, [C.POINTER(TrackParams)]),
     "gh_track_group_lanes": (C.c_int, []),
     "gh_triangulate_tracks_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(TrackParams), _vp, _vp, _vp, _vp]),
+    "gh_link_tracks_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gh_pg_solve": (C.c_int, [_vp, C.POINTER(PgProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_graph_solve": (C.c_int, [_vp, C.POINTER(GraphProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_align_sim3": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),

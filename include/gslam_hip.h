@@ -808,6 +808,50 @@ gh_status gh_triangulate_tracks_dev(gh_ctx* ctx, const double* cam_pose_dev, int
                                     const uint8_t* obs_use_dev, const uint8_t* point_select_dev,
                                     const gh_track_params* params, double* point_xyz_dev, int32_t* status_dev,
                                     int32_t* n_good_dev, uint8_t* obs_good_dev);
+/* Multi-view tracks from pair matches, device-resident: the step between the pair entries (gh_match_mask_dev,
+ * gh_ransac_pairs_dev, gh_two_view_pairs_dev: idx1 and a byte per query row of every frame pair) and the per-point arrays
+ * gh_triangulate_tracks_dev and a gh_ba_problem take (obs_cam, obs_point, obs_xy).  Every pointer is a DEVICE pointer, nothing
+ * is copied to the host, the call is asynchronous on the context's stream.  kps_dev n_frames x cap records, counts_dev
+ * n_frames, pair_q_dev / pair_t_dev npairs, idx1_dev npairs x cap as the pair entries take and return them; inlier_dev
+ * npairs x cap or NULL (all rows): `keep` of gh_match_mask_dev, `inlier` of gh_ransac_pairs_dev, `inlier` / `good` of
+ * gh_two_view_pairs_dev.
+ *   nodes      N = n_frames * cap; the node of (frame f, row i) is f * cap + i; it EXISTS when 0 <= i < clamp(counts[f], 0, cap).
+ *   edges      pair p is read only when 0 <= pair_q[p], pair_t[p] < n_frames and pair_q[p] != pair_t[p]; otherwise the whole
+ *              pair is ignored and nothing of it is addressed beyond pair_q[p] / pair_t[p].  Query row i of the pair gives the
+ *              edge (pair_q[p], i) -- (pair_t[p], j), j = idx1[p * cap + i], when i < clamp(counts[pair_q[p]], 0, cap),
+ *              (inlier_dev == NULL || inlier_dev[p * cap + i] != 0) and 0 <= j < clamp(counts[pair_t[p]], 0, cap): the gather
+ *              rule of gh_ransac_pairs_dev.  An index outside its range drops the row; it is never dereferenced.  The same edge
+ *              may occur any number of times and in both directions.
+ *   components the connected components of the undirected graph on the existing nodes; the LABEL of a component is its
+ *              smallest node id, whatever the order of the pairs, the launch geometry or the outcome of any race.
+ *   class      of a component, checked in this order: CONFLICT two of its nodes lie in the same frame -- the whole component
+ *              is dropped, as OpenMVG's track filter does (a many-to-one match produces exactly this); SHORT fewer than
+ *              min_views nodes (an existing node without any edge is a component of one); otherwise it is a TRACK.
+ *   numbering  tracks get the point ids 0, 1, ... in ascending label; the observations are the nodes of tracks in ascending
+ *              node id (frame-major, then row), the observation index is the rank in that list.
+ * Outputs, ALL written for their full capacity on every call (dirty buffers never show): node_point_dev N: the point id
+ * (>= 0), GH_LINK_SHORT, GH_LINK_CONFLICT or GH_LINK_NO_ROW (the node does not exist); obs_cam_dev, obs_point_dev,
+ * obs_node_dev N each and obs_xy_dev N x 2: for observation k < n_obs the frame, the point id, the node id and
+ * (((double)x - cx) / fx, ((double)y - cy) / fy) of that keypoint (the normalisation of gh_two_view_pairs_dev: two IEEE
+ * operations each, nothing fused); for k >= n_obs obs_cam = obs_point = obs_node = -1 and obs_xy = (0, 0); point_len_dev
+ * N / 2 (enough because min_views >= 2): the number of observations of point p, 0 for p >= n_points; totals_dev 4: n_obs,
+ * n_points, the number of CONFLICT components, the number of SHORT components with at least two nodes.
+ * The padding is the point of the layout: the arrays go to gh_triangulate_tracks_dev as they are, with n_cams = n_frames,
+ * n_obs = N and n_points = N / 2, without a count being read back -- that contract drops an observation whose index is out
+ * of range and reports a point without observations as GH_TRACK_TOO_FEW.  Everything is integer work except the two
+ * divisions: the same bits on every run.  tests/track_link_restate.py restates all of it.
+ * GH_ERR_ARG, and then nothing is written: ctx NULL; n_frames, cap or npairs negative; cap > 65535; n_frames * cap >
+ * INT32_MAX - 1; min_views < 2; fx or fy not > 0 (a NaN included); a NULL among kps, counts or the seven outputs; with
+ * npairs > 0 a NULL among pair_q, pair_t, idx1.  N == 0: GH_OK, only totals_dev (zeros) is written.  npairs == 0 with
+ * N > 0: every existing node is SHORT, everything else is padding. */
+#define GH_LINK_SHORT (-1)
+#define GH_LINK_CONFLICT (-2)
+#define GH_LINK_NO_ROW (-3)
+gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int n_frames, int cap,
+                             const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                             const uint8_t* inlier_dev, double fx, double fy, double cx, double cy, int min_views,
+                             int32_t* node_point_dev, int32_t* obs_cam_dev, int32_t* obs_point_dev, double* obs_xy_dev,
+                             int32_t* obs_node_dev, int32_t* point_len_dev, int32_t* totals_dev);
 
 /* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
