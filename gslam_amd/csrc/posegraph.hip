@@ -1946,7 +1946,10 @@ extern "C" gh_status gh_pg_solve(gh_ctx* ctx, gh_pg_problem* pr, const gh_ba_opt
 // ---------------------------------------------------------------- 3-D alignment
 namespace {
 
-// 17 sums per correspondence block of 256, then a fixed-order fold: {sum a, sum b, sum a b^T, sum |a|^2, sum |b|^2}
+// 17 sums per correspondence block of 256, then a fixed-order fold: {sum a, sum b, sum a b^T, sum |a|^2, sum |b|^2}, with
+// a = src - src[0] and b = dst - dst[0].  About that pivot the centred moments cancel at the size of the cloud, not at the
+// size of its coordinates (a trajectory in GPS coordinates: 1e6 m away, metres across), so the result is translation-
+// invariant to rounding; every thread reads the pivot itself (one cached line), no extra launch.
 __global__ __launch_bounds__(256) void align_sums_kernel(const double* __restrict__ src, const double* __restrict__ dst, int n,
                                                          double* __restrict__ partial) {
   __shared__ double sh[256];
@@ -1954,8 +1957,8 @@ __global__ __launch_bounds__(256) void align_sums_kernel(const double* __restric
   double v[17];
   for (int q = 0; q < 17; ++q) v[q] = 0.0;
   if (k < n) {
-    const double a[3] = {src[3 * (size_t)k], src[3 * (size_t)k + 1], src[3 * (size_t)k + 2]};
-    const double b[3] = {dst[3 * (size_t)k], dst[3 * (size_t)k + 1], dst[3 * (size_t)k + 2]};
+    const double a[3] = {src[3 * (size_t)k] - src[0], src[3 * (size_t)k + 1] - src[1], src[3 * (size_t)k + 2] - src[2]};
+    const double b[3] = {dst[3 * (size_t)k] - dst[0], dst[3 * (size_t)k + 1] - dst[1], dst[3 * (size_t)k + 2] - dst[2]};
     for (int e = 0; e < 3; ++e) {
       v[e] = a[e];
       v[3 + e] = b[e];
@@ -1976,21 +1979,25 @@ __global__ __launch_bounds__(256) void align_sums_kernel(const double* __restric
   }
 }
 
-// residual sum of squares and the 7 x 7 information at the solution: 50 values per block of 256, same fold
+// residual sum of squares and the 7 x 7 information at the solution: 50 values per block of 256, same fold.  S8 = the
+// transform followed by its translation in pivot coordinates tp (11 doubles): the residual is taken as
+// (b - b0) - (s R (a - a0) + tp), the same residual as dst - S src without the rounding of coordinates that are large
+// against it.  The information is built from the uncentred a (the Jacobian of a right-multiplied delta).
 __global__ __launch_bounds__(256) void align_info_kernel(const double* __restrict__ src, const double* __restrict__ dst, int n,
                                                          const double* __restrict__ S8, int dof, double* __restrict__ partial) {
   __shared__ double sh[256];
   const int k = blockIdx.x * 256 + threadIdx.x;
-  double S[8];
-  for (int e = 0; e < 8; ++e) S[e] = S8[e];
+  double S[11];
+  for (int e = 0; e < 11; ++e) S[e] = S8[e];
   double a[3] = {0, 0, 0}, ssq = 0.0;
   const bool on = k < n;
   if (on) {
     for (int e = 0; e < 3; ++e) a[e] = src[3 * (size_t)k + e];
+    const double ap[3] = {a[0] - src[0], a[1] - src[1], a[2] - src[2]};
     double Ra[3];
-    q_rot(S, a, Ra);
+    q_rot(S, ap, Ra);
     for (int e = 0; e < 3; ++e) {
-      const double r = dst[3 * (size_t)k + e] - (S[7] * Ra[e] + S[4 + e]);
+      const double r = (dst[3 * (size_t)k + e] - dst[e]) - (S[7] * Ra[e] + S[8 + e]);
       ssq += r * r;
     }
   }
@@ -2048,19 +2055,23 @@ void jacobi4(double a[4][4], double v[4][4]) {
       }
 }
 
-// Horn's closed form from the 17 sums (host: a 4 x 4 eigenproblem) -- pg_oracle.c oracle_align_from_sums
-bool align_from_sums(const double* sums, int n, bool with_scale, double* out8) {
+// Horn's closed form from the 17 sums about the pivot (a0, b0) (host: a 4 x 4 eigenproblem) -- pg_oracle.c
+// oracle_align_from_sums.  The centroids are a0 + mean, b0 + mean.
+// tp: the translation in pivot coordinates, mb - s R ma.
+bool align_from_sums(const double* sums, const double* a0, const double* b0, int n, bool with_scale, double* out8, double* tp) {
   if (n < 3) return false;
   const double inv = 1.0 / n;
-  double ca[3], cb[3], M[3][3];
+  double ma[3], mb[3], ca[3], cb[3], M[3][3];
   for (int e = 0; e < 3; ++e) {
-    ca[e] = sums[e] * inv;
-    cb[e] = sums[3 + e] * inv;
+    ma[e] = sums[e] * inv;
+    mb[e] = sums[3 + e] * inv;
+    ca[e] = a0[e] + ma[e];
+    cb[e] = b0[e] + mb[e];
   }
   for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) M[r][c] = sums[6 + 3 * r + c] - n * ca[r] * cb[c];
-  const double na = sums[15] - n * (ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]);
-  const double nb = sums[16] - n * (cb[0] * cb[0] + cb[1] * cb[1] + cb[2] * cb[2]);
+    for (int c = 0; c < 3; ++c) M[r][c] = sums[6 + 3 * r + c] - n * ma[r] * mb[c];
+  const double na = sums[15] - n * (ma[0] * ma[0] + ma[1] * ma[1] + ma[2] * ma[2]);
+  const double nb = sums[16] - n * (mb[0] * mb[0] + mb[1] * mb[1] + mb[2] * mb[2]);
   if (!(na > 1e-300) || !(nb > 1e-300)) return false;
   double N[4][4] = {{M[0][0] + M[1][1] + M[2][2], M[1][2] - M[2][1], M[2][0] - M[0][2], M[0][1] - M[1][0]},
                     {0, M[0][0] - M[1][1] - M[2][2], M[0][1] + M[1][0], M[2][0] + M[0][2]},
@@ -2080,11 +2091,13 @@ bool align_from_sums(const double* sums, int n, bool with_scale, double* out8) {
   qw /= qn; qx /= qn; qy /= qn; qz /= qn;
   const double sc = with_scale ? sqrt(nb / na) : 1.0;
   const double q[4] = {qx, qy, qz, qw};
-  double Rca[3];
+  double Rca[3], Rma[3];
   q_rot(q, ca, Rca);
+  q_rot(q, ma, Rma);
   out8[0] = qx; out8[1] = qy; out8[2] = qz; out8[3] = qw;
   for (int e = 0; e < 3; ++e) out8[4 + e] = cb[e] - sc * Rca[e];
   out8[7] = sc;
+  for (int e = 0; e < 3; ++e) tp[e] = mb[e] - sc * Rma[e];
   return true;
 }
 
@@ -2124,14 +2137,16 @@ extern "C" gh_status gh_align_sim3(gh_ctx* ctx, const double* src, const double*
     for (int b = 0; b < nb; ++b) s += hp[(size_t)b * 17 + q];  // block order
     sums[q] = s;
   }
-  if (!align_from_sums(sums, n, ((dof >> 6) & 1) != 0, sim3_out)) {
+  double tp[3];
+  if (!align_from_sums(sums, src, dst, n, ((dof >> 6) & 1) != 0, sim3_out, tp)) {
     for (int e = 0; e < 8; ++e) sim3_out[e] = e == 3 || e == 7 ? 1.0 : 0.0;
     return GH_OK;  // degenerate set: *ok_out stays 0
   }
   *ok_out = 1;
   if (information_out || ssq_out) {
     memcpy(hb + 2 * pts + part, sim3_out, 64);
-    GH_HIP(ctx, hipMemcpyAsync(d_S, hb + 2 * pts + part, 64, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(hb + 2 * pts + part + 64, tp, 24);
+    GH_HIP(ctx, hipMemcpyAsync(d_S, hb + 2 * pts + part, 88, hipMemcpyHostToDevice, ctx->stream));
     GH_LAUNCH(ctx, "align_info", align_info_kernel, dim3(nb), dim3(256), 0, (const double*)d_src, (const double*)d_dst, n,
               (const double*)d_S, dof, d_part);
     GH_HIP(ctx, hipMemcpyAsync(hp, d_part, (size_t)nb * 50 * 8, hipMemcpyDeviceToHost, ctx->stream));

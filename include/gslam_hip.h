@@ -955,7 +955,12 @@ gh_status gh_graph_solve(gh_ctx* ctx, gh_graph_problem* problem, const gh_ba_opt
  * synchronised trajectories, :220-225) compute.  dof & GH_KF_SCALE decides whether s is estimated (else s = 1).
  * sim3_out 8 doubles [qx qy qz qw tx ty tz s]; information_out (49 doubles, may be NULL) = J^T J of the residuals
  * dst - S exp(delta) src at the solution, rows / columns of masked dof zero; ssq_out (may be NULL) = sum of squared
- * residuals; *ok_out = 0 for fewer than 3 or degenerate (coincident) correspondences. */
+ * residuals; *ok_out = 0 for fewer than 3 or degenerate (coincident) correspondences.
+ * Translation-invariant: the moments are accumulated about the first correspondence (src[0], dst[0]) and the centroids
+ * formed as pivot + mean, so R and s come out the same to rounding wherever the two clouds sit (a trajectory in GPS
+ * coordinates, 1e6 m from the origin and metres across, loses nothing) and t is exact to the rounding of the centroids.
+ * information_out keeps its definition: it is built from the uncentred src, as the Jacobian of a right-multiplied
+ * delta is. */
 gh_status gh_align_sim3(gh_ctx* ctx, const double* src, const double* dst, int n, int dof, double* sim3_out,
                         double* information_out, double* ssq_out, int* ok_out);
 

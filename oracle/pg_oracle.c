@@ -31,6 +31,9 @@
  *   alignment  dst ~ s R src + t over n 3-D correspondences: Horn's closed form (quaternion of the largest eigenvalue of
  *              the 4x4 N matrix, scale sqrt(sum |b|^2 / sum |a|^2), or 1 when the scale is not a degree of freedom),
  *              then the information J^T J of the residual dst - S src at the solution for the right-multiplicative delta.
+ *              The moments are taken about the first correspondence (src[0], dst[0]), so the transform is the same to
+ *              rounding wherever the two clouds sit; the information is built from the uncentred src (that is what the
+ *              Jacobian with respect to a right-multiplied delta is).
  */
 #include <math.h>
 #include <stdint.h>
@@ -459,20 +462,27 @@ static void jacobi4(double a[4][4], double v[4][4]) {
       }
 }
 
-/* From the 13 sums {sum a (3), sum b (3), sum a b^T (9 row-major), sum |a|^2, sum |b|^2} of n correspondences:
- * dst ~ s R src + t.  with_scale = 0 fixes s = 1.  Returns 0 for a degenerate set. */
-int oracle_align_from_sums(const double* sums, int n, int with_scale, double* out8) {
+/* From the 17 sums {sum a' (3), sum b' (3), sum a' b'^T (9 row-major), sum |a'|^2, sum |b'|^2} of n correspondences taken
+ * about a pivot, a' = a - a0 and b' = b - b0 (the caller passes the first correspondence): dst ~ s R src + t.  The
+ * centred moments sum a' b'^T - n ma mb^T cancel at the size of the cloud, not at the size of its coordinates, so the
+ * result does not depend on where the clouds sit (a trajectory in GPS coordinates: 1e6 m away, metres across).  The
+ * centroids are a0 + ma and b0 + mb.  with_scale = 0 fixes s = 1.  Returns 0 for a degenerate set.  tp (3, may be NULL)
+ * receives the translation in pivot coordinates, mb - s R ma: b - b0 ~ s R (a - a0) + tp. */
+int oracle_align_from_sums(const double* sums, const double* a0, const double* b0, int n, int with_scale, double* out8,
+                           double* tp) {
   if (n < 3) return 0;
   const double inv = 1.0 / n;
-  double ca[3], cb[3], M[3][3];
+  double ma[3], mb[3], ca[3], cb[3], M[3][3];
   for (int e = 0; e < 3; ++e) {
-    ca[e] = sums[e] * inv;
-    cb[e] = sums[3 + e] * inv;
+    ma[e] = sums[e] * inv;
+    mb[e] = sums[3 + e] * inv;
+    ca[e] = a0[e] + ma[e];
+    cb[e] = b0[e] + mb[e];
   }
   for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) M[r][c] = sums[6 + 3 * r + c] - n * ca[r] * cb[c];
-  const double na = sums[15] - n * (ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]);
-  const double nb = sums[16] - n * (cb[0] * cb[0] + cb[1] * cb[1] + cb[2] * cb[2]);
+    for (int c = 0; c < 3; ++c) M[r][c] = sums[6 + 3 * r + c] - n * ma[r] * mb[c];
+  const double na = sums[15] - n * (ma[0] * ma[0] + ma[1] * ma[1] + ma[2] * ma[2]);
+  const double nb = sums[16] - n * (mb[0] * mb[0] + mb[1] * mb[1] + mb[2] * mb[2]);
   if (!(na > 1e-300) || !(nb > 1e-300)) return 0;
   double N[4][4] = {{M[0][0] + M[1][1] + M[2][2], M[1][2] - M[2][1], M[2][0] - M[0][2], M[0][1] - M[1][0]},
                     {0, M[0][0] - M[1][1] - M[2][2], M[0][1] + M[1][0], M[2][0] + M[0][2]},
@@ -492,23 +502,32 @@ int oracle_align_from_sums(const double* sums, int n, int with_scale, double* ou
   qw /= qn; qx /= qn; qy /= qn; qz /= qn;
   const double sc = with_scale ? sqrt(nb / na) : 1.0;
   const double q[4] = {qx, qy, qz, qw};
-  double Rca[3];
+  double Rca[3], Rma[3];
   q_rot(q, ca, Rca);
+  q_rot(q, ma, Rma);
   out8[0] = qx; out8[1] = qy; out8[2] = qz; out8[3] = qw;
   for (int e = 0; e < 3; ++e) out8[4 + e] = cb[e] - sc * Rca[e];
   out8[7] = sc;
+  if (tp)
+    for (int e = 0; e < 3; ++e) tp[e] = mb[e] - sc * Rma[e];
   return 1;
 }
 
 /* dst ~ S src: closed form + the 7x7 information J^T J of r_k = dst_k - S src_k w.r.t. the right-multiplicative delta
  * (S exp(delta) src = S (src + v + w x src + sigma src) to first order: J_k = -s R [I | -[src]x | src], masked by dof).
- * Returns the sum of squared residuals through *ssq. */
+ * Returns the sum of squared residuals through *ssq.  0 = refused (n < 3 or a cloud without spread): the outputs are then
+ * the identity, a zero information and ssq = 0. */
 int oracle_align_sim3(const double* src, const double* dst, int n, int dof, double* out8, double* info49, double* ssq) {
   double sums[17];
   memset(sums, 0, sizeof(sums));
+  for (int e = 0; e < 8; ++e) out8[e] = e == 3 || e == 7 ? 1.0 : 0.0; /* a refused set leaves the identity, as gh_align_sim3 */
+  if (info49) memset(info49, 0, 49 * 8);
+  if (ssq) *ssq = 0.0;
+  if (n < 3) return 0;
+  const double a0[3] = {src[0], src[1], src[2]}, b0[3] = {dst[0], dst[1], dst[2]}; /* the pivot */
   for (int k = 0; k < n; ++k) {
-    const double* a = src + 3 * k;
-    const double* b = dst + 3 * k;
+    const double a[3] = {src[3 * k] - a0[0], src[3 * k + 1] - a0[1], src[3 * k + 2] - a0[2]};
+    const double b[3] = {dst[3 * k] - b0[0], dst[3 * k + 1] - b0[1], dst[3 * k + 2] - b0[2]};
     for (int e = 0; e < 3; ++e) {
       sums[e] += a[e];
       sums[3 + e] += b[e];
@@ -517,16 +536,20 @@ int oracle_align_sim3(const double* src, const double* dst, int n, int dof, doub
     sums[15] += a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
     sums[16] += b[0] * b[0] + b[1] * b[1] + b[2] * b[2];
   }
-  if (!oracle_align_from_sums(sums, n, (dof >> 6) & 1, out8)) return 0;
+  double tp[3];
+  if (!oracle_align_from_sums(sums, a0, b0, n, (dof >> 6) & 1, out8, tp)) return 0;
   if (info49) memset(info49, 0, 49 * 8);
   double acc = 0;
   for (int k = 0; k < n; ++k) {
     const double* a = src + 3 * k;
+    /* the residual in pivot coordinates, (b - b0) - (s R (a - a0) + tp): the same residual as dst - S src, without the
+     * rounding of coordinates that are large against the residual */
+    const double ap[3] = {a[0] - a0[0], a[1] - a0[1], a[2] - a0[2]};
     double Ra[3];
-    q_rot(out8, a, Ra);
+    q_rot(out8, ap, Ra);
     double r[3];
     for (int e = 0; e < 3; ++e) {
-      r[e] = dst[3 * k + e] - (out8[7] * Ra[e] + out8[4 + e]);
+      r[e] = (dst[3 * k + e] - b0[e]) - (out8[7] * Ra[e] + tp[e]);
       acc += r[e] * r[e];
     }
     if (info49) {

@@ -7,24 +7,9 @@ import pytest
 
 import oracle_lib
 from gslam_amd.pg_synth import make_pose_graph
+from pg_parity import compare as _compare
 
 pytestmark = pytest.mark.gpu
-
-
-def _compare(ctx, oracle, truth, start, dof, prob, max_it=40):
-    from gslam_amd import ba, posegraph
-    So, so, sto = oracle.pg_solve(start, dof, prob, oracle_lib.ba_options(max_iterations=max_it), threads=4)
-    Sg, sg, stg = posegraph.solve(ctx, start, dof, prob, ba.default_options(max_iterations=max_it))
-    assert stg == sto == 0
-    assert abs(sg.initial_cost - so.initial_cost) <= 1e-12 * max(so.initial_cost, 1e-30)
-    assert (sg.iterations, sg.accepted, sg.termination, sg.trace_len) == (so.iterations, so.accepted, so.termination, so.trace_len)
-    for i in range(so.trace_len):
-        assert sg.trace_accepted[i] == so.trace_accepted[i], i
-        assert abs(sg.trace_radius[i] - so.trace_radius[i]) <= 1e-9 * so.trace_radius[i]
-        assert abs(sg.trace_cost[i] - so.trace_cost[i]) <= 1e-9 * max(so.trace_cost[i], 1e-30) + 1e-20
-    assert np.abs(Sg - So).max() <= 1e-7
-    assert Sg[0].tobytes() == start[0].tobytes()
-    return Sg, sg
 
 
 @pytest.mark.parametrize("kind,gps,info", [("se3", 0, False), ("sim3", 0, True), ("mixed", 6, False), ("se3", 5, True)])
