@@ -437,6 +437,31 @@ __device__ __forceinline__ uint32_t fast_compass4(const CompassK& k, uint32_t wc
   return __builtin_amdgcn_bitop3_b32(ye, yo, 0x80008000u, 0xE4);  // (a & c) | (b & ~c)
 }
 
+// The CONSERVATIVE compass test on pixels quantised to 6 bits, q(x) = x >> 2: all four pixels of wc in one dword, one 8-bit
+// field each, no even / odd split.  With t' = (t + 1) >> 2: x >= c + t + 1 implies q(x) >= q(c) + t' and x <= c - t - 1 implies
+// q(x) <= q(c) - t' (floor(a) + floor(b) <= floor(a + b)), so a neighbour that the exact test calls brighter (darker) is never
+// "certainly not brighter" (always "possibly darker") here: the flags are a SUPERSET of fast_compass4's.  Pass 2 scores every
+// queued pixel exactly and keeps S > t only, so a superset gives the same score tile.
+// With A = q(c) + t' + 127 per field, A - q(x) keeps bit 7 iff q(x) <= q(c) + t' - 1, and with D = q(c) - t' + 128, D - q(x) keeps
+// it iff q(x) <= q(c) - t'.  t' <= 64: A - q(x) lies in 64 .. 254 and D - q(x) in 1 .. 191, no field borrows from its neighbour.
+struct CompassQ {
+  uint32_t a, d;
+  __device__ __forceinline__ explicit CompassQ(uint32_t t) : a((((t + 1u) >> 2) + 127u) * 0x01010101u), d((128u - ((t + 1u) >> 2)) * 0x01010101u) {}
+};
+// -> the flags of pixels 0, 1, 2, 3 at bits 7, 15, 23, 31 (other bits: garbage)
+__device__ __forceinline__ uint32_t fast_compass4_q(const CompassQ& k, uint32_t wc, uint32_t wl, uint32_t wr, uint32_t wu, uint32_t wd) {
+  constexpr uint32_t kQ = 0x3F3F3F3Fu;
+  // left neighbours: cols 4m - 3 .. 4m = bytes 1 .. 3 of wl and byte 0 of wc; right: cols 4m + 3 .. 4m + 6 = byte 3 of wc, bytes 0 .. 2 of wr
+  const uint32_t c = (wc >> 2) & kQ, u = (wu >> 2) & kQ, d = (wd >> 2) & kQ;
+  const uint32_t l = (__builtin_amdgcn_alignbyte(wc, wl, 1) >> 2) & kQ, r = (__builtin_amdgcn_alignbyte(wr, wc, 3) >> 2) & kQ;
+  const uint32_t A = c + k.a, Dk = c + k.d;
+  const uint32_t not_bright_lr = (A - l) & (A - r);
+  const uint32_t bright = __builtin_amdgcn_bitop3_b32(A - u, A - d, not_bright_lr, 0x15);  // ~(a & b) & ~c
+  const uint32_t dark_lr = (Dk - l) | (Dk - r);
+  const uint32_t dark = __builtin_amdgcn_bitop3_b32(Dk - u, Dk - d, dark_lr, 0xA8);  // (a | b) & c
+  return bright | dark;
+}
+
 #ifndef GH_FAST_WAVES
 #define GH_FAST_WAVES 8
 #endif
@@ -653,6 +678,9 @@ __device__ __forceinline__ int fast_cell_stage(const uint8_t* sc, uint16_t* list
 // plan's advice for this level and batch slot, written by orb_select of the previous call) or, hint == null, th_a.  The same
 // argument holds with T for ini_th; what a record then lacks, its entries in (ini_th, T], orb_select either proves invisible
 // or redoes (select_weak_cells).  The flat-tile shortcut needs a complete record: T == ini_th only.
+// Above ini_th pass 1 is the conservative test on 6-bit pixels (fast_compass4_q; profiles/orb_pass1_quant.txt): pass 2 is exact and
+// stores S > T only, so the longer queue changes no score.  At T == ini_th, where the shortcut asks what the EXACT test queued,
+// and on every single-phase path pass 1 stays fast_compass4.
 template <bool PLANE, bool TWO_PHASE>
 __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th, bool two,
                                                 const uint32_t* __restrict__ hint, int th_a, uint32_t epoch,
@@ -689,6 +717,8 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
       score_th = th_a;
     }
   }
+  // pass 1 is a filter in front of the exact pass 2: above ini_th it may be the cheaper conservative test (workgroup-uniform)
+  const bool pass1_quant = TWO_PHASE && phase_a && th_a > ini_th;
 #ifdef GH_ORB_PHASES
   if (threadIdx.x == 0) {
     const unsigned int slot_ = (unsigned int)(frame * cells_per_frame + cell_off + by * nbx + bx);
@@ -720,9 +750,11 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   }
   // 16 B per lane: rows of the level are 16-byte aligned (pitch % 16 == 0, checked by the launcher)
   for (int i = tid; i < kTileH * (kTileW / 16); i += 256) *reinterpret_cast<uint4*>(&tile[16 * i]) = *fast_tile_src(lv, frame, bx, by, i);
-  // candidate bit b of a thread (see pass 1): b ^ 15 = 16 (k >> 1) + 2 trip + (k & 1) -> score offset 1024 trip + 1 + k
+  // candidate bit b of a thread (see pass 1): b ^ 15 = 16 (k >> 1) + 2 trip + (k & 1) -> score offset 1024 trip + 1 + k;
+  // the quantised pass 1: b = 8 k + 7 - trip
   if (tid < 32) {
-    const int ix = tid ^ 15, k = (ix & 1) + 2 * (ix >> 4), trip = (ix >> 1) & 7;
+    const int ix = tid ^ 15;
+    const int k = pass1_quant ? tid >> 3 : (ix & 1) + 2 * (ix >> 4), trip = pass1_quant ? 7 - (tid & 7) : (ix >> 1) & 7;
     bit_pos[tid] = (uint16_t)(1024 * trip + 1 + k);
   }
   __syncthreads();
@@ -755,22 +787,33 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   constexpr int kTrips = (kItems + 255) / 256;  // 5
   static_assert(2 * kTrips <= 14 && kScoreW == 4 * kItemsPerRow, "candidate bits of all trips share one dword");
   const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-  auto pass1 = [&](int th) {
+  // quant (uniform): the conservative test on 6-bit pixels, four per instruction (fast_compass4_q), flags of pixel k at bit
+  // 8 k + 7, trip t parks them t bits lower.  Only phase A above ini_th takes it (pass1_quant): the flat-tile shortcut below
+  // asks what the EXACT test queued.
+  auto pass1 = [&](int th, bool quant) {
     const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(th, 0), 255));  // (scalar: the constants below are s_mul)
-    const CompassK ck(t);
     const uint32_t tid3856 = (uint32_t)tid * 3856u;  // (item * 3856) >> 16 == item / 17 for item < 3855
     uint32_t allbits = 0;
+    auto trips = [&](auto flags4, int shift, uint32_t mask) {
 #pragma unroll
-    for (int trip = 0; trip < kTrips; ++trip) {
-      const int item = 256 * trip + tid;
-      if (item < kItems) {
-        const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
-        const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
-        const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
-        const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
-        const uint32_t w = fast_compass4(ck, wc, wl, wr, wu, wd);
-        allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (2 * trip), 0xC000C000u >> (2 * trip), 0xF8);  // a | (b & c)
+      for (int trip = 0; trip < kTrips; ++trip) {
+        const int item = 256 * trip + tid;
+        if (item < kItems) {
+          const uint32_t sy = (tid3856 + 3856u * 256u * (uint32_t)trip) >> 16;
+          const uint32_t ix = (uint32_t)item + 7u * sy + (3 * (kTileW / 4) + 4);  // (sy + 3) * 24 + m, m = item - 17 sy + 4
+          const uint32_t wc = tile32[ix], wl = tile32[ix - 1], wr = tile32[ix + 1];
+          const uint32_t wu = tile32[ix - 3 * (kTileW / 4)], wd = tile32[ix + 3 * (kTileW / 4)];
+          const uint32_t w = flags4(wc, wl, wr, wu, wd);
+          allbits = __builtin_amdgcn_bitop3_b32(allbits, w >> (shift * trip), mask >> (shift * trip), 0xF8);  // a | (b & c)
+        }
       }
+    };
+    if (quant) {
+      const CompassQ cq(t);
+      trips([&](uint32_t wc, uint32_t wl, uint32_t wr, uint32_t wu, uint32_t wd) { return fast_compass4_q(cq, wc, wl, wr, wu, wd); }, 1, 0x80808080u);
+    } else {
+      const CompassK ck(t);
+      trips([&](uint32_t wc, uint32_t wl, uint32_t wr, uint32_t wu, uint32_t wd) { return fast_compass4(ck, wc, wl, wr, wu, wd); }, 2, 0xC000C000u);
     }
     // ONE queue reservation per wave for all trips; an entry is (bit << 8 | tid), decoded in pass 2 where every lane is busy
     const int cnt = __popc(allbits);
@@ -787,7 +830,7 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
       }
     }
   };
-  pass1(score_th);
+  pass1(score_th, pass1_quant);
   __syncthreads();
   GH_PHASE(1);
   int nq = q_count;
@@ -800,7 +843,7 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
       phase_a = false;
       score_th = min_th;
       __syncthreads();  // (every thread has read q_count == 0 before a wave adds to it again)
-      pass1(score_th);
+      pass1(score_th, false);
       __syncthreads();
       nq = q_count;
     }
