@@ -96,4 +96,13 @@ gh_status ransac_batch_ranges(gh_ctx* ctx, int model, const double* src, const d
                               int nproblems, double threshold, const double* thresholds, uint64_t seed, const uint64_t* seeds,
                               double* models, uint8_t* mask, int32_t* inliers, void* work);
 
+// gh_pnp_batch_dev on a scratch block the caller owns (pnp_batch.hip), for localize.hip: pnp_batch_scratch_bytes(nproblems,
+// nrows) bytes at `work`.  pnp_batch_args_ok is the entry's check of its scalars; the caller has checked the pointers.
+bool pnp_batch_args_ok(int nproblems, int nrows, double ransac_threshold, int min_rows, double inlier_threshold);
+size_t pnp_batch_scratch_bytes(int nproblems, int nrows);
+gh_status pnp_batch_on(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev, int nproblems, int nrows,
+                       double ransac_threshold, uint64_t seed, int dof, const gh_ba_options* options, int min_rows,
+                       double inlier_threshold, double* models_dev, int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
+                       gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, void* work);
+
 }  // namespace gh_ransac

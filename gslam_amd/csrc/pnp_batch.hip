@@ -203,32 +203,47 @@ extern "C" gh_status gh_pnp_refine_batch_dev(gh_ctx* ctx, const double* xyz_dev,
   return refine_launch(ctx, a);
 }
 
-extern "C" gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev,
-                                      int nproblems, int nrows, double ransac_threshold, uint64_t seed, int dof,
-                                      const gh_ba_options* options, int min_rows, double inlier_threshold, double* models_dev,
-                                      int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
-                                      gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev) {
-  if (!ctx) return GH_ERR_ARG;
-  GH_ENTER(ctx);
-  GH_CHECK_ARG(ctx, nproblems >= 0 && nproblems <= (1 << 27) && nrows >= 0 && min_rows >= 0);
-  GH_CHECK_ARG(ctx, ransac_threshold >= 0 && inlier_threshold >= 0);  // (a NaN fails both)
-  if (nproblems == 0) return GH_OK;
-  GH_CHECK_ARG(ctx, xyz_dev && xy_dev && offsets_dev && models_dev && ransac_inliers_dev && poses_dev && summaries_dev);
-  // ONE scratch block for all stages (gh_scratch hands out one block per context):
-  // row list | RANSAC mask | round-1 inliers | round-1 poses | row_begin | row_end | the RANSAC core's own block
+namespace gh_ransac {
+
+bool pnp_batch_args_ok(int nproblems, int nrows, double ransac_threshold, int min_rows, double inlier_threshold) {
+  return nproblems >= 0 && nproblems <= (1 << 27) && nrows >= 0 && min_rows >= 0 && ransac_threshold >= 0 &&
+         inlier_threshold >= 0;  // (a NaN fails both)
+}
+
+// row list | RANSAC mask | round-1 inliers | round-1 poses | row_begin | row_end | the RANSAC core's own block
+struct PnpChainLayout {
+  size_t o_mask, o_in1, o_pose1, o_begin, o_end, o_work;
+};
+
+static PnpChainLayout pnp_chain_layout(int nproblems, int nrows) {
   const size_t np = (size_t)nproblems;
-  const size_t o_mask = gh_round256((size_t)nrows * 4), o_in1 = o_mask + gh_round256((size_t)nrows), o_pose1 = o_in1 + gh_round256((size_t)nrows),
-               o_begin = o_pose1 + gh_round256(np * 56), o_end = o_begin + gh_round256(np * 4), o_work = o_end + gh_round256(np * 4);
-  void* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_work + ransac_batch_scratch_bytes(nproblems), &base));
-  uint8_t* b = (uint8_t*)base;
-  int32_t* row_begin = (int32_t*)(b + o_begin);
-  int32_t* row_end = (int32_t*)(b + o_end);
+  PnpChainLayout L;
+  L.o_mask = gh_round256((size_t)nrows * 4);
+  L.o_in1 = L.o_mask + gh_round256((size_t)nrows);
+  L.o_pose1 = L.o_in1 + gh_round256((size_t)nrows);
+  L.o_begin = L.o_pose1 + gh_round256(np * 56);
+  L.o_end = L.o_begin + gh_round256(np * 4);
+  L.o_work = L.o_end + gh_round256(np * 4);
+  return L;
+}
+
+size_t pnp_batch_scratch_bytes(int nproblems, int nrows) {
+  return pnp_chain_layout(nproblems, nrows).o_work + ransac_batch_scratch_bytes(nproblems);
+}
+
+gh_status pnp_batch_on(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev, int nproblems, int nrows,
+                       double ransac_threshold, uint64_t seed, int dof, const gh_ba_options* options, int min_rows,
+                       double inlier_threshold, double* models_dev, int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
+                       gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev, void* work) {
+  const PnpChainLayout L = pnp_chain_layout(nproblems, nrows);
+  uint8_t* b = (uint8_t*)work;
+  int32_t* row_begin = (int32_t*)(b + L.o_begin);
+  int32_t* row_end = (int32_t*)(b + L.o_end);
   GH_LAUNCH(ctx, "pnp_batch_ranges", pnp_batch_ranges_kernel, dim3(gh_div_up(nproblems, 256)), dim3(256), 0,
             RowRanges{offsets_dev, offsets_dev + 1, offsets_dev + nproblems, nrows}, nproblems, row_begin, row_end);
   const RowRanges range = {row_begin, row_end, nullptr, nrows};
   GH_TRY(ransac_batch_ranges(ctx, kModelPnP, xyz_dev, xy_dev, range, nproblems, ransac_threshold, nullptr, seed, nullptr, models_dev,
-                             b + o_mask, ransac_inliers_dev, b + o_work));
+                             b + L.o_mask, ransac_inliers_dev, b + L.o_work));
   PnpBatchArgs a = {};
   a.xyz = xyz_dev;
   a.xy = xy_dev;
@@ -241,18 +256,18 @@ extern "C" gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const 
   a.rows = (int32_t*)b;
   a.summary_stride = 2;
   // round 1: the fit's inliers from the fit's model (the Huber fit)
-  a.mask = b + o_mask;
+  a.mask = b + L.o_mask;
   a.start = models_dev;
   a.start_stride = 12;
-  a.poses = (double*)(b + o_pose1);
+  a.poses = (double*)(b + L.o_pose1);
   a.info = nullptr;
   a.summaries = summaries_dev;
-  a.inlier = b + o_in1;
+  a.inlier = b + L.o_in1;
   a.n_inliers = nullptr;
   GH_TRY(refine_launch(ctx, a));
   // round 2: the rows within `inlier_threshold` of round 1, from round 1's pose
-  a.mask = b + o_in1;
-  a.start = (const double*)(b + o_pose1);
+  a.mask = b + L.o_in1;
+  a.start = (const double*)(b + L.o_pose1);
   a.start_stride = 7;
   a.poses = poses_dev;
   a.info = info_dev;
@@ -260,4 +275,24 @@ extern "C" gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const 
   a.inlier = inlier_dev;
   a.n_inliers = n_inliers_dev;
   return refine_launch(ctx, a);
+}
+
+}  // namespace gh_ransac
+
+extern "C" gh_status gh_pnp_batch_dev(gh_ctx* ctx, const double* xyz_dev, const double* xy_dev, const int32_t* offsets_dev,
+                                      int nproblems, int nrows, double ransac_threshold, uint64_t seed, int dof,
+                                      const gh_ba_options* options, int min_rows, double inlier_threshold, double* models_dev,
+                                      int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
+                                      gh_pnp_batch_summary* summaries_dev, uint8_t* inlier_dev, int32_t* n_inliers_dev) {
+  if (!ctx) return GH_ERR_ARG;
+  GH_ENTER(ctx);
+  GH_CHECK_ARG(ctx, pnp_batch_args_ok(nproblems, nrows, ransac_threshold, min_rows, inlier_threshold));
+  if (nproblems == 0) return GH_OK;
+  GH_CHECK_ARG(ctx, xyz_dev && xy_dev && offsets_dev && models_dev && ransac_inliers_dev && poses_dev && summaries_dev);
+  // ONE scratch block for all stages (gh_scratch hands out one block per context)
+  void* base = nullptr;
+  GH_TRY(gh_scratch(ctx, pnp_batch_scratch_bytes(nproblems, nrows), &base));
+  return pnp_batch_on(ctx, xyz_dev, xy_dev, offsets_dev, nproblems, nrows, ransac_threshold, seed, dof, options, min_rows,
+                      inlier_threshold, models_dev, ransac_inliers_dev, poses_dev, info_dev, summaries_dev, inlier_dev, n_inliers_dev,
+                      base);
 }

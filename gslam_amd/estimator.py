@@ -6,7 +6,9 @@ two_view_pairs (gh_two_view_batch_dev / gh_two_view_pairs_dev) go on from an ess
 3-D points, batched and device-resident in the same way.  pnp_refine_batch / pnp_batch (gh_pnp_refine_batch_dev /
 gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba_pnp would on its inliers.
 triangulate_tracks (gh_triangulate_tracks_dev) gives every map point of a gh_ba_problem its start from all of its observations;
-link_tracks (gh_link_tracks_dev) builds those per-point arrays from the inlier rows of the pair entries."""
+link_tracks (gh_link_tracks_dev) builds those per-point arrays from the inlier rows of the pair entries.
+gather_map_matches (gh_pnp_gather_pairs_dev) reads the pair matches of new frames through that map into the arrays pnp_batch
+takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call and says which keypoint rows were inliers."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +21,8 @@ PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinemen
 # GH_TRACK_*: status per point of triangulate_tracks
 TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_INCONSISTENT, TRACK_LOW_PARALLAX, TRACK_SKIPPED = 0, 1, 2, 3, 4, 5
 LINK_SHORT, LINK_CONFLICT, LINK_NO_ROW = -1, -2, -3  # GH_LINK_*: what node_point of link_tracks holds where there is no point id
+# GH_LOC_*: what row_point of gather_map_matches / localize_pairs holds where there is no point id
+LOC_NO_POINT, LOC_AMBIGUOUS, LOC_NO_ROW, LOC_SHARED = -1, -2, -3, -4
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
 
 
@@ -342,6 +346,75 @@ def link_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, int
     ctx.check(hip.lib.gh_link_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
                                          C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(min_views),
                                          *(p(out[k]) for k in out)))
+    return out
+
+
+def _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status):
+    """The inputs of the two map entries, checked, and the gather's output tensors in the order of the C arguments
+    -> (F, cap, P, n_points, out)."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1, node_point))
+    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
+    N, dev = F * cap, kps.device
+    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap and node_point.numel() == N
+    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
+    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() % 3 == 0
+    n_points = point_xyz.numel() // 3
+    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
+                                    point_status.numel() == n_points)
+    out = {"row_point": torch.empty(N, dtype=torch.int32, device=dev),
+           "offsets": torch.empty(F + 1, dtype=torch.int32, device=dev),
+           "xyz": torch.empty((N, 3), dtype=torch.float64, device=dev),
+           "xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
+           "corr_node": torch.empty(N, dtype=torch.int32, device=dev),
+           "totals": torch.empty(4, dtype=torch.int32, device=dev)}
+    return F, cap, P, n_points, out
+
+
+def gather_map_matches(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status, intrinsics):
+    """gh_pnp_gather_pairs_dev, the call between a map (link_tracks, triangulate_tracks) and pnp_batch.  kps: F x cap x 7 float32
+    view of the KeyPoint records, counts: F int32, pair_q / pair_t: P int32 (new frame, map frame), idx1: P x cap int32, keep:
+    P x cap uint8 or None (all rows); node_point: F * cap int32 as link_tracks returns it, point_xyz: n_points x 3 float64,
+    point_status: n_points int32 (only TRACK_OK points are used) or None (all points) -- all cuda; intrinsics: (fx, fy, cx, cy).
+    With N = F * cap -> dict of device tensors: row_point N int32 (a point id, LOC_NO_POINT, LOC_AMBIGUOUS, LOC_NO_ROW or
+    LOC_SHARED), offsets F + 1 int32, xyz N x 3 and xy N x 2 float64 (zeros past n_corr), corr_node N int32 (-1 past n_corr),
+    totals 4 int32 (n_corr, AMBIGUOUS nodes, SHARED nodes, frames with a correspondence); nothing is synchronised and nothing is
+    read back: xyz, xy, offsets go to pnp_batch as they are."""
+    F, cap, P, n_points, out = _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_pnp_gather_pairs_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(keep),
+                                              p(node_point), n_points, p(point_xyz), _p(point_status), C.c_double(fx),
+                                              C.c_double(fy), C.c_double(cx), C.c_double(cy), *(p(out[k]) for k in out)))
+    return out
+
+
+def localize_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status, intrinsics,
+                   ransac_threshold, seed, inlier_threshold, dof=63, options=None, min_rows=0, want_information=False):
+    """gh_localize_pairs_dev: every frame registered against the map in one call -- gather_map_matches, pnp_batch on its arrays
+    (one problem per frame), and the inlier bytes of the last round scattered back to keypoint rows.  Inputs as
+    gather_map_matches and pnp_batch take them.  -> dict of device tensors: the gather's (row_point, offsets, xyz, xy, corr_node,
+    totals), then models F x 12, ransac_inliers F, poses F x 7, info F x 36 or None, summaries F x 2 x 32 uint8 (view the host
+    copy as SUMMARY_DTYPE), row_inlier F * cap uint8 (1 where the row's correspondence is an inlier of the last round); nothing
+    is synchronised.  row_point and row_inlier are what extends the tracks with the new observations."""
+    import torch
+    F, cap, P, n_points, out = _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    dev = kps.device
+    out.update({"models": torch.empty((F, 12), dtype=torch.float64, device=dev),
+                "ransac_inliers": torch.empty(F, dtype=torch.int32, device=dev),
+                "poses": torch.empty((F, 7), dtype=torch.float64, device=dev),
+                "info": torch.empty((F, 36), dtype=torch.float64, device=dev) if want_information else None,
+                "summaries": torch.empty((F, 2, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
+                "row_inlier": torch.empty(F * cap, dtype=torch.uint8, device=dev)})
+    opt = _ba_options(options)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_localize_pairs_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(keep),
+                                            p(node_point), n_points, p(point_xyz), _p(point_status), C.c_double(fx), C.c_double(fy),
+                                            C.c_double(cx), C.c_double(cy), C.c_double(ransac_threshold), C.c_uint64(seed), int(dof),
+                                            C.byref(opt), int(min_rows), C.c_double(inlier_threshold), *(p(out[k]) for k in out)))
     return out
 
 

@@ -27,6 +27,8 @@ lib = _load()
 
 GH_OK = 0
 GH_BA_MAX_TRACE = 512
+# what row_point of gh_pnp_gather_pairs_dev / gh_localize_pairs_dev holds where there is no point id
+GH_LOC_NO_POINT, GH_LOC_AMBIGUOUS, GH_LOC_NO_ROW, GH_LOC_SHARED = -1, -2, -3, -4
 
 
 class KeyPoint(C.Structure):
@@ -223,6 +225,12 @@ SIGNATURES = {
     "gh_triangulate_tracks_dev": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(TrackParams), _vp, _vp, _vp, _vp]),
     "gh_link_tracks_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _i,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_pnp_gather_pairs_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp,
+                                          C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_localize_pairs_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp,
+                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, _i,
+                                        C.POINTER(BaOptions), _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
     "gh_pg_solve": (C.c_int, [_vp, C.POINTER(PgProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_graph_solve": (C.c_int, [_vp, C.POINTER(GraphProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_align_sim3": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),

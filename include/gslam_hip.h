@@ -852,6 +852,71 @@ gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int3
                              const uint8_t* inlier_dev, double fx, double fy, double cx, double cy, int min_views,
                              int32_t* node_point_dev, int32_t* obs_cam_dev, int32_t* obs_point_dev, double* obs_xy_dev,
                              int32_t* obs_node_dev, int32_t* point_len_dev, int32_t* totals_dev);
+/* The 3D-2D gather: new frames matched against map frames, read through the map -- the step between gh_link_tracks_dev /
+ * gh_triangulate_tracks_dev (a map exists) and gh_pnp_batch_dev (xyz, xy, offsets of one problem per frame).  Every pointer is a
+ * DEVICE pointer, nothing is copied to the host, the call is asynchronous on the context's stream, scratch comes from the
+ * context.  kps_dev, counts_dev, n_frames, cap, pair_q_dev, pair_t_dev, npairs, idx1_dev as gh_link_tracks_dev takes them;
+ * keep_dev npairs x cap or NULL (all rows).  The map: node_point_dev N = n_frames * cap entries as gh_link_tracks_dev writes them
+ * (>= 0: a point id, anything negative: no point), point_xyz_dev n_points x 3, point_status_dev n_points or NULL -- a point is
+ * USABLE when point_status_dev is NULL or its status equals GH_TRACK_OK.
+ *   candidates pair p is read under the rule of gh_link_tracks_dev (both frame indices in range and different, else nothing of
+ *              it is addressed).  Query row i of the pair passes when i < clamp(counts[pair_q[p]], 0, cap), (keep_dev == NULL ||
+ *              keep_dev[p * cap + i] != 0) and 0 <= j = idx1[p * cap + i] < clamp(counts[pair_t[p]], 0, cap): the gather rule of
+ *              gh_ransac_pairs_dev.  A passing row gives the candidate c = node_point[pair_t[p] * cap + j] to the node
+ *              (pair_q[p], i) when 0 <= c < n_points and point c is usable; a value outside that range drops the candidate, it is
+ *              never used as an index.  The node_point entries of a frame are read only where the frame is the TRAIN frame of a
+ *              pair: what a query node itself holds plays no part.  The same pair may occur any number of times.
+ *   per node   S = the set of its candidates over all pairs.  The node does not exist: GH_LOC_NO_ROW.  S empty: GH_LOC_NO_POINT.
+ *              min S != max S: GH_LOC_AMBIGUOUS -- two map frames disagree about what this keypoint is; the row is dropped, not
+ *              voted on.  Otherwise the node CLAIMS the one point of S.
+ *   per (frame, point)  two or more nodes of one frame claim the same point: all of them are GH_LOC_SHARED (a many-to-one
+ *              match, as the CONFLICT rule of gh_link_tracks_dev).  A node that is the only one of its frame to claim its point
+ *              is a CORRESPONDENCE; nodes of different frames may claim one point, each stays.
+ *   numbering  correspondences are numbered in ascending node id (frame-major, then row); problem f (one per frame) owns
+ *              offsets[f] .. offsets[f + 1] - 1, offsets[n_frames] = n_corr; a frame without correspondences has an empty range.
+ * Outputs, ALL written for their full capacity on every call (dirty buffers never show): row_point_dev N: the point id or a
+ * GH_LOC_* code; offsets_dev n_frames + 1; xyz_dev N x 3: for k < n_corr an exact copy of the point's three doubles; xy_dev
+ * N x 2: (((double)x - cx) / fx, ((double)y - cy) / fy) of the keypoint (two IEEE operations each, nothing fused: the
+ * normalisation of gh_link_tracks_dev); corr_node_dev N: the node of correspondence k; for k >= n_corr xyz = xy = zeros and
+ * corr_node = -1; totals_dev 4: n_corr, the AMBIGUOUS nodes, the SHARED nodes, the frames with at least one correspondence.
+ * xyz_dev, xy_dev, offsets_dev go to gh_pnp_batch_dev as they are, with nproblems = n_frames and nrows = N.  Everything is integer
+ * work except the two divisions: the same bits on every run.  tests/localize_restate.py restates all of it.
+ * GH_ERR_ARG, and then nothing is written: ctx NULL; n_frames, cap, npairs or n_points negative; cap > 65535; n_frames * cap >
+ * INT32_MAX - 1; fx or fy not > 0 (a NaN included); a NULL among kps, counts, node_point or the six outputs; with n_points > 0 a
+ * NULL point_xyz; with npairs > 0 a NULL among pair_q, pair_t, idx1.  N == 0: GH_OK, only offsets_dev (zeros) and totals_dev
+ * (zeros) are written.  npairs == 0 or n_points == 0 with N > 0: every existing node is NO_POINT. */
+#define GH_LOC_NO_POINT (-1)
+#define GH_LOC_AMBIGUOUS (-2)
+#define GH_LOC_NO_ROW (-3)
+#define GH_LOC_SHARED (-4)
+gh_status gh_pnp_gather_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int n_frames, int cap,
+                                  const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                                  const uint8_t* keep_dev, const int32_t* node_point_dev, int n_points, const double* point_xyz_dev,
+                                  const int32_t* point_status_dev, double fx, double fy, double cx, double cy,
+                                  int32_t* row_point_dev, int32_t* offsets_dev, double* xyz_dev, double* xy_dev,
+                                  int32_t* corr_node_dev, int32_t* totals_dev);
+/* Register every frame against the map in one call.  It equals, bit for bit, the composition of the public pieces:
+ *   1. gh_pnp_gather_pairs_dev -> row_point_dev, offsets_dev, xyz_dev, xy_dev, corr_node_dev, totals_dev (outputs of this call
+ *      too, the caller supplies the arrays);
+ *   2. gh_pnp_batch_dev(xyz_dev, xy_dev, offsets_dev, nproblems = n_frames, nrows = N, ransac_threshold, seed, dof, options,
+ *      min_rows, inlier_threshold) -> models_dev n_frames x 12, ransac_inliers_dev n_frames, poses_dev n_frames x 7, info_dev
+ *      n_frames x 36 or NULL, summaries_dev n_frames x 2; its inlier bytes per correspondence and n_inliers stay in scratch;
+ *   3. a scatter -> row_inlier_dev N bytes: 1 exactly at the nodes whose correspondence is an inlier of the last round, 0
+ *      everywhere else.
+ * row_point_dev and row_inlier_dev together are what a later stage needs to add the new observations to the tracks.  A frame
+ * without correspondences is an empty range of gh_pnp_batch_dev and comes out as that contract says.  GH_ERR_ARG: whatever
+ * either stage rejects, and row_inlier_dev NULL -- checked before anything is launched, and then nothing is written.
+ * N == 0: GH_OK, only offsets_dev and totals_dev are written, and with n_frames > 0 what gh_pnp_batch_dev writes for empty
+ * ranges. */
+gh_status gh_localize_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int n_frames, int cap,
+                                const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                                const uint8_t* keep_dev, const int32_t* node_point_dev, int n_points, const double* point_xyz_dev,
+                                const int32_t* point_status_dev, double fx, double fy, double cx, double cy,
+                                double ransac_threshold, uint64_t seed, int dof, const gh_ba_options* options, int min_rows,
+                                double inlier_threshold, int32_t* row_point_dev, int32_t* offsets_dev, double* xyz_dev,
+                                double* xy_dev, int32_t* corr_node_dev, int32_t* totals_dev, double* models_dev,
+                                int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
+                                gh_pnp_batch_summary* summaries_dev, uint8_t* row_inlier_dev);
 
 /* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
