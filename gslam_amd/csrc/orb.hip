@@ -109,9 +109,9 @@ struct ResizeTabs {
   const uint32_t* ytab;  // idx << 16 | frac per output row
   // fused MFMA resize (resize_tile_mfma): per 8-column output group g the A operand of v_mfma_f32_16x16x32_f16 for the 16 output
   // columns 8 g .. 8 g + 15 -- A[m][k] = the weight of source column mcw[g] + k for output column 8 g + m (2048 - fx at the left
-  // tap, fx at the right one, f16) -- as 64 lanes x 4 dwords, and the window start mcw[g] = sx(8 g) & ~7.  Null: not available.
+  // tap, fx at the right one, f16) -- as 64 lanes x 4 dwords, with the window start mcw[g] = sx(8 g) & ~7 (the kernel gets it through
+  // its tile's record, TileColRec).  Null: not available.
   const uint32_t* mtab = nullptr;
-  const uint32_t* mcw = nullptr;
 };
 
 // One work item: output columns x8 .. x8 + 7, output rows y0 .. y_end - 1 (at most kResizeRows of them) of one frame.
@@ -132,11 +132,14 @@ __device__ __forceinline__ void resize_item(const LevelView& src, const uint8_t*
   const bool guard = guard_frame && (int)d0 + 16 > src.pitch;
   const uint32_t last_dw = (uint32_t)src.pitch - 4u;
   const uint32_t pitch = (uint32_t)src.pitch;
+  // the item's four table rows in ONE load, with the column's entries (the table is padded and followed by others: rows >= y_end
+  // are read and not used) -- entry by entry, each went out behind the previous row's store: three more dependent round trips
+  const u32x4_a4 ty4 = *reinterpret_cast<const u32x4_a4*>(tb.ytab + y0);
 #pragma unroll
   for (int rr = 0; rr < kResizeRows; ++rr) {
     const int y = y0 + rr;
     if (y >= y_end) break;
-    const uint32_t ty = tb.ytab[y];
+    const uint32_t ty = ty4[rr];
     const uint32_t sy = ty >> 16;
     const uint32_t fy = ty & 0xFFFFu;
     const uint32_t sy1 = sy + 1 < (uint32_t)src.h ? sy + 1 : (uint32_t)src.h - 1;
@@ -203,15 +206,40 @@ struct NextLevel {
   const int32_t* gx0;      // [nbx + 1] first owned output group per tile column
   const int32_t* gy0;      // [nby + 1] first owned output row per tile row
   int tail_unsafe_frame;
-  // tile id -> (frame, tile row, tile column) without integer divisions: q = __umulhi(n, inv) == n / d for every tile id of
-  // the launch (checked on the host: magic_div); 0 = divide (the one-launch-for-all-levels path of small calls)
-  uint32_t tiles_inv = 0, nbx_inv = 0;
   // PLANE variant of the kernel (the quadtree mode's score plane, orb_quadtree.hip): S of this level, pixel (y, x) of a frame at
   // plane[y * plane_pitch + x + kQtPlaneX]
   uint8_t* plane = nullptr;
   size_t plane_frame_stride = 0;
   int plane_pitch = 0;
 };
+
+// What the fused MFMA resize of an INTERIOR tile needs to know about its tile column and tile row, packed at plan creation
+// (build_tile_records) so that the kernel fetches it in ONE scalar round trip (the two records' loads are issued together)
+// instead of chasing gx0[bx], gx0[bx + 1], gy0[by], gy0[by + 1] and four mcw[g] one dependent load after the other.  A level's
+// table: nbx column records, then nby row records.  The VALU path of the edge tiles keeps gx0 / gy0 (NextLevel).
+struct alignas(32) TileColRec {
+  int g0, ng;   // first owned output 8-column group of the next level / how many; ng > 8: the tile takes the VALU path
+  int cw[4];    // K-window start of column-block pair cb (ResizeTabs::mcw[g0 + 2 cb], cb clamped as resize_tile_mfma_load does), tile relative
+  int pad[2];
+};
+struct alignas(8) TileRowRec {
+  int r0, r1;   // owned output rows r0 .. r1 - 1
+};
+static_assert(sizeof(TileColRec) == 32 && sizeof(TileRowRec) == 8, "one aligned scalar load per record");
+
+// Everything a tile needs before its image loads can go out, contiguous and LEADING in the kernel's argument segment, with the
+// advice and record pointers right behind it: fast_cells_kernel reads these 64 bytes in one scalar round trip, where the
+// compiler fetched the same fields in seven dependent pieces.
+struct TileHead {
+  const uint8_t* base;     // the level (LevelView)
+  size_t frame_stride;
+  int pitch, w, h;
+  int ncx, ncy, n_frames;
+  // tile id -> (frame, tile row, tile column) without integer divisions: q = __umulhi(n, inv) == n / d for every tile id of
+  // the launch (checked on the host: magic_div); 0 = divide (the one-launch-for-all-levels path of small calls)
+  uint32_t tiles_inv, nbx_inv;
+};
+static_assert(sizeof(TileHead) == 48, "with the two pointers behind it: the 64 leading argument bytes");
 
 // inv with __umulhi(n, inv) == n / d for every n <= n_max, or 0 when no such 32-bit constant is guaranteed
 inline uint32_t magic_div(uint32_t d, uint32_t n_max) {
@@ -238,18 +266,18 @@ struct ResizeOps {  // what resize_tile_mfma reads from global memory: one round
   int cwv[4];      // tile column of their K windows
   uint32_t ty;     // source row << 16 | fy of this lane's output row
 };
-__device__ __forceinline__ ResizeOps resize_tile_mfma_load(int ax, const ResizeTabs& tb, int g0, int ng, int r0, int r1) {
+__device__ __forceinline__ ResizeOps resize_tile_mfma_load(const ResizeTabs& tb, const TileColRec& c, int r0, int r1) {
   const int lane = threadIdx.x & 63, n16 = lane & 15;
   const int rb = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int ncb = (ng + 1) >> 1;  // <= 4
+  const int ncb = (c.ng + 1) >> 1;  // <= 4
   const int yq = r0 + 16 * rb + n16, y = yq < r1 ? yq : r1 - 1;
   ResizeOps o;
   o.ty = tb.ytab[y];
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb) {
-    const int g = g0 + 2 * (cb < ncb ? cb : 0);
+    const int g = c.g0 + 2 * (cb < ncb ? cb : 0);
     o.aw[cb] = *reinterpret_cast<const uint4*>(tb.mtab + ((size_t)g * 64 + lane) * 4);
-    o.cwv[cb] = (int)tb.mcw[g] - ax;  // tile column of the K window (a multiple of 8)
+    o.cwv[cb] = c.cw[cb];  // tile column of the K window (a multiple of 8): mcw[g] - 64 bx, from the record
   }
   return o;
 }
@@ -484,11 +512,11 @@ constexpr int kScoreH = 66;   // score window: 64x64 region + 1 px NMS halo
 constexpr int kScoreOff = 3;  // window col sx is stored at byte sx + 3 so that both cells of a row start dword aligned
 
 // tile id -> (frame, tile row, tile column)
-__device__ __forceinline__ void fast_tile_coords(const NextLevel& nx, int nbx, int nby, int tile_id, int& frame, int& bx, int& by) {
-  if (nx.tiles_inv != 0u && nx.nbx_inv != 0u) {  // (two integer divisions were ~40 VALU per wave: 4 % of the kernel)
-    frame = (int)__umulhi((uint32_t)tile_id, nx.tiles_inv);
+__device__ __forceinline__ void fast_tile_coords(const TileHead& hd, int nbx, int nby, int tile_id, int& frame, int& bx, int& by) {
+  if (hd.tiles_inv != 0u && hd.nbx_inv != 0u) {  // (two integer divisions were ~40 VALU per wave: 4 % of the kernel)
+    frame = (int)__umulhi((uint32_t)tile_id, hd.tiles_inv);
     const int trem = tile_id - frame * (nbx * nby);
-    by = (int)__umulhi((uint32_t)trem, nx.nbx_inv);
+    by = (int)__umulhi((uint32_t)trem, hd.nbx_inv);
     bx = trem - by * nbx;
   } else {
     frame = tile_id / (nbx * nby);
@@ -498,7 +526,7 @@ __device__ __forceinline__ void fast_tile_coords(const NextLevel& nx, int nbx, i
   }
 }
 // 16-byte item i (< kTileH * 6) of the image tile of (frame, bx, by): LDS byte offset 16 i, global source clamped to the level
-__device__ __forceinline__ const uint4* fast_tile_src(const LevelView& lv, int frame, int bx, int by, int i) {
+__device__ __forceinline__ const uint4* fast_tile_src(const TileHead& lv, int frame, int bx, int by, int i) {
   // i / 6 on the full-rate 24-bit multiplier: exact for i < 420 since 10923 / 65536 - 1 / 6 = 5e-6 (a division by a
   // constant costs a quarter-rate v_mul_hi)
   const int row = (int)(__umul24((uint32_t)i, 10923u) >> 16), c = i - row * 6;
@@ -681,12 +709,19 @@ __device__ __forceinline__ int fast_cell_stage(const uint8_t* sc, uint16_t* list
 // Above ini_th pass 1 is the conservative test on 6-bit pixels (fast_compass4_q; profiles/orb_pass1_quant.txt): pass 2 is exact and
 // stores S > T only, so the longer queue changes no score.  At T == ini_th, where the shortcut asks what the EXACT test queued,
 // and on every single-phase path pass 1 stays fast_compass4.
+// The prologue asks for everything the tile needs as early as its address is known (profiles/orb_tile_prologue.txt): hd (one
+// scalar round trip, the kernel's) gives the tile's coordinates and the addresses of BOTH 16-byte items of a thread, which go
+// out first; behind them, together, the advice word and the tile's column and row record (a second scalar round trip), then
+// the operands of the fused resize.  (Vector loads return in order and the operands are L2 hits queued behind the image bytes:
+// the compiler drains the counter in front of the LDS writes, which costs little -- the operands could not arrive first.)
 template <bool PLANE, bool TWO_PHASE>
-__device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, int ncy, int min_th, int ini_th, bool two,
-                                                const uint32_t* __restrict__ hint, int th_a, uint32_t epoch,
+__device__ __forceinline__ void fast_cells_tile(const TileHead& hd, const uint32_t* __restrict__ hint,
+                                                const TileColRec* __restrict__ tile_rec, int min_th, int ini_th, bool two, int th_a, uint32_t epoch,
                                                 uint32_t* __restrict__ cell_cnt, uint32_t* __restrict__ cell_ent,
-                                                int cells_per_frame, int cell_off, int n_frames, const NextLevel& nx,
+                                                int cells_per_frame, int cell_off, const NextLevel& nx,
                                                 uint32_t* __restrict__ dbg, int tile_id) {
+  const LevelView lv{hd.base, hd.frame_stride, hd.pitch, hd.w, hd.h};
+  const int ncx = hd.ncx, ncy = hd.ncy;
   bool phase_a = TWO_PHASE && two;
   int score_th = min_th;  // scores at or below it are stored as 0 (phase A: T, once the frame is known)
   // Pass 1 covers a window row with 17 aligned dwords (window cols -2 .. 65) and the score tile is FLAT with 68 bytes
@@ -710,10 +745,34 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
   __builtin_assume(tid >= 0 && tid < 256);
   const int nbx = (ncx + 1) >> 1, nby = (ncy + 1) >> 1;
   int frame, bx, by;
-  fast_tile_coords(nx, nbx, nby, tile_id, frame, bx, by);
+  fast_tile_coords(hd, nbx, nby, tile_id, frame, bx, by);
+  // 16 B per lane and item: rows of the level are 16-byte aligned (pitch % 16 == 0, checked by the launcher).  Both items of a
+  // thread are requested here, before anything is waited for (as a loop, the second went out only after the first had arrived:
+  // two HBM round trips per tile); the threads without a second item read the last one again and drop it.
+  constexpr int kTileItems = kTileH * (kTileW / 16);
+  static_assert(kTileW / 16 == 6 && kTileItems <= 512 && kTileItems > 256, "two 16-byte items per thread");
+  const uint4 item0 = *fast_tile_src(hd, frame, bx, by, tid);
+  const uint4 item1 = *fast_tile_src(hd, frame, bx, by, min(tid + 256, kTileItems - 1));
+  // the second scalar round trip, all of it requested at once: the advice word (first used at pass 1) ...
+  uint32_t hint_word = 0u;
   if constexpr (TWO_PHASE) {
-    if (phase_a) {  // (frame is workgroup-uniform: one scalar load)
-      if (hint != nullptr) th_a = hint_threshold(hint[__builtin_amdgcn_readfirstlane(frame) * kMaxL], epoch, ini_th);
+    if (hint != nullptr) hint_word = hint[frame * kMaxL];  // (hint != null: the host passes it with `two` only; frame is workgroup-uniform)
+  }
+  // ... and the records of an interior tile's column and row
+  TileColRec crec{};
+  TileRowRec rrec{};
+  const bool has_rec = tile_rec != nullptr && by > 0 && by < nby - 1 && bx < nbx - 1;
+  if (has_rec) {
+    crec = tile_rec[bx];
+    rrec = reinterpret_cast<const TileRowRec*>(tile_rec + nbx)[by];
+  }
+  // ... with the arguments the threshold is made of (an empty statement that needs them where the record is first needed: see
+  // fast_cells_kernel) -- fetched where they are used, they were one more round trip between the tile's arrival and the barrier
+  int rng = crec.ng;
+  asm("" : "+s"(rng) : "s"(min_th), "s"(ini_th), "s"((int)two), "s"(th_a), "s"(epoch));
+  if constexpr (TWO_PHASE) {
+    if (phase_a) {
+      if (hint != nullptr) th_a = hint_threshold(hint_word, epoch, ini_th);
       score_th = th_a;
     }
   }
@@ -726,37 +785,25 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
     g_orb_phase_buf[(size_t)slot_ * 8 + 6] = 1u;
   }
 #endif
-  static_assert(kTileW / 16 == 6 && kTileH * (kTileW / 16) <= 512 && kTileH * (kTileW / 16) > 256, "two 16-byte items per thread");
   if (tid == 0) q_count = 0;
-  const int x0 = kEdge + 64 * bx, y0 = kEdge + 64 * by;  // region origin
+  const int x0 = kEdge + 64 * bx, y0 = kEdge + 64 * by;  // region origin (the 16-byte aligned tile origin column is 64 bx: x0 - 4 == 64 bx + 15)
   const int oy = y0 - 4;                       // tile origin row
-  const int ax = 64 * bx;                      // 16-byte aligned tile origin column: x0 - 4 == ax + 15
-  const uint8_t* img = lv.base + (size_t)frame * lv.frame_stride;
 
-  // interior tile: the operands of the fused MFMA resize are requested FIRST, in front of the tile loads -- their round trip (L2)
-  // runs under the tile's (HBM) instead of behind the first barrier (round 6: -2 % on the kernel)
-  bool resized = false;
+  // interior tile: the operands of the fused MFMA resize are requested behind the tile's bytes and in front of the first wait for
+  // them -- their round trip (L2) runs under the tile's (HBM) instead of behind the first barrier (round 6: -2 % on the kernel)
+  const bool resized = has_rec && rng <= 8;
   ResizeOps rops;
-  int rg0 = 0, rng = 0, rr0 = 0, rr1 = 0;
-  if (nx.dst_base != nullptr && nx.tb.mtab != nullptr && by > 0 && by < nby - 1 && bx < nbx - 1) {
-    rg0 = nx.gx0[bx];
-    rng = nx.gx0[bx + 1] - rg0;
-    if (rng <= 8) {
-      rr0 = nx.gy0[by];
-      rr1 = nx.gy0[by + 1];
-      rops = resize_tile_mfma_load(ax, nx.tb, rg0, rng, rr0, rr1);
-      resized = true;
-    }
-  }
-  // 16 B per lane: rows of the level are 16-byte aligned (pitch % 16 == 0, checked by the launcher)
-  for (int i = tid; i < kTileH * (kTileW / 16); i += 256) *reinterpret_cast<uint4*>(&tile[16 * i]) = *fast_tile_src(lv, frame, bx, by, i);
+  const int rg0 = crec.g0, rr0 = rrec.r0, rr1 = rrec.r1;
+  if (resized) rops = resize_tile_mfma_load(nx.tb, crec, rr0, rr1);
   // candidate bit b of a thread (see pass 1): b ^ 15 = 16 (k >> 1) + 2 trip + (k & 1) -> score offset 1024 trip + 1 + k;
-  // the quantised pass 1: b = 8 k + 7 - trip
+  // the quantised pass 1: b = 8 k + 7 - trip  (in front of the tile's stores: nothing here waits for the image)
   if (tid < 32) {
     const int ix = tid ^ 15;
     const int k = pass1_quant ? tid >> 3 : (ix & 1) + 2 * (ix >> 4), trip = pass1_quant ? 7 - (tid & 7) : (ix >> 1) & 7;
     bit_pos[tid] = (uint16_t)(1024 * trip + 1 + k);
   }
+  *reinterpret_cast<uint4*>(&tile[16 * tid]) = item0;
+  if (tid + 256 < kTileItems) *reinterpret_cast<uint4*>(&tile[16 * (tid + 256)]) = item1;
   __syncthreads();
   GH_PHASE(0);
   // The next pyramid level of an INTERIOR tile, now, out of the image tile (which the NMS lists overwrite after pass 2): h-taps
@@ -938,18 +985,24 @@ __device__ __forceinline__ void fast_cells_tile(const LevelView& lv, int ncx, in
 
 // (8 waves per SIMD -- at most 64 VGPRs -- and 20.4 KB of LDS let 8 workgroups share a CU)
 template <bool PLANE>
-__global__ __launch_bounds__(256, GH_FAST_WAVES) void fast_cells_kernel(LevelView lv, int ncx, int ncy, int min_th, int ini_th,
+__global__ __launch_bounds__(256, GH_FAST_WAVES) void fast_cells_kernel(TileHead hd, const uint32_t* __restrict__ hint,
+                                                         const TileColRec* __restrict__ tile_rec, int min_th, int ini_th,
                                                          uint32_t* __restrict__ cell_cnt,
                                                          uint32_t* __restrict__ cell_ent, int cells_per_frame,
-                                                         int cell_off, int n_frames, NextLevel nx,
-                                                         uint32_t* __restrict__ dbg, int two_phase,
-                                                         const uint32_t* __restrict__ hint, int th_a, uint32_t epoch) {
-  const int total = ((ncx + 1) >> 1) * ((ncy + 1) >> 1) * n_frames;
+                                                         int cell_off, NextLevel nx,
+                                                         uint32_t* __restrict__ dbg, int two_phase, int th_a, uint32_t epoch) {
+  // every leading argument in scalar registers HERE, in front of the early exit: the 64 bytes come in one scalar round trip (left
+  // to itself the compiler fetches each field in the block that first uses it: seven dependent round trips).  The statement is
+  // empty and NOT volatile -- a volatile one counts as a store to anything, after which no uniform load is a scalar load -- and
+  // the early exit needs its output.
+  int ncx = hd.ncx;
+  asm("" : "+s"(ncx) : "s"(hd.base), "s"(hd.frame_stride), "s"(hd.pitch), "s"(hd.w), "s"(hd.h), "s"(hd.ncy), "s"(hd.n_frames),
+                        "s"(hd.tiles_inv), "s"(hd.nbx_inv), "s"(hint), "s"(tile_rec));
+  const int total = ((ncx + 1) >> 1) * ((hd.ncy + 1) >> 1) * hd.n_frames;
   const int tile_id = xcd_strip_tile(blockIdx.x, total);
   if (tile_id >= total) return;
   // (the score plane of the quadtree mode wants S itself: single-phase)
-  fast_cells_tile<PLANE, !PLANE>(lv, ncx, ncy, min_th, ini_th, two_phase != 0, hint, th_a, epoch, cell_cnt, cell_ent, cells_per_frame, cell_off,
-                                 n_frames, nx, dbg, tile_id);
+  fast_cells_tile<PLANE, !PLANE>(hd, hint, tile_rec, min_th, ini_th, two_phase != 0, th_a, epoch, cell_cnt, cell_ent, cells_per_frame, cell_off, nx, dbg, tile_id);
 }
 
 // Every level in ONE launch, over a pyramid that exists already (stand-alone resize launches): what a small call wants --
@@ -968,8 +1021,11 @@ __global__ __launch_bounds__(256) void fast_cells_all_kernel(AllLevels A, int mi
   for (int k = 1; k < A.n_levels; ++k)
     if ((int)blockIdx.x >= A.tile_start[k]) l = k;
   const NextLevel none{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
-  fast_cells_tile<false, false>(A.lv[l], A.ncx[l], A.ncy[l], min_th, ini_th, false, nullptr, ini_th, 0u, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l],
-                                n_frames, none, dbg, (int)blockIdx.x - A.tile_start[l]);
+  const LevelView& lv = A.lv[l];
+  // (no magic divisors: the tile divides; no advice, no records)
+  const TileHead hd{lv.base, lv.frame_stride, lv.pitch, lv.w, lv.h, A.ncx[l], A.ncy[l], n_frames, 0u, 0u};
+  fast_cells_tile<false, false>(hd, nullptr, nullptr, min_th, ini_th, false, ini_th, 0u, cell_cnt, cell_ent, cells_per_frame, A.cell_off[l], none, dbg,
+                                (int)blockIdx.x - A.tile_start[l]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2005,6 +2061,7 @@ struct gh_orb_plan {
   int32_t* level_cnt = nullptr;
   const int32_t* own_gx[kMaxL] = {nullptr};  // fused pyramid: first owned output group / row per tile column / row of level l
   const int32_t* own_gy[kMaxL] = {nullptr};
+  const TileColRec* tile_rec[kMaxL] = {nullptr};  // the same, packed per tile column / row for the interior tiles (TileColRec); null = level l + 1 has no MFMA tables
   int8_t* d_pattern = nullptr;
   int8_t* d_base_pattern = nullptr;  // the unrotated tests, 256 x 4 int8 (continuous steering)
   int8_t base_pattern[256 * 4] = {};
@@ -2274,12 +2331,15 @@ static size_t mfma_words(int wd) {
 }
 // ownership of the next level by the tile columns / rows of fast_cells: one word per tile + 1
 static size_t own_words(int ncells) { return pad8((size_t)(ncells + 1) / 2 + 1); }
+// the tile records of a level: 8 words per tile column, then 2 per tile row
+static size_t tile_rec_words(int ncx, int ncy) { return 8 * (size_t)((ncx + 1) / 2) + pad8(2 * (size_t)((ncy + 1) / 2)); }
 
 static size_t plan_table_words(const gh_orb_plan* p) {
   size_t words = 0;
   for (int l = 1; l < p->L; ++l) words += axis_words(p->lw[l]) + lerp_words(p->lw[l]) + axis_words(p->lh[l]);
   for (int l = 1; l < p->L; ++l) words += mfma_words(p->lw[l]);
   for (int l = 0; l + 1 < p->L; ++l) words += own_words(p->ncx[l]) + own_words(p->ncy[l]);
+  for (int l = 0; l + 1 < p->L; ++l) words += tile_rec_words(p->ncx[l], p->ncy[l]);
   return words;
 }
 
@@ -2415,8 +2475,36 @@ static void build_own_tables(gh_orb_plan* p, int l, std::vector<uint32_t>& htab,
   while (tw & 7) htab[tw++] = (uint32_t)hd;
 }
 
+// The tile records of level l (TileColRec / TileRowRec), from its ownership tables and the window starts of level l + 1: what
+// resize_tile_mfma_load needs of both, one record per tile column and one per tile row.
+static void build_tile_records(gh_orb_plan* p, int l, std::vector<uint32_t>& htab, size_t& tw) {
+  const int nbx = (p->ncx[l] + 1) / 2, nby = (p->ncy[l] + 1) / 2;
+  const size_t words = tile_rec_words(p->ncx[l], p->ncy[l]);
+  const bool ok = p->mcw[l + 1] != nullptr;
+  if (ok) {
+    const uint32_t* gx = htab.data() + (reinterpret_cast<const uint32_t*>(p->own_gx[l]) - p->tabs);
+    const uint32_t* gy = htab.data() + (reinterpret_cast<const uint32_t*>(p->own_gy[l]) - p->tabs);
+    const uint32_t* mc = htab.data() + (p->mcw[l + 1] - p->tabs);
+    for (int bx = 0; bx < nbx; ++bx) {
+      const int g0 = (int)gx[bx], ng = (int)gx[bx + 1] - g0, ncb = (ng + 1) / 2;
+      uint32_t* r = htab.data() + tw + 8 * (size_t)bx;
+      r[0] = (uint32_t)g0;
+      r[1] = (uint32_t)ng;
+      for (int cb = 0; cb < 4; ++cb)  // (ng == 0 or > 8: the tile never takes the MFMA path, the windows are not read)
+        r[2 + cb] = ng >= 1 && ng <= 8 ? (uint32_t)((int)mc[g0 + 2 * (cb < ncb ? cb : 0)] - 64 * bx) : 0u;
+      r[6] = r[7] = 0u;
+    }
+    for (int by = 0; by < nby; ++by) {
+      htab[tw + 8 * (size_t)nbx + 2 * (size_t)by] = gy[by];
+      htab[tw + 8 * (size_t)nbx + 2 * (size_t)by + 1] = gy[by + 1];
+    }
+  }
+  p->tile_rec[l] = ok ? reinterpret_cast<const TileColRec*>(p->tabs + tw) : nullptr;
+  tw += words;
+}
+
 // Fills the host copy of the table block and points the plan's table pointers into the device copy.  Layout: per level
-// x | selector | weight | y, then the MFMA tables of every level, then the ownership tables.  The cursor tw must end at
+// x | selector | weight | y, then the MFMA tables of every level, then the ownership tables, then the tile records.  The cursor tw must end at
 // the size plan_table_words planned.
 static gh_status plan_build_tables(gh_orb_plan* p, std::vector<uint32_t>& htab, size_t tab_words) {
   const int L = p->L;
@@ -2434,6 +2522,7 @@ static gh_status plan_build_tables(gh_orb_plan* p, std::vector<uint32_t>& htab, 
   }
   for (int l = 1; l < L; ++l) build_mfma_tables(p, l, htab, tw);
   for (int l = 0; l + 1 < L; ++l) build_own_tables(p, l, htab, tw);
+  for (int l = 0; l + 1 < L; ++l) build_tile_records(p, l, htab, tw);
   if (tw != tab_words) return gh_set_error(p->ctx, GH_ERR_ARG, "gh_orb_plan_create: the tables take %zu words, %zu were planned", tw, tab_words);
   return GH_OK;
 }
@@ -2673,18 +2762,24 @@ static gh_status launch_select(const OrbCall& c, const SelectArgs& sa, int l0, i
   return GH_OK;
 }
 
-// what fast_cells(l) needs to produce level l + 1, and the magic divisors of its `tiles` tile ids
-static NextLevel next_level_args(const OrbCall& c, int l, long long tiles) {
+// what fast_cells(l) needs to produce level l + 1
+static NextLevel next_level_args(const OrbCall& c, int l) {
   const gh_orb_plan* p = c.p;
   NextLevel nx{nullptr, 0, 0, 0, ResizeTabs{nullptr, nullptr, nullptr, nullptr}, nullptr, nullptr, -1};
   if (l + 1 < p->L)
     nx = NextLevel{p->pyr + p->lvl_off[l + 1], p->slab, p->pitch[l + 1], p->lh[l + 1],
-                   ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1], p->mcw[l + 1]},
+                   ResizeTabs{p->xtab[l + 1], p->xsel[l + 1], p->xwgt[l + 1], p->ytab[l + 1], p->mtab[l + 1]},
                    p->own_gx[l], p->own_gy[l], (l == 0 && c.s.zero_copy0) ? c.batch - 1 : -1};
-  const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
-  nx.tiles_inv = magic_div(tpf, (uint32_t)tiles);
-  nx.nbx_inv = magic_div(nbx, tpf);
   return nx;
+}
+
+// the leading argument of fast_cells(l): the level and its grid with the magic divisors of the launch's `tiles` tile ids
+static TileHead tile_head_args(const OrbCall& c, int l, long long tiles) {
+  const gh_orb_plan* p = c.p;
+  const LevelView& lv = c.lv[l];
+  const uint32_t nbx = (uint32_t)gh_div_up(p->ncx[l], 2), tpf = nbx * (uint32_t)gh_div_up(p->ncy[l], 2);
+  return TileHead{lv.base, lv.frame_stride, lv.pitch, lv.w, lv.h, p->ncx[l], p->ncy[l], c.batch,
+                  magic_div(tpf, (uint32_t)tiles), magic_div(nbx, tpf)};
 }
 
 // fast_cells(l): FAST, NMS and the cell lists of level l -- or, plane, the level's score plane for the quadtree mode -- with
@@ -2694,18 +2789,21 @@ static gh_status fast_level(const OrbCall& c, int l, bool plane) {
   gh_ctx* ctx = p->ctx;
   const long long tiles = (long long)gh_div_up(p->ncx[l], 2) * gh_div_up(p->ncy[l], 2) * c.batch;
   GH_CHECK_ARG(ctx, tiles < (1LL << 30));
-  NextLevel nx = next_level_args(c, l, tiles);
+  NextLevel nx = next_level_args(c, l);
   const dim3 grid(8 * gh_div_up(tiles, 8));
+  const TileColRec* trec = l + 1 < p->L ? p->tile_rec[l] : nullptr;  // the records of the interior tiles
   if (plane) {
     nx.plane = p->score_plane + p->plane_off[l];
     nx.plane_frame_stride = p->plane_slab;
     nx.plane_pitch = p->plane_pitch[l];
-    GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, 0, nullptr, 0, 0u);
+    GH_LAUNCH(ctx, "orb_fast_plane", fast_cells_kernel<true>, grid, dim3(256), 0, tile_head_args(c, l, tiles), nullptr, trec, p->prm.min_th_fast,
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], nx, c.dbg, 0, 0, 0u);
   } else {
-    GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0, c.lv[l], p->ncx[l], p->ncy[l], p->prm.min_th_fast,
-              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], c.batch, nx, c.dbg, c.s.two_phase ? 1 : 0,
-              c.s.hint_adaptive ? p->hint + l : nullptr, c.s.th_a, c.s.hint_epoch);
+    // (hint_adaptive implies two_phase: orb_schedule)
+    GH_LAUNCH(ctx, "orb_fast_cells", fast_cells_kernel<false>, grid, dim3(256), 0,
+              tile_head_args(c, l, tiles), c.s.hint_adaptive ? p->hint + l : nullptr, trec, p->prm.min_th_fast,
+              p->prm.ini_th_fast, p->cell_cnt, p->cell_ent, p->cells_per_frame, p->cell_off[l], nx, c.dbg, c.s.two_phase ? 1 : 0,
+              c.s.th_a, c.s.hint_epoch);
   }
   return GH_OK;
 }
