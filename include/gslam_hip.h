@@ -610,6 +610,14 @@ gh_status gh_two_view_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const i
 #define GH_KF_SCALE 64 /* UPDATE_KF_SCALE: only the pose-graph solver and gh_align_sim3 have a scale to update */
 #define GH_KF_SIM3 127
 
+/* Values the solvers take as they are given:
+ *   cam_pose   the quaternion is used AS IT STANDS, not normalised on the way in: X_c = M(q)^T (X - t) with
+ *              M(q) = I + 2 qw [v]x + 2 [v]x^2, which is the rotation only for a unit q (q and -q are the same pose).  The first
+ *              accepted step renormalises the quaternion of every camera that is not fixed; a fixed camera keeps its bits.
+ *   obs_info   must be symmetric positive semi-definite.  Rank-deficient and all-zero matrices are allowed (a zero matrix
+ *              removes the observation from the cost); an indefinite matrix is unspecified.
+ *   cam_dof    only the bits GH_KF_X .. GH_KF_RZ count; GH_KF_SCALE and higher bits are ignored.
+ * An observation whose camera-frame depth is not above 1e-9 does not exist for that evaluation (a NaN depth included). */
 typedef struct gh_ba_problem {
   int32_t n_cams, n_points, n_obs;
   /* T_wc (camera -> world) per keyframe: 7 doubles [qx,qy,qz,qw,tx,ty,tz]  (in/out) */
