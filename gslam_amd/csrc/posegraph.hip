@@ -748,23 +748,30 @@ __device__ inline bool graph_obs(int kind, const double* Sj, int dof_j, const do
 // reproducible summation), and h / l are added -- with the same atomics -- into two ZEROED accumulators shaped like the target;
 // a fold kernel adds hi + lo to the target afterwards.  With |v| <= B and at most 2^K contributions per word,
 // E1 = log2 B + K + 1 keeps 51 - K bits of the largest contributions in h, and l (quantum 2^(E1 - 104 + K)) the next 51 - K:
-// what is dropped is below 2^(2K - 103) B -- beyond double precision for the K <= 20 of any real graph.  B comes from
-// gr_obs_lin_kernel (an atomicMax of a per-observation bound: order-independent by itself): every later contribution is an
-// entry of J^T L J, J^T L r or of a Schur product W V^-1 W^T <= the same landmark's J^T L J (the per-landmark Hessian is
-// positive semi-definite), with 2^8 of head room.  Twice the atomics of the plain mode, bit-identical results run to run.
+// what is dropped is below 2^(2K - 103) B -- beyond double precision of a word of size B for the K <= 20 of any real graph.
+// B is a bound PER BLOCK of the reduced system, not one for the whole of it: a word far below the bound keeps only
+// 103 - 2K - log2(B / |word|) bits, and one observation with large Jacobians (a keyframe of scale 1e3, a point 2e-9 in front
+// of a camera) must not set the quantum of blocks it does not add to.  gr_obs_lin_kernel takes, per keyframe f (and for
+// the intrinsics), B_f = the maximum over the observations with a slot in f of 16 |L| |J_f|^2 (an atomicMax: order-
+// independent by itself); a word of block (f, g) uses max(B_f, B_g).  Every contribution to that block is an entry of
+// J_f^T L J_g, or of a Schur product W_f V^-1 W_g^T, which the positive semi-definite per-landmark Hessian bounds by the
+// geometric mean of the landmark's J_f^T L J_f and J_g^T L J_g -- the landmark's own Jacobian J_p does not enter (it cancels
+// in W V^-1 W^T), so it is not part of the bound.  The right-hand sides (J_f^T L r, U g_p) couple a keyframe to the
+// residuals of every observation of its landmarks: their words use one bound for all, the maximum of 16 |L| max(|J_f|, |r|)^2.
+// 2^8 of head room.  Twice the atomics of the plain mode, bit-identical results run to run.
 struct DetAcc {
   double* hi;   // matrix-shaped accumulators (null: plain atomics straight into the target)
   double* lo;
   double* vhi;  // vector-shaped ones (right-hand side)
   double* vlo;
-  const unsigned long long* bound_bits;  // bits of B (a non-negative double)
+  const unsigned long long* bound_bits;  // bits of the bounds (non-negative doubles): [f] keyframe f, [n_frames] intrinsics, [n_frames + 1] vectors
   int K;
+  int n_frames;
 };
 struct DetConst { double M1, M2; };
-__device__ inline DetConst det_consts(const DetAcc& A) {
+__device__ inline DetConst det_consts_of(const DetAcc& A, double B) {
   DetConst c{0.0, 0.0};
   if (A.hi == nullptr) return c;
-  const double B = __longlong_as_double((long long)*A.bound_bits);
   int e = B > 0.0 ? ilogb(B) + 1 : -900;   // |v| <= B < 2^e
   e += 8;                                  // head room
   if (e < -900) e = -900;
@@ -773,6 +780,24 @@ __device__ inline DetConst det_consts(const DetAcc& A) {
   c.M1 = ldexp(1.5, E1);
   c.M2 = ldexp(1.5, E2);
   return c;
+}
+// the constants of the right-hand-side words ...
+__device__ inline DetConst det_consts_vec(const DetAcc& A) {
+  if (A.hi == nullptr) return DetConst{0.0, 0.0};
+  return det_consts_of(A, __longlong_as_double((long long)A.bound_bits[A.n_frames + 1]));
+}
+// ... and of the words of block (fa, fb); the intrinsics are block index n_frames
+__device__ inline DetConst det_consts_block(const DetAcc& A, int fa, int fb) {
+  if (A.hi == nullptr) return DetConst{0.0, 0.0};
+  return det_consts_of(A, fmax(__longlong_as_double((long long)A.bound_bits[fa]), __longlong_as_double((long long)A.bound_bits[fb])));
+}
+// *word = max(*word, bits of B) for a bound B (non-negative doubles order like their bit patterns).  Most observations do not
+// raise the maximum: the word is read first (any stale value is a smaller one, and then the atomic decides), so that the
+// observations of a keyframe do not queue on one address.
+__device__ __forceinline__ void bound_max(unsigned long long* word, double B) {
+  if (!(B > 0.0 && B < 1e300)) return;
+  const unsigned long long b = (unsigned long long)__double_as_longlong(B);
+  if (b > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, b);
 }
 // target[off] += v: plain atomic, or the two pre-rounded parts into the accumulators
 __device__ __forceinline__ void acc_add(double* target, double* hi, double* lo, size_t off, double v, const DetConst& c) {
@@ -887,17 +912,19 @@ __global__ __launch_bounds__(128) void gr_obs_lin_kernel(GrLandmarks G, const in
       Lr[0] = L[0] * r[0] + L[1] * r[1];
       Lr[1] = L[2] * r[0] + L[3] * r[1];
       if (bound_bits != nullptr) {
-        // reproducible mode: the bound B of every contribution this observation will make (see DetAcc), and the landmark sums
-        // are left to gr_lm_sum_kernel (one thread per landmark, its observations in list order)
-        double jm = 0.0, lm = 0.0;
-        for (int e = 0; e < 14; ++e) jm = fmax(jm, fmax(fabs(Jj[e]), fabs(Jh[e])));
-        for (int e = 0; e < 6; ++e) jm = fmax(jm, fabs(Jp[e]));
+        // reproducible mode: the bounds of the contributions this observation will make, per block it has a slot in and for
+        // the right-hand sides (see DetAcc), and the landmark sums are left to gr_lm_sum_kernel (one thread per landmark, its
+        // observations in list order)
+        double jj = 0.0, jh = 0.0, jc = 0.0, lm = 0.0;
+        for (int e = 0; e < 14; ++e) { jj = fmax(jj, fabs(Jj[e])); jh = fmax(jh, fabs(Jh[e])); }
         if (G.with_cam)
-          for (int e = 0; e < 18; ++e) jm = fmax(jm, fabs(Jc[e]));
+          for (int e = 0; e < 18; ++e) jc = fmax(jc, fabs(Jc[e]));
         for (int e = 0; e < 4; ++e) lm = fmax(lm, fabs(L[e]));
-        const double mx = fmax(jm, fmax(fabs(r[0]), fabs(r[1])));
-        const double B = 16.0 * lm * mx * mx;
-        if (B > 0.0 && B < 1e300) atomicMax(bound_bits, (unsigned long long)__double_as_longlong(B));
+        bound_max(bound_bits + o.fj, 16.0 * lm * jj * jj);
+        if (o.fh >= 0) bound_max(bound_bits + o.fh, 16.0 * lm * jh * jh);
+        if (G.with_cam) bound_max(bound_bits + G.n_frames, 16.0 * lm * jc * jc);
+        const double mx = fmax(fmax(jj, fmax(jh, jc)), fmax(fabs(r[0]), fabs(r[1])));
+        bound_max(bound_bits + G.n_frames + 1, 16.0 * lm * mx * mx);
       }
       // (the keyframe rows of g and H are summed from the records by gr_frame_rows_kernel, seven consecutive words at a time)
       for (int a = 0; bound_bits == nullptr && a < o.dp; ++a) {
@@ -995,7 +1022,6 @@ __global__ __launch_bounds__(256) void gr_frame_rows_kernel(GrLandmarks G, const
   const int sa = t >> 3, r = t & 7;
   const int k = sa >> 1, x = sa & 1;
   if (k >= G.n_obs || !valid[k]) return;
-  const DetConst dc = det_consts(DA);
   const ObsRef o = obs_ref(G, k);
   const int fx = x == 0 ? o.fj : o.fh;
   if (fx < 0) return;
@@ -1005,10 +1031,11 @@ __global__ __launch_bounds__(256) void gr_frame_rows_kernel(GrLandmarks G, const
   if (r < 7) {
     const double j0 = Jx[r], j1 = Jx[7 + r];
     const double gv = j0 * (L0 * R[0] + L1 * R[1]) + j1 * (L2 * R[0] + L3 * R[1]);
-    if (gv != 0.0) acc_add(g, DA.vhi, DA.vlo, (size_t)(7 * fx + r), gv, dc);
+    if (gv != 0.0) acc_add(g, DA.vhi, DA.vlo, (size_t)(7 * fx + r), gv, det_consts_vec(DA));
     for (int y = 0; y < 2; ++y) {
       const int fy = y == 0 ? o.fj : o.fh;
       if (fy < 0 || fy > fx) continue;
+      const DetConst dc = det_consts_block(DA, fx, fy);
       const double* Jy = R + (y == 0 ? 6 : 20);
       const size_t col = (size_t)(7 * fy) * lda + 7 * fx + r;
 #pragma unroll
@@ -1023,6 +1050,7 @@ __global__ __launch_bounds__(256) void gr_frame_rows_kernel(GrLandmarks G, const
     const double* Jc = R + 40;
     const double c0 = Jc[r], c1 = Jc[9 + r];
     const size_t col = (size_t)(7 * fx) * lda + 7 * G.n_frames;
+    const DetConst dc = det_consts_block(DA, G.n_frames, fx);
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
       const double LJ0 = L0 * Jx[q] + L1 * Jx[7 + q], LJ1 = L2 * Jx[q] + L3 * Jx[7 + q];
@@ -1147,7 +1175,6 @@ __global__ __launch_bounds__(256) void gr_schur_kernel(GrLandmarks G, const uint
   const int sa = t >> 3, r = t & 7;
   const int ka = sa >> 1, x = sa & 1;
   if (r == 7 || ka >= G.n_obs || !valid[ka]) return;
-  const DetConst dc = det_consts(DA);
   const ObsRef oa = obs_ref(G, ka);
   const int fa = x == 0 ? oa.fj : oa.fh;
   if (fa < 0) return;
@@ -1167,7 +1194,7 @@ __global__ __launch_bounds__(256) void gr_schur_kernel(GrLandmarks G, const uint
   for (int b = 0; b < 3; ++b) ua[b] = wa[0] * Hi[b] + wa[1] * Hi[3 + b] + wa[2] * Hi[6 + b];
   {
     const double v = ua[0] * gp[3 * (size_t)oa.lm] + ua[1] * gp[3 * (size_t)oa.lm + 1] + ua[2] * gp[3 * (size_t)oa.lm + 2];
-    if (v != 0.0) acc_add(d, DA.vhi, DA.vlo, (size_t)(7 * fa + r), v, dc);
+    if (v != 0.0) acc_add(d, DA.vhi, DA.vlo, (size_t)(7 * fa + r), v, det_consts_vec(DA));
   }
   for (int q = G.lstart[oa.lm]; q < G.lstart[oa.lm + 1]; ++q) {
     const int kb = G.llist[q];
@@ -1180,6 +1207,7 @@ __global__ __launch_bounds__(256) void gr_schur_kernel(GrLandmarks G, const uint
       //  lower triangle of the symmetric sum -- the solver reads nothing else)
       const double* Rb = orec + (size_t)G.rec * kb;
       const size_t col = (size_t)(7 * fb) * lda + 7 * fa + r;
+      const DetConst dc = det_consts_block(DA, fa, fb);
 #pragma unroll
       for (int c7 = 0; c7 < 7; ++c7) {
         double wb[3];
@@ -1206,7 +1234,6 @@ __global__ __launch_bounds__(256) void gr_schur_cam_kernel(GrLandmarks G, const 
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int kb = t >> 4, r = t & 15;
   double ua[3];
-  const DetConst dc = det_consts(DA);
   const int cb = 7 * G.n_frames;
   if (kb < G.n_obs && r < 9 && valid[kb]) {
     const ObsRef ob = obs_ref(G, kb);
@@ -1223,6 +1250,7 @@ __global__ __launch_bounds__(256) void gr_schur_cam_kernel(GrLandmarks G, const 
         if (fb < 0 || (y == 1 && kb != rep)) continue;
         const double* Rb = orec + (size_t)G.rec * kb;
         const size_t col = (size_t)(7 * fb) * lda + cb + r;
+        const DetConst dc = det_consts_block(DA, G.n_frames, fb);
 #pragma unroll
         for (int c7 = 0; c7 < 7; ++c7) {
           double wb[3];
@@ -1248,7 +1276,7 @@ __global__ __launch_bounds__(128) void gr_schur_cam_cc_kernel(GrLandmarks G, con
                                                               double* __restrict__ Hd, int lda, double* __restrict__ d, DetAcc DA) {
   const int p = blockIdx.x * 128 + threadIdx.x;
   const int nlm = G.n_xyz + G.n_idp;
-  const DetConst dc = det_consts(DA);
+  const DetConst dc = det_consts_block(DA, G.n_frames, G.n_frames), dv = det_consts_vec(DA);
   double W[27], U[27];
 #pragma unroll
   for (int e = 0; e < 27; ++e) W[e] = U[e] = 0.0;
@@ -1271,7 +1299,7 @@ __global__ __launch_bounds__(128) void gr_schur_cam_cc_kernel(GrLandmarks G, con
   for (int r9 = 0; r9 < 9; ++r9) {
     if (!((G.cam_free >> r9) & 1)) continue;
     const double v = wave_add_f64(U[3 * r9] * g0 + U[3 * r9 + 1] * g1 + U[3 * r9 + 2] * g2);
-    if (lead && v != 0.0) acc_add(d, DA.vhi, DA.vlo, (size_t)(cb + r9), v, dc);
+    if (lead && v != 0.0) acc_add(d, DA.vhi, DA.vlo, (size_t)(cb + r9), v, dv);
 #pragma unroll
     for (int c9 = 0; c9 <= r9; ++c9) {
       if (!((G.cam_free >> c9) & 1)) continue;
@@ -1538,7 +1566,7 @@ struct GraphDev {
            (!Z.with_cam || (A.alloc(&cam_new, 9) && A.alloc(&Wc, nlm1 * 27) && A.alloc(&cam_part, (size_t)kCamPart * 2 * Z.ob()))) &&
            (Z.sparse || (A.alloc(&H, nn) && A.alloc(&Hd, nn))) &&
            // DetAcc
-           (!Z.det || (A.alloc(&acc_hi, nn) && A.alloc(&acc_lo, nn) && A.alloc(&vacc, 2 * n) && A.alloc(&bound, 1)));
+           (!Z.det || (A.alloc(&acc_hi, nn) && A.alloc(&acc_lo, nn) && A.alloc(&vacc, 2 * n) && A.alloc(&bound, nf + 2)));
   }
 };
 
@@ -1550,7 +1578,7 @@ struct GraphRun {
   PgGraph G;
   PgLists Ls;
   GrLandmarks LM;
-  DetAcc DA{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  DetAcc DA{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
   GraphReadback* rb = nullptr;
   explicit GraphRun(const gh_graph_problem* gpr) : Z(gpr) {}
 };
@@ -1705,7 +1733,7 @@ gh_status graph_enqueue_linearise(gh_ctx* ctx, GraphRun& R, GraphLoop& L) {
     GH_HIP(ctx, hipMemsetAsync(D.acc_hi, 0, (size_t)n * lda * sizeof(double), ctx->stream));
     GH_HIP(ctx, hipMemsetAsync(D.acc_lo, 0, (size_t)n * lda * sizeof(double), ctx->stream));
     GH_HIP(ctx, hipMemsetAsync(D.vacc, 0, (size_t)2 * n * sizeof(double), ctx->stream));
-    GH_HIP(ctx, hipMemsetAsync(D.bound, 0, 8, ctx->stream));
+    GH_HIP(ctx, hipMemsetAsync(D.bound, 0, (size_t)(nf + 2) * 8, ctx->stream));
   }
   if (Z.ne > 0) GH_LAUNCH(ctx, "pg_edge", pg_edge_kernel, dim3(Z.eb4()), dim3(64), 0, R.G, (const double*)D.S, D.rec, D.cost_e);
   // stores the pose-edge sums into every diagonal block, every edge pair block and g (zeros where there is no edge)
@@ -1886,7 +1914,7 @@ extern "C" gh_status gh_graph_solve(gh_ctx* ctx, gh_graph_problem* gpr, const gh
   }
   if (Z.sparse) R.BS.h_flag = &R.rb->bs_flag;
   const int cam_free = Z.with_cam ? gpr->intrinsics_free : 0;
-  if (Z.det) R.DA = DetAcc{D.acc_hi, D.acc_lo, D.vacc, D.vacc + Z.n, D.bound, graph_det_budget(gpr, Z)};
+  if (Z.det) R.DA = DetAcc{D.acc_hi, D.acc_lo, D.vacc, D.vacc + Z.n, D.bound, graph_det_budget(gpr, Z), Z.nf};
   R.G = PgGraph{Z.nf, Z.ne, D.dof, D.etype, D.ei, D.ej, D.meas, D.info};
   R.Ls = PgLists{D.vstart, D.vlist, D.pstart, D.plist, D.prow, D.pcol, Z.n_pairs};
   R.LM = GrLandmarks{Z.nx, Z.ni, Z.no, D.xfree, D.host, D.anchor, D.ifree, D.okind, D.opoint, D.oframe, D.oxy, D.oinfo, D.lstart, D.llist,
