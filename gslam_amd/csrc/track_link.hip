@@ -40,12 +40,14 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "dense_solve.h"
+#include "track_uf.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxUnionBlocks = 1 << 16;  // grid-stride beyond this many workgroups
+// the union-find, its labels and the run bounds (link_init / link_union / link_label / link_runs): track_uf.h, shared with
+// track_extend.hip
+using namespace gh_uf;
+
 constexpr int kMaxFlagBlocks = 1024;
 
 struct LinkArgs {
@@ -67,93 +69,6 @@ struct LinkArgs {
   int32_t* point_len;
   int32_t* totals;
 };
-
-__device__ __forceinline__ int link_count(const int32_t* __restrict__ counts, int f, int cap) {
-  const int c = counts[f];
-  return c < 0 ? 0 : (c > cap ? cap : c);
-}
-
-__device__ __forceinline__ int link_load(const int32_t* parent, int x) {
-  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x as far as this lane can see it, p = parent[x] as just read; every step taken also lowers parent[x] to its
-// grandparent (path halving)
-__device__ __forceinline__ int link_find_halve(int32_t* parent, int x, int p) {
-  while (p != x) {  // p < x
-    const int g = link_load(parent, p);
-    if (g != p) (void)__hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-    p = g;
-  }
-  return x;
-}
-
-__device__ __forceinline__ int link_find(const int32_t* parent, int x) {
-  int p = link_load(parent, x);
-  while (p != x) {
-    x = p;
-    p = link_load(parent, x);
-  }
-  return x;
-}
-
-__global__ __launch_bounds__(kBlock) void link_init_kernel(int32_t* __restrict__ parent, int N) {
-  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (g < N) parent[g] = (int32_t)g;
-}
-
-__global__ __launch_bounds__(kBlock) void link_union_kernel(const int32_t* __restrict__ counts, int n_frames, int cap,
-                                                            const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_t,
-                                                            long long rows, const int32_t* __restrict__ idx1,
-                                                            const uint8_t* __restrict__ inlier, int32_t* parent) {
-  const long long step = (long long)gridDim.x * kBlock;
-  for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += step) {
-    const int p = (int)(r / cap), i = (int)(r - (long long)p * cap);
-    const int fq = pair_q[p], ft = pair_t[p];
-    if (fq < 0 || fq >= n_frames || ft < 0 || ft >= n_frames || fq == ft) continue;
-    if (i >= link_count(counts, fq, cap)) continue;
-    if (inlier && inlier[r] == 0) continue;
-    const int j = idx1[r];
-    if (j < 0 || j >= link_count(counts, ft, cap)) continue;
-    const int u = fq * cap + i, v = ft * cap + j;
-    const int pu = link_load(parent, u), pv = link_load(parent, v);
-    if (pu == pv) continue;  // one tree already: in a flat component this spares the root's hot word two reads per edge
-    int a = link_find_halve(parent, u, pu), b = link_find_halve(parent, v, pv);
-    while (a != b) {
-      const int hi = a > b ? a : b, lo = a > b ? b : a;
-      const int old = atomicCAS(parent + hi, hi, lo);
-      if (old == hi) break;
-      a = link_find_halve(parent, old, link_load(parent, old));  // < hi
-      b = link_find_halve(parent, lo, link_load(parent, lo));
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void link_label_kernel(const int32_t* __restrict__ counts, int cap, int N,
-                                                            const int32_t* parent, int32_t* __restrict__ key,
-                                                            int32_t* __restrict__ item) {
-  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (g >= N) return;
-  const int n = (int)g;
-  const int f = n / cap, i = n - f * cap;
-  key[n] = i < link_count(counts, f, cap) ? link_find(parent, n) : N;
-  item[n] = n;
-}
-
-__global__ __launch_bounds__(kBlock) void link_runs_kernel(const int32_t* __restrict__ skey, const int32_t* __restrict__ list, int cap,
-                                                           int N, int32_t* __restrict__ begin, int32_t* __restrict__ end,
-                                                           uint8_t* __restrict__ conflict) {
-  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (g >= N) return;
-  const int s = (int)g;
-  const int l = skey[s];
-  if (l == N) return;  // (the nodes that do not exist come last)
-  const int prev = s > 0 ? skey[s - 1] : -1, next = s + 1 < N ? skey[s + 1] : N;
-  if (prev != l) begin[l] = s;
-  if (next != l) end[l] = s + 1;
-  else if (list[s] / cap == list[s + 1] / cap) conflict[l] = 1;
-}
 
 __global__ __launch_bounds__(kBlock) void link_flags_kernel(const int32_t* __restrict__ key, const int32_t* __restrict__ begin,
                                                             const int32_t* __restrict__ end, const uint8_t* __restrict__ conflict, int N,
@@ -238,19 +153,13 @@ __global__ __launch_bounds__(kBlock) void link_emit_kernel(LinkArgs a) {
   a.node_point[n] = code;
 }
 
-int link_key_bits(int N) {  // the keys are 0 .. N
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) <= N) ++bits;
-  return bits;
-}
-
 // temporary storage that serves both the sort of N pairs and the scan of N + 1 flags
 bool link_rocprim_bytes(hipStream_t stream, int N, size_t* bytes) {
   uint64_t* null_u = nullptr;
   int32_t* null_i = nullptr;
   size_t scan = 0, sort = 0;
   if (rocprim::exclusive_scan(nullptr, scan, null_u, null_u, (uint64_t)0, (size_t)N + 1, rocprim::plus<uint64_t>(), stream) != hipSuccess ||
-      rocprim::radix_sort_pairs(nullptr, sort, null_i, null_i, null_i, null_i, (size_t)N, 0, link_key_bits(N), stream) != hipSuccess)
+      rocprim::radix_sort_pairs(nullptr, sort, null_i, null_i, null_i, null_i, (size_t)N, 0, key_bits(N), stream) != hipSuccess)
     return false;
   *bytes = gh_round256(std::max(std::max(scan, sort), (size_t)1));
   return true;
@@ -309,13 +218,13 @@ extern "C" gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev,
   if (rows > 0) {
     const long long want = (rows + kBlock - 1) / kBlock;
     GH_LAUNCH(ctx, "link_union", link_union_kernel, dim3((unsigned)(want < kMaxUnionBlocks ? want : kMaxUnionBlocks)), block, 0,
-              counts_dev, n_frames, cap, pair_q_dev, pair_t_dev, rows, idx1_dev, inlier_dev, parent);
+              counts_dev, n_frames, cap, pair_q_dev, pair_t_dev, rows, idx1_dev, inlier_dev, (const uint8_t*)nullptr, parent);
   }
-  GH_LAUNCH(ctx, "link_label", link_label_kernel, grid, block, 0, counts_dev, cap, N, parent, key, item);
+  GH_LAUNCH(ctx, "link_label", link_label_kernel, grid, block, 0, counts_dev, cap, N, (const uint8_t*)nullptr, parent, key, item);
   {
     const int prof = gh_prof_begin(ctx, "link_sort");
     size_t tb = tmp_bytes;
-    const hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tb, key, skey, item, list, n, 0, link_key_bits(N), ctx->stream);
+    const hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tb, key, skey, item, list, n, 0, key_bits(N), ctx->stream);
     gh_prof_end(ctx, prof);
     if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: sort");
   }

@@ -8,7 +8,9 @@ gh_pnp_batch_dev) refine the poses of many PnP fits in one launch, each as gh_ba
 triangulate_tracks (gh_triangulate_tracks_dev) gives every map point of a gh_ba_problem its start from all of its observations;
 link_tracks (gh_link_tracks_dev) builds those per-point arrays from the inlier rows of the pair entries.
 gather_map_matches (gh_pnp_gather_pairs_dev) reads the pair matches of new frames through that map into the arrays pnp_batch
-takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call and says which keypoint rows were inliers."""
+takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call and says which keypoint rows were inliers;
+extend_tracks (gh_extend_tracks_dev) adds those rows to the tracks of the map and links the other rows of the new frames into
+new tracks numbered after the map's, so that the map grows batch after batch without a read-back."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +23,7 @@ PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinemen
 # GH_TRACK_*: status per point of triangulate_tracks
 TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_INCONSISTENT, TRACK_LOW_PARALLAX, TRACK_SKIPPED = 0, 1, 2, 3, 4, 5
 LINK_SHORT, LINK_CONFLICT, LINK_NO_ROW = -1, -2, -3  # GH_LINK_*: what node_point of link_tracks holds where there is no point id
+EXT_REJECTED = -4  # GH_EXT_REJECTED: beside LINK_*, what node_point of extend_tracks holds at a claimant that was turned down
 # GH_LOC_*: what row_point of gather_map_matches / localize_pairs holds where there is no point id
 LOC_NO_POINT, LOC_AMBIGUOUS, LOC_NO_ROW, LOC_SHARED = -1, -2, -3, -4
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
@@ -415,6 +418,51 @@ def localize_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, no
                                             p(node_point), n_points, p(point_xyz), _p(point_status), C.c_double(fx), C.c_double(fy),
                                             C.c_double(cx), C.c_double(cy), C.c_double(ransac_threshold), C.c_uint64(seed), int(dof),
                                             C.byref(opt), int(min_rows), C.c_double(inlier_threshold), *(p(out[k]) for k in out)))
+    return out
+
+
+def extend_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, node_point, n_points, row_point, row_inlier, intrinsics,
+                  min_views=2):
+    """gh_extend_tracks_dev, the call after localize_pairs: the map grows by the new frames.  kps, counts, pair_q, pair_t, idx1,
+    inlier, intrinsics, min_views as link_tracks takes them; node_point: F * cap int32 as link_tracks or an earlier extend_tracks
+    returned it, or None (no map); n_points: the number of map points; row_point F * cap int32 and row_inlier F * cap uint8 as
+    localize_pairs returns them, or both None (no claims) -- all cuda.  With N = F * cap and PC = n_points + N // 2 -> dict of
+    device tensors: node_point N int32 (a point id, LINK_SHORT, LINK_CONFLICT, EXT_REJECTED or LINK_NO_ROW), obs_cam / obs_point /
+    obs_node N int32 and obs_xy N x 2 float64 (padded past n_obs with -1 and zeros), point_len PC int32, point_new PC uint8 (1 at
+    the points this call created), point_grew PC uint8 (1 at the old points that got an observation), totals 6 int32 (n_obs,
+    n_points_total, ADOPTED nodes, REJECTED nodes, CONFLICT components, SHORT components of two nodes or more); nothing is
+    synchronised and nothing is read back: obs_cam, obs_point, obs_xy go to triangulate_tracks as they are, with n_points = PC
+    and point_select = point_new (keep the map's status array apart: that call marks every old point TRACK_SKIPPED)."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
+    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
+    N, dev, n_points = F * cap, kps.device, int(n_points)
+    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap and n_points >= 0
+    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
+    assert node_point is None or (node_point.is_cuda and node_point.dtype == torch.int32 and node_point.is_contiguous() and
+                                  node_point.numel() == N)
+    assert (row_point is None) == (row_inlier is None)
+    assert row_point is None or (row_point.is_cuda and row_point.dtype == torch.int32 and row_point.is_contiguous() and
+                                 row_point.numel() == N and row_inlier.is_cuda and row_inlier.dtype == torch.uint8 and
+                                 row_inlier.is_contiguous() and row_inlier.numel() == N)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    PC = n_points + N // 2
+    out = {"node_point": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_cam": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_point": torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
+           "obs_node": torch.empty(N, dtype=torch.int32, device=dev),
+           "point_len": torch.empty(PC, dtype=torch.int32, device=dev),
+           "point_new": torch.empty(PC, dtype=torch.uint8, device=dev),
+           "point_grew": torch.empty(PC, dtype=torch.uint8, device=dev),
+           "totals": torch.empty(6, dtype=torch.int32, device=dev)}
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    q = lambda t: None if t is None else p(t)  # (NULL means "not given" for these three, also when N == 0)
+    ctx.check(hip.lib.gh_extend_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
+                                           q(node_point), n_points, q(row_point), q(row_inlier), C.c_double(fx), C.c_double(fy),
+                                           C.c_double(cx), C.c_double(cy), int(min_views), *(p(out[k]) for k in out)))
     return out
 
 

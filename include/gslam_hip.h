@@ -911,7 +911,7 @@ gh_status gh_pnp_gather_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const
  *      n_frames x 36 or NULL, summaries_dev n_frames x 2; its inlier bytes per correspondence and n_inliers stay in scratch;
  *   3. a scatter -> row_inlier_dev N bytes: 1 exactly at the nodes whose correspondence is an inlier of the last round, 0
  *      everywhere else.
- * row_point_dev and row_inlier_dev together are what a later stage needs to add the new observations to the tracks.  A frame
+ * row_point_dev and row_inlier_dev together are what gh_extend_tracks_dev needs to add the new observations to the tracks.  A frame
  * without correspondences is an empty range of gh_pnp_batch_dev and comes out as that contract says.  GH_ERR_ARG: whatever
  * either stage rejects, and row_inlier_dev NULL -- checked before anything is launched, and then nothing is written.
  * N == 0: GH_OK, only offsets_dev and totals_dev are written, and with n_frames > 0 what gh_pnp_batch_dev writes for empty
@@ -925,6 +925,62 @@ gh_status gh_localize_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const i
                                 double* xy_dev, int32_t* corr_node_dev, int32_t* totals_dev, double* models_dev,
                                 int32_t* ransac_inliers_dev, double* poses_dev, double* info_dev,
                                 gh_pnp_batch_summary* summaries_dev, uint8_t* row_inlier_dev);
+/* Extending the map: the rows of new frames that gh_localize_pairs_dev registered are added to the tracks of the points they
+ * saw, and the remaining rows are linked into NEW tracks whose ids go on where the map's end -- gh_link_tracks_dev cannot do
+ * this, it numbers every track from scratch.  Every pointer is a DEVICE pointer, nothing is copied to the host, the call is
+ * asynchronous on the context's stream, scratch comes from the context.  kps_dev, counts_dev, n_frames, cap, pair_q_dev,
+ * pair_t_dev, npairs, idx1_dev, inlier_dev, the intrinsics and min_views as gh_link_tracks_dev takes them.  The map:
+ * node_point_in_dev N entries or NULL (no map), n_points.  The claims: row_point_dev N and row_inlier_dev N bytes as
+ * gh_localize_pairs_dev writes them, or both NULL (no claims).
+ *   sizes      N = n_frames * cap, PC = n_points + N / 2: a new track uses up at least two nodes that had no point, so PC point
+ *              entries are always enough and no count is read back.
+ *   nodes, pairs, edges  exactly the rules of gh_link_tracks_dev: node (f, i) EXISTS when 0 <= i < clamp(counts[f], 0, cap); a pair
+ *              is read only when both frame indices are in range and different; query row i of a pair is an edge under the
+ *              gather rule of gh_ransac_pairs_dev; an index outside its range drops the row, it is never dereferenced.
+ *   state      of an existing node n, checked in this order.  MAPPED: node_point_in_dev != NULL and 0 <= node_point_in[n] <
+ *              n_points -- the node keeps that point; any other value (negative, >= n_points) means "no point" and is never
+ *              used as an index; two MAPPED nodes of one frame that hold one point are the caller's map and are emitted as they
+ *              stand.  CLAIMANT: not MAPPED, the claim arrays given, row_inlier[n] != 0 and 0 <= c = row_point[n] < n_points.  A
+ *              claimant is REJECTED (GH_EXT_REJECTED) when its frame holds a MAPPED node of point c or another CLAIMANT of point
+ *              c -- every such claimant of that (frame, point) is, and a rejected node takes no further part in anything; in
+ *              every other case it is ADOPTED: node_point[n] = c.  Nodes of different frames may adopt one point: that is what
+ *              a track is.  FREE: every other existing node.
+ *   new tracks an edge counts only when BOTH of its ends are FREE (an edge between a FREE node and a node with a point would
+ *              merge or re-assign map points: it is ignored).  Components, the label (the smallest node id), the classes
+ *              CONFLICT / SHORT / TRACK and their order of checking are those of gh_link_tracks_dev on the graph of the FREE
+ *              nodes; tracks get the ids n_points, n_points + 1, ... in ascending label.
+ *   observations  the nodes whose final node_point is >= 0 (MAPPED, ADOPTED, nodes of new tracks) in ascending node id; the
+ *              observation index is the rank in that list.
+ * Outputs, ALL written for their full capacity on every call (dirty buffers never show): node_point_dev N: the point id,
+ * GH_LINK_SHORT, GH_LINK_CONFLICT, GH_EXT_REJECTED or GH_LINK_NO_ROW; obs_cam_dev, obs_point_dev, obs_node_dev N each and
+ * obs_xy_dev N x 2 as gh_link_tracks_dev writes them (-1 and (0, 0) past n_obs, ((double)x - cx) / fx: two IEEE operations each);
+ * point_len_dev PC: the number of observations of point p, 0 for p >= n_points_total; point_new_dev PC bytes: 1 exactly for
+ * n_points <= p < n_points_total; point_grew_dev PC bytes: 1 exactly for the old points with at least one ADOPTED node;
+ * totals_dev 6: n_obs, n_points_total, the ADOPTED nodes, the REJECTED nodes, the CONFLICT components, the SHORT components
+ * with at least two nodes.  node_point_dev must not overlap node_point_in_dev.
+ * The arrays go to gh_triangulate_tracks_dev as they are, with n_cams = n_frames, n_obs = N, n_points = PC and
+ * point_select_dev = point_new_dev: only the new points are triangulated, the old points are GH_TRACK_SKIPPED and keep their
+ * coordinates, the padding is SKIPPED too.  That call OVERWRITES the status of the skipped points with GH_TRACK_SKIPPED, so a
+ * caller keeps the map's status array apart from the one it passes there.
+ * Everything is integer work except the two divisions: the same bits on every run.  tests/track_extend_restate.py restates all
+ * of it.  With node_point_in_dev NULL (or n_points == 0) and no claim arrays, node_point, the four observation arrays and the
+ * first N / 2 entries of point_len equal those of gh_link_tracks_dev on the same inputs byte for byte, and totals [0], [1],
+ * [4], [5] equal its totals [0], [1], [2], [3].
+ * GH_ERR_ARG, and then nothing is written: ctx NULL; n_frames, cap, npairs or n_points negative; cap > 65535; n_points +
+ * n_frames * cap > INT32_MAX - 1; min_views < 2; fx or fy not > 0 (a NaN included); a NULL among kps, counts or the nine
+ * outputs; with npairs > 0 a NULL among pair_q, pair_t, idx1; exactly one of row_point_dev / row_inlier_dev NULL.  N == 0:
+ * GH_OK, totals_dev is zeros except [1] = n_points and the PC = n_points entries of the three point arrays are zeros.
+ * npairs == 0: no new tracks.  Both claim arrays NULL: no adoptions. */
+#define GH_EXT_REJECTED (-4)   /* beside GH_LINK_SHORT -1, GH_LINK_CONFLICT -2, GH_LINK_NO_ROW -3 */
+gh_status gh_extend_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const int32_t* counts_dev, int n_frames, int cap,
+                               const int32_t* pair_q_dev, const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev,
+                               const uint8_t* inlier_dev,
+                               const int32_t* node_point_in_dev, int n_points,
+                               const int32_t* row_point_dev, const uint8_t* row_inlier_dev,
+                               double fx, double fy, double cx, double cy, int min_views,
+                               int32_t* node_point_dev, int32_t* obs_cam_dev, int32_t* obs_point_dev, double* obs_xy_dev,
+                               int32_t* obs_node_dev, int32_t* point_len_dev, uint8_t* point_new_dev, uint8_t* point_grew_dev,
+                               int32_t* totals_dev);
 
 /* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
