@@ -254,3 +254,74 @@ def marginalize(ctx: hip.Context, graph: dict, huber=0.01, min_shared=1):
         ctx.check(hip.lib.gh_ba_marginalize(ctx.h, C.byref(pr), float(huber), int(min_shared), ne, _ptr(first), _ptr(second),
                                             _ptr(shared), _ptr(lam), C.byref(n)))
     return first, second, shared, lam
+
+
+WIN_NONE, WIN_LOCAL, WIN_FIXED = 0, 1, 2   # gh_ba_window_dev: cam_class
+WINDOW_OUTPUTS = ("cam_class", "cam_shared", "cam_slot", "point_slot", "win_cam", "win_cam_dof", "win_cam_pose", "win_point",
+                  "win_point_xyz", "win_obs_cam", "win_obs_point", "win_obs_src", "win_obs_xy", "totals")
+
+
+def window(ctx: hip.Context, cam_pose, point_xyz, obs_cam, obs_point, obs_xy, cam_seed, obs_use=None, point_use=None, cam_hold=None,
+           min_shared=15, min_point_obs=2):
+    """gh_ba_window_dev, the call after extend_tracks and triangulate_tracks: the local window of the new frames, selected by
+    co-visibility, culled and compacted on the device.  All tensors cuda and contiguous, at the capacities of the map: cam_pose
+    n_cams x 7 float64, point_xyz n_points x 3 float64, obs_cam / obs_point n_obs int32 and obs_xy n_obs x 2 float64 as
+    triangulate_tracks takes them (padding included), cam_seed n_cams uint8 (non-zero = a new frame); obs_use n_obs uint8 or None
+    (where obs_good goes), point_use n_points uint8 or None (status == TRACK_OK, merged over the calls), cam_hold n_cams uint8 or
+    None (non-zero = dof 0 even if LOCAL).  -> dict of device tensors (the rules and the layout: include/gslam_hip.h): cam_class
+    n_cams uint8 (WIN_NONE / WIN_LOCAL / WIN_FIXED), cam_shared, cam_slot n_cams int32, point_slot n_points int32, win_cam,
+    win_cam_dof n_cams int32, win_cam_pose n_cams x 7, win_point n_points int32, win_point_xyz n_points x 3, win_obs_cam,
+    win_obs_point, win_obs_src n_obs int32, win_obs_xy n_obs x 2, totals 8 int32 (window cameras, LOCAL, FIXED, held LOCAL, window
+    points, window observations, seeds in the window, usable observations).  Nothing is synchronised and nothing is read back:
+    window_problem does that."""
+    import torch
+    f64 = lambda t, w: t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() % w == 0
+    assert f64(cam_pose, 7) and f64(point_xyz, 3) and f64(obs_xy, 2)
+    nc, npts, no, dev = cam_pose.numel() // 7, point_xyz.numel() // 3, obs_xy.numel() // 2, cam_pose.device
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == no for t in (obs_cam, obs_point))
+    for t, n in ((cam_seed, nc), (obs_use, no), (point_use, npts), (cam_hold, nc)):
+        assert t is None or (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n)
+    assert cam_seed is not None
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    d64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    out = {"cam_class": torch.empty(nc, dtype=torch.uint8, device=dev), "cam_shared": i32(nc), "cam_slot": i32(nc), "point_slot": i32(npts),
+           "win_cam": i32(nc), "win_cam_dof": i32(nc), "win_cam_pose": d64(nc, 7), "win_point": i32(npts), "win_point_xyz": d64(npts, 3),
+           "win_obs_cam": i32(no), "win_obs_point": i32(no), "win_obs_src": i32(no), "win_obs_xy": d64(no, 2), "totals": i32(8)}
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    q = lambda t: None if t is None else p(t)
+    params = hip.BaWindowParams(int(min_shared), int(min_point_obs))
+    ctx.check(hip.lib.gh_ba_window_dev(ctx.h, nc, npts, no, p(cam_pose), p(point_xyz), p(obs_cam), p(obs_point), p(obs_xy), q(obs_use),
+                                       q(point_use), p(cam_seed), q(cam_hold), C.byref(params), *(p(out[k]) for k in WINDOW_OUTPUTS)))
+    return out
+
+
+def window_problem(win: dict):
+    """The one synchronisation of the window: reads the 32 bytes of totals, downloads the compact prefixes and returns the dict
+    solve() and Graph() take (cam_pose, cam_dof, point_xyz, obs_cam, obs_point, obs_xy), with win_cam and win_point (the ids in
+    the map), win_obs_src and totals (a list of 8) beside them."""
+    totals = win["totals"].cpu().numpy().tolist()
+    n_cams, n_points, n_obs = totals[0], totals[4], totals[5]
+    host = lambda k, n: win[k][:n].cpu().numpy()
+    return {"cam_pose": host("win_cam_pose", n_cams), "cam_dof": host("win_cam_dof", n_cams), "point_xyz": host("win_point_xyz", n_points),
+            "obs_cam": host("win_obs_cam", n_obs), "obs_point": host("win_obs_point", n_obs), "obs_xy": host("win_obs_xy", n_obs),
+            "win_cam": host("win_cam", n_cams), "win_point": host("win_point", n_points), "win_obs_src": host("win_obs_src", n_obs),
+            "totals": totals}
+
+
+def window_scatter(ctx: hip.Context, win: dict, poses, points, cam_pose, point_xyz):
+    """gh_ba_window_scatter_dev: the solved poses (n_win_cams x 7) and points (n_win_points x 3) of a window -- numpy arrays as
+    solve() returns them, or cuda tensors -- into the map's device arrays cam_pose and point_xyz, in place.  Cameras with dof 0
+    (FIXED and held) and everything outside the window keep their bits.  Asynchronous."""
+    import torch
+    dev = cam_pose.device
+    up = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    poses, points = up(poses), up(points)
+    assert all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() for t in (poses, points, cam_pose, point_xyz))
+    assert poses.numel() % 7 == 0 and points.numel() % 3 == 0 and cam_pose.numel() % 7 == 0 and point_xyz.numel() % 3 == 0
+    n_win_cams, n_win_points = poses.numel() // 7, points.numel() // 3
+    assert n_win_cams <= win["win_cam"].numel() and n_win_points <= win["win_point"].numel()
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_ba_window_scatter_dev(ctx.h, p(win["win_cam"]), p(win["win_cam_dof"]), n_win_cams, p(poses), p(win["win_point"]),
+                                               n_win_points, p(points), p(cam_pose), cam_pose.numel() // 7, p(point_xyz), point_xyz.numel() // 3))
+    win["scatter_source"] = (poses, points)  # (the call is asynchronous: what it reads must outlive this function)

@@ -100,6 +100,11 @@ class PnpBatchSummary(C.Structure):
                 ("initial_cost", C.c_double), ("final_cost", C.c_double)]
 
 
+class BaWindowParams(C.Structure):
+    """gh_ba_window_params (8 bytes) of gh_ba_window_dev."""
+    _fields_ = [("min_shared", C.c_int32), ("min_point_obs", C.c_int32)]
+
+
 class TrackParams(C.Structure):
     """gh_track_params (24 bytes) of gh_triangulate_tracks_dev."""
     _fields_ = [("min_parallax_cos", C.c_double), ("max_reproj", C.c_double), ("min_views", C.c_int32),
@@ -234,6 +239,10 @@ SIGNATURES = {
     "gh_extend_tracks_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp,
                                        C.c_double, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp]),
+    "gh_ba_window_default_params": (None, [C.POINTER(BaWindowParams)]),
+    "gh_ba_window_dev": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BaWindowParams),
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_ba_window_scatter_dev": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "gh_pg_solve": (C.c_int, [_vp, C.POINTER(PgProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_graph_solve": (C.c_int, [_vp, C.POINTER(GraphProblem), C.POINTER(BaOptions), C.POINTER(BaSummary)]),
     "gh_align_sim3": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_double), C.POINTER(_i)]),

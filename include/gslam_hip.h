@@ -982,7 +982,81 @@ gh_status gh_extend_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const in
                                int32_t* obs_node_dev, int32_t* point_len_dev, uint8_t* point_new_dev, uint8_t* point_grew_dev,
                                int32_t* totals_dev);
 
-/* Optimizer::magin (GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
+/* The local window of a bundle adjustment, selected and compacted on the device: the last arrow of match -> localize -> extend ->
+ * triangulate the new points -> BA.  The map's arrays go in as gh_extend_tracks_dev and gh_triangulate_tracks_dev leave them,
+ * padding included, with a byte per camera that marks the new frames; out come the compact arrays of a gh_ba_problem (cam_pose,
+ * cam_dof, point_xyz, obs_cam, obs_point, obs_xy), the index maps back to the map and eight totals.  The host reads the 32
+ * bytes of totals and the compact prefixes and calls gh_ba_solve or gh_ba_graph_create unchanged.  Every pointer is a DEVICE
+ * pointer, the call is asynchronous on the context's stream, scratch comes from the context, nothing is synchronised or
+ * allocated per call.
+ * Inputs: n_cams, n_points, n_obs are CAPACITIES (the N and PC of gh_extend_tracks_dev go in as they are); cam_pose_dev
+ * n_cams x 7, point_xyz_dev n_points x 3; obs_cam_dev, obs_point_dev n_obs each and obs_xy_dev n_obs x 2 as
+ * gh_triangulate_tracks_dev takes them; obs_use_dev n_obs bytes or NULL (this is where obs_good goes); point_use_dev n_points
+ * bytes or NULL: non-zero = the point is in the map (status == GH_TRACK_OK, merged over the caller's calls); cam_seed_dev n_cams
+ * bytes: non-zero marks a new frame; cam_hold_dev n_cams bytes or NULL: non-zero = the camera enters the problem with dof 0
+ * even if it is LOCAL (frame 0 as the gauge, for instance); params: gh_ba_window_default_params gives min_shared 15
+ * (ORB-SLAM's co-visibility threshold) and min_point_obs 2 (a point needs two rays).
+ * The rules, each a function of sets and integer counts, never of arrival order:
+ *   USABLE     observation k: obs_use is NULL or non-zero at k, 0 <= obs_cam[k] < n_cams, 0 <= obs_point[k] < n_points, and
+ *              point_use is NULL or non-zero at that point.  An index outside its range drops the observation and is never
+ *              dereferenced.
+ *   n_use[p]   the number of usable observations of p.  The same (camera, point) pair given twice counts twice, here and
+ *              everywhere below.
+ *   LIVE       point p when n_use[p] >= min_point_obs; an observation when it is usable and its point is LIVE.
+ *   SEEN[p]    p is LIVE and a live observation of p lies in a seed camera.
+ *   shared[c]  the number of live observations of camera c whose point is SEEN.
+ *   LOCAL[c]   (cam_seed[c] != 0 and shared[c] >= 1) or shared[c] >= max(min_shared, 1).  A seed camera without a live observation
+ *              is not in the window: a camera without observations is a singular block.
+ *   window point  p is LIVE and a live observation of p lies in a LOCAL camera.  Every usable observation of a window point is a
+ *              WINDOW OBSERVATION.
+ *   FIXED[c]   c is not LOCAL and holds a window observation.  Every other camera is NONE.
+ *   dof        GH_KF_SE3 for a LOCAL camera with cam_hold NULL or zero; 0 for a held LOCAL camera; 0 for a FIXED camera.
+ *   numbering  window cameras (LOCAL and FIXED together) get 0, 1, ... in ascending camera id; window points get 0, 1, ... in
+ *              ascending point id; window observations are emitted in ascending observation index.
+ * Outputs, ALL written for their full capacity on every call (dirty buffers never show): cam_class_dev n_cams bytes: GH_WIN_NONE,
+ * GH_WIN_LOCAL or GH_WIN_FIXED; cam_shared_dev n_cams: shared[c]; cam_slot_dev n_cams and point_slot_dev n_points: the compact id
+ * or -1; win_cam_dev n_cams: the original camera id, pad -1; win_cam_dof_dev n_cams: the dof, pad 0; win_cam_pose_dev n_cams x
+ * 7: the seven doubles copied bit for bit, pad 0.0; win_point_dev n_points: the original point id, pad -1; win_point_xyz_dev
+ * n_points x 3: copied bits, pad 0.0; win_obs_cam_dev, win_obs_point_dev n_obs each: the compact ids, pad -1; win_obs_src_dev
+ * n_obs: the original observation index, pad -1; win_obs_xy_dev n_obs x 2: copied bits, pad (0, 0).  totals_dev 8: window
+ * cameras, LOCAL cameras, FIXED cameras, LOCAL cameras held at dof 0, window points, window observations, seed cameras in the
+ * window, usable observations.
+ * GH_ERR_ARG, and then nothing is written: ctx or params NULL; a negative count; min_shared < 0; min_point_obs < 1; a NULL among
+ * cam_seed or the fourteen outputs; a NULL among cam_pose, point_xyz or the three observation arrays while the count that sizes
+ * it is positive.  n_cams == 0: GH_OK, the totals are zeros and the point and observation outputs are padding.  No seed, or
+ * n_obs == 0: an empty window -- everything is padding or NONE and the totals are zeros except the last.
+ * tests/ba_window_restate.py restates all of it; the device gives the same bytes on every run and in every order of the
+ * observations (the observation outputs up to that order: map them through win_obs_src). */
+#define GH_WIN_NONE 0
+#define GH_WIN_LOCAL 1
+#define GH_WIN_FIXED 2
+typedef struct gh_ba_window_params {
+  int32_t min_shared;    /* 15 */
+  int32_t min_point_obs; /* 2 */
+} gh_ba_window_params;
+void gh_ba_window_default_params(gh_ba_window_params* p);
+gh_status gh_ba_window_dev(gh_ctx* ctx, int n_cams, int n_points, int n_obs, const double* cam_pose_dev,
+                           const double* point_xyz_dev, const int32_t* obs_cam_dev, const int32_t* obs_point_dev,
+                           const double* obs_xy_dev, const uint8_t* obs_use_dev, const uint8_t* point_use_dev,
+                           const uint8_t* cam_seed_dev, const uint8_t* cam_hold_dev, const gh_ba_window_params* params,
+                           uint8_t* cam_class_dev, int32_t* cam_shared_dev, int32_t* cam_slot_dev, int32_t* point_slot_dev,
+                           int32_t* win_cam_dev, int32_t* win_cam_dof_dev, double* win_cam_pose_dev, int32_t* win_point_dev,
+                           double* win_point_xyz_dev, int32_t* win_obs_cam_dev, int32_t* win_obs_point_dev,
+                           int32_t* win_obs_src_dev, double* win_obs_xy_dev, int32_t* totals_dev);
+/* The way back: the solved poses and points of a window into the map's device arrays.  win_cam_dev, win_cam_dof_dev and
+ * win_point_dev as gh_ba_window_dev wrote them; cam_pose_win_dev n_win_cams x 7 and point_xyz_win_dev n_win_points x 3 hold the
+ * solved values (DEVICE pointers); n_win_cams and n_win_points are host integers, which the caller has after the solve.  For
+ * i < n_win_cams with win_cam_dof[i] != 0 and 0 <= win_cam[i] < n_cams the seven doubles of row i go to row win_cam[i] of
+ * cam_pose_dev; for j < n_win_points with 0 <= win_point[j] < n_points the three doubles go to row win_point[j] of
+ * point_xyz_dev: copies of bits.  Fixed and held cameras, every camera and point outside the window and padding keep their bits.
+ * The ids of one list must be distinct; with duplicates the row that lands is unspecified.  Asynchronous on the context's
+ * stream.  GH_ERR_ARG, and then nothing is written: ctx NULL; a negative count; a NULL among the arrays a positive count sizes. */
+gh_status gh_ba_window_scatter_dev(gh_ctx* ctx, const int32_t* win_cam_dev, const int32_t* win_cam_dof_dev, int n_win_cams,
+                                   const double* cam_pose_win_dev, const int32_t* win_point_dev, int n_win_points,
+                                   const double* point_xyz_win_dev, double* cam_pose_dev, int n_cams, double* point_xyz_dev,
+                                   int n_points);
+
+/* Optimizer::magin(GSLAM/core/Optimizer.h:230-232, "Convert bundle graph to pose graph"; the reference ships the
  * declaration only): one SE3 edge per pair of cameras (first < second) that share at least min_shared points, with the 6x6
  * information (row-major, [v, w] order of SE3::exp) of the second camera's pose relative to the first held fixed -- the
  * Schur complement of the two-view problem over the shared points at the current estimate, Huber-weighted like
