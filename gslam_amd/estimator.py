@@ -10,7 +10,8 @@ link_tracks (gh_link_tracks_dev) builds those per-point arrays from the inlier r
 gather_map_matches (gh_pnp_gather_pairs_dev) reads the pair matches of new frames through that map into the arrays pnp_batch
 takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call and says which keypoint rows were inliers;
 extend_tracks (gh_extend_tracks_dev) adds those rows to the tracks of the map and links the other rows of the new frames into
-new tracks numbered after the map's, so that the map grows batch after batch without a read-back."""
+new tracks numbered after the map's, so that the map grows batch after batch without a read-back; merge_points
+(gh_merge_points_dev) renames the points that the matches show to be one to the oldest id of their group."""
 import ctypes as C
 
 import numpy as np
@@ -24,6 +25,8 @@ PNP_NO_START, PNP_TOO_FEW = 4, 5  # GH_PNP_*: termination of a batched refinemen
 TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_INCONSISTENT, TRACK_LOW_PARALLAX, TRACK_SKIPPED = 0, 1, 2, 3, 4, 5
 LINK_SHORT, LINK_CONFLICT, LINK_NO_ROW = -1, -2, -3  # GH_LINK_*: what node_point of link_tracks holds where there is no point id
 EXT_REJECTED = -4  # GH_EXT_REJECTED: beside LINK_*, what node_point of extend_tracks holds at a claimant that was turned down
+# GH_MERGE_*: the state byte per point of merge_points
+MERGE_NONE, MERGE_SURVIVOR, MERGE_ABSORBED, MERGE_CONFLICT, MERGE_FAR = 0, 1, 2, 3, 4
 # GH_LOC_*: what row_point of gather_map_matches / localize_pairs holds where there is no point id
 LOC_NO_POINT, LOC_AMBIGUOUS, LOC_NO_ROW, LOC_SHARED = -1, -2, -3, -4
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
@@ -463,6 +466,49 @@ def extend_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, n
     ctx.check(hip.lib.gh_extend_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
                                            q(node_point), n_points, q(row_point), q(row_inlier), C.c_double(fx), C.c_double(fy),
                                            C.c_double(cx), C.c_double(cy), int(min_views), *(p(out[k]) for k in out)))
+    return out
+
+
+def merge_points(ctx: hip.Context, counts, cap, pair_q, pair_t, idx1, inlier, node_point, n_points, point_status=None, point_xyz=None,
+                 max_dist=0.0, bridge=True, obs_point=None, in_place=False):
+    """gh_merge_points_dev, the call after extend_tracks: map points that the pair matches join are merged into the smallest id
+    of their group.  counts: F int32, cap: the rows per frame, pair_q / pair_t: P int32, idx1: P x cap int32, inlier: P x cap
+    uint8 or None (all rows), as link_tracks takes them; node_point: F * cap int32 as extend_tracks returns it; n_points: the
+    capacity of the point arrays (the PC of extend_tracks); point_status: n_points int32 (only TRACK_OK points take part) or None
+    (all points); point_xyz: n_points x 3 float64 or None (no distance gate), max_dist: the gate; bridge: rows without a point
+    may carry a merge; obs_point: F * cap int32 as extend_tracks returns it, or None -- all cuda.  in_place: node_point and
+    obs_point are updated where they are and returned.  With N = F * cap -> dict of device tensors: point_remap n_points int32
+    (the surviving id of every point), point_state n_points uint8 (MERGE_NONE, MERGE_SURVIVOR, MERGE_ABSORBED, MERGE_CONFLICT,
+    MERGE_FAR), point_select n_points uint8 (1 at the survivors), node_point N int32, obs_point N int32 or None, point_len
+    n_points int32, totals 6 int32 (MERGED groups, ABSORBED points, CONFLICT groups, FAR groups, nodes whose point changed, points
+    in CONFLICT or FAR groups); nothing is synchronised and nothing is read back: obs_cam / obs_xy of extend_tracks stay valid,
+    and triangulate_tracks with point_select = point_select gives the survivors their coordinates from all of their
+    observations."""
+    import torch
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1, node_point))
+    F, cap, P = counts.numel(), int(cap), pair_q.shape[0]
+    N, dev, n_points = F * cap, counts.device, int(n_points)
+    assert pair_t.shape[0] == P and idx1.numel() == P * cap and node_point.numel() == N and n_points >= 0
+    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
+    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
+                                    point_status.numel() == n_points)
+    assert point_xyz is None or (point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and
+                                 point_xyz.numel() == 3 * n_points)
+    assert obs_point is None or (obs_point.is_cuda and obs_point.dtype == torch.int32 and obs_point.is_contiguous() and
+                                 obs_point.numel() == N)
+    out = {"point_remap": torch.empty(n_points, dtype=torch.int32, device=dev),
+           "point_state": torch.empty(n_points, dtype=torch.uint8, device=dev),
+           "point_select": torch.empty(n_points, dtype=torch.uint8, device=dev),
+           "node_point": node_point if in_place else torch.empty(N, dtype=torch.int32, device=dev),
+           "obs_point": None if obs_point is None else (obs_point if in_place else torch.empty(N, dtype=torch.int32, device=dev)),
+           "point_len": torch.empty(n_points, dtype=torch.int32, device=dev),
+           "totals": torch.empty(6, dtype=torch.int32, device=dev)}
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    q = lambda t: None if t is None else p(t)  # (NULL means "not given", also when the array holds nothing)
+    ctx.check(hip.lib.gh_merge_points_dev(ctx.h, p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier), p(node_point),
+                                          n_points, q(point_status), q(point_xyz), C.c_double(float(max_dist)), 1 if bridge else 0,
+                                          q(obs_point), *(q(out[k]) for k in out)))
     return out
 
 

@@ -239,6 +239,8 @@ SIGNATURES = {
     "gh_extend_tracks_dev": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp,
                                        C.c_double, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp]),
+    "gh_merge_points_dev": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, C.c_double, _i, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gh_ba_window_default_params": (None, [C.POINTER(BaWindowParams)]),
     "gh_ba_window_dev": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BaWindowParams),
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -981,6 +981,62 @@ gh_status gh_extend_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const in
                                int32_t* node_point_dev, int32_t* obs_cam_dev, int32_t* obs_point_dev, double* obs_xy_dev,
                                int32_t* obs_node_dev, int32_t* point_len_dev, uint8_t* point_new_dev, uint8_t* point_grew_dev,
                                int32_t* totals_dev);
+/* Merging map points that the matches show to be one: a track that broke comes back under a second point id, and until the two
+ * ids are merged gh_extend_tracks_dev ignores every edge between them and gh_pnp_gather_pairs_dev turns a keypoint that both
+ * answer into GH_LOC_AMBIGUOUS.  This call finds the groups of points that the pair matches join, keeps the smallest id of each
+ * and renames the others in node_point and in the observation list; no observation moves.  Every pointer is a DEVICE pointer,
+ * nothing is copied to the host, the call is asynchronous on the context's stream, scratch comes from the context.  counts_dev,
+ * n_frames, cap, pair_q_dev, pair_t_dev, npairs, idx1_dev, inlier_dev (or NULL) as gh_link_tracks_dev takes them.  The map:
+ * node_point_in_dev N = n_frames * cap entries as gh_extend_tracks_dev leaves them; n_points is a CAPACITY (the PC of
+ * gh_extend_tracks_dev goes in as it is); point_status_dev n_points or NULL; point_xyz_dev n_points x 3 or NULL (no gate);
+ * max_dist; bridge; obs_point_in_dev N entries or NULL.
+ *   nodes, pairs, edges  exactly the rules of gh_link_tracks_dev: node (f, i) EXISTS when 0 <= i < clamp(counts[f], 0, cap); a pair
+ *              is read only when both frame indices are in range and different; query row i of a pair is an edge under the
+ *              gather rule of gh_ransac_pairs_dev; an index outside its range drops the row, it is never dereferenced.
+ *   classes    point p is USABLE when point_status_dev is NULL or status[p] == GH_TRACK_OK.  An existing node n with 0 <=
+ *              node_point_in[n] < n_points is a HOLDER of that point when the point is usable and OUT when it is not.  Any other
+ *              existing node (a negative code, a value >= n_points) is a BRIDGE when bridge != 0 and OUT when bridge == 0.  An
+ *              edge that touches an OUT node is ignored; a value that is not a valid id is never used as an index.
+ *   graph      the elements are the usable points and the BRIDGE nodes; an edge (u, v) links e(u) and e(v), where e(HOLDER) is
+ *              its point and e(BRIDGE) the node itself; an edge whose two ends hold the same point links nothing.  A GROUP is a
+ *              connected component that contains at least two points, its LABEL the smallest point id in it -- the oldest id
+ *              survives -- whatever the order of the pairs.  A component with one point or with none is left exactly as it
+ *              is (new tracks are the business of gh_extend_tracks_dev).
+ *   verdict    of a group, checked in this order.  CONFLICT: two HOLDER nodes of its points lie in one frame (the merged point
+ *              would be seen twice there); two holders of the SAME point that the caller's map already had in one frame count
+ *              too; the whole group is left apart, as gh_link_tracks_dev drops a conflicting component.  FAR: point_xyz_dev !=
+ *              NULL and some point p of the group fails d2(p, label) <= max_dist * max_dist, with d2 = (dx * dx + dy * dy) +
+ *              dz * dz, every difference, product and sum rounded once and nothing fused, max_dist * max_dist one double
+ *              product; a NaN fails.  MERGED: otherwise; every point of the group is renamed to the label.
+ * Outputs, ALL written for their full capacity on every call (dirty buffers never show): point_remap_dev n_points: the label for
+ * the points of MERGED groups, p itself for every other p; point_state_dev n_points bytes: GH_MERGE_NONE, GH_MERGE_SURVIVOR (the
+ * label of a MERGED group), GH_MERGE_ABSORBED (its other points), GH_MERGE_CONFLICT / GH_MERGE_FAR (every point of such a group);
+ * point_select_dev n_points bytes: 1 exactly at the survivors -- it goes to gh_triangulate_tracks_dev as point_select_dev, as
+ * point_new_dev of gh_extend_tracks_dev does, and a survivor keeps its old coordinates until then; node_point_dev N: remap[v]
+ * where 0 <= v = node_point_in[n] < n_points, otherwise v copied -- a function of that entry and the remap table alone, for
+ * existing and non-existing nodes alike; obs_point_dev N: the same function of obs_point_in_dev (both NULL or both given; the
+ * observation list keeps its order and length, obs_cam, obs_xy and obs_node stay valid as they are); point_len_dev n_points: the
+ * number of existing nodes whose output node_point equals p, so an absorbed point ends at 0, drops out of gh_ba_window_dev and
+ * is unreachable through node_point; totals_dev 6: the MERGED groups, the ABSORBED points, the CONFLICT groups, the FAR groups,
+ * the existing nodes whose node_point changed, the points in CONFLICT or FAR groups.  node_point_dev may be node_point_in_dev
+ * and obs_point_dev may be obs_point_in_dev (identical or disjoint): the map is updated in place.
+ * Everything is integer work except the gate: the same bits on every run.  tests/track_merge_restate.py restates all of it.
+ * GH_ERR_ARG, and then nothing is written: ctx NULL; n_frames, cap, npairs or n_points negative; cap > 65535; n_points +
+ * n_frames * cap > INT32_MAX - 1; a NULL among counts, node_point_in, point_remap, point_state, point_select, node_point,
+ * point_len, totals; exactly one of obs_point_in_dev / obs_point_dev NULL; with npairs > 0 a NULL among pair_q, pair_t, idx1;
+ * with point_xyz_dev given, max_dist negative or NaN.  N == 0 or npairs == 0: GH_OK, the identity remap, states and selects 0,
+ * totals zeros, node_point and obs_point copied and point_len counted as above. */
+#define GH_MERGE_NONE 0
+#define GH_MERGE_SURVIVOR 1
+#define GH_MERGE_ABSORBED 2
+#define GH_MERGE_CONFLICT 3
+#define GH_MERGE_FAR 4
+gh_status gh_merge_points_dev(gh_ctx* ctx, const int32_t* counts_dev, int n_frames, int cap, const int32_t* pair_q_dev,
+                              const int32_t* pair_t_dev, int npairs, const int32_t* idx1_dev, const uint8_t* inlier_dev,
+                              const int32_t* node_point_in_dev, int n_points, const int32_t* point_status_dev,
+                              const double* point_xyz_dev, double max_dist, int bridge, const int32_t* obs_point_in_dev,
+                              int32_t* point_remap_dev, uint8_t* point_state_dev, uint8_t* point_select_dev,
+                              int32_t* node_point_dev, int32_t* obs_point_dev, int32_t* point_len_dev, int32_t* totals_dev);
 
 /* The local window of a bundle adjustment, selected and compacted on the device: the last arrow of match -> localize -> extend ->
  * triangulate the new points -> BA.  The map's arrays go in as gh_extend_tracks_dev and gh_triangulate_tracks_dev leave them,
