@@ -9,15 +9,15 @@
 // WHY THE VERDICTS DO NOT DEPEND ON A RACE.  Every rule is a function of sets and of integer counts, and every pass reads only
 // what an EARLIER launch finished.  usable[k] has one lane and one writer per byte.  n_use[p] and shared[c] are sums of ones:
 // integer atomic adds on words the call zeroed -- commutative and exact -- after the lanes of a wave that sit next to each other
-// with the same key have folded their ones into the first of them (baw_add_runs: a ballot and a bit scan, no second
+// with the same key have folded their ones into the first of them (gh_map::add_runs: a ballot and a bit scan, no second
 // atomic), so observations in frame-major order cost one atomic per camera and wave in baw_shared, and in track-major order
 // one per point and wave in baw_count.  seen[p], window[p] and has[c] get the byte 1 from every writer (the same value from all
 // of them) on bytes the call zeroed.  LOCAL is one lane per camera.  Slots are an exclusive prefix sum over ids; an
 // observation's slot is its rank among the window observations in ascending index.
 //
-// CDNA4 mapping (the skeleton of track_extend.hip):
-//   * baw_count    one lane per observation: the USABLE byte, n_use[point] += 1, the usable total (ballot, LDS, one atomic per
-//                  workgroup);
+// CDNA4 mapping (add_runs and the counter tail block_counts_add are gh_map's, map_dev.h; the scan is dev_prims.h's):
+//   * baw_count    one lane per observation: the USABLE byte, n_use[point] += 1, the usable total (block_counts_add: ballot,
+//                  LDS, one atomic per workgroup);
 //   * baw_seen     per usable observation: LIVE (n_use >= min_point_obs) and in a seed camera -> seen[point] = 1;
 //   * baw_shared   per usable observation: LIVE and its point SEEN -> shared[camera] += 1;
 //   * baw_local    one lane per camera: LOCAL, cam_shared_dev, and the LOCAL / held / seed totals;
@@ -30,18 +30,14 @@
 //                  the word at n_cams) -- three scans in one rocPRIM call at every size the arguments can take;
 //   * baw_emit     every entry of every remaining output: classes, slots, the compact arrays at their slots, the padding past
 //                  the totals, the totals.
-// One context scratch block: n_use | shared | seen | window | has | four counters (ONE memset over these) | usable | local |
-// flags | rank | rocPRIM storage.
 #include <algorithm>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include "common.h"
+#include "dev_prims.h"
+#include "map_dev.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kMaxFlagBlocks = 1024;
+using namespace gh_map;
 
 struct BawArgs {
   int n_cams, n_points, n_obs;
@@ -72,28 +68,10 @@ struct BawArgs {
   int32_t* totals;
 };
 
-// words[key] += 1 for every lane with on != 0, exactly, with one atomic per RUN of neighbouring lanes that share the key.  Every
-// lane of the wave must call it (on = false where a lane has nothing to add).
-__device__ __forceinline__ void baw_add_runs(int32_t* words, int key, bool on) {
-  const int lane = threadIdx.x & 63;
-  const int prev_key = __shfl_up(key, 1);
-  const unsigned long long on_mask = __ballot(on);
-  const bool prev_on = lane > 0 && ((on_mask >> (lane - 1)) & 1ull) != 0;
-  const bool head = on && (!prev_on || prev_key != key);
-  const unsigned long long stops = __ballot(head || !on);  // the lanes at which a run cannot go on
-  if (head) {
-    const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
-    atomicAdd(words + key, above ? __ffsll(above) : 64 - lane);
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void baw_count_kernel(const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_point,
                                                            const uint8_t* __restrict__ obs_use, const uint8_t* __restrict__ point_use,
                                                            int n_cams, int n_points, int n_obs, uint8_t* __restrict__ usable,
                                                            int32_t* n_use, int32_t* counters) {
-  __shared__ int s_count;
-  if (threadIdx.x == 0) s_count = 0;
-  __syncthreads();
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   bool u = false;
   int p = 0;
@@ -104,11 +82,8 @@ __global__ __launch_bounds__(kBlock) void baw_count_kernel(const int32_t* __rest
     if (u && point_use) u = point_use[p] != 0;
     usable[g] = u ? 1 : 0;
   }
-  baw_add_runs(n_use, p, u);
-  const int n = __popcll(__ballot(u));
-  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&s_count, n);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_count) atomicAdd(counters, s_count);
+  add_runs(n_use, p, u);
+  block_counts_add<1>({wave_count(u)}, counters);
 }
 
 __global__ __launch_bounds__(kBlock) void baw_seen_kernel(const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_point,
@@ -133,16 +108,13 @@ __global__ __launch_bounds__(kBlock) void baw_shared_kernel(const int32_t* __res
     c = obs_cam[g];
     on = n_use[p] >= min_point_obs && seen[p] != 0;
   }
-  baw_add_runs(shared, c, on);
+  add_runs(shared, c, on);
 }
 
 __global__ __launch_bounds__(kBlock) void baw_local_kernel(const int32_t* __restrict__ shared, const uint8_t* __restrict__ cam_seed,
                                                            const uint8_t* __restrict__ cam_hold, int n_cams, int min_shared,
                                                            uint8_t* __restrict__ local, int32_t* __restrict__ cam_shared,
                                                            int32_t* counters) {
-  __shared__ int s_count[3];
-  if (threadIdx.x < 3) s_count[threadIdx.x] = 0;
-  __syncthreads();
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   bool is_local = false, is_held = false, is_seed = false;
   if (g < n_cams) {
@@ -154,14 +126,7 @@ __global__ __launch_bounds__(kBlock) void baw_local_kernel(const int32_t* __rest
     local[g] = is_local ? 1 : 0;
     cam_shared[g] = s;
   }
-  const int nl = __popcll(__ballot(is_local)), nh = __popcll(__ballot(is_held)), ns = __popcll(__ballot(is_seed));
-  if ((threadIdx.x & 63) == 0) {
-    if (nl) atomicAdd(&s_count[0], nl);
-    if (nh) atomicAdd(&s_count[1], nh);
-    if (ns) atomicAdd(&s_count[2], ns);
-  }
-  __syncthreads();
-  if (threadIdx.x < 3 && s_count[threadIdx.x]) atomicAdd(counters + 1 + threadIdx.x, s_count[threadIdx.x]);
+  block_counts_add<3>({wave_count(is_local), wave_count(is_held), wave_count(is_seed)}, counters + 1);
 }
 
 __global__ __launch_bounds__(kBlock) void baw_points_kernel(const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_point,
@@ -316,20 +281,16 @@ extern "C" gh_status gh_ba_window_dev(gh_ctx* ctx, int n_cams, int n_points, int
 
   const size_t nc = (size_t)n_cams, np = (size_t)n_points, no = (size_t)n_obs;
   const size_t last = std::max(no, nc + np);  // the scan covers the entries 0 .. last
-  size_t tmp_bytes = 0;
-  {
-    uint64_t* null_u = nullptr;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, null_u, null_u, (uint64_t)0, last + 1, rocprim::plus<uint64_t>(), ctx->stream) != hipSuccess)
-      return gh_set_error(ctx, GH_ERR_HIP, "gh_ba_window_dev: rocPRIM size query failed");
-    tmp_bytes = gh_round256(std::max(tmp_bytes, (size_t)1));
-  }
-  const size_t o_shared = gh_round256(np * 4), o_seen = o_shared + gh_round256(nc * 4), o_window = o_seen + gh_round256(np);
-  const size_t o_has = o_window + gh_round256(np), o_counters = o_has + gh_round256(nc), o_usable = o_counters + 256;
-  const size_t o_local = o_usable + gh_round256(no), o_flags = o_local + gh_round256(nc);
-  const size_t o_rank = o_flags + gh_round256((last + 1) * 8), o_tmp = o_rank + gh_round256((last + 1) * 8);
+  // The scratch block.  n_use, shared, seen, window, has and the four counters are neighbours: one memset clears them.
+  const size_t tmp_bytes = gh_scan_u64_bytes(ctx, last + 1);
+  if (!tmp_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_ba_window_dev: rocPRIM size query failed");
+  gh_carve c;
+  const size_t o_n_use = c.take(np * 4), o_shared = c.take(nc * 4), o_seen = c.take(np), o_window = c.take(np), o_has = c.take(nc);
+  const size_t o_counters = c.take(4 * sizeof(int32_t)), o_usable = c.take(no), o_local = c.take(nc);
+  const size_t o_flags = c.take((last + 1) * 8), o_rank = c.take((last + 1) * 8), o_tmp = c.take(tmp_bytes);
   char* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_tmp + tmp_bytes, (void**)&base));
-  int32_t* n_use = (int32_t*)base;
+  GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
+  int32_t* n_use = (int32_t*)(base + o_n_use);
   int32_t* shared = (int32_t*)(base + o_shared);
   uint8_t* seen = (uint8_t*)(base + o_seen);
   uint8_t* window = (uint8_t*)(base + o_window);
@@ -342,7 +303,7 @@ extern "C" gh_status gh_ba_window_dev(gh_ctx* ctx, int n_cams, int n_points, int
 
   const dim3 block(kBlock), obs_grid(gh_div_up(n_obs, kBlock)), cam_grid(gh_div_up(n_cams, kBlock));
   const int mpo = params->min_point_obs;
-  GH_HIP(ctx, hipMemsetAsync(base, 0, o_usable, ctx->stream));
+  GH_HIP(ctx, hipMemsetAsync(n_use, 0, o_usable - o_n_use, ctx->stream));
   if (n_obs > 0) {
     GH_LAUNCH(ctx, "baw_count", baw_count_kernel, obs_grid, block, 0, obs_cam_dev, obs_point_dev, obs_use_dev, point_use_dev, n_cams,
               n_points, n_obs, usable, n_use, counters);
@@ -364,43 +325,13 @@ extern "C" gh_status gh_ba_window_dev(gh_ctx* ctx, int n_cams, int n_points, int
   GH_LAUNCH(ctx, "baw_flags", baw_flags_kernel, dim3(flag_blocks < kMaxFlagBlocks ? flag_blocks : kMaxFlagBlocks), block, 0,
             (const uint8_t*)local, (const uint8_t*)has, (const uint8_t*)window, n_cams, n_points, n_obs, (long long)last,
             (uint32_t*)flags);
-  {
-    const int prof = gh_prof_begin(ctx, "baw_scan");
-    size_t tb = tmp_bytes;
-    const hipError_t e = rocprim::exclusive_scan(base + o_tmp, tb, flags, rank, (uint64_t)0, last + 1, rocprim::plus<uint64_t>(), ctx->stream);
-    gh_prof_end(ctx, prof);
-    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_ba_window_dev: scan");
-  }
+  GH_TRY(gh_scan_u64(ctx, "baw_scan", "gh_ba_window_dev: scan", base + o_tmp, tmp_bytes, flags, rank, last + 1));
 
-  BawArgs a = {};
-  a.n_cams = n_cams;
-  a.n_points = n_points;
-  a.n_obs = n_obs;
-  a.cam_pose = cam_pose_dev;
-  a.point_xyz = point_xyz_dev;
-  a.obs_cam = obs_cam_dev;
-  a.obs_point = obs_point_dev;
-  a.obs_xy = obs_xy_dev;
-  a.cam_hold = cam_hold_dev;
-  a.local = local;
-  a.has = has;
-  a.window = window;
-  a.flags = flags;
-  a.rank = rank;
-  a.counters = counters;
-  a.cam_class = cam_class_dev;
-  a.cam_slot = cam_slot_dev;
-  a.point_slot = point_slot_dev;
-  a.win_cam = win_cam_dev;
-  a.win_cam_dof = win_cam_dof_dev;
-  a.win_cam_pose = win_cam_pose_dev;
-  a.win_point = win_point_dev;
-  a.win_point_xyz = win_point_xyz_dev;
-  a.win_obs_cam = win_obs_cam_dev;
-  a.win_obs_point = win_obs_point_dev;
-  a.win_obs_src = win_obs_src_dev;
-  a.win_obs_xy = win_obs_xy_dev;
-  a.totals = totals_dev;
+  const BawArgs a = {n_cams, n_points, n_obs, cam_pose_dev, point_xyz_dev, obs_cam_dev, obs_point_dev, obs_xy_dev, cam_hold_dev,  // inputs
+                     local, has, window, flags, rank, counters,                                                                   // scratch
+                     cam_class_dev, cam_slot_dev, point_slot_dev,                                                                 // per id
+                     win_cam_dev, win_cam_dof_dev, win_cam_pose_dev, win_point_dev, win_point_xyz_dev,                            // compact
+                     win_obs_cam_dev, win_obs_point_dev, win_obs_src_dev, win_obs_xy_dev, totals_dev};
   const int most = std::max(std::max(n_cams, n_points), std::max(n_obs, 1));
   GH_LAUNCH(ctx, "baw_emit", baw_emit_kernel, dim3(gh_div_up(most, kBlock)), block, 0, a);
   return GH_OK;

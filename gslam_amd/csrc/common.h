@@ -127,3 +127,13 @@ void gh_prof_end(gh_ctx* ctx, int pending);
 static inline int gh_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 // Segments of a scratch block start on 256-byte boundaries.
 static inline size_t gh_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// Carves a scratch block: the sequence of take() calls IS the layout.  take() returns the offset of the next segment; `at` is
+// the size of the block so far, and the offset at which the next segment will start.
+struct gh_carve {
+  size_t at = 0;
+  size_t take(size_t bytes) {
+    const size_t offset = at;
+    at += gh_round256(bytes);
+    return offset;
+  }
+};

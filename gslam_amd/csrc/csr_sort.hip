@@ -1,16 +1,15 @@
 // Index lists (CSR) of a large graph built on the GPU: items sorted by key, ascending item index inside a key -- what
 // build_csr (ba.hip) does on the host with a counting sort.  For the 6 M observations of BASELINE configs[2] (C5) the host
 // teams take ~60 ms per solve, a stable LSD radix sort of (key, item) pairs on the device ~1 ms plus the transfers.
-// rocPRIM is the sort (plumbing, like the runtime's memcpy); what this index needs of it is in this file (track_link.hip sorts
-// and scans for itself: its keys have one hot bin, which the histogram below would serialise).
+// The sort and the scan are rocPRIM's, behind dev_prims.h (track_link.hip sorts and scans for itself: its keys have one hot bin,
+// which the histogram below would serialise).
 // gh_csr_index_dev is the device-side core (keys on the device in, start and list on the device out, work space passed in, nothing
 // synchronised); gh_csr_build_dev wraps it for host arrays, tracks.hip calls it on the stream with context scratch.
+#include <algorithm>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "dense_solve.h"
+#include "dev_prims.h"
 
 namespace {
 
@@ -27,29 +26,18 @@ __global__ __launch_bounds__(256) void csr_prepare_kernel(const int32_t* __restr
   atomicAdd(&count[k], 1);
 }
 
-}  // namespace
-
-namespace {
-
-int csr_key_bits(int n_keys) {
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) < n_keys) ++bits;
-  return bits;
-}
-
 // work space: key_out | item | item_out | count | start | bad flag | rocPRIM temporary storage, segments on 256-byte boundaries
 struct CsrLayout {
+  int bits;  // of the sort: the keys are 0 .. n_keys - 1
   size_t o_item, o_item_out, o_count, o_start, o_bad, o_tmp, tmp_bytes, total;
 };
 
-bool csr_layout(hipStream_t stream, int n_items, int n_keys, CsrLayout* L) {
+bool csr_layout(gh_ctx* ctx, int n_items, int n_keys, CsrLayout* L) {
   const size_t N = (size_t)n_items, K = (size_t)n_keys + 1;
-  size_t sort_bytes = 0, scan_bytes = 0;
-  int32_t* null_i = nullptr;
-  if (rocprim::radix_sort_pairs(nullptr, sort_bytes, null_i, null_i, null_i, null_i, N, 0, csr_key_bits(n_keys), stream) != hipSuccess ||
-      rocprim::exclusive_scan(nullptr, scan_bytes, null_i, null_i, 0, K, rocprim::plus<int32_t>(), stream) != hipSuccess)
-    return false;
-  L->tmp_bytes = gh_round256(std::max(sort_bytes, scan_bytes));
+  L->bits = gh_key_bits(n_keys - 1);
+  const size_t sort_bytes = gh_sort_pairs_bytes(ctx, N, L->bits), scan_bytes = gh_scan_i32_bytes(ctx, K);
+  if (!sort_bytes || !scan_bytes) return false;
+  L->tmp_bytes = std::max(sort_bytes, scan_bytes);
   L->o_item = gh_round256(N * 4);
   L->o_item_out = L->o_item + gh_round256(N * 4);
   L->o_count = L->o_item_out + gh_round256(N * 4);
@@ -64,7 +52,7 @@ bool csr_layout(hipStream_t stream, int n_items, int n_keys, CsrLayout* L) {
 
 size_t gh_csr_index_bytes(gh_ctx* ctx, int n_items, int n_keys) {
   CsrLayout L;
-  if (n_items <= 0 || n_keys <= 0 || !csr_layout(ctx->stream, n_items, n_keys, &L)) return 0;
+  if (n_items <= 0 || n_keys <= 0 || !csr_layout(ctx, n_items, n_keys, &L)) return 0;
   return L.total;
 }
 
@@ -72,7 +60,7 @@ gh_status gh_csr_index_dev(gh_ctx* ctx, const int32_t* keys_dev, int n_items, in
                            const int32_t** start_dev, const int32_t** list_dev, const int** bad_dev) {
   CsrLayout L;
   if (n_items <= 0 || n_keys <= 0) return gh_set_error(ctx, GH_ERR_ARG, "gh_csr_index_dev: empty input");
-  if (!csr_layout(ctx->stream, n_items, n_keys, &L)) return gh_set_error(ctx, GH_ERR_HIP, "gh_csr_index_dev: rocPRIM size query failed");
+  if (!csr_layout(ctx, n_items, n_keys, &L)) return gh_set_error(ctx, GH_ERR_HIP, "gh_csr_index_dev: rocPRIM size query failed");
   if (!work || work_bytes < L.total || ((uintptr_t)work & 255)) return gh_set_error(ctx, GH_ERR_ARG, "gh_csr_index_dev: work space");
   const size_t N = (size_t)n_items, K = (size_t)n_keys + 1;
   char* base = (char*)work;
@@ -87,12 +75,9 @@ gh_status gh_csr_index_dev(gh_ctx* ctx, const int32_t* keys_dev, int n_items, in
     return gh_set_error(ctx, GH_ERR_HIP, "gh_csr_index_dev: memset");
   hipLaunchKernelGGL(csr_prepare_kernel, dim3(gh_div_up(n_items, 256)), dim3(256), 0, ctx->stream, keys_dev, n_items, n_keys, d_item,
                      d_count, d_bad);
-  size_t tb = L.tmp_bytes;
-  if (rocprim::exclusive_scan(d_tmp, tb, d_count, d_start, 0, K, rocprim::plus<int32_t>(), ctx->stream) != hipSuccess)
-    return gh_set_error(ctx, GH_ERR_HIP, "gh_csr_index_dev: scan");
-  tb = L.tmp_bytes;
-  if (rocprim::radix_sort_pairs(d_tmp, tb, keys_dev, d_key_out, d_item, d_item_out, N, 0, csr_key_bits(n_keys), ctx->stream) != hipSuccess)
-    return gh_set_error(ctx, GH_ERR_HIP, "gh_csr_index_dev: sort");
+  // (not timed one by one: the caller times the index as a whole)
+  GH_TRY(gh_scan_i32(ctx, nullptr, "gh_csr_index_dev: scan", d_tmp, L.tmp_bytes, d_count, d_start, K));
+  GH_TRY(gh_sort_pairs_i32(ctx, nullptr, "gh_csr_index_dev: sort", d_tmp, L.tmp_bytes, keys_dev, d_key_out, d_item, d_item_out, N, L.bits));
   *start_dev = d_start;
   *list_dev = d_item_out;
   if (bad_dev) *bad_dev = d_bad;

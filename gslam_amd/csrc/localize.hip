@@ -11,39 +11,39 @@
 // launch has ended: every later stage is a launch of its own on the same stream and takes plain loads.  SHARED is decided on the
 // sorted list, where every writer stores the same byte 1; the counts are integer sums.
 //
-// CDNA4 mapping (the skeleton of track_link.hip):
+// CDNA4 mapping (the shared pieces are gh_map's, map_dev.h):
 //   * loc_init    lo[n] = INT_MAX, hi[n] = -1;
-//   * loc_vote    one lane per (pair, query row), grid-stride; the gather rule of gh_ransac_pairs_dev decides whether the row
-//                 passes, then one read of the train node's point, the range and status tests, and the two atomics;
+//   * loc_vote    one lane per (pair, query row), grid-stride; pair_edge decides whether the row passes, then one read of the
+//                 train node's point, the range and status tests, and the two atomics;
 //   * loc_key     key[n] = lo[n] for an existing node with lo == hi, the extra bin n_points otherwise;
 //   * sort        rocPRIM's stable radix sort of (key, node) over the bits of n_points + 1 values: within one point the nodes
 //                 come in ascending id, so the claimants of one frame are neighbours.  No histogram per point: a popular map
 //                 point would be one hot word;
 //   * loc_runs    neighbours with one key below n_points and one frame both store the byte 1 to shared[node];
 //   * loc_flags   per node: the code of row_point (written here), the flag "is a correspondence"; AMBIGUOUS and SHARED nodes
-//                 counted in registers, then LDS, then one integer atomic per workgroup; grid-stride over at most 1024
-//                 workgroups; entry N of the flags is the scan's room for the total;
+//                 counted in registers, then block_counts_add: LDS, one integer atomic per workgroup; grid-stride over at most
+//                 1024 workgroups; entry N of the flags is the scan's room for the total;
 //   * scan        one rocPRIM exclusive scan; offsets[f] is its value at node f * cap, so the offsets cost nothing extra;
 //   * loc_emit    every remaining entry of every output exactly once: the correspondence of a node at its rank, the padding past
 //                 n_corr, offsets, totals (the frames with a correspondence: one ballot per wave of frames, integer atomics on
 //                 a word the call zeroed);
 //   * loc_scatter composed call only, after a memset of row_inlier: one lane per correspondence k < n_corr (read from
 //                 offsets[n_frames] on the device) stores its inlier byte at corr_node[k].
-// rocPRIM (one sort, one scan) is plumbing here as in track_link.hip; the work space comes from the context's scratch.  The
+// The sort and the scan are dev_prims.h's; the work space comes from the context's scratch.  The
 // composed call takes ONE scratch block: inlier bytes | n_inliers | the block of the stage that runs (the gather's is dead when
 // gh_pnp_batch_dev's begins: every result of the gather lives in the caller's arrays).
+#include <algorithm>
 #include <climits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "dev_prims.h"
 #include "estimate_batch.h"
+#include "map_dev.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using namespace gh_map;
+
 constexpr int kMaxVoteBlocks = 1 << 16;  // grid-stride beyond this many workgroups
-constexpr int kMaxFlagBlocks = 1024;
 
 struct GatherIn {
   const gh_keypoint* kps;
@@ -70,7 +70,7 @@ struct GatherIn {
 struct EmitArgs {
   const gh_keypoint* kps;
   int n_frames, cap, N;
-  double fx, fy, cx, cy;
+  Pinhole pin;
   const double* point_xyz;
   const int32_t* row_point;  // written by loc_flags
   const int32_t* rank;       // N + 1: exclusive scan of the flags; [N] = n_corr
@@ -81,11 +81,6 @@ struct EmitArgs {
   int32_t* corr_node;
   int32_t* totals;           // [3] is zero when loc_emit starts
 };
-
-__device__ __forceinline__ int loc_count(const int32_t* __restrict__ counts, int f, int cap) {
-  const int c = counts[f];
-  return c < 0 ? 0 : (c > cap ? cap : c);
-}
 
 __global__ __launch_bounds__(kBlock) void loc_init_kernel(int32_t* __restrict__ lo, int32_t* __restrict__ hi, int N) {
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -100,19 +95,14 @@ __global__ __launch_bounds__(kBlock) void loc_vote_kernel(const int32_t* __restr
                                                           const uint8_t* __restrict__ keep, const int32_t* __restrict__ node_point,
                                                           int n_points, const int32_t* __restrict__ point_status, int32_t* lo,
                                                           int32_t* hi) {
+  const PairRows e = {counts, n_frames, cap, pair_q, pair_t, idx1, keep};
   const long long step = (long long)gridDim.x * kBlock;
   for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += step) {
-    const int p = (int)(r / cap), i = (int)(r - (long long)p * cap);
-    const int fq = pair_q[p], ft = pair_t[p];
-    if (fq < 0 || fq >= n_frames || ft < 0 || ft >= n_frames || fq == ft) continue;
-    if (i >= loc_count(counts, fq, cap)) continue;
-    if (keep && keep[r] == 0) continue;
-    const int j = idx1[r];
-    if (j < 0 || j >= loc_count(counts, ft, cap)) continue;
-    const int c = node_point[ft * cap + j];
+    int u, v;
+    if (!pair_edge(e, r, &u, &v)) continue;
+    const int c = node_point[v];
     if (c < 0 || c >= n_points) continue;
     if (point_status && point_status[c] != GH_TRACK_OK) continue;
-    const int u = fq * cap + i;
     (void)__hip_atomic_fetch_min(lo + u, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     (void)__hip_atomic_fetch_max(hi + u, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void loc_key_kernel(const int32_t* __restri
   const int n = (int)g;
   const int f = n / cap, i = n - f * cap;
   const int l = lo[n];
-  key[n] = (i < loc_count(counts, f, cap) && l == hi[n]) ? l : n_points;  // (no candidate: INT_MAX != -1)
+  key[n] = (i < row_count(counts, f, cap) && l == hi[n]) ? l : n_points;  // (no candidate: INT_MAX != -1)
   item[n] = n;
 }
 
@@ -149,9 +139,6 @@ __global__ __launch_bounds__(kBlock) void loc_flags_kernel(const int32_t* __rest
                                                            const int32_t* __restrict__ hi, const uint8_t* __restrict__ shared,
                                                            int32_t* __restrict__ flags, int32_t* __restrict__ row_point,
                                                            int32_t* __restrict__ counters) {
-  __shared__ int s_count[2];
-  if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
-  __syncthreads();
   int na = 0, ns = 0;  // the same in every lane of a wave
   const long long step = (long long)gridDim.x * kBlock;
   for (long long base = (long long)blockIdx.x * kBlock; base <= N; base += step) {  // (entry N is the scan's room for the total)
@@ -163,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void loc_flags_kernel(const int32_t* __rest
       if (n < N) {
         const int f = n / cap, i = n - f * cap;
         int code = GH_LOC_NO_ROW;
-        if (i < loc_count(counts, f, cap)) {
+        if (i < row_count(counts, f, cap)) {
           const int k = key[n];
           if (k != n_points) {
             is_shared = shared[n] != 0;
@@ -178,15 +165,10 @@ __global__ __launch_bounds__(kBlock) void loc_flags_kernel(const int32_t* __rest
       }
       flags[n] = flag;
     }
-    na += __popcll(__ballot(is_ambiguous));
-    ns += __popcll(__ballot(is_shared));
+    na += wave_count(is_ambiguous);
+    ns += wave_count(is_shared);
   }
-  if ((threadIdx.x & 63) == 0) {
-    if (na) atomicAdd(&s_count[0], na);
-    if (ns) atomicAdd(&s_count[1], ns);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && s_count[threadIdx.x]) atomicAdd(counters + threadIdx.x, s_count[threadIdx.x]);
+  block_counts_add<2>({na, ns}, counters);
 }
 
 __global__ __launch_bounds__(kBlock) void loc_emit_kernel(EmitArgs a) {
@@ -221,12 +203,10 @@ __global__ __launch_bounds__(kBlock) void loc_emit_kernel(EmitArgs a) {
   const int c = a.row_point[n];
   if (c < 0) return;
   const int k = a.rank[n];
-  const float x = a.kps[n].x, y = a.kps[n].y;
   a.xyz[3 * (size_t)k] = a.point_xyz[3 * (size_t)c];
   a.xyz[3 * (size_t)k + 1] = a.point_xyz[3 * (size_t)c + 1];
   a.xyz[3 * (size_t)k + 2] = a.point_xyz[3 * (size_t)c + 2];
-  a.xy[2 * (size_t)k] = ((double)x - a.cx) / a.fx;
-  a.xy[2 * (size_t)k + 1] = ((double)y - a.cy) / a.fy;
+  normalised_xy(a.kps[n], a.pin, a.xy + 2 * (size_t)k);
   a.corr_node[k] = n;
 }
 
@@ -239,32 +219,20 @@ __global__ __launch_bounds__(kBlock) void loc_scatter_kernel(const int32_t* __re
   if (node >= 0 && node < N && inlier[g]) row_inlier[node] = 1;
 }
 
-int loc_key_bits(int n_points) {  // the keys are 0 .. n_points
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) <= n_points) ++bits;
-  return bits;
-}
-
-// temporary storage that serves both the sort of N pairs and the scan of N + 1 flags
-bool loc_rocprim_bytes(hipStream_t stream, int N, int n_points, size_t* bytes) {
-  int32_t* null_i = nullptr;
-  size_t scan = 0, sort = 0;
-  if (rocprim::exclusive_scan(nullptr, scan, null_i, null_i, (int32_t)0, (size_t)N + 1, rocprim::plus<int32_t>(), stream) != hipSuccess ||
-      rocprim::radix_sort_pairs(nullptr, sort, null_i, null_i, null_i, null_i, (size_t)N, 0, loc_key_bits(n_points), stream) != hipSuccess)
-    return false;
-  *bytes = gh_round256(std::max(std::max(scan, sort), (size_t)1));
-  return true;
-}
-
 // The gather's scratch block: lo | hi | key | sorted keys | item | list | shared bytes, two counters (one memset) | flags | rank |
-// rocPRIM storage.
+// rocPRIM storage, which serves the sort of N pairs and the scan of N + 1 flags.  (Not carved with gh_carve: six equal segments
+// and five offsets are shorter this way.)
 struct GatherLayout {
+  int bits;  // of the sort: the keys are 0 .. n_points
   size_t ints, o_shared, o_counters, o_flags, o_rank, o_tmp, tmp_bytes, total;
 };
 
-bool gather_layout(hipStream_t stream, int N, int n_points, GatherLayout* L) {
+bool gather_layout(gh_ctx* ctx, int N, int n_points, GatherLayout* L) {
   const size_t n = (size_t)N;
-  if (!loc_rocprim_bytes(stream, N, n_points, &L->tmp_bytes)) return false;
+  L->bits = gh_key_bits(n_points);
+  const size_t sort_bytes = gh_sort_pairs_bytes(ctx, n, L->bits), scan_bytes = gh_scan_i32_bytes(ctx, n + 1);
+  if (!sort_bytes || !scan_bytes) return false;
+  L->tmp_bytes = std::max(sort_bytes, scan_bytes);
   L->ints = gh_round256(n * 4);
   L->o_shared = 6 * L->ints;
   L->o_counters = L->o_shared + gh_round256(n);
@@ -306,6 +274,7 @@ gh_status gather_on(gh_ctx* ctx, const GatherIn& g, const GatherLayout& L, char*
   int32_t* counters = (int32_t*)(base + L.o_counters);
   int32_t* flags = (int32_t*)(base + L.o_flags);
   int32_t* rank = (int32_t*)(base + L.o_rank);
+  void* tmp = base + L.o_tmp;
 
   const dim3 grid(gh_div_up(N, kBlock)), block(kBlock);
   GH_HIP(ctx, hipMemsetAsync(shared, 0, L.o_flags - L.o_shared, ctx->stream));
@@ -318,43 +287,16 @@ gh_status gather_on(gh_ctx* ctx, const GatherIn& g, const GatherLayout& L, char*
               g.n_frames, g.cap, g.pair_q, g.pair_t, rows, g.idx1, g.keep, g.node_point, g.n_points, g.point_status, lo, hi);
   }
   GH_LAUNCH(ctx, "loc_key", loc_key_kernel, grid, block, 0, g.counts, g.cap, N, g.n_points, lo, hi, key, item);
-  {
-    const int prof = gh_prof_begin(ctx, "loc_sort");
-    size_t tb = L.tmp_bytes;
-    const hipError_t e = rocprim::radix_sort_pairs(base + L.o_tmp, tb, key, skey, item, list, n, 0, loc_key_bits(g.n_points), ctx->stream);
-    gh_prof_end(ctx, prof);
-    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_pnp_gather_pairs_dev: sort");
-  }
+  GH_TRY(gh_sort_pairs_i32(ctx, "loc_sort", "gh_pnp_gather_pairs_dev: sort", tmp, L.tmp_bytes, key, skey, item, list, n, L.bits));
   GH_LAUNCH(ctx, "loc_runs", loc_runs_kernel, grid, block, 0, skey, list, g.cap, N, g.n_points, shared);
   const int flag_blocks = gh_div_up((long long)N + 1, kBlock);
   GH_LAUNCH(ctx, "loc_flags", loc_flags_kernel, dim3(flag_blocks < kMaxFlagBlocks ? flag_blocks : kMaxFlagBlocks), block, 0, g.counts, g.cap,
             N, g.n_points, key, lo, hi, shared, flags, g.row_point, counters);
-  {
-    const int prof = gh_prof_begin(ctx, "loc_scan");
-    size_t tb = L.tmp_bytes;
-    const hipError_t e = rocprim::exclusive_scan(base + L.o_tmp, tb, flags, rank, (int32_t)0, n + 1, rocprim::plus<int32_t>(), ctx->stream);
-    gh_prof_end(ctx, prof);
-    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_pnp_gather_pairs_dev: scan");
-  }
+  GH_TRY(gh_scan_i32(ctx, "loc_scan", "gh_pnp_gather_pairs_dev: scan", tmp, L.tmp_bytes, flags, rank, n + 1));
 
-  EmitArgs a = {};
-  a.kps = g.kps;
-  a.n_frames = g.n_frames;
-  a.cap = g.cap;
-  a.N = N;
-  a.fx = g.fx;
-  a.fy = g.fy;
-  a.cx = g.cx;
-  a.cy = g.cy;
-  a.point_xyz = g.point_xyz;
-  a.row_point = g.row_point;
-  a.rank = rank;
-  a.counters = counters;
-  a.offsets = g.offsets;
-  a.xyz = g.xyz;
-  a.xy = g.xy;
-  a.corr_node = g.corr_node;
-  a.totals = g.totals;
+  const EmitArgs a = {g.kps, g.n_frames, g.cap, N, {g.fx, g.fy, g.cx, g.cy}, g.point_xyz, g.row_point,  // the inputs
+                      rank, counters,                                                               // scratch
+                      g.offsets, g.xyz, g.xy, g.corr_node, g.totals};
   GH_LAUNCH(ctx, "loc_emit", loc_emit_kernel, dim3(gh_div_up((long long)N + 1, kBlock)), block, 0, a);
   return GH_OK;
 }
@@ -377,7 +319,7 @@ extern "C" gh_status gh_pnp_gather_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps
   GatherLayout L = {};
   char* base = nullptr;
   if (n_frames * cap > 0) {
-    if (!gather_layout(ctx->stream, n_frames * cap, n_points, &L))
+    if (!gather_layout(ctx, n_frames * cap, n_points, &L))
       return gh_set_error(ctx, GH_ERR_HIP, "gh_pnp_gather_pairs_dev: rocPRIM size query failed");
     GH_TRY(gh_scratch(ctx, L.total, (void**)&base));
   }
@@ -407,7 +349,7 @@ extern "C" gh_status gh_localize_pairs_dev(gh_ctx* ctx, const gh_keypoint* kps_d
 
   // ONE scratch block (gh_scratch hands out one block per context): inlier bytes | n_inliers | the stage's own block
   GatherLayout L = {};
-  if (N > 0 && !gather_layout(ctx->stream, N, n_points, &L))
+  if (N > 0 && !gather_layout(ctx, N, n_points, &L))
     return gh_set_error(ctx, GH_ERR_HIP, "gh_localize_pairs_dev: rocPRIM size query failed");
   const size_t o_n_inliers = gh_round256((size_t)N), o_stage = o_n_inliers + gh_round256((size_t)n_frames * 4);
   const size_t stage = std::max(L.total, gh_ransac::pnp_batch_scratch_bytes(n_frames, N));

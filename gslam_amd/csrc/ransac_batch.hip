@@ -21,10 +21,12 @@
 // sampler (whose rejection loop does not end for n < s): it is "no model".  Row ranges are clamped to the arrays before
 // they address anything.
 #include "estimate_batch.h"
+#include "map_dev.h"
 
 namespace {
 
 using namespace gh_ransac;
+using gh_map::Pinhole;
 
 constexpr int kTileRows = 512;         // correspondences staged per tile: 512 x (3 + 3) doubles = 24 KB of LDS at the most
 constexpr int kParts = kHyp / 256;     // workgroups per problem in the scoring kernel
@@ -148,10 +150,7 @@ __global__ __launch_bounds__(256) void ransac_batch_finish_kernel(BatchArgs a) {
 // Pair p's correspondences: the query rows i < counts[pair_q[p]], ascending, with keep[i] (if given) and
 // 0 <= idx1[i] < counts[pair_t[p]].  Written to rows p * cap ... of src / dst (float -> double is exact) with the query row of
 // each in row_map; the pair's row of the inlier mask is cleared here.  NORMALISE (gh_two_view_pairs_dev): pinhole intrinsics
-// k turn the pixels into normalised coordinates, ((double)x - k.cx) / k.fx, in double.
-struct Pinhole {
-  double fx, fy, cx, cy;
-};
+// k turn the pixels into normalised coordinates in double (gh_map::normalised_xy, map_dev.h).
 template <bool NORMALISE>
 __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, const gh_keypoint* __restrict__ kps,
                                                                   const int32_t* __restrict__ counts,
@@ -183,10 +182,8 @@ __global__ __launch_bounds__(256) void ransac_pairs_gather_kernel(Pinhole k, con
       const gh_keypoint* kt = kps + (size_t)ft * cap + j;
       const size_t r = row0 + at;
       if (NORMALISE) {
-        src[2 * r] = ((double)kq->x - k.cx) / k.fx;
-        src[2 * r + 1] = ((double)kq->y - k.cy) / k.fy;
-        dst[2 * r] = ((double)kt->x - k.cx) / k.fx;
-        dst[2 * r + 1] = ((double)kt->y - k.cy) / k.fy;
+        gh_map::normalised_xy(*kq, k, src + 2 * r);
+        gh_map::normalised_xy(*kt, k, dst + 2 * r);
       } else {
         src[2 * r] = (double)kq->x;
         src[2 * r + 1] = (double)kq->y;

@@ -17,9 +17,8 @@
 //
 // CDNA4 mapping (this is the Jayanti-Tarjan / ECL-CC scheme; linking by index is what makes the root the minimum):
 //   * link_init     parent[n] = n;
-//   * link_union    one lane per (pair, query row), grid-stride; the gather rule of gh_ransac_pairs_dev decides whether the row is
-//                   an edge; find with path halving on both ends, hook the larger root under the smaller, retry from the new roots
-//                   when the compare-and-swap fails (the larger root strictly descends: the loop ends);
+//   * link_union    one lane per (pair, query row), grid-stride; gh_map::pair_edge (map_dev.h) decides whether the row is an edge,
+//                   uf_unite (track_uf.h) joins the two trees;
 //   * link_label    a launch of its own: key[n] = find(n) without any write for an existing node, the extra bin N otherwise.  The
 //                   labels do not depend on how far link_union compressed the paths;
 //   * sort          rocPRIM's stable radix sort of (key, node) pairs lists a component in ascending node id, so two nodes of one
@@ -31,30 +30,28 @@
 //                   neighbours with one label and one frame store the byte 1 to the label's flag (the same value from every writer);
 //   * link_flags    per node: observation? (low word) and, at the label itself, track? (high word) packed into one uint64, so that
 //                   ONE rocPRIM exclusive scan numbers the observations and the points; grid-stride over at most 1024 workgroups,
-//                   the CONFLICT and SHORT components counted in registers, then LDS, then one integer atomic per workgroup;
-//   * link_emit     writes every entry of every output: node_point, the observation of a track node at its rank, the padding past
-//                   n_obs, point_len at the labels and zeros past n_points, totals.
-// rocPRIM (one sort, one scan) is plumbing here as in csr_sort.hip; the work space comes from the context's scratch.
+//                   the CONFLICT and SHORT components (gh_map::component_verdict) counted in registers, then
+//                   gh_map::block_counts_add: LDS, one integer atomic per workgroup;
+//   * link_emit     writes every entry of every output: node_point, the observation of a track node at its rank (gh_map::emit_obs),
+//                   the padding past n_obs (pad_obs), point_len at the labels and zeros past n_points, totals.
+// The sort and the scan are dev_prims.h's; the work space comes from the context's scratch.
+#include <algorithm>
 #include <climits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "dev_prims.h"
 #include "track_uf.h"
 
 namespace {
 
 // the union-find, its labels and the run bounds (link_init / link_union / link_label / link_runs): track_uf.h, shared with
-// track_extend.hip
+// track_extend.hip; the edge rule, the verdict on a component, the observation writers and the counter tail: map_dev.h
 using namespace gh_uf;
-
-constexpr int kMaxFlagBlocks = 1024;
 
 struct LinkArgs {
   const gh_keypoint* kps;
   int cap, N;
   int min_views;
-  double fx, fy, cx, cy;
+  Pinhole pin;
   const int32_t* key;        // N: label, or N for a node that does not exist
   const int32_t* begin;      // N, by label: the component's range in the sorted list
   const int32_t* end;
@@ -62,10 +59,7 @@ struct LinkArgs {
   const uint64_t* rank;      // N + 1: exclusive scan of the flags; [N] = the totals
   const int32_t* counters;   // CONFLICT components, SHORT components of two nodes or more
   int32_t* node_point;
-  int32_t* obs_cam;
-  int32_t* obs_point;
-  double* obs_xy;
-  int32_t* obs_node;
+  ObsOut obs;
   int32_t* point_len;
   int32_t* totals;
 };
@@ -73,9 +67,6 @@ struct LinkArgs {
 __global__ __launch_bounds__(kBlock) void link_flags_kernel(const int32_t* __restrict__ key, const int32_t* __restrict__ begin,
                                                             const int32_t* __restrict__ end, const uint8_t* __restrict__ conflict, int N,
                                                             int min_views, uint64_t* __restrict__ flags, int32_t* __restrict__ counters) {
-  __shared__ int s_count[2];
-  if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
-  __syncthreads();
   int nc = 0, ns = 0;  // the same in every lane of a wave
   const long long step = (long long)gridDim.x * kBlock;
   for (long long base = (long long)blockIdx.x * kBlock; base <= N; base += step) {  // (entry N is the scan's room for the totals)
@@ -86,27 +77,21 @@ __global__ __launch_bounds__(kBlock) void link_flags_kernel(const int32_t* __res
       uint64_t f = 0;
       const int l = n < N ? key[n] : N;
       if (l != N) {
-        const int size = end[l] - begin[l];
-        const bool bad = conflict[l] != 0;
-        const bool track = !bad && size >= min_views;
+        const Component c = component_verdict(l, begin, end, conflict, min_views);
+        const bool track = c.verdict == kTrack;
         f = track ? 1u : 0u;
         if (n == l) {
           if (track) f |= 1ull << 32;
-          is_conflict = bad;
-          is_short = !bad && !track && size >= 2;
+          is_conflict = c.verdict == kConflict;
+          is_short = c.counted_short();
         }
       }
       flags[n] = f;
     }
-    nc += __popcll(__ballot(is_conflict));
-    ns += __popcll(__ballot(is_short));
+    nc += wave_count(is_conflict);
+    ns += wave_count(is_short);
   }
-  if ((threadIdx.x & 63) == 0) {
-    if (nc) atomicAdd(&s_count[0], nc);
-    if (ns) atomicAdd(&s_count[1], ns);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && s_count[threadIdx.x]) atomicAdd(counters + threadIdx.x, s_count[threadIdx.x]);
+  block_counts_add<2>({nc, ns}, counters);
 }
 
 __global__ __launch_bounds__(kBlock) void link_emit_kernel(LinkArgs a) {
@@ -121,48 +106,23 @@ __global__ __launch_bounds__(kBlock) void link_emit_kernel(LinkArgs a) {
     a.totals[2] = a.counters[0];
     a.totals[3] = a.counters[1];
   }
-  if (n >= n_obs) {  // the padding; the entries below n_obs are written by the nodes that own them
-    a.obs_cam[n] = -1;
-    a.obs_point[n] = -1;
-    a.obs_node[n] = -1;
-    a.obs_xy[2 * (size_t)n] = 0.0;
-    a.obs_xy[2 * (size_t)n + 1] = 0.0;
-  }
+  if (n >= n_obs) pad_obs(a.obs, n);
   if (n >= n_points && n < a.N / 2) a.point_len[n] = 0;
   const int l = a.key[n];
   int code = GH_LINK_NO_ROW;
   if (l != a.N) {
-    const int size = a.end[l] - a.begin[l];
-    if (a.conflict[l]) {
+    const Component c = component_verdict(l, a.begin, a.end, a.conflict, a.min_views);
+    if (c.verdict == kConflict) {
       code = GH_LINK_CONFLICT;
-    } else if (size < a.min_views) {
+    } else if (c.verdict == kShort) {
       code = GH_LINK_SHORT;
     } else {
       code = (int)(a.rank[l] >> 32);
-      const int k = (int)(uint32_t)a.rank[n];
-      const int f = n / a.cap;
-      const float x = a.kps[n].x, y = a.kps[n].y;
-      a.obs_cam[k] = f;
-      a.obs_point[k] = code;
-      a.obs_node[k] = n;
-      a.obs_xy[2 * (size_t)k] = ((double)x - a.cx) / a.fx;
-      a.obs_xy[2 * (size_t)k + 1] = ((double)y - a.cy) / a.fy;
-      if (n == l) a.point_len[code] = size;
+      emit_obs(a.obs, (int)(uint32_t)a.rank[n], n / a.cap, code, n, a.kps[n], a.pin);
+      if (n == l) a.point_len[code] = c.size;
     }
   }
   a.node_point[n] = code;
-}
-
-// temporary storage that serves both the sort of N pairs and the scan of N + 1 flags
-bool link_rocprim_bytes(hipStream_t stream, int N, size_t* bytes) {
-  uint64_t* null_u = nullptr;
-  int32_t* null_i = nullptr;
-  size_t scan = 0, sort = 0;
-  if (rocprim::exclusive_scan(nullptr, scan, null_u, null_u, (uint64_t)0, (size_t)N + 1, rocprim::plus<uint64_t>(), stream) != hipSuccess ||
-      rocprim::radix_sort_pairs(nullptr, sort, null_i, null_i, null_i, null_i, (size_t)N, 0, key_bits(N), stream) != hipSuccess)
-    return false;
-  *bytes = gh_round256(std::max(std::max(scan, sort), (size_t)1));
-  return true;
 }
 
 }  // namespace
@@ -187,29 +147,31 @@ extern "C" gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev,
     return GH_OK;
   }
 
-  // scratch: parent | key | sorted keys | item | list | conflict bytes, two counters (one memset) | flags | rank | rocPRIM storage.
-  // begin lives in parent's place (dead after link_label), end in item's (the sort's input, dead after the sort).
+  // The scratch block.  conflict and the two counters are neighbours: one memset clears both.  The rocPRIM storage serves the
+  // sort of N pairs and the scan of N + 1 flags.
   const size_t n = (size_t)N;
-  size_t tmp_bytes = 0;
-  if (!link_rocprim_bytes(ctx->stream, N, &tmp_bytes)) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: rocPRIM size query failed");
-  const size_t ints = gh_round256(n * 4);
-  const size_t o_key = ints, o_skey = 2 * ints, o_item = 3 * ints, o_list = 4 * ints, o_conflict = 5 * ints;
-  const size_t o_counters = o_conflict + gh_round256(n);
-  const size_t o_flags = o_counters + 256;
-  const size_t o_rank = o_flags + gh_round256((n + 1) * 8);
-  const size_t o_tmp = o_rank + gh_round256((n + 1) * 8);
+  const int bits = gh_key_bits(N);
+  const size_t sort_bytes = gh_sort_pairs_bytes(ctx, n, bits), scan_bytes = gh_scan_u64_bytes(ctx, n + 1);
+  if (!sort_bytes || !scan_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: rocPRIM size query failed");
+  const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+  gh_carve c;
+  const size_t o_parent = c.take(n * 4), o_key = c.take(n * 4), o_skey = c.take(n * 4), o_item = c.take(n * 4), o_list = c.take(n * 4);
+  const size_t o_conflict = c.take(n), o_counters = c.take(2 * sizeof(int32_t));
+  const size_t o_flags = c.take((n + 1) * 8), o_rank = c.take((n + 1) * 8), o_tmp = c.take(tmp_bytes);
   char* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_tmp + tmp_bytes, (void**)&base));
-  int32_t* parent = (int32_t*)base;
+  GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
+  int32_t* parent = (int32_t*)(base + o_parent);
   int32_t* key = (int32_t*)(base + o_key);
   int32_t* skey = (int32_t*)(base + o_skey);
   int32_t* item = (int32_t*)(base + o_item);
   int32_t* list = (int32_t*)(base + o_list);
-  int32_t *begin = parent, *end = item;
+  int32_t* begin = parent;  // (parent is dead after link_label)
+  int32_t* end = item;      // (the sort's input, dead after the sort)
   uint8_t* conflict = (uint8_t*)(base + o_conflict);
   int32_t* counters = (int32_t*)(base + o_counters);
   uint64_t* flags = (uint64_t*)(base + o_flags);
   uint64_t* rank = (uint64_t*)(base + o_rank);
+  void* tmp = base + o_tmp;
 
   const dim3 grid(gh_div_up(N, kBlock)), block(kBlock);
   GH_HIP(ctx, hipMemsetAsync(conflict, 0, o_flags - o_conflict, ctx->stream));
@@ -221,47 +183,16 @@ extern "C" gh_status gh_link_tracks_dev(gh_ctx* ctx, const gh_keypoint* kps_dev,
               counts_dev, n_frames, cap, pair_q_dev, pair_t_dev, rows, idx1_dev, inlier_dev, (const uint8_t*)nullptr, parent);
   }
   GH_LAUNCH(ctx, "link_label", link_label_kernel, grid, block, 0, counts_dev, cap, N, (const uint8_t*)nullptr, parent, key, item);
-  {
-    const int prof = gh_prof_begin(ctx, "link_sort");
-    size_t tb = tmp_bytes;
-    const hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tb, key, skey, item, list, n, 0, key_bits(N), ctx->stream);
-    gh_prof_end(ctx, prof);
-    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: sort");
-  }
+  GH_TRY(gh_sort_pairs_i32(ctx, "link_sort", "gh_link_tracks_dev: sort", tmp, tmp_bytes, key, skey, item, list, n, bits));
   GH_LAUNCH(ctx, "link_runs", link_runs_kernel, grid, block, 0, skey, list, cap, N, begin, end, conflict);
   const int flag_blocks = gh_div_up((long long)N + 1, kBlock);
   GH_LAUNCH(ctx, "link_flags", link_flags_kernel, dim3(flag_blocks < kMaxFlagBlocks ? flag_blocks : kMaxFlagBlocks), block, 0, key, begin,
             end, conflict, N, min_views, flags, counters);
-  {
-    const int prof = gh_prof_begin(ctx, "link_scan");
-    size_t tb = tmp_bytes;
-    const hipError_t e = rocprim::exclusive_scan(base + o_tmp, tb, flags, rank, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), ctx->stream);
-    gh_prof_end(ctx, prof);
-    if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_link_tracks_dev: scan");
-  }
+  GH_TRY(gh_scan_u64(ctx, "link_scan", "gh_link_tracks_dev: scan", tmp, tmp_bytes, flags, rank, n + 1));
 
-  LinkArgs a = {};
-  a.kps = kps_dev;
-  a.cap = cap;
-  a.N = N;
-  a.min_views = min_views;
-  a.fx = fx;
-  a.fy = fy;
-  a.cx = cx;
-  a.cy = cy;
-  a.key = key;
-  a.begin = begin;
-  a.end = end;
-  a.conflict = conflict;
-  a.rank = rank;
-  a.counters = counters;
-  a.node_point = node_point_dev;
-  a.obs_cam = obs_cam_dev;
-  a.obs_point = obs_point_dev;
-  a.obs_xy = obs_xy_dev;
-  a.obs_node = obs_node_dev;
-  a.point_len = point_len_dev;
-  a.totals = totals_dev;
+  const LinkArgs a = {kps_dev, cap, N, min_views, {fx, fy, cx, cy},   // the inputs
+                      key, begin, end, conflict, rank, counters,      // scratch
+                      node_point_dev, {obs_cam_dev, obs_point_dev, obs_xy_dev, obs_node_dev}, point_len_dev, totals_dev};
   GH_LAUNCH(ctx, "link_emit", link_emit_kernel, grid, block, 0, a);
   return GH_OK;
 }

@@ -18,14 +18,15 @@
 // holders of one group come in ascending node id and those of one frame are neighbours; a position looks at its right
 // neighbour and stores the byte 1 to conflict[label].  mrg_points has one lane and one writer per point and reads only bytes that
 // earlier launches completed.  point_len and the totals are integer atomic adds on words the call zeroed -- commutative and
-// exact -- after a reduction inside the wave (mrg_add_runs) or the workgroup (ballot, LDS).  No float atomic anywhere.
+// exact -- after a reduction inside the wave (gh_map::add_runs) or the workgroup (gh_map::block_counts_add).  No float atomic
+// anywhere.
 // mrg_emit has one writer per entry and reads its input entry before it writes the same index, which is what makes
 // node_point_dev == node_point_in_dev (and the same for obs_point) safe; every earlier launch that read node_point_in has
 // completed by then (one stream).
 //
-// CDNA4 mapping (the skeleton of track_extend.hip):
+// CDNA4 mapping (the shared pieces are gh_map's, map_dev.h, and the union-find's, track_uf.h):
 //   * mrg_init    one lane per element: parent[g] = g; the lanes of the nodes also write elem[n];
-//   * mrg_union   one lane per (pair, query row), grid-stride; the edge rule of link_union, the ends taken through elem[];
+//   * mrg_union   one lane per (pair, query row), grid-stride; pair_edge, the ends taken through elem[], uf_unite;
 //   * mrg_label   one lane per point: root[p] = find(p) without any write to parent[]; root != p marks the root's group byte and,
 //                 with the gate on, its far byte when the point fails the gate against the root (the root itself is at
 //                 distance 0 of itself unless a coordinate is not finite, and then every other point of the group fails);
@@ -33,14 +34,11 @@
 //   * sort        rocPRIM's stable radix sort of (key, node) over the bits of n_points + 1 values;
 //   * mrg_runs    over that list: neighbours with one label and one frame -> conflict[label] = 1;
 //   * mrg_points  one lane per point: remap, state and select, and five of the totals;
-//   * mrg_emit    one lane per node: node_point, obs_point, point_len (mrg_add_runs) and the changed total.
-// Without an edge (npairs == 0 or cap == 0) nothing can be in a group: union, key, sort and runs are skipped.  One context
-// scratch block: parent | elem | root | key | item | sorted keys | list | group, conflict and far bytes (one memset) | rocPRIM
-// storage.
+//   * mrg_emit    one lane per node: node_point, obs_point, point_len (add_runs) and the changed total.
+// Without an edge (npairs == 0 or cap == 0) nothing can be in a group: union, key, sort and runs are skipped.
 #include <climits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "dev_prims.h"
 #include "track_uf.h"
 
 namespace {
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void mrg_init_kernel(const int32_t* __restr
   const int n = (int)(g - n_points);
   const int f = n / cap, i = n - f * cap;
   int e = kNoElem;
-  if (i < link_count(counts, f, cap)) {
+  if (i < row_count(counts, f, cap)) {
     const int v = node_point_in[n];
     if (v >= 0 && v < n_points) {
       if (!status || status[v] == GH_TRACK_OK) e = v;  // HOLDER
@@ -71,35 +69,20 @@ __global__ __launch_bounds__(kBlock) void mrg_init_kernel(const int32_t* __restr
   elem[n] = e;
 }
 
-// The loop ends by the argument of link_union_kernel: a failed compare-and-swap means that parent[hi] was lowered by somebody
-// else (THE INVARIANT: nothing ever raises it), so the root found from `old` is strictly smaller than hi, and the larger of the
-// two roots strictly descends from one round to the next; it is bounded below by 0.  No lane waits for another lane's store.
+// (the loop inside uf_unite ends: the argument is stated there, track_uf.h)
 __global__ __launch_bounds__(kBlock) void mrg_union_kernel(const int32_t* __restrict__ counts, int n_frames, int cap,
                                                            const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_t,
                                                            long long rows, const int32_t* __restrict__ idx1,
                                                            const uint8_t* __restrict__ inlier, const int32_t* __restrict__ elem,
                                                            int32_t* parent) {
+  const PairRows e = {counts, n_frames, cap, pair_q, pair_t, idx1, inlier};
   const long long step = (long long)gridDim.x * kBlock;
   for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += step) {
-    const int p = (int)(r / cap), i = (int)(r - (long long)p * cap);
-    const int fq = pair_q[p], ft = pair_t[p];
-    if (fq < 0 || fq >= n_frames || ft < 0 || ft >= n_frames || fq == ft) continue;
-    if (i >= link_count(counts, fq, cap)) continue;
-    if (inlier && inlier[r] == 0) continue;
-    const int j = idx1[r];
-    if (j < 0 || j >= link_count(counts, ft, cap)) continue;
-    const int u = elem[fq * cap + i], v = elem[ft * cap + j];
+    int nu, nv;
+    if (!pair_edge(e, r, &nu, &nv)) continue;
+    const int u = elem[nu], v = elem[nv];
     if (u < 0 || v < 0 || u == v) continue;  // an OUT end; or both ends hold one point: nearly every edge of a healthy map
-    const int pu = link_load(parent, u), pv = link_load(parent, v);
-    if (pu == pv) continue;  // one tree already
-    int a = link_find_halve(parent, u, pu), b = link_find_halve(parent, v, pv);
-    while (a != b) {
-      const int hi = a > b ? a : b, lo = a > b ? b : a;
-      const int old = atomicCAS(parent + hi, hi, lo);
-      if (old == hi) break;
-      a = link_find_halve(parent, old, link_load(parent, old));  // < hi
-      b = link_find_halve(parent, lo, link_load(parent, lo));
-    }
+    uf_unite(parent, u, v);
   }
 }
 
@@ -156,9 +139,6 @@ __global__ __launch_bounds__(kBlock) void mrg_points_kernel(const int32_t* __res
                                                             const uint8_t* __restrict__ conflict, const uint8_t* __restrict__ far,
                                                             int n_points, int32_t* __restrict__ remap, uint8_t* __restrict__ state,
                                                             uint8_t* __restrict__ select, int32_t* totals) {
-  __shared__ int s_count[5];
-  if (threadIdx.x < 5) s_count[threadIdx.x] = 0;
-  __syncthreads();
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   bool merged = false, absorbed = false, is_conflict = false, is_far = false, apart = false;
   if (g < n_points) {
@@ -177,32 +157,8 @@ __global__ __launch_bounds__(kBlock) void mrg_points_kernel(const int32_t* __res
     state[p] = s;
     select[p] = merged ? 1 : 0;
   }
-  const int n0 = __popcll(__ballot(merged)), n1 = __popcll(__ballot(absorbed)), n2 = __popcll(__ballot(is_conflict));
-  const int n3 = __popcll(__ballot(is_far)), n4 = __popcll(__ballot(apart));
-  if ((threadIdx.x & 63) == 0) {
-    if (n0) atomicAdd(&s_count[0], n0);
-    if (n1) atomicAdd(&s_count[1], n1);
-    if (n2) atomicAdd(&s_count[2], n2);
-    if (n3) atomicAdd(&s_count[3], n3);
-    if (n4) atomicAdd(&s_count[4], n4);
-  }
-  __syncthreads();
-  if (threadIdx.x < 5 && s_count[threadIdx.x]) atomicAdd(totals + (threadIdx.x < 4 ? threadIdx.x : 5), s_count[threadIdx.x]);
-}
-
-// words[key] += 1 for every lane that is `on`; neighbouring lanes with one key fold their ones into the first of them (a ballot
-// and a bit scan, as baw_add_runs of ba_window.hip).  Every lane of the wave must call it.
-__device__ __forceinline__ void mrg_add_runs(int32_t* words, int key, bool on) {
-  const int lane = threadIdx.x & 63;
-  const int prev_key = __shfl_up(key, 1);
-  const unsigned long long on_mask = __ballot(on);
-  const bool prev_on = lane > 0 && ((on_mask >> (lane - 1)) & 1ull) != 0;
-  const bool head = on && (!prev_on || prev_key != key);
-  const unsigned long long stops = __ballot(head || !on);  // the lanes at which a run cannot go on
-  if (head) {
-    const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
-    atomicAdd(words + key, above ? __ffsll(above) : 64 - lane);
-  }
+  block_counts_add<5>({wave_count(merged), wave_count(absorbed), wave_count(is_conflict), wave_count(is_far), wave_count(apart)},
+                      [totals](int k) { return totals + (k < 4 ? k : 5); });
 }
 
 // node_point / obs_point may be their inputs: no __restrict__ on the four, and each lane reads entry n before it writes entry n
@@ -210,9 +166,6 @@ __global__ __launch_bounds__(kBlock) void mrg_emit_kernel(const int32_t* __restr
                                                           const int32_t* __restrict__ remap, const int32_t* node_point_in,
                                                           const int32_t* obs_point_in, int32_t* node_point, int32_t* obs_point,
                                                           int32_t* point_len, int32_t* totals) {
-  __shared__ int s_changed;
-  if (threadIdx.x == 0) s_changed = 0;
-  __syncthreads();
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   bool counted = false, changed = false;
   int out = 0;
@@ -227,14 +180,11 @@ __global__ __launch_bounds__(kBlock) void mrg_emit_kernel(const int32_t* __restr
       obs_point[n] = (o >= 0 && o < n_points) ? remap[o] : o;
     }
     const int f = n / cap, i = n - f * cap;
-    counted = id && i < link_count(counts, f, cap);
+    counted = id && i < row_count(counts, f, cap);
     changed = counted && out != v;
   }
-  mrg_add_runs(point_len, out, counted);
-  const int nc = __popcll(__ballot(changed));
-  if ((threadIdx.x & 63) == 0 && nc) atomicAdd(&s_changed, nc);
-  __syncthreads();
-  if (threadIdx.x == 0 && s_changed) atomicAdd(totals + 4, s_changed);
+  add_runs(point_len, out, counted);
+  block_counts_add<1>({wave_count(changed)}, totals + 4);
 }
 
 }  // namespace
@@ -263,21 +213,18 @@ extern "C" gh_status gh_merge_points_dev(gh_ctx* ctx, const int32_t* counts_dev,
   if (n_points > 0) GH_HIP(ctx, hipMemsetAsync(point_len_dev, 0, (size_t)n_points * sizeof(int32_t), ctx->stream));
   if (N == 0 && n_points == 0) return GH_OK;
 
+  // The scratch block.  group, conflict and far are neighbours: one memset clears them.
   const size_t n = (size_t)N, np = (size_t)n_points;
-  size_t tmp_bytes = 0;
-  if (edges) {
-    int32_t* null_i = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, null_i, null_i, null_i, null_i, n, 0, key_bits(n_points), ctx->stream) != hipSuccess)
-      return gh_set_error(ctx, GH_ERR_HIP, "gh_merge_points_dev: rocPRIM size query failed");
-    tmp_bytes = gh_round256(std::max(tmp_bytes, (size_t)1));
-  }
-  const size_t ints = gh_round256(n * 4), pints = gh_round256(np * 4), pbytes = gh_round256(np);
-  const size_t o_elem = gh_round256((np + n) * 4), o_root = o_elem + ints, o_key = o_root + pints, o_item = o_key + ints;
-  const size_t o_skey = o_item + ints, o_list = o_skey + ints, o_group = o_list + ints, o_conflict = o_group + pbytes;
-  const size_t o_far = o_conflict + pbytes, o_tmp = o_far + pbytes;
+  const int bits = gh_key_bits(n_points);
+  const size_t tmp_bytes = edges ? gh_sort_pairs_bytes(ctx, n, bits) : 0;
+  if (edges && !tmp_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_merge_points_dev: rocPRIM size query failed");
+  gh_carve c;
+  const size_t o_parent = c.take((np + n) * 4), o_elem = c.take(n * 4), o_root = c.take(np * 4), o_key = c.take(n * 4);
+  const size_t o_item = c.take(n * 4), o_skey = c.take(n * 4), o_list = c.take(n * 4);
+  const size_t o_group = c.take(np), o_conflict = c.take(np), o_far = c.take(np), o_tmp = c.take(tmp_bytes);
   char* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_tmp + tmp_bytes, (void**)&base));
-  int32_t* parent = (int32_t*)base;
+  GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
+  int32_t* parent = (int32_t*)(base + o_parent);
   int32_t* elem = (int32_t*)(base + o_elem);
   int32_t* root = (int32_t*)(base + o_root);
   int32_t* key = (int32_t*)(base + o_key);
@@ -303,13 +250,7 @@ extern "C" gh_status gh_merge_points_dev(gh_ctx* ctx, const int32_t* counts_dev,
   if (edges) {
     GH_LAUNCH(ctx, "mrg_key", mrg_key_kernel, node_grid, block, 0, (const int32_t*)elem, (const int32_t*)root, (const uint8_t*)group, N,
               n_points, key, item);
-    {
-      const int prof = gh_prof_begin(ctx, "mrg_sort");
-      size_t tb = tmp_bytes;
-      const hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tb, key, skey, item, list, n, 0, key_bits(n_points), ctx->stream);
-      gh_prof_end(ctx, prof);
-      if (e != hipSuccess) return gh_set_error(ctx, GH_ERR_HIP, "gh_merge_points_dev: sort");
-    }
+    GH_TRY(gh_sort_pairs_i32(ctx, "mrg_sort", "gh_merge_points_dev: sort", base + o_tmp, tmp_bytes, key, skey, item, list, n, bits));
     GH_LAUNCH(ctx, "mrg_runs", mrg_runs_kernel, node_grid, block, 0, (const int32_t*)skey, (const int32_t*)list, cap, N, n_points,
               conflict);
   }

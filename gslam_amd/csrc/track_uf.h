@@ -8,22 +8,19 @@
 // bytes are written by an earlier launch and are constant while these kernels run.  link_union tests both ends' byte BEFORE it
 // touches parent[], so a node outside the subset stays the root of itself and is never read through; link_label gives it the
 // extra bin N.  With live == NULL every existing node takes part (gh_link_tracks_dev).
+//
+// The edge rule, the clamp of a frame's row count and kBlock are gh_map's (map_dev.h); gh_merge_points_dev (track_merge.hip) runs
+// uf_unite on its own elements.
 #pragma once
-#include <algorithm>
-
-#include "common.h"
+#include "map_dev.h"
 
 namespace gh_uf {
 namespace {  // (internal linkage: every translation unit that includes this header gets its own kernels)
 
-constexpr int kBlock = 256;
+using namespace gh_map;
+
 constexpr int kMaxUnionBlocks = 1 << 16;  // grid-stride beyond this many workgroups
 constexpr uint8_t kUfLive = 1;
-
-__device__ __forceinline__ int link_count(const int32_t* __restrict__ counts, int f, int cap) {
-  const int c = counts[f];
-  return c < 0 ? 0 : (c > cap ? cap : c);
-}
 
 __device__ __forceinline__ int link_load(const int32_t* parent, int x) {
   return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -50,6 +47,23 @@ __device__ __forceinline__ int link_find(const int32_t* parent, int x) {
   return x;
 }
 
+// Joins the trees of u and v: find with path halving on both ends, hook the larger root under the smaller, retry from the new
+// roots when the compare-and-swap fails.  The loop ends: a failed compare-and-swap means that parent[hi] was lowered by somebody
+// else (THE INVARIANT: nothing ever raises it), so the root found from `old` is strictly smaller than hi, and the larger of the
+// two roots strictly descends from one round to the next; it is bounded below by 0.  No lane waits for another lane's store.
+__device__ __forceinline__ void uf_unite(int32_t* parent, int u, int v) {
+  const int pu = link_load(parent, u), pv = link_load(parent, v);
+  if (pu == pv) return;  // one tree already: in a flat component this spares the root's hot word two reads per edge
+  int a = link_find_halve(parent, u, pu), b = link_find_halve(parent, v, pv);
+  while (a != b) {
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    const int old = atomicCAS(parent + hi, hi, lo);
+    if (old == hi) break;
+    a = link_find_halve(parent, old, link_load(parent, old));  // < hi
+    b = link_find_halve(parent, lo, link_load(parent, lo));
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void link_init_kernel(int32_t* __restrict__ parent, int N) {
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (g < N) parent[g] = (int32_t)g;
@@ -60,27 +74,13 @@ __global__ __launch_bounds__(kBlock) void link_union_kernel(const int32_t* __res
                                                             long long rows, const int32_t* __restrict__ idx1,
                                                             const uint8_t* __restrict__ inlier, const uint8_t* __restrict__ live,
                                                             int32_t* parent) {
+  const PairRows e = {counts, n_frames, cap, pair_q, pair_t, idx1, inlier};
   const long long step = (long long)gridDim.x * kBlock;
   for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += step) {
-    const int p = (int)(r / cap), i = (int)(r - (long long)p * cap);
-    const int fq = pair_q[p], ft = pair_t[p];
-    if (fq < 0 || fq >= n_frames || ft < 0 || ft >= n_frames || fq == ft) continue;
-    if (i >= link_count(counts, fq, cap)) continue;
-    if (inlier && inlier[r] == 0) continue;
-    const int j = idx1[r];
-    if (j < 0 || j >= link_count(counts, ft, cap)) continue;
-    const int u = fq * cap + i, v = ft * cap + j;
+    int u, v;
+    if (!pair_edge(e, r, &u, &v)) continue;
     if (live && (live[u] != kUfLive || live[v] != kUfLive)) continue;
-    const int pu = link_load(parent, u), pv = link_load(parent, v);
-    if (pu == pv) continue;  // one tree already: in a flat component this spares the root's hot word two reads per edge
-    int a = link_find_halve(parent, u, pu), b = link_find_halve(parent, v, pv);
-    while (a != b) {
-      const int hi = a > b ? a : b, lo = a > b ? b : a;
-      const int old = atomicCAS(parent + hi, hi, lo);
-      if (old == hi) break;
-      a = link_find_halve(parent, old, link_load(parent, old));  // < hi
-      b = link_find_halve(parent, lo, link_load(parent, lo));
-    }
+    uf_unite(parent, u, v);
   }
 }
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void link_label_kernel(const int32_t* __res
   if (g >= N) return;
   const int n = (int)g;
   const int f = n / cap, i = n - f * cap;
-  const bool in = live ? live[n] == kUfLive : i < link_count(counts, f, cap);
+  const bool in = live ? live[n] == kUfLive : i < row_count(counts, f, cap);
   key[n] = in ? link_find(parent, n) : N;
   item[n] = n;
 }
@@ -108,12 +108,6 @@ __global__ __launch_bounds__(kBlock) void link_runs_kernel(const int32_t* __rest
   if (prev != l) begin[l] = s;
   if (next != l) end[l] = s + 1;
   else if (list[s] / cap == list[s + 1] / cap) conflict[l] = 1;
-}
-
-inline int key_bits(int max_key) {  // the keys are 0 .. max_key
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) <= max_key) ++bits;
-  return bits;
 }
 
 }  // namespace

@@ -163,3 +163,16 @@ def test_library_exports_both_entries_and_they_reject_a_null_context():
     gather = [None, None, None, 1, 1, None, None, 0, None, None, None, 0, None, None, one, one, one, one]
     assert hip.lib.gh_pnp_gather_pairs_dev(*gather, *([None] * 6)) == 1  # GH_ERR_ARG
     assert hip.lib.gh_localize_pairs_dev(*gather, one, C.c_uint64(1), 63, None, 0, one, *([None] * 12)) == 1
+
+
+def test_wide_case_reaches_every_verdict_past_the_second_trip_of_the_flags_kernel():
+    """tests/map_wide_cases.py: N + 1 > 1024 * 256; correspondences, AMBIGUOUS and SHARED nodes -- which loc_flags counts -- past
+    node 262144."""
+    import map_wide_cases as wide
+    c = wide.localize_case()
+    assert c["n_frames"] * c["cap"] + 1 > wide.SECOND_TRIP
+    e = wide.localize_restated()
+    high = e["row_point"][wide.SECOND_TRIP + 1:]
+    assert high.count(lr.AMBIGUOUS) == 3 and high.count(lr.SHARED) == 6 and sum(v >= 0 for v in high) == 3 * 17 - 1  # (node 262144 itself is left out)
+    assert e["totals"] == [4 * 17, 4, 8, 4]
+    assert wide.localize_restated(False, False)["totals"] == [4 * 17, 8, 8, 4]

@@ -1,5 +1,6 @@
 """GPU parity of gh_pnp_gather_pairs_dev with the plain-Python restatement tests/localize_restate.py, byte for byte, on the
-inputs of tests/localize_cases.py (tests/test_localize_cpu.py shows what they reach): the census, a hub voted on by 256 pairs,
+inputs of tests/localize_cases.py (tests/test_localize_cpu.py shows what they reach): the census (and with it the input of
+tests/map_wide_cases.py, more than 1024 * 256 nodes), a hub voted on by 256 pairs,
 a random map in three pair orders; the argument contract; then gh_localize_pairs_dev on a synthetic scene, held bit for bit
 to the composition of the public pieces and to the planted truth.  Every output buffer goes in with every byte 0xA5 and 16
 bytes longer than its capacity, so that an entry left out and a write past the end both show."""
@@ -10,6 +11,7 @@ import pytest
 
 import localize_cases as lc
 import localize_restate as lr
+import map_wide_cases as wide
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +119,8 @@ def _assert_same(got, e, c):
 def test_census_matches_the_restatement_byte_for_byte(ctx, use_keep, use_status):
     for c in lc.census():  # per case first: a failure names the case
         _assert_same(_run(ctx, c, use_keep, use_status), lc.restate(c, use_keep, use_status), c)
+    c = wide.localize_case()  # N + 1 > 1024 * 256: the second trip through the loop of loc_flags, with verdicts to count in it
+    _assert_same(_run(ctx, c, use_keep, use_status), wide.localize_restated(use_keep, use_status), c)
 
 
 def test_hub_voted_on_by_256_pairs(ctx):

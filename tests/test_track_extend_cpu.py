@@ -188,3 +188,21 @@ def test_library_exports_the_entry_and_rejects_a_null_context():
     dummy = C.c_void_p(256)  # (never dereferenced: the context is checked first)
     args = [None, dummy, dummy, 1, 1, None, None, 0, None, None, None, 0, None, None] + [C.c_double(v) for v in lc.INTRINSICS] + [2] + [dummy] * 9
     assert fn(*args) == 1  # GH_ERR_ARG
+
+
+def test_wide_case_reaches_every_verdict_past_the_second_trip_of_the_flags_kernel():
+    """tests/map_wide_cases.py: N + 1 > 1024 * 256; an ADOPTED and a REJECTED claimant, and the labels of a new track, of a counted
+    SHORT component and of a CONFLICT -- where ext_flags counts them -- all lie past node 262144; so do observations."""
+    import map_wide_cases as wide
+    c = wide.extend_case()
+    assert c["n_frames"] * c["cap"] + 1 > wide.SECOND_TRIP and c["min_views"] == 3
+    e = wide.extend_restated()
+    n_obs, n_total, n_adopted, n_rejected, n_conflict, n_short = e["totals"]
+    assert n_total > c["n_points"] and n_adopted == 2 and n_rejected == 5 and n_conflict == 2 and n_short == 16
+    assert any(n > wide.SECOND_TRIP for n in e["adopted"]) and sum(n > wide.SECOND_TRIP for n in e["rejected"]) == 3
+    high = {label: nodes for label, nodes in e["components"].items() if label >= wide.SECOND_TRIP}
+    codes = {label: e["node_point"][label] for label in high}
+    assert any(v >= c["n_points"] for v in codes.values()) and any(v == er.CONFLICT for v in codes.values())
+    assert any(v == er.SHORT and len(high[label]) >= 2 for label, v in codes.items())
+    assert max(e["obs_node"][:n_obs]) > wide.SECOND_TRIP
+    assert wide.extend_restated(True, True, True, 2)["totals"][5] == 0

@@ -1,5 +1,6 @@
 """GPU parity of gh_extend_tracks_dev with the plain-Python restatement tests/track_extend_restate.py, byte for byte, on the
-inputs of tests/track_extend_cases.py (tests/test_track_extend_cpu.py shows what they reach): the census, a point adopted from
+inputs of tests/track_extend_cases.py (tests/test_track_extend_cpu.py shows what they reach): the census (and with it the input
+of tests/map_wide_cases.py, more than 1024 * 256 nodes), a point adopted from
 256 frames, a new track through 64 frames and a random growing map in three pair orders, a random soup at N = 512 and N = 513;
 the device against gh_link_tracks_dev where the contract says they agree; the argument contract; then the call in its place:
 link -> triangulate -> localize -> extend -> triangulate the new points, without a read-back in between.  Every output buffer
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import localize_cases as loc
+import map_wide_cases as wide
 import track_extend_cases as ec
 import track_extend_restate as er
 import track_link_cases as lc
@@ -117,6 +119,8 @@ VARIANTS = [(True, True, True), (False, True, True), (True, True, False), (True,
 def test_census_matches_the_restatement_byte_for_byte(ctx, use_inlier, use_map, use_claims, min_views):
     c = ec.census()
     _assert_same(_run(ctx, c, use_inlier, use_map, use_claims, min_views), ec.restate(c, use_inlier, use_map, use_claims, min_views), c)
+    c = wide.extend_case()  # N + 1 > 1024 * 256: the second trip through the loop of ext_flags, with verdicts to count in it
+    _assert_same(_run(ctx, c, use_inlier, use_map, use_claims, min_views), wide.extend_restated(use_inlier, use_map, use_claims, min_views), c)
 
 
 @pytest.mark.parametrize("mapped_in_frame_128", [False, True])

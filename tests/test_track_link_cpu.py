@@ -102,3 +102,22 @@ def test_properties_of_every_output():
             assert sorted(frames) == list(range(n_points))
             for p, fs in frames.items():  # every track: pairwise distinct frames, at least min_views of them
                 assert len(set(fs)) == len(fs) == e["point_len"][p] >= mv, (c["name"], p)
+
+
+def test_wide_case_reaches_every_verdict_past_the_second_trip_of_the_flags_kernel():
+    """tests/map_wide_cases.py: N + 1 > 1024 * 256, and a track, a counted SHORT component and a CONFLICT each have their label --
+    where link_flags counts them -- past node 262144; so have observations."""
+    import map_wide_cases as wide
+    c = wide.link_case()
+    assert c["n_frames"] * c["cap"] + 1 > wide.SECOND_TRIP and set(np.flatnonzero(c["counts"])) == set(wide.LOW + wide.HIGH)
+    for min_views in (2, 3):
+        e = wide.link_restated(True, min_views)
+        assert e["totals"][1] >= 2 and e["totals"][2] == 2 and e["totals"][3] == (16 if min_views == 3 else 0)
+        high = {label: nodes for label, nodes in e["components"].items() if label >= wide.SECOND_TRIP}
+        codes = {label: e["node_point"][label] for label in high}
+        assert any(v >= 0 for v in codes.values()) and any(v == lr.CONFLICT for v in codes.values())
+        assert any(v == lr.SHORT and len(high[label]) >= 2 for label, v in codes.items()) == (min_views == 3)
+        n_obs = e["totals"][0]
+        assert max(e["obs_node"][:n_obs]) > wide.SECOND_TRIP
+    # the inlier byte 0 keeps row 12 of either group at two views
+    assert wide.link_restated(False, 3)["totals"][3] == 14

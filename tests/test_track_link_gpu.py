@@ -1,5 +1,6 @@
 """GPU parity of gh_link_tracks_dev with the plain-Python restatement tests/track_link_restate.py, byte for byte, on the inputs
-of tests/track_link_cases.py (tests/test_track_link_cpu.py shows what they reach): the census, a chain longer than a
+of tests/track_link_cases.py (tests/test_track_link_cpu.py shows what they reach): the census (and with it the input of
+tests/map_wide_cases.py, more than 1024 * 256 nodes), a chain longer than a
 workgroup in three pair orders, a hub contended by 256 unions, random windows with wrong rows; the argument contract; then
 the call in its place, between exact pair matches and gh_triangulate_tracks_dev.  Output buffers go in dirty (-5 for ints,
 7.0 for doubles) and four entries longer than their capacity, so that a write past the end shows too."""
@@ -8,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import map_wide_cases as wide
 import track_link_cases as lc
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +88,8 @@ def _assert_same(got, e, name):
 def test_census_matches_the_restatement_byte_for_byte(ctx, use_inlier, min_views):
     for c in lc.census():  # per case first: a failure names the case
         _assert_same(_run(ctx, c, use_inlier, min_views), lc.restate(c, use_inlier, min_views), c["name"])
+    c = wide.link_case()  # N + 1 > 1024 * 256: the second trip through the loop of link_flags, with verdicts to count in it
+    _assert_same(_run(ctx, c, use_inlier, min_views), wide.link_restated(use_inlier, min_views), c["name"])
 
 
 def test_long_chain_in_any_pair_order_gives_the_same_bytes(ctx):
