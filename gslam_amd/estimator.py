@@ -11,7 +11,8 @@ gather_map_matches (gh_pnp_gather_pairs_dev) reads the pair matches of new frame
 takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call and says which keypoint rows were inliers;
 extend_tracks (gh_extend_tracks_dev) adds those rows to the tracks of the map and links the other rows of the new frames into
 new tracks numbered after the map's, so that the map grows batch after batch without a read-back; merge_points
-(gh_merge_points_dev) renames the points that the matches show to be one to the oldest id of their group."""
+(gh_merge_points_dev) renames the points that the matches show to be one to the oldest id of their group; describe_points
+(gh_describe_points_dev) gives every map point its representative descriptor, mean viewing direction and distance range."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +28,7 @@ LINK_SHORT, LINK_CONFLICT, LINK_NO_ROW = -1, -2, -3  # GH_LINK_*: what node_poin
 EXT_REJECTED = -4  # GH_EXT_REJECTED: beside LINK_*, what node_point of extend_tracks holds at a claimant that was turned down
 # GH_MERGE_*: the state byte per point of merge_points
 MERGE_NONE, MERGE_SURVIVOR, MERGE_ABSORBED, MERGE_CONFLICT, MERGE_FAR = 0, 1, 2, 3, 4
+PDESC_OK, PDESC_EMPTY, PDESC_NOT_OK, PDESC_SKIPPED = 0, 1, 2, 3  # GH_PDESC_*: the state byte per point of describe_points
 # GH_LOC_*: what row_point of gather_map_matches / localize_pairs holds where there is no point id
 LOC_NO_POINT, LOC_AMBIGUOUS, LOC_NO_ROW, LOC_SHARED = -1, -2, -3, -4
 RANSAC, LMEDS, NOSAMPLE = 0, 1, 2  # GSLAM::EstimatorMethod sampling flags (Estimator.h:86-89) as gh_ransac_estimate_ex takes them
@@ -509,6 +511,65 @@ def merge_points(ctx: hip.Context, counts, cap, pair_q, pair_t, idx1, inlier, no
     ctx.check(hip.lib.gh_merge_points_dev(ctx.h, p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier), p(node_point),
                                           n_points, q(point_status), q(point_xyz), C.c_double(float(max_dist)), 1 if bridge else 0,
                                           q(obs_point), *(q(out[k]) for k in out)))
+    return out
+
+
+def point_desc_default_params():
+    """gh_point_desc_default_params -> hip.PointDescParams (scale_factor, n_levels, max_views)."""
+    p = hip.PointDescParams()
+    hip.lib.gh_point_desc_default_params(C.byref(p))
+    return p
+
+
+DESCRIBE_OUTPUTS = ("point_state", "point_desc", "point_obs", "point_views", "point_normal", "point_dist", "totals")
+
+
+def describe_points(ctx: hip.Context, kps, desc, counts, cam_pose, obs_cam, obs_point, obs_node, n_points, point_xyz, obs_use=None,
+                    point_status=None, point_select=None, params=None, out=None):
+    """gh_describe_points_dev, the call after triangulate_tracks (and after extend_tracks / merge_points, for the points that
+    changed): every map point gets the descriptor of the observation closest to its other observations, the mean direction it
+    was seen from and the distance range its reference keypoint's octave predicts -- what a search by projection needs.
+    kps: F x cap x 7 float32 view of the KeyPoint records, desc: F x cap x 32 uint8, counts: F int32, cam_pose: F x 7 float64
+    T_wc; obs_cam / obs_point / obs_node: n_obs int32 as link_tracks / extend_tracks / merge_points leave them; n_points: the
+    capacity of the point arrays; point_xyz: n_points x 3 float64; obs_use: n_obs uint8 (obs_good of triangulate_tracks) or
+    None; point_status: n_points int32 (only TRACK_OK points are described) or None; point_select: n_points uint8 or None (all
+    points) -- all cuda; params: hip.PointDescParams or None (the defaults); out: the dict an earlier call returned, to be
+    refreshed where point_select says so (the other points keep what they hold), or None for zeroed arrays.  -> dict of device
+    tensors: point_state n_points uint8 (PDESC_*), point_desc n_points x 32 uint8, point_obs n_points x 2 int32 (the chosen
+    observation, the reference observation), point_views n_points int32, point_normal n_points x 3 and point_dist n_points x 2
+    float64 (min, max), totals 4 int32 (OK, EMPTY, NOT_OK points, OK points with more than max_views observations); nothing is
+    synchronised and nothing is read back."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    F, cap = kps.shape[0], kps.shape[1]
+    N, dev, n_points = F * cap, kps.device, int(n_points)
+    assert desc.is_cuda and desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() == 32 * N
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, obs_cam, obs_point, obs_node))
+    n_obs = obs_cam.numel()
+    assert counts.numel() == F and obs_point.numel() == n_obs and obs_node.numel() == n_obs and n_points >= 0
+    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() == 7 * F
+    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
+    assert obs_use is None or (obs_use.is_cuda and obs_use.dtype == torch.uint8 and obs_use.is_contiguous() and obs_use.numel() == n_obs)
+    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
+                                    point_status.numel() == n_points)
+    assert point_select is None or (point_select.is_cuda and point_select.dtype == torch.uint8 and point_select.is_contiguous() and
+                                    point_select.numel() == n_points)
+    shapes = {"point_state": ((n_points,), torch.uint8), "point_desc": ((n_points, 32), torch.uint8),
+              "point_obs": ((n_points, 2), torch.int32), "point_views": ((n_points,), torch.int32),
+              "point_normal": ((n_points, 3), torch.float64), "point_dist": ((n_points, 2), torch.float64),
+              "totals": ((4,), torch.int32)}
+    if out is None:
+        out = {k: torch.zeros(shape, dtype=dtype, device=dev) for k, (shape, dtype) in shapes.items()}
+    else:
+        assert list(out) == list(DESCRIBE_OUTPUTS)
+        assert all(out[k].is_cuda and out[k].dtype == dtype and out[k].is_contiguous() and tuple(out[k].shape) == shape
+                   for k, (shape, dtype) in shapes.items())
+    prm = params if params is not None else point_desc_default_params()
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    ctx.check(hip.lib.gh_describe_points_dev(ctx.h, p(kps), p(desc), p(counts), F, cap, p(cam_pose), p(obs_cam), p(obs_point),
+                                             p(obs_node), _p(obs_use), n_obs, n_points, p(point_xyz), _p(point_status),
+                                             _p(point_select), C.byref(prm), *(p(out[k]) for k in DESCRIBE_OUTPUTS)))
     return out
 
 

@@ -111,6 +111,11 @@ class TrackParams(C.Structure):
                 ("max_drops", C.c_int32)]
 
 
+class PointDescParams(C.Structure):
+    """gh_point_desc_params (16 bytes) of gh_describe_points_dev."""
+    _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32), ("max_views", C.c_int32)]
+
+
 # Every symbol include/gslam_hip.h declares.  tests/test_abi.py checks header <-> this table <-> .so.
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SIGNATURES = {
@@ -241,6 +246,9 @@ SIGNATURES = {
                                        _vp]),
     "gh_merge_points_dev": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, C.c_double, _i, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_point_desc_default_params": (None, [C.POINTER(PointDescParams)]),
+    "gh_describe_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp,
+                                         C.POINTER(PointDescParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gh_ba_window_default_params": (None, [C.POINTER(BaWindowParams)]),
     "gh_ba_window_dev": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BaWindowParams),
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

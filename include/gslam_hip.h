@@ -1037,6 +1037,73 @@ gh_status gh_merge_points_dev(gh_ctx* ctx, const int32_t* counts_dev, int n_fram
                               const double* point_xyz_dev, double max_dist, int bridge, const int32_t* obs_point_in_dev,
                               int32_t* point_remap_dev, uint8_t* point_state_dev, uint8_t* point_select_dev,
                               int32_t* node_point_dev, int32_t* obs_point_dev, int32_t* point_len_dev, int32_t* totals_dev);
+/* Map-point summaries: what a search by projection or a fusion of duplicate points needs per point and the map did not have --
+ * the three things ORB-SLAM keeps in MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth: the descriptor of the
+ * observation closest, by median Hamming distance, to the point's other observations; the mean direction from which the point
+ * was seen; the distance range over which the octave of its reference keypoint predicts it can be found again.  Every pointer
+ * is a DEVICE pointer, nothing is copied to the host, the call is asynchronous on the context's stream, scratch comes from the
+ * context, nothing is allocated or synchronised per call.  The inputs are the map's arrays as gh_extend_tracks_dev,
+ * gh_merge_points_dev and gh_triangulate_tracks_dev leave them, padding included; no count is read back.
+ * Inputs: kps_dev n_frames x cap records; desc_dev n_frames x cap x 32 bytes, the descriptors of the same rows (4-byte aligned);
+ * counts_dev n_frames; cam_pose_dev n_frames x 7 T_wc, taken as it stands; obs_cam_dev, obs_point_dev, obs_node_dev n_obs each
+ * (the N of gh_extend_tracks_dev goes in as it is); obs_use_dev n_obs bytes or NULL (this is where obs_good goes); n_points is a
+ * CAPACITY (PC goes in as it is); point_xyz_dev n_points x 3; point_status_dev n_points or NULL: a point is USABLE when
+ * point_status_dev is NULL or its status equals GH_TRACK_OK; point_select_dev n_points bytes or NULL (all points); params:
+ * gh_point_desc_default_params gives scale_factor 1.2, n_levels 8 (the ORB pyramid) and max_views 64.
+ *   nodes      N = n_frames * cap; node n is (frame n / cap, row n % cap) and EXISTS when n % cap < clamp(counts[n / cap], 0, cap).
+ *   usable     observation k is usable when (obs_use_dev == NULL || obs_use[k] != 0), 0 <= p = obs_point[k] < n_points,
+ *              0 <= n = obs_node[k] < N, node n exists and obs_cam[k] == n / cap.  An index outside its range drops the
+ *              observation; it is never dereferenced.
+ *   track      of point p: its usable observations in ascending observation index, whatever order the arrays have; the LIVE INDEX
+ *              of an observation is its position in that list, L the length of the list.
+ *   state      one byte per point, checked in this order: GH_PDESC_SKIPPED point_select_dev is given and point_select[p] == 0;
+ *              GH_PDESC_NOT_OK the point is not usable; GH_PDESC_EMPTY L == 0; GH_PDESC_OK otherwise.
+ *   descriptor M = min(L, max_views) candidates; candidate c is the observation at live index c when L <= max_views and at
+ *              (c * L) / M otherwise (a 64-bit product, integer division: strictly increasing in c).  d(a, b) = the popcount of
+ *              the xor of the two 256-bit descriptors; row a holds the M values d(a, .), its own 0 included; med(a) = the
+ *              element at index (M - 1) / 2 of the sorted row (ORB-SLAM's vDists[0.5 * (N - 1)]).  Chosen: the candidate with the
+ *              smallest med, the lowest c on ties.
+ *   direction  IEEE doubles, every operation rounded once, nothing fused.  For each live observation: t = the last three
+ *              entries of the pose of frame obs_node / cap; v = X - t entry by entry; r2 = (v0 * v0 + v1 * v1) + v2 * v2;
+ *              u = v * (1 / sqrt(r2)).  gh_track_group_lanes() = 8 partial sums, each from +0.0: partial j adds the u of the live
+ *              indices with index % 8 == j in ascending order; total = ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)) entry
+ *              by entry, the order of gh_triangulate_tracks_dev; normal = total / (double)L entry by entry.
+ *   range      the REFERENCE is live index 0; dist = sqrt(r2 of the reference); level = clamp(kps[its node].octave, 0,
+ *              n_levels - 1); max_dist = dist * pow[level]; min_dist = max_dist / pow[n_levels - 1], with pow[0] = 1 and
+ *              pow[l] = pow[l - 1] * scale_factor formed on the host in doubles.
+ *   NaN        a point that coincides with a camera centre gives 0 * inf: the direction is NaN.  IEEE 754 fixes neither the
+ *              sign nor the payload of a NaN that an operation makes (x86 sets the sign, gfx950 does not), so every NaN among the
+ *              five doubles is written as the quiet NaN 0x7ff8000000000000.
+ * Outputs: point_state_dev n_points bytes, written for EVERY point; point_desc_dev n_points x 32 bytes (4-byte aligned): the
+ * chosen descriptor; point_obs_dev n_points x 2: the observation index of the chosen candidate and of the reference;
+ * point_views_dev n_points: L; point_normal_dev n_points x 3; point_dist_dev n_points x 2: min_dist, max_dist; totals_dev 4: the
+ * OK points, the EMPTY points, the NOT_OK points, the OK points with L > max_views (whose descriptor saw a sample of the track).
+ * Everything except the state byte and the totals is IN/OUT: written as above for an OK point; zeros, with -1 in both entries
+ * of point_obs, for an EMPTY or NOT_OK point; NOT written for a SKIPPED point -- a caller refreshes only what changed with
+ * point_select = point_new | point_grew | the survivors of a merge.  The same inputs give the same bits on every run.
+ * tests/point_describe_restate.py restates all of it.
+ * GH_ERR_ARG, and then nothing is written: ctx or params NULL; n_frames, cap, n_obs or n_points negative; cap > 65535; n_points +
+ * n_frames * cap > INT32_MAX - 1; scale_factor not finite or < 1; n_levels outside 1 .. 32; max_views outside 1 .. 64; a NULL
+ * among kps, desc, counts, cam_pose, obs_cam, obs_point, obs_node, point_xyz or the seven outputs; desc_dev or point_desc_dev
+ * not 4-byte aligned.  n_points == 0: GH_OK, only totals_dev (zeros) is written.  n_obs == 0 with n_points > 0: every selected
+ * usable point is EMPTY. */
+#define GH_PDESC_OK 0
+#define GH_PDESC_EMPTY 1      /* usable, but no usable observation */
+#define GH_PDESC_NOT_OK 2     /* point_status says: not a map point */
+#define GH_PDESC_SKIPPED 3    /* point_select says: not this point */
+typedef struct gh_point_desc_params {  /* 16 bytes */
+  double scale_factor;  /* 1.2 */
+  int32_t n_levels;     /* 8 */
+  int32_t max_views;    /* 64: the candidates of the descriptor choice, at most 64 */
+} gh_point_desc_params;
+void gh_point_desc_default_params(gh_point_desc_params* p);
+gh_status gh_describe_points_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const uint8_t* desc_dev, const int32_t* counts_dev,
+                                 int n_frames, int cap, const double* cam_pose_dev, const int32_t* obs_cam_dev,
+                                 const int32_t* obs_point_dev, const int32_t* obs_node_dev, const uint8_t* obs_use_dev, int n_obs,
+                                 int n_points, const double* point_xyz_dev, const int32_t* point_status_dev,
+                                 const uint8_t* point_select_dev, const gh_point_desc_params* params, uint8_t* point_state_dev,
+                                 uint8_t* point_desc_dev, int32_t* point_obs_dev, int32_t* point_views_dev,
+                                 double* point_normal_dev, double* point_dist_dev, int32_t* totals_dev);
 
 /* The local window of a bundle adjustment, selected and compacted on the device: the last arrow of match -> localize -> extend ->
  * triangulate the new points -> BA.  The map's arrays go in as gh_extend_tracks_dev and gh_triangulate_tracks_dev leave them,
