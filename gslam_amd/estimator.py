@@ -12,7 +12,10 @@ takes; localize_pairs (gh_localize_pairs_dev) registers every frame in one call 
 extend_tracks (gh_extend_tracks_dev) adds those rows to the tracks of the map and links the other rows of the new frames into
 new tracks numbered after the map's, so that the map grows batch after batch without a read-back; merge_points
 (gh_merge_points_dev) renames the points that the matches show to be one to the oldest id of their group; describe_points
-(gh_describe_points_dev) gives every map point its representative descriptor, mean viewing direction and distance range."""
+(gh_describe_points_dev) gives every map point its representative descriptor, mean viewing direction and distance range;
+search_projection (gh_search_projection_dev) projects those points into the localized frames and adds the keypoints it finds in
+a window to the claims: localize_pairs -> search_projection -> extend_tracks -> triangulate_tracks -> describe_points(point_new |
+point_grew)."""
 import ctypes as C
 
 import numpy as np
@@ -570,6 +573,66 @@ def describe_points(ctx: hip.Context, kps, desc, counts, cam_pose, obs_cam, obs_
     ctx.check(hip.lib.gh_describe_points_dev(ctx.h, p(kps), p(desc), p(counts), F, cap, p(cam_pose), p(obs_cam), p(obs_point),
                                              p(obs_node), _p(obs_use), n_obs, n_points, p(point_xyz), _p(point_status),
                                              _p(point_select), C.byref(prm), *(p(out[k]) for k in DESCRIBE_OUTPUTS)))
+    return out
+
+
+def search_default_params():
+    """gh_search_default_params -> hip.SearchParams."""
+    p = hip.SearchParams()
+    hip.lib.gh_search_default_params(C.byref(p))
+    return p
+
+
+SEARCH_OUTPUTS = ("row_point", "row_inlier", "row_dist", "frame_totals", "totals")
+SEARCH_VERDICTS = ("HELD", "BEHIND", "OUTSIDE", "RANGE", "ANGLE", "NO_CANDIDATE", "WEAK", "RATIO", "LOST", "WON")
+
+
+def search_projection(ctx: hip.Context, kps, desc, counts, cam_pose, frame_search, n_points, point_xyz, summaries, intrinsics, size,
+                      node_point=None, row_point=None, row_inlier=None, point_status=None, point_select=None, params=None,
+                      in_place=False):
+    """gh_search_projection_dev, the call between localize_pairs and extend_tracks: the map's points are projected into the
+    frames marked in frame_search and matched against the keypoints that have no point yet, in a window around the projection.
+    kps, desc, counts, cam_pose, n_points, point_xyz, point_status, point_select as describe_points takes them (cam_pose may be
+    the poses of localize_pairs); frame_search: F uint8; summaries: the dict describe_points returned (point_views, point_desc,
+    point_normal, point_dist are read); intrinsics: fx, fy, cx, cy; size: (width, height); node_point: F * cap int32 (the map) or
+    None; row_point F * cap int32 and row_inlier F * cap uint8: the claims of localize_pairs, or both None -- all cuda; params:
+    hip.SearchParams or None (the defaults); in_place: the claims are updated where they are.  -> dict of device tensors:
+    row_point N int32 and row_inlier N uint8 (the claims with the search's winners added: what extend_tracks takes), row_dist N
+    uint16 (the Hamming distance of a winner, 0xFFFF elsewhere), frame_totals F x 10 int32 (the pairs per verdict,
+    SEARCH_VERDICTS), totals 12 int32 (the column sums, the searched frames, the searchable points); nothing is synchronised and
+    nothing is read back."""
+    import torch
+    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
+    F, cap = kps.shape[0], kps.shape[1]
+    N, dev, n_points = F * cap, kps.device, int(n_points)
+    assert desc.is_cuda and desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() == 32 * N
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == F
+    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() == 7 * F
+    assert frame_search.is_cuda and frame_search.dtype == torch.uint8 and frame_search.is_contiguous() and frame_search.numel() == F
+    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
+    want = {"point_views": (torch.int32, n_points), "point_desc": (torch.uint8, 32 * n_points),
+            "point_normal": (torch.float64, 3 * n_points), "point_dist": (torch.float64, 2 * n_points)}
+    assert all(summaries[k].is_cuda and summaries[k].dtype == dt and summaries[k].is_contiguous() and summaries[k].numel() == n
+               for k, (dt, n) in want.items())
+    for t, dt, n in ((node_point, torch.int32, N), (row_point, torch.int32, N), (row_inlier, torch.uint8, N),
+                     (point_status, torch.int32, n_points), (point_select, torch.uint8, n_points)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n)
+    assert (row_point is None) == (row_inlier is None) and not (in_place and row_point is None)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    out = {"row_point": row_point if in_place else torch.empty(N, dtype=torch.int32, device=dev),
+           "row_inlier": row_inlier if in_place else torch.empty(N, dtype=torch.uint8, device=dev),
+           "row_dist": torch.empty(N, dtype=torch.uint16, device=dev),
+           "frame_totals": torch.empty((F, 10), dtype=torch.int32, device=dev),
+           "totals": torch.empty(12, dtype=torch.int32, device=dev)}
+    prm = params if params is not None else search_default_params()
+    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
+    p = lambda t: C.c_void_p(t.data_ptr() or 256)
+    q = lambda t: None if t is None else p(t)  # (NULL means "not given", also when the array holds nothing)
+    ctx.check(hip.lib.gh_search_projection_dev(ctx.h, p(kps), p(desc), p(counts), F, cap, p(cam_pose), p(frame_search), q(node_point),
+                                               q(row_point), q(row_inlier), n_points, p(point_xyz), q(point_status), q(point_select),
+                                               *(p(summaries[k]) for k in want), C.c_double(fx), C.c_double(fy), C.c_double(cx),
+                                               C.c_double(cy), int(size[0]), int(size[1]), C.byref(prm),
+                                               *(p(out[k]) for k in SEARCH_OUTPUTS)))
     return out
 
 

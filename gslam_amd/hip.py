@@ -116,6 +116,13 @@ class PointDescParams(C.Structure):
     _fields_ = [("scale_factor", C.c_double), ("n_levels", C.c_int32), ("max_views", C.c_int32)]
 
 
+class SearchParams(C.Structure):
+    """gh_search_params (80 bytes) of gh_search_projection_dev."""
+    _fields_ = [("scale_factor", C.c_double), ("radius_near", C.c_double), ("radius_far", C.c_double), ("near_cos", C.c_double),
+                ("radius_scale", C.c_double), ("min_view_cos", C.c_double), ("range_lo", C.c_double), ("range_hi", C.c_double),
+                ("nn_ratio", C.c_double), ("n_levels", C.c_int32), ("max_hamming", C.c_int32)]
+
+
 # Every symbol include/gslam_hip.h declares.  tests/test_abi.py checks header <-> this table <-> .so.
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SIGNATURES = {
@@ -249,6 +256,11 @@ SIGNATURES = {
     "gh_point_desc_default_params": (None, [C.POINTER(PointDescParams)]),
     "gh_describe_points_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp,
                                          C.POINTER(PointDescParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gh_search_default_params": (None, [C.POINTER(SearchParams)]),
+    "gh_search_cell_pixels": (C.c_int, []),
+    "gh_search_projection_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, C.POINTER(SearchParams),
+                                           _vp, _vp, _vp, _vp, _vp]),
     "gh_ba_window_default_params": (None, [C.POINTER(BaWindowParams)]),
     "gh_ba_window_dev": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(BaWindowParams),
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

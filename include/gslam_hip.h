@@ -1104,6 +1104,88 @@ gh_status gh_describe_points_dev(gh_ctx* ctx, const gh_keypoint* kps_dev, const 
                                  const uint8_t* point_select_dev, const gh_point_desc_params* params, uint8_t* point_state_dev,
                                  uint8_t* point_desc_dev, int32_t* point_obs_dev, int32_t* point_views_dev,
                                  double* point_normal_dev, double* point_dist_dev, int32_t* totals_dev);
+/* Search by projection: the consumer of the summaries above.  The searchable points of the map are projected into the frames
+ * marked in frame_search_dev (their pose is known: gh_localize_pairs_dev's poses go in as they are), gated by point_dist and by
+ * the angle to point_normal, compared with the OPEN keypoints in a window around the projection, and the winners leave as claims
+ * in the form gh_extend_tracks_dev takes.  The order of calls is localize -> search -> extend -> triangulate ->
+ * describe(point_new | point_grew).  Every pointer is a DEVICE pointer, the call is asynchronous on the context's stream, scratch
+ * comes from the context (a function of N = n_frames * cap, n_points and n_frames only, linear in each), nothing is allocated,
+ * synchronised or read back per call.
+ * Inputs: kps_dev, desc_dev, counts_dev, cam_pose_dev (T_wc, taken as it stands), n_points (a CAPACITY), point_xyz_dev,
+ * point_status_dev (NULL, or compared with GH_TRACK_OK) and point_select_dev (NULL: all) as gh_describe_points_dev takes them;
+ * point_views_dev, point_desc_dev, point_normal_dev, point_dist_dev as it writes them; frame_search_dev n_frames bytes, non-zero:
+ * search this frame; node_point_in_dev N entries or NULL: the map; row_point_in_dev / row_inlier_in_dev N entries each, both or
+ * neither: the claims of gh_localize_pairs_dev; fx, fy, cx, cy, width, height: the pinhole and the image; params:
+ * gh_search_default_params gives the values noted at the fields.
+ *   nodes      node n = f * cap + i EXISTS when i < clamp(counts[f], 0, cap).  An existing node is TAKEN when it is MAPPED
+ *              (node_point_in given and 0 <= node_point_in[n] < n_points) or else CLAIMED (claims given, row_inlier_in[n] != 0 and
+ *              0 <= row_point_in[n] < n_points); its point is that value.  HELD(f, p): some TAKEN node of frame f has point p.
+ *              Every other existing node is OPEN.  A value outside its range is never used as an index.
+ *   points     p is SEARCHABLE when point_select is NULL or non-zero at p, point_status is NULL or GH_TRACK_OK at p, and
+ *              point_views[p] > 0.
+ *   pairs      every (searched frame f, searchable point p) gets exactly one verdict, checked in this order, in IEEE doubles
+ *              with + - * / and sqrt, every operation rounded once, nothing fused, in the order written; a comparison with a
+ *              NaN fails.  pow[0] = 1, pow[l] = pow[l - 1] * scale_factor, formed on the host.  q, t = the pose of f.
+ *              0 HELD          HELD(f, p).
+ *              1 BEHIND        d = X - t entry by entry; Xc = quat_rotate((-qx, -qy, -qz, qw), d), the formula under
+ *                              gh_triangulate_tracks_dev; BEHIND unless Xc[2] > 1e-9.
+ *              2 OUTSIDE       iz = 1 / Xc[2]; u = fx * (Xc[0] * iz) + cx; v = fy * (Xc[1] * iz) + cy; OUTSIDE unless
+ *                              0 <= u && u < (double)width && 0 <= v && v < (double)height.
+ *              3 RANGE         r2 = (d0 * d0 + d1 * d1) + d2 * d2; dist = sqrt(r2); (min_dist, max_dist) = point_dist[p]; RANGE
+ *                              unless dist >= range_lo * min_dist && dist <= range_hi * max_dist.
+ *              4 ANGLE         c = ((d0 * n0 + d1 * n1) + d2 * n2) / dist with n = point_normal[p], not renormalised
+ *                              (ORB-SLAM's isInFrustum); ANGLE unless c >= min_view_cos.
+ *              5 NO_CANDIDATE  level = the number of l in 0 .. n_levels - 2 with pow[l] * dist < max_dist; radius =
+ *                              (radius_scale * (c > near_cos ? radius_near : radius_far)) * pow[level].  The CANDIDATES are the
+ *                              OPEN nodes i of frame f with level - 1 <= kps[i].octave <= level, fabs((double)kps[i].x - u) <
+ *                              radius and fabs((double)kps[i].y - v) < radius: strict, on the widened floats, and nothing else
+ *                              decides -- a keypoint with NaN, infinite or out-of-image coordinates obeys the same three
+ *                              comparisons.  NO_CANDIDATE when there is none.
+ *              6 WEAK          h(i) = popcount(desc[i] xor point_desc[p]) over 256 bits; the candidates are ordered by the key
+ *                              (h, i); best is the smallest key, second the next (one candidate: h_second = 256, octave -1).
+ *                              WEAK when h_best > max_hamming.
+ *              7 RATIO         octave(best) == octave(second) and (double)h_best > nn_ratio * (double)h_second.
+ *              otherwise (f, p) PROPOSES node best with distance h_best.  A node takes the proposal with the smallest (h, p):
+ *              that pair is 9 WON, every other proposal to the node is 8 LOST.  The result is a function of sets.
+ * Outputs, all written for their full capacity on every call: for a node that won p with distance h, row_point[n] = p,
+ * row_inlier[n] = 1, row_dist[n] = h.  For every other node row_dist = 0xFFFF, and row_point[n] = row_point_in[n], row_inlier[n]
+ * = (row_inlier_in[n] != 0) when the claims were given; otherwise row_point = GH_LOC_NO_POINT for an existing node, GH_LOC_NO_ROW
+ * for the others, and row_inlier = 0.  row_point_dev / row_inlier_dev may BE the claim inputs (identical or disjoint); the pair
+ * then goes to gh_extend_tracks_dev as it is: no two claimants of a frame share a point and no claimant's point is MAPPED in its
+ * frame, so extend's REJECTED rule never fires on what this call adds.  frame_totals_dev n_frames x 10: the pairs of the frame per
+ * verdict in the order of the numbers above (zeros for a frame that was not searched); totals_dev 12: the ten column sums, the
+ * searched frames, the searchable points (counted when a frame is searched).  The same inputs give the same bytes on every run.
+ * tests/search_projection_restate.py restates all of it.
+ * GH_ERR_ARG, and then nothing is written: ctx or params NULL; n_frames, cap or n_points negative; cap > 65535; n_points +
+ * n_frames * cap > INT32_MAX - 1; width or height < 1; fx or fy not > 0; scale_factor not finite or < 1; n_levels outside 1 .. 32;
+ * max_hamming outside 0 .. 256; a NaN among the eight other doubles of params; radius_near, radius_far or radius_scale negative; a
+ * NULL among kps, desc, counts, cam_pose, frame_search or the five outputs; with n_points > 0 a NULL among point_xyz and the four
+ * summaries; exactly one of the two claim inputs NULL; desc_dev or point_desc_dev not 4-byte aligned.  N == 0: GH_OK, only
+ * totals_dev (zeros) is written.  n_points == 0, or no searched frame: GH_OK, the node outputs fall through as above and every
+ * count is zero except the searched frames. */
+typedef struct gh_search_params {   /* 80 bytes */
+  double scale_factor;   /* 1.2 */
+  double radius_near;    /* 2.5   window half-width at level 0 when the view is close to the mean direction */
+  double radius_far;     /* 4.0 */
+  double near_cos;       /* 0.998 */
+  double radius_scale;   /* 1.0   ORB-SLAM's th */
+  double min_view_cos;   /* 0.5 */
+  double range_lo;       /* 0.8 */
+  double range_hi;       /* 1.2 */
+  double nn_ratio;       /* 0.8 */
+  int32_t n_levels;      /* 8 */
+  int32_t max_hamming;   /* 100 */
+} gh_search_params;
+void gh_search_default_params(gh_search_params* p);
+int  gh_search_cell_pixels(void);   /* host only: the side of the keypoint grid's cells, so tests can sit on its boundaries */
+gh_status gh_search_projection_dev(gh_ctx* ctx,
+    const gh_keypoint* kps_dev, const uint8_t* desc_dev, const int32_t* counts_dev, int n_frames, int cap,
+    const double* cam_pose_dev, const uint8_t* frame_search_dev,
+    const int32_t* node_point_in_dev, const int32_t* row_point_in_dev, const uint8_t* row_inlier_in_dev,
+    int n_points, const double* point_xyz_dev, const int32_t* point_status_dev, const uint8_t* point_select_dev,
+    const int32_t* point_views_dev, const uint8_t* point_desc_dev, const double* point_normal_dev, const double* point_dist_dev,
+    double fx, double fy, double cx, double cy, int width, int height, const gh_search_params* params,
+    int32_t* row_point_dev, uint8_t* row_inlier_dev, uint16_t* row_dist_dev, int32_t* frame_totals_dev, int32_t* totals_dev);
 
 /* The local window of a bundle adjustment, selected and compacted on the device: the last arrow of match -> localize -> extend ->
  * triangulate the new points -> BA.  The map's arrays go in as gh_extend_tracks_dev and gh_triangulate_tracks_dev leave them,
