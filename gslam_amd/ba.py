@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import hip
+from .devargs import alloc, dev, ptr_array, ptr_opt, require
 
 
 def _ptr(a):
@@ -274,25 +275,22 @@ def window(ctx: hip.Context, cam_pose, point_xyz, obs_cam, obs_point, obs_xy, ca
     win_obs_point, win_obs_src n_obs int32, win_obs_xy n_obs x 2, totals 8 int32 (window cameras, LOCAL, FIXED, held LOCAL, window
     points, window observations, seeds in the window, usable observations).  Nothing is synchronised and nothing is read back:
     window_problem does that."""
-    import torch
-    f64 = lambda t, w: t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() % w == 0
-    assert f64(cam_pose, 7) and f64(point_xyz, 3) and f64(obs_xy, 2)
-    nc, npts, no, dev = cam_pose.numel() // 7, point_xyz.numel() // 3, obs_xy.numel() // 2, cam_pose.device
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == no for t in (obs_cam, obs_point))
-    for t, n in ((cam_seed, nc), (obs_use, no), (point_use, npts), (cam_hold, nc)):
-        assert t is None or (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n)
-    assert cam_seed is not None
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-    d64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-    out = {"cam_class": torch.empty(nc, dtype=torch.uint8, device=dev), "cam_shared": i32(nc), "cam_slot": i32(nc), "point_slot": i32(npts),
-           "win_cam": i32(nc), "win_cam_dof": i32(nc), "win_cam_pose": d64(nc, 7), "win_point": i32(npts), "win_point_xyz": d64(npts, 3),
-           "win_obs_cam": i32(no), "win_obs_point": i32(no), "win_obs_src": i32(no), "win_obs_xy": d64(no, 2), "totals": i32(8)}
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    q = lambda t: None if t is None else p(t)
+    nc = dev("cam_pose", cam_pose, "float64", multiple_of=7).numel() // 7
+    npts = dev("point_xyz", point_xyz, "float64", multiple_of=3).numel() // 3
+    no = dev("obs_xy", obs_xy, "float64", multiple_of=2).numel() // 2
+    dev("obs_cam", obs_cam, "int32", no)
+    dev("obs_point", obs_point, "int32", no)
+    dev("cam_seed", cam_seed, "uint8", nc)
+    for name, t, n in (("obs_use", obs_use, no), ("point_use", point_use, npts), ("cam_hold", cam_hold, nc)):
+        dev(name, t, "uint8", n, optional=True)
+    i32, f64 = "int32", "float64"
+    out = alloc(cam_pose.device, dict(zip(WINDOW_OUTPUTS, (  # (one row per line of WINDOW_OUTPUTS)
+        (nc, "uint8"), (nc, i32), (nc, i32), (npts, i32), (nc, i32), (nc, i32), ((nc, 7), f64), (npts, i32),
+        ((npts, 3), f64), (no, i32), (no, i32), (no, i32), ((no, 2), f64), (8, i32)))))
     params = hip.BaWindowParams(int(min_shared), int(min_point_obs))
-    ctx.check(hip.lib.gh_ba_window_dev(ctx.h, nc, npts, no, p(cam_pose), p(point_xyz), p(obs_cam), p(obs_point), p(obs_xy), q(obs_use),
-                                       q(point_use), p(cam_seed), q(cam_hold), C.byref(params), *(p(out[k]) for k in WINDOW_OUTPUTS)))
+    ctx.check(hip.lib.gh_ba_window_dev(ctx.h, nc, npts, no, ptr_array(cam_pose), ptr_array(point_xyz), ptr_array(obs_cam),
+                                       ptr_array(obs_point), ptr_array(obs_xy), ptr_opt(obs_use), ptr_opt(point_use),
+                                       ptr_array(cam_seed), ptr_opt(cam_hold), C.byref(params), *map(ptr_array, out.values())))
     return out
 
 
@@ -314,14 +312,16 @@ def window_scatter(ctx: hip.Context, win: dict, poses, points, cam_pose, point_x
     solve() returns them, or cuda tensors -- into the map's device arrays cam_pose and point_xyz, in place.  Cameras with dof 0
     (FIXED and held) and everything outside the window keep their bits.  Asynchronous."""
     import torch
-    dev = cam_pose.device
-    up = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    up = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(cam_pose.device)
     poses, points = up(poses), up(points)
-    assert all(t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() for t in (poses, points, cam_pose, point_xyz))
-    assert poses.numel() % 7 == 0 and points.numel() % 3 == 0 and cam_pose.numel() % 7 == 0 and point_xyz.numel() % 3 == 0
-    n_win_cams, n_win_points = poses.numel() // 7, points.numel() // 3
-    assert n_win_cams <= win["win_cam"].numel() and n_win_points <= win["win_point"].numel()
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_ba_window_scatter_dev(ctx.h, p(win["win_cam"]), p(win["win_cam_dof"]), n_win_cams, p(poses), p(win["win_point"]),
-                                               n_win_points, p(points), p(cam_pose), cam_pose.numel() // 7, p(point_xyz), point_xyz.numel() // 3))
+    n_win_cams = dev("poses", poses, "float64", multiple_of=7).numel() // 7
+    n_win_points = dev("points", points, "float64", multiple_of=3).numel() // 3
+    dev("cam_pose", cam_pose, "float64", multiple_of=7)
+    dev("point_xyz", point_xyz, "float64", multiple_of=3)
+    require(n_win_cams <= win["win_cam"].numel() and n_win_points <= win["win_point"].numel(),
+            "poses / points: %d cameras and %d points, more than the window holds" % (n_win_cams, n_win_points))
+    ctx.check(hip.lib.gh_ba_window_scatter_dev(ctx.h, ptr_array(win["win_cam"]), ptr_array(win["win_cam_dof"]), n_win_cams,
+                                               ptr_array(poses), ptr_array(win["win_point"]), n_win_points, ptr_array(points),
+                                               ptr_array(cam_pose), cam_pose.numel() // 7, ptr_array(point_xyz),
+                                               point_xyz.numel() // 3))
     win["scatter_source"] = (poses, points)  # (the call is asynchronous: what it reads must outlive this function)

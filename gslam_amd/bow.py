@@ -7,10 +7,7 @@ import numpy as np
 import torch
 
 from . import hip
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from .devargs import ptr
 
 
 class Vocabulary:
@@ -54,7 +51,7 @@ class Vocabulary:
         """desc: B x cap x desc_bytes u8 (cuda) -> (word, weight, node, bow_word, bow_val, bow_n) device tensors."""
         B, cap = desc.shape[0], desc.shape[1]
         out = out or self.alloc(B, cap, desc.device)
-        self.ctx.check(hip.lib.gh_bow_transform_dev(self.h, _p(desc), _p(counts), cap, B, int(levelsup), *[_p(t) for t in out]))
+        self.ctx.check(hip.lib.gh_bow_transform_dev(self.h, ptr(desc), ptr(counts), cap, B, int(levelsup), *[ptr(t) for t in out]))
         return out
 
     def transform_host(self, desc: np.ndarray, levelsup=2):
@@ -79,8 +76,8 @@ def score(ctx: hip.Context, scoring: int, q, db):
     qw, qv, qn = q
     dw, dv, dn = db
     out = torch.empty((qw.shape[0], dw.shape[0]), dtype=torch.float64, device=qw.device)
-    ctx.check(hip.lib.gh_bow_score_dev(ctx.h, int(scoring), _p(qw), _p(qv), _p(qn), qw.shape[0], qw.shape[1], _p(dw), _p(dv),
-                                       _p(dn), dw.shape[0], dw.shape[1], _p(out)))
+    ctx.check(hip.lib.gh_bow_score_dev(ctx.h, int(scoring), ptr(qw), ptr(qv), ptr(qn), qw.shape[0], qw.shape[1], ptr(dw), ptr(dv),
+                                       ptr(dn), dw.shape[0], dw.shape[1], ptr(out)))
     return out
 
 

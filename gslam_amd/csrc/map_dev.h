@@ -1,7 +1,9 @@
 // The device-side pieces that the map stages share: gh_link_tracks_dev (track_link.hip), gh_extend_tracks_dev (track_extend.hip),
 // gh_merge_points_dev (track_merge.hip), gh_pnp_gather_pairs_dev / gh_localize_pairs_dev (localize.hip) and gh_ba_window_dev
-// (ba_window.hip); gh_ransac_pairs_dev (ransac_batch.hip) takes the pinhole from here.  Everything is __device__ __forceinline__:
-// a kernel that calls one of these compiles to what it was with the lines written out.
+// (ba_window.hip); gh_ransac_pairs_dev (ransac_batch.hip) takes the pinhole from here, gh_describe_points_dev (point_describe.hip)
+// and gh_search_projection_dev (search_projection.hip) the spare bins, the scale table and the Hamming distance.  Everything is
+// __device__ __forceinline__: a kernel that calls one of these compiles to what it was with the lines written out.  The host-side
+// pieces of the same stages are in map_host.h.
 #pragma once
 #include "common.h"
 
@@ -85,6 +87,27 @@ __device__ __forceinline__ void block_counts_add(const int (&n)[K], Dst dst) {
 template <int K>
 __device__ __forceinline__ void block_counts_add(const int (&n)[K], int32_t* first) {
   block_counts_add<K>(n, [first](int k) { return first + k; });
+}
+
+// THE SPARE BINS.  A stage that indexes its items by key (gh_csr_index_dev) gives the items that are not indexed -- the padding
+// of a map's arrays, mostly -- a key past the real ones, and the index counts its keys with one atomic each: 1.7 M of them on one
+// extra bin took 19.8 ms of a 20.4 ms gh_describe_points_dev.  Spread over kSpareBins bins by the item's own
+// index they are neighbours' atomics on neighbouring words.  mask is spare_bins(..) - 1 (map_host.h): a power of two less one.
+constexpr int kSpareBins = 4096;
+__device__ __forceinline__ int spare_key(int first_spare, int i, int mask) { return first_spare + (i & mask); }
+
+// v[l] = scale_factor^l for the levels of an image pyramid (scale_powers, map_host.h, builds it); a kernel takes it by value
+constexpr int kMaxLevels = 32;
+struct ScalePowers {
+  double v[kMaxLevels];
+};
+
+// the Hamming distance of two 256-bit descriptors held as 8 words
+__device__ __forceinline__ int hamming256(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+  int d = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
+  return d;
 }
 
 struct Pinhole {

@@ -14,11 +14,8 @@
 // call zeroed, after a reduction inside the workgroup (gh_map::block_counts_add).  No float atomic anywhere.
 //
 // CDNA4 mapping (the shared pieces are gh_map's, map_dev.h, and gh_csr_index_dev's, csr_sort.hip):
-//   * pdsc_keys    one lane per observation: its point when the observation is USABLE, one of 4096 extra bins from n_points on
-//                  otherwise (an index out of range is never dereferenced).  The padded arrays of a map are mostly unusable
-//                  entries, and the index counts its keys with one atomic each: into a single extra bin, 1.7 M of them on one
-//                  address took 19.8 ms of a 20.4 ms call; spread by observation index they are neighbours'
-//                  atomics on neighbouring words;
+//   * pdsc_keys    one lane per observation: its point when the observation is USABLE, one of the spare bins from n_points on
+//                  otherwise (an index out of range is never dereferenced; why the bins are many: map_dev.h, THE SPARE BINS);
 //   * index        gh_csr_index_dev turns the keys into start / list: the track of a point in ascending observation index,
 //                  whatever order the caller's arrays have;
 //   * pdsc_narrow  one group of 8 lanes per point, 8 points per wave, 32 per 256-thread workgroup: state, views, direction, range
@@ -33,24 +30,19 @@
 #include <climits>
 #include <cmath>
 
-#include "dense_solve.h"
-#include "map_dev.h"
+#include "map_host.h"
 
 namespace {
 
+using gh_map::hamming256;
 using gh_map::kBlock;
+using gh_map::kMaxLevels;
 
 constexpr int kGroupLanes = 8;                        // the group of gh_triangulate_tracks_dev: the summation order depends on it
 constexpr int kPointsPerBlock = kBlock / kGroupLanes;
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kMaxViews = 64;                         // one candidate per lane of a wave
-constexpr int kMaxLevels = 32;
-constexpr int kSpareBins = 4096;                      // a power of two: where the unusable observations are counted
 constexpr unsigned long long kQuietNaN = 0x7ff8000000000000ull;
-
-struct PowTable {
-  double v[kMaxLevels];  // v[l] = scale_factor^l, built on the host by repeated multiplication
-};
 
 struct DescArgs {
   const gh_keypoint* kps;
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void pdsc_keys_kernel(const int32_t* __rest
     const int f = n / cap;
     usable = n - f * cap < gh_map::row_count(counts, f, cap) && obs_cam[k] == f;
   }
-  key[k] = usable ? p : n_points + (k & spare_mask);
+  key[k] = usable ? p : gh_map::spare_key(n_points, k, spare_mask);
 }
 
 // the live index of candidate c of a track of L observations with M = min(L, max_views) candidates
@@ -94,14 +86,7 @@ __device__ __forceinline__ int candidate_index(int c, int L, int M) { return L =
 // a NaN leaves as the one quiet NaN with a clear sign and no payload: IEEE 754 fixes neither for a NaN that an operation makes
 __device__ __forceinline__ double canonical(double x) { return x != x ? __longlong_as_double((long long)kQuietNaN) : x; }
 
-__device__ __forceinline__ int hamming(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
-  int d = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
-  return d;
-}
-
-__global__ __launch_bounds__(kBlock) void pdsc_narrow_kernel(DescArgs a, PowTable pw) {
+__global__ __launch_bounds__(kBlock) void pdsc_narrow_kernel(DescArgs a, gh_map::ScalePowers pw) {
   const int tid = threadIdx.x, j = tid & (kGroupLanes - 1);
   const long long gp = (long long)blockIdx.x * kPointsPerBlock + (tid >> 3);
   const bool in_range = gp < a.n_points;
@@ -164,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void pdsc_narrow_kernel(DescArgs a, PowTabl
     uint32_t o[8];
 #pragma unroll
     for (int w = 0; w < 8; ++w) o[w] = __shfl(d[w], b, kGroupLanes);
-    row[b] = hamming(d, o);
+    row[b] = hamming256(d, o);
   }
   const int mid = (M - 1) / 2;
   int med = 0;
@@ -256,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void pdsc_wide_kernel(DescArgs a) {
     uint32_t o[8];
 #pragma unroll
     for (int w = 0; w < 8; ++w) o[w] = __shfl(d[w], b);
-    col[b * 64] = (uint16_t)hamming(d, o);
+    col[b * 64] = (uint16_t)hamming256(d, o);
   }
   // the element at index (M - 1) / 2 of the sorted column: the smallest v with at least (M - 1) / 2 + 1 values <= v
   const int need = (M - 1) / 2 + 1;
@@ -309,41 +294,27 @@ extern "C" gh_status gh_describe_points_dev(gh_ctx* ctx, const gh_keypoint* kps_
   GH_CHECK_ARG(ctx, kps_dev && desc_dev && counts_dev && cam_pose_dev && obs_cam_dev && obs_point_dev && obs_node_dev && point_xyz_dev);
   GH_CHECK_ARG(ctx, point_state_dev && point_desc_dev && point_obs_dev && point_views_dev && point_normal_dev && point_dist_dev &&
                         totals_dev);
-  GH_CHECK_ARG(ctx, (((uintptr_t)desc_dev | (uintptr_t)point_desc_dev) & 3) == 0);  // descriptors move as 32-bit words
+  GH_CHECK_ARG(ctx, gh_map::word_aligned(desc_dev, point_desc_dev));
   const int N = n_frames * cap;
 
   GH_HIP(ctx, hipMemsetAsync(totals_dev, 0, 4 * sizeof(int32_t), ctx->stream));
   if (n_points == 0) return GH_OK;
 
-  PowTable pw;
-  pw.v[0] = 1.0;
-  for (int l = 1; l < kMaxLevels; ++l) pw.v[l] = pw.v[l - 1] * params->scale_factor;
-
-  // scratch: keys | the index's work space (start and list live there); without observations only an all-zero start
-  const int spare = n_points <= INT32_MAX - 1 - kSpareBins ? kSpareBins : 1;
+  // scratch: keys | the index's work space (start and list live there)
+  const int spare = gh_map::spare_bins(n_points);
   const int n_keys = n_points + spare;
-  size_t work_bytes = gh_round256(((size_t)n_keys + 1) * 4);
-  if (n_obs > 0) {
-    work_bytes = gh_csr_index_bytes(ctx, n_obs, n_keys);
-    if (!work_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_describe_points_dev: rocPRIM size query failed");
-  }
+  size_t work_bytes = 0;
+  GH_TRY(gh_map::index_bytes(ctx, "gh_describe_points_dev", n_obs, n_keys, &work_bytes));
   gh_carve c;
   const size_t o_keys = c.take((size_t)n_obs * 4), o_work = c.take(work_bytes);
   char* base = nullptr;
   GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
-  const int32_t *start = nullptr, *list = nullptr;
-  if (n_obs > 0) {
-    int32_t* keys = (int32_t*)(base + o_keys);
+  int32_t* keys = (int32_t*)(base + o_keys);
+  if (n_obs > 0)
     GH_LAUNCH(ctx, "pdsc_keys", pdsc_keys_kernel, dim3(gh_div_up(n_obs, kBlock)), dim3(kBlock), 0, counts_dev, cap, N, obs_cam_dev,
               obs_point_dev, obs_node_dev, obs_use_dev, n_obs, n_points, spare - 1, keys);
-    const int prof = gh_prof_begin(ctx, "pdsc_index");
-    const gh_status st = gh_csr_index_dev(ctx, keys, n_obs, n_keys, base + o_work, work_bytes, &start, &list, nullptr);
-    gh_prof_end(ctx, prof);
-    GH_TRY(st);
-  } else {
-    GH_HIP(ctx, hipMemsetAsync(base + o_work, 0, work_bytes, ctx->stream));
-    start = (const int32_t*)(base + o_work);
-  }
+  const int32_t *start = nullptr, *list = nullptr;
+  GH_TRY(gh_map::build_index(ctx, "pdsc_index", keys, n_obs, n_keys, base + o_work, work_bytes, &start, &list));
 
   DescArgs a = {};
   a.kps = kps_dev;
@@ -366,7 +337,8 @@ extern "C" gh_status gh_describe_points_dev(gh_ctx* ctx, const gh_keypoint* kps_
   a.normal = point_normal_dev;
   a.dist = point_dist_dev;
   a.totals = totals_dev;
-  GH_LAUNCH(ctx, "pdsc_narrow", pdsc_narrow_kernel, dim3(gh_div_up(n_points, kPointsPerBlock)), dim3(kBlock), 0, a, pw);
+  GH_LAUNCH(ctx, "pdsc_narrow", pdsc_narrow_kernel, dim3(gh_div_up(n_points, kPointsPerBlock)), dim3(kBlock), 0, a,
+            gh_map::scale_powers(params->scale_factor));
   if (params->max_views > kGroupLanes && n_obs > kGroupLanes)  // (else no track has more than eight candidates)
     GH_LAUNCH(ctx, "pdsc_wide", pdsc_wide_kernel, dim3(gh_div_up(n_points, kWavesPerBlock)), dim3(kBlock), 0, a);
   return GH_OK;

@@ -15,8 +15,8 @@
 //                    device (totals[10]);
 //   * sproj_grid     one lane per node of a searched frame: a TAKEN node puts its point into its frame's table of 2 * cap
 //                    words (atomicCAS, linear probing, at most half full), an OPEN node gets the key frame * stride + cell of a
-//                    grid of gh_search_cell_pixels() pixels; every other node goes to one of 4096 spare bins (one bin would
-//                    take a million atomics on one word).  The cell of a coordinate is a CLAMP into the grid,
+//                    grid of gh_search_cell_pixels() pixels; every other node goes to one of the spare bins (map_dev.h,
+//                    THE SPARE BINS).  The cell of a coordinate is a CLAMP into the grid,
 //                    monotone in the coordinate, NaN and negatives to cell 0: no coordinate becomes an index unclamped, and a
 //                    window's clamped cell range holds every keypoint that can pass the strict comparisons, out of image or not;
 //   * index          gh_csr_index_dev: per cell the OPEN nodes in ascending node order; the cells of one grid row are neighbours;
@@ -34,26 +34,20 @@
 #include <cmath>
 
 #include "ba_obs.h"
-#include "dense_solve.h"
-#include "map_dev.h"
+#include "map_host.h"
 
 namespace {
 
 using gh_map::kBlock;
+using gh_map::kMaxLevels;
 
 constexpr int kCellPixels = 32;
 constexpr int kMaxGridSide = 64;   // at most 64 x 64 cells per frame, and never more cells than the frame has rows
 constexpr int kGroupLanes = 8;
-constexpr int kMaxLevels = 32;
-constexpr int kSpareBins = 4096;   // a power of two: where the nodes that are not indexed are counted
 constexpr int kVerdicts = 10;      // HELD BEHIND OUTSIDE RANGE ANGLE NO_CANDIDATE WEAK RATIO LOST WON
 constexpr int kProposed = 8;       // the LOST column counts the proposals until sproj_finish subtracts WON
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 constexpr unsigned long long kNoProposal = ~0ull;
-
-struct PowTable {
-  double v[kMaxLevels];  // v[l] = scale_factor^l, built on the host by repeated multiplication
-};
 
 struct Grid {
   int gx, gy, stride;  // gx * gy <= stride cells of a frame are in use; the keys of frame f start at f * stride
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void sproj_grid_kernel(SearchArgs a) {
   if (n >= a.N) return;
   a.proposal[n] = kNoProposal;
   const int f = n / a.cap, i = n - f * a.cap;
-  int key = a.n_frames * a.grid.stride + (n & a.spare_mask);
+  int key = gh_map::spare_key(a.n_frames * a.grid.stride, n, a.spare_mask);
   if (a.frame_search[f] != 0 && i < gh_map::row_count(a.counts, f, a.cap)) {
     const int p = taken_point(a, n);
     if (p >= 0) {
@@ -176,7 +170,7 @@ __device__ __forceinline__ void keep_two(uint32_t key, uint32_t& best, uint32_t&
   second = larger < second ? larger : second;
 }
 
-__global__ __launch_bounds__(kBlock) void sproj_search_kernel(SearchArgs a, PowTable pw) {
+__global__ __launch_bounds__(kBlock) void sproj_search_kernel(SearchArgs a, gh_map::ScalePowers pw) {
   __shared__ double s_pow[kMaxLevels];
   if (threadIdx.x < kMaxLevels) s_pow[threadIdx.x] = pw.v[threadIdx.x];
   __syncthreads();
@@ -287,10 +281,8 @@ __global__ __launch_bounds__(kBlock) void sproj_search_kernel(SearchArgs a, PowT
             const int oct = kp.octave;
             if (!(sl - 1 <= oct && oct <= sl)) continue;
             if (!(fabs((double)kp.x - su) < sr && fabs((double)kp.y - sv) < sr)) continue;
-            const uint32_t* dn = a.desc + (size_t)n * 8;
-            int h = 0;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) h += __popc(dn[w] ^ pd[w]);
+            const uint32_t(&dn)[8] = *(const uint32_t(*)[8])(a.desc + (size_t)n * 8);  // (read in place, word by word)
+            const int h = gh_map::hamming256(dn, pd);
             keep_two(((uint32_t)h << 16) | (uint32_t)(n - f * a.cap), best, second);
           }
         }
@@ -442,7 +434,7 @@ extern "C" gh_status gh_search_projection_dev(gh_ctx* ctx, const gh_keypoint* kp
   GH_CHECK_ARG(ctx, row_point_dev && row_inlier_dev && row_dist_dev && frame_totals_dev && totals_dev);
   GH_CHECK_ARG(ctx, n_points == 0 || (point_xyz_dev && point_views_dev && point_desc_dev && point_normal_dev && point_dist_dev));
   GH_CHECK_ARG(ctx, (row_point_in_dev == nullptr) == (row_inlier_in_dev == nullptr));
-  GH_CHECK_ARG(ctx, (((uintptr_t)desc_dev | (uintptr_t)point_desc_dev) & 3) == 0);  // descriptors move as 32-bit words
+  GH_CHECK_ARG(ctx, gh_map::word_aligned(desc_dev, point_desc_dev));
   const int N = n_frames * cap;
 
   GH_HIP(ctx, hipMemsetAsync(totals_dev, 0, 12 * sizeof(int32_t), ctx->stream));
@@ -483,15 +475,15 @@ extern "C" gh_status gh_search_projection_dev(gh_ctx* ctx, const gh_keypoint* kp
   // scratch: searched frames | HELD tables | proposals | keys | the index's work space.  The stride of a frame's keys depends
   // on cap = N / n_frames alone, so the size is a function of N, n_points and n_frames whatever the image is.
   const long long frame_keys = (long long)n_frames * a.grid.stride;  // (<= N)
-  const int spare = frame_keys <= (long long)INT32_MAX - 1 - kSpareBins ? kSpareBins : 1;
+  const int spare = gh_map::spare_bins(frame_keys);
   const int n_keys = (int)frame_keys + spare;
   a.spare_mask = spare - 1;
   gh_carve c;
   const size_t o_flist = c.take((size_t)n_frames * 4);
   char* base = nullptr;
   if (n_points > 0) {
-    const size_t work_bytes = gh_csr_index_bytes(ctx, N, n_keys);
-    if (!work_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_search_projection_dev: rocPRIM size query failed");
+    size_t work_bytes = 0;
+    GH_TRY(gh_map::index_bytes(ctx, "gh_search_projection_dev", N, n_keys, &work_bytes));
     const size_t o_held = c.take((size_t)N * 2 * 4), o_prop = c.take((size_t)N * 8), o_keys = c.take((size_t)N * 4),
                  o_work = c.take(work_bytes);
     GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
@@ -502,19 +494,14 @@ extern "C" gh_status gh_search_projection_dev(gh_ctx* ctx, const gh_keypoint* kp
     GH_LAUNCH(ctx, "sproj_frames", sproj_frames_kernel, dim3(1), dim3(kBlock), 0, frame_search_dev, n_frames, a.flist, totals_dev);
     GH_HIP(ctx, hipMemsetAsync(a.held, 0xFF, (size_t)N * 2 * 4, ctx->stream));
     GH_LAUNCH(ctx, "sproj_grid", sproj_grid_kernel, dim3(gh_div_up(N, kBlock)), dim3(kBlock), 0, a);
-    const int prof = gh_prof_begin(ctx, "sproj_index");
-    const gh_status st = gh_csr_index_dev(ctx, a.key, N, n_keys, base + o_work, work_bytes, &a.start, &a.list, nullptr);
-    gh_prof_end(ctx, prof);
-    GH_TRY(st);
+    GH_TRY(gh_map::build_index(ctx, "sproj_index", a.key, N, n_keys, base + o_work, work_bytes, &a.start, &a.list));  // (N > 0)
 
-    PowTable pw;
-    pw.v[0] = 1.0;
-    for (int l = 1; l < kMaxLevels; ++l) pw.v[l] = pw.v[l - 1] * params->scale_factor;
     // the frames of a call are spread over the y dimension where the points alone do not fill the device
     const int bx = gh_div_up(n_points, kBlock);
     int by = 2048 / bx;
     by = by < 1 ? 1 : (by > n_frames ? n_frames : by);
-    GH_LAUNCH(ctx, "sproj_search", sproj_search_kernel, dim3(bx, by), dim3(kBlock), 0, a, pw);
+    GH_LAUNCH(ctx, "sproj_search", sproj_search_kernel, dim3(bx, by), dim3(kBlock), 0, a,
+              gh_map::scale_powers(params->scale_factor));
   } else {
     GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
     a.flist = (int32_t*)(base + o_flist);

@@ -28,12 +28,13 @@
 #include <climits>
 
 #include "ba_obs.h"
-#include "dense_solve.h"
+#include "map_host.h"
 
 namespace {
 
+using gh_map::kBlock;
+
 constexpr int kGroupLanes = 8;
-constexpr int kBlock = 256;
 constexpr int kPointsPerBlock = kBlock / kGroupLanes;
 constexpr double kMinPivot = 1e-12;
 constexpr int kRunning = -1, kConverged = -2;  // inside the kernel only: rounds go on / all live observations good, parallax pending
@@ -60,10 +61,10 @@ struct Ray {
   double d[3];     // unit ray in the world
 };
 
-__global__ __launch_bounds__(256) void tracks_keys_kernel(const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_point,
-                                                          const uint8_t* __restrict__ obs_use, int n_obs, int n_cams, int n_points,
-                                                          int32_t* __restrict__ key, uint8_t* __restrict__ obs_good) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void tracks_keys_kernel(const int32_t* __restrict__ obs_cam, const int32_t* __restrict__ obs_point,
+                                                             const uint8_t* __restrict__ obs_use, int n_obs, int n_cams, int n_points,
+                                                             int32_t* __restrict__ key, uint8_t* __restrict__ obs_good) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n_obs) return;
   const int c = obs_cam[i], p = obs_point[i];
   const bool usable = (!obs_use || obs_use[i] != 0) && c >= 0 && c < n_cams && p >= 0 && p < n_points;
@@ -306,29 +307,20 @@ extern "C" gh_status gh_triangulate_tracks_dev(gh_ctx* ctx, const double* cam_po
   GH_CHECK_ARG(ctx, cam_pose_dev && obs_cam_dev && obs_point_dev && obs_xy_dev);
   GH_CHECK_ARG(ctx, point_xyz_dev && status_dev && n_good_dev && obs_good_dev);
 
-  // scratch: keys | the index's work space (start and list live there); without observations only an all-zero start
+  // scratch: keys | the index's work space (start and list live there).  One spare bin, not gh_map::spare_bins: DESIGN.md 6
   const int n_keys = n_points + 1;
-  const size_t o_work = gh_round256((size_t)n_obs * 4);
-  size_t work_bytes = gh_round256(((size_t)n_keys + 1) * 4);
-  if (n_obs > 0) {
-    work_bytes = gh_csr_index_bytes(ctx, n_obs, n_keys);
-    if (!work_bytes) return gh_set_error(ctx, GH_ERR_HIP, "gh_triangulate_tracks_dev: rocPRIM size query failed");
-  }
-  void* base = nullptr;
-  GH_TRY(gh_scratch(ctx, o_work + work_bytes, &base));
-  const int32_t *start = nullptr, *list = nullptr;
-  if (n_obs > 0) {
-    int32_t* keys = (int32_t*)base;
-    GH_LAUNCH(ctx, "tracks_keys", tracks_keys_kernel, dim3(gh_div_up(n_obs, 256)), dim3(256), 0, obs_cam_dev, obs_point_dev,
+  size_t work_bytes = 0;
+  GH_TRY(gh_map::index_bytes(ctx, "gh_triangulate_tracks_dev", n_obs, n_keys, &work_bytes));
+  gh_carve c;
+  const size_t o_keys = c.take((size_t)n_obs * 4), o_work = c.take(work_bytes);
+  char* base = nullptr;
+  GH_TRY(gh_scratch(ctx, c.at, (void**)&base));
+  int32_t* keys = (int32_t*)(base + o_keys);
+  if (n_obs > 0)
+    GH_LAUNCH(ctx, "tracks_keys", tracks_keys_kernel, dim3(gh_div_up(n_obs, kBlock)), dim3(kBlock), 0, obs_cam_dev, obs_point_dev,
               obs_use_dev, n_obs, n_cams, n_points, keys, obs_good_dev);
-    const int prof = gh_prof_begin(ctx, "tracks_index");
-    const gh_status st = gh_csr_index_dev(ctx, keys, n_obs, n_keys, (char*)base + o_work, work_bytes, &start, &list, nullptr);
-    gh_prof_end(ctx, prof);
-    GH_TRY(st);
-  } else {
-    GH_HIP(ctx, hipMemsetAsync((char*)base + o_work, 0, work_bytes, ctx->stream));
-    start = (const int32_t*)((char*)base + o_work);
-  }
+  const int32_t *start = nullptr, *list = nullptr;
+  GH_TRY(gh_map::build_index(ctx, "tracks_index", keys, n_obs, n_keys, base + o_work, work_bytes, &start, &list));
 
   TrackArgs a = {};
   a.cam_pose = cam_pose_dev;

@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import hip
+from .devargs import alloc, defaults, dev, keypoints, pair_arrays, pinhole, ptr, ptr_array, ptr_opt, require
 
 HOMOGRAPHY, AFFINE2D, FUNDAMENTAL, AFFINE3D, ESSENTIAL, SIM3, PLANE, PNP = 0, 1, 2, 3, 4, 5, 6, 7
 TWO_VIEW_OK, TWO_VIEW_NO_MODEL, TWO_VIEW_TOO_FEW, TWO_VIEW_AMBIGUOUS = 0, 1, 2, 3  # GH_TWO_VIEW_*: status per problem
@@ -68,10 +69,6 @@ def estimate(ctx: hip.Context, model, src, dst, threshold, seed=1):
                           with_used=False)
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def batch_tile_rows(model):
     """gh_ransac_batch_tile_rows: correspondences the batched scoring kernel stages at a time (<= 0: unknown model)."""
     return int(hip.lib.gh_ransac_batch_tile_rows(int(model)))
@@ -82,34 +79,28 @@ def estimate_batch(ctx: hip.Context, model, src, dst, offsets, threshold, seed, 
     offsets[p] .. offsets[p + 1] - 1; thresholds (float64) / seeds (int64 holding the uint64 bits) per problem or None for
     the scalars.  -> (models nproblems x 12 float64, mask rows uint8, inliers nproblems int32), all on the device; nothing
     is synchronised.  Problem p equals estimate(ctx, model, src_p, dst_p, threshold_p, seed_p)."""
-    import torch
-    assert src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == torch.float64 and src.is_contiguous() and dst.is_contiguous()
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
-    assert thresholds is None or (thresholds.is_cuda and thresholds.dtype == torch.float64 and thresholds.is_contiguous())
-    assert seeds is None or (seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous())
+    dev("src", src, "float64")
+    dev("dst", dst, "float64")
+    dev("offsets", offsets, "int32")
+    require(offsets.numel() >= 1, "offsets: empty, expected nproblems + 1 entries")
     n = offsets.numel() - 1
-    assert (thresholds is None or thresholds.numel() == n) and (seeds is None or seeds.numel() == n)
-    models = torch.empty((n, 12), dtype=torch.float64, device=src.device)
-    mask = torch.zeros(src.shape[0], dtype=torch.uint8, device=src.device)  # (rows past offsets[n], if any, belong to nobody)
-    inliers = torch.empty(n, dtype=torch.int32, device=src.device)
-    ctx.check(hip.lib.gh_ransac_batch_dev(ctx.h, int(model), _p(src), _p(dst), _p(offsets), n, C.c_double(threshold), _p(thresholds),
-                                          C.c_uint64(seed), _p(seeds), _p(models), _p(mask), _p(inliers)))
-    return models, mask, inliers
+    dev("thresholds", thresholds, "float64", n, optional=True)
+    dev("seeds", seeds, "int64", n, optional=True)
+    out = alloc(src.device, {"models": ((n, 12), "float64"),
+                             "mask": (src.shape[0], "uint8", True),  # (rows past offsets[n], if any, belong to nobody)
+                             "inliers": (n, "int32")})
+    ctx.check(hip.lib.gh_ransac_batch_dev(ctx.h, int(model), ptr(src), ptr(dst), ptr(offsets), n, C.c_double(threshold),
+                                          ptr(thresholds), C.c_uint64(seed), ptr(seeds), *map(ptr, out.values())))
+    return tuple(out.values())
 
 
 def _pair_io(kps, counts, pair_q, pair_t, idx1, keep):
     """The inputs of the pair entries, checked, and the output tensors both have, in the order of the C arguments
     -> (P, cap, out)."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
-    P, cap = pair_q.shape[0], kps.shape[1]
-    assert pair_t.shape[0] == P and idx1.numel() == P * cap
-    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
-    out = {"models": torch.empty((P, 12), dtype=torch.float64, device=kps.device),
-           "inlier": torch.empty((P, cap), dtype=torch.uint8, device=kps.device),
-           "n_corr": torch.empty(P, dtype=torch.int32, device=kps.device),
-           "inliers": torch.empty(P, dtype=torch.int32, device=kps.device)}
+    F, cap = keypoints(kps)
+    P = pair_arrays(counts, F, cap, pair_q, pair_t, idx1, keep)
+    out = alloc(kps.device, {"models": ((P, 12), "float64"), "inlier": ((P, cap), "uint8"),
+                             "n_corr": (P, "int32"), "inliers": (P, "int32")})
     return P, cap, out
 
 
@@ -119,8 +110,8 @@ def estimate_pairs(ctx: hip.Context, model, kps, counts, pair_q, pair_t, idx1, k
     model: HOMOGRAPHY, AFFINE2D or FUNDAMENTAL.  -> (models P x 12, inlier P x cap uint8, n_corr P int32, inliers P int32)
     on the device; pair p equals estimate() on the rows correspondences_from_matches lists for it."""
     P, cap, out = _pair_io(kps, counts, pair_q, pair_t, idx1, keep)
-    ctx.check(hip.lib.gh_ransac_pairs_dev(ctx.h, int(model), _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
-                                          C.c_double(threshold), C.c_uint64(seed), *(_p(out[k]) for k in out)))
+    ctx.check(hip.lib.gh_ransac_pairs_dev(ctx.h, int(model), ptr(kps), ptr(counts), cap, ptr(pair_q), ptr(pair_t), P, ptr(idx1),
+                                          ptr(keep), C.c_double(threshold), C.c_uint64(seed), *map(ptr, out.values())))
     return tuple(out.values())
 
 
@@ -153,9 +144,7 @@ def correspondences_from_matches(kps, counts, pair_q, pair_t, idx1, keep=None):
 
 def two_view_default_params():
     """gh_two_view_default_params -> hip.TwoViewParams (min_parallax_cos, max_reproj, min_good, min_good_permille)."""
-    p = hip.TwoViewParams()
-    hip.lib.gh_two_view_default_params(C.byref(p))
-    return p
+    return defaults(None, hip.TwoViewParams, hip.lib.gh_two_view_default_params)
 
 
 def two_view_batch(ctx: hip.Context, E, src, dst, offsets, mask=None, params=None):
@@ -164,24 +153,21 @@ def two_view_batch(ctx: hip.Context, E, src, dst, offsets, mask=None, params=Non
     take part).  -> (poses nproblems x 7 [qx qy qz qw tx ty tz] ref -> cur, points rows x 3 in the reference frame, good rows
     uint8, counts nproblems x 4 int32, n_used nproblems int32, status nproblems int32: TWO_VIEW_*), all on the device;
     nothing is synchronised."""
-    import torch
-    assert E.is_cuda and E.dtype == torch.float64 and E.is_contiguous() and E.dim() == 2 and E.shape[1] >= 9
-    assert src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == torch.float64 and src.is_contiguous() and dst.is_contiguous()
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == E.shape[0] + 1
-    rows = src.shape[0]
-    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == rows)
-    n = E.shape[0]
-    prm = params if params is not None else two_view_default_params()
-    dev = src.device
-    poses = torch.empty((n, 7), dtype=torch.float64, device=dev)
-    points = torch.zeros((rows, 3), dtype=torch.float64, device=dev)  # (rows past offsets[n], if any, belong to nobody)
-    good = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    counts = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    n_used = torch.empty(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    ctx.check(hip.lib.gh_two_view_batch_dev(ctx.h, _p(E), int(E.shape[1]), _p(src), _p(dst), _p(offsets), n, _p(mask), C.byref(prm),
-                                            _p(poses), _p(points), _p(good), _p(counts), _p(n_used), _p(status)))
-    return poses, points, good, counts, n_used, status
+    dev("E", E, "float64")
+    require(E.dim() == 2 and E.shape[1] >= 9, "E: shape %s, expected nproblems x e_stride with e_stride >= 9" % (tuple(E.shape),))
+    dev("src", src, "float64")
+    dev("dst", dst, "float64")
+    n, rows = E.shape[0], src.shape[0]
+    dev("offsets", offsets, "int32", n + 1)
+    dev("mask", mask, "uint8", rows, optional=True)
+    prm = defaults(params, hip.TwoViewParams, hip.lib.gh_two_view_default_params)
+    out = alloc(src.device, {"poses": ((n, 7), "float64"),
+                             "points": ((rows, 3), "float64", True),  # (rows past offsets[n], if any, belong to nobody)
+                             "good": (rows, "uint8", True), "counts": ((n, 4), "int32"),
+                             "n_used": (n, "int32"), "status": (n, "int32")})
+    ctx.check(hip.lib.gh_two_view_batch_dev(ctx.h, ptr(E), int(E.shape[1]), ptr(src), ptr(dst), ptr(offsets), n, ptr(mask),
+                                            C.byref(prm), *map(ptr, out.values())))
+    return tuple(out.values())
 
 
 def two_view_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, intrinsics, threshold, seed, params=None):
@@ -190,19 +176,13 @@ def two_view_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, in
     -> dict of device tensors: models P x 12, inlier P x cap uint8, n_corr P, inliers P, poses P x 7, points P x cap x 3,
     good P x cap uint8, votes P x 4 (the four candidate counts), status P.  Pair p equals estimate_batch(ESSENTIAL) and
     two_view_batch on the normalised rows correspondences_from_matches lists for it, scattered back to query rows."""
-    import torch
     P, cap, out = _pair_io(kps, counts, pair_q, pair_t, idx1, keep)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    prm = params if params is not None else two_view_default_params()
-    dev = kps.device
-    out.update({"poses": torch.empty((P, 7), dtype=torch.float64, device=dev),
-                "points": torch.empty((P, cap, 3), dtype=torch.float64, device=dev),
-                "good": torch.empty((P, cap), dtype=torch.uint8, device=dev),
-                "votes": torch.empty((P, 4), dtype=torch.int32, device=dev),
-                "status": torch.empty(P, dtype=torch.int32, device=dev)})
-    ctx.check(hip.lib.gh_two_view_pairs_dev(ctx.h, _p(kps), _p(counts), cap, _p(pair_q), _p(pair_t), P, _p(idx1), _p(keep),
-                                            C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(threshold),
-                                            C.c_uint64(seed), C.byref(prm), *(_p(out[k]) for k in out)))
+    prm = defaults(params, hip.TwoViewParams, hip.lib.gh_two_view_default_params)
+    out.update(alloc(kps.device, {"poses": ((P, 7), "float64"), "points": ((P, cap, 3), "float64"),
+                                  "good": ((P, cap), "uint8"), "votes": ((P, 4), "int32"), "status": (P, "int32")}))
+    ctx.check(hip.lib.gh_two_view_pairs_dev(ctx.h, ptr(kps), ptr(counts), cap, ptr(pair_q), ptr(pair_t), P, ptr(idx1), ptr(keep),
+                                            *pinhole(intrinsics), C.c_double(threshold), C.c_uint64(seed), C.byref(prm),
+                                            *map(ptr, out.values())))
     return out
 
 
@@ -219,35 +199,29 @@ def pnp_pose_from_model(model):
     return pose, bool(ok)
 
 
-def _ba_options(options):
-    if options is not None:
-        return options
-    o = hip.BaOptions()
-    hip.lib.gh_ba_default_options(C.byref(o))
-    return o
+def _pnp_outputs(n, want_information, chain):
+    """The outputs of a PnP batch of n problems, without the row bytes (chain: with the fit's outputs in front and a summary per
+    round), in the order of the C arguments."""
+    size = C.sizeof(hip.PnpBatchSummary)
+    spec = {"models": ((n, 12), "float64"), "ransac_inliers": (n, "int32")} if chain else {}
+    spec.update({"poses": ((n, 7), "float64"), "info": ((n, 36), "float64") if want_information else None,
+                 "summaries": ((n, 2, size) if chain else (n, size), "uint8")})
+    return spec
 
 
 def _pnp_io(xyz, xy, offsets, want_information, chain=False):
     """The inputs both PnP batch entries share, checked, and their output tensors in the order of the C arguments (chain: with
     the fit's outputs in front and a summary per round) -> (nproblems, rows, out)."""
-    import torch
-    assert xyz.is_cuda and xy.is_cuda and xyz.dtype == xy.dtype == torch.float64 and xyz.is_contiguous() and xy.is_contiguous()
-    rows = xyz.shape[0]
-    assert xyz.numel() == 3 * rows and xy.numel() == 2 * rows
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    rows = dev("xyz", xyz, "float64").shape[0]
+    require(xyz.numel() == 3 * rows, "xyz: shape %s, expected rows x 3" % (tuple(xyz.shape),))
+    dev("xy", xy, "float64", 2 * rows)
+    dev("offsets", offsets, "int32")
+    require(offsets.numel() >= 1, "offsets: empty, expected nproblems + 1 entries")
     n = offsets.numel() - 1
-    dev = xyz.device
-    out = {}
-    if chain:
-        out["models"] = torch.empty((n, 12), dtype=torch.float64, device=dev)
-        out["ransac_inliers"] = torch.empty(n, dtype=torch.int32, device=dev)
-    size = C.sizeof(hip.PnpBatchSummary)
-    out.update({"poses": torch.empty((n, 7), dtype=torch.float64, device=dev),
-                "info": torch.empty((n, 36), dtype=torch.float64, device=dev) if want_information else None,
-                "summaries": torch.empty((n, 2, size) if chain else (n, size), dtype=torch.uint8, device=dev),
-                "inlier": torch.zeros(rows, dtype=torch.uint8, device=dev),  # (rows no range owns belong to nobody)
-                "n_inliers": torch.empty(n, dtype=torch.int32, device=dev)})
-    return n, rows, out
+    spec = _pnp_outputs(n, want_information, chain)
+    spec.update({"inlier": (rows, "uint8", True),  # (rows no range owns belong to nobody)
+                 "n_inliers": (n, "int32")})
+    return n, rows, alloc(xyz.device, spec)
 
 
 def pnp_refine_batch(ctx: hip.Context, xyz, xy, offsets, start, mask=None, dof=63, options=None, min_rows=0,
@@ -257,15 +231,15 @@ def pnp_refine_batch(ctx: hip.Context, xyz, xy, offsets, start, mask=None, dof=6
     options: hip.BaOptions or None for the defaults.  -> dict of device tensors: poses nproblems x 7, info nproblems x 36 or
     None, summaries nproblems x 32 uint8 (view the host copy as SUMMARY_DTYPE), inlier rows uint8, n_inliers nproblems int32;
     nothing is synchronised.  A problem that is optimised equals ba.pnp on its participating rows, bit for bit."""
-    import torch
     n, rows, out = _pnp_io(xyz, xy, offsets, want_information)
-    assert start.is_cuda and start.dtype == torch.float64 and start.is_contiguous() and start.dim() == 2 and start.shape[0] == n
-    assert start.shape[1] in (7, 12)
-    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == rows)
-    opt = _ba_options(options)
-    ctx.check(hip.lib.gh_pnp_refine_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, _p(mask), _p(start), int(start.shape[1]),
-                                              int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
-                                              *(_p(out[k]) for k in out)))
+    dev("start", start, "float64")
+    require(start.dim() == 2 and start.shape[0] == n and start.shape[1] in (7, 12),
+            "start: shape %s, expected %d x 7 or %d x 12" % (tuple(start.shape), n, n))
+    dev("mask", mask, "uint8", rows, optional=True)
+    opt = defaults(options, hip.BaOptions, hip.lib.gh_ba_default_options)
+    ctx.check(hip.lib.gh_pnp_refine_batch_dev(ctx.h, ptr(xyz), ptr(xy), ptr(offsets), n, rows, ptr(mask), ptr(start),
+                                              int(start.shape[1]), int(dof), C.byref(opt), int(min_rows),
+                                              C.c_double(inlier_threshold), *map(ptr, out.values())))
     return out
 
 
@@ -276,18 +250,16 @@ def pnp_batch(ctx: hip.Context, xyz, xy, offsets, ransac_threshold, seed, inlier
     models nproblems x 12, ransac_inliers nproblems, poses nproblems x 7, info nproblems x 36 or None, summaries
     nproblems x 2 x 32 uint8 (round 1, round 2), inlier rows uint8, n_inliers nproblems; nothing is synchronised."""
     n, rows, out = _pnp_io(xyz, xy, offsets, want_information, chain=True)
-    opt = _ba_options(options)
-    ctx.check(hip.lib.gh_pnp_batch_dev(ctx.h, _p(xyz), _p(xy), _p(offsets), n, rows, C.c_double(ransac_threshold), C.c_uint64(seed),
-                                       int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
-                                       *(_p(out[k]) for k in out)))
+    opt = defaults(options, hip.BaOptions, hip.lib.gh_ba_default_options)
+    ctx.check(hip.lib.gh_pnp_batch_dev(ctx.h, ptr(xyz), ptr(xy), ptr(offsets), n, rows, C.c_double(ransac_threshold),
+                                       C.c_uint64(seed), int(dof), C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
+                                       *map(ptr, out.values())))
     return out
 
 
 def track_default_params():
     """gh_track_default_params -> hip.TrackParams (min_parallax_cos, max_reproj, min_views, max_drops)."""
-    p = hip.TrackParams()
-    hip.lib.gh_track_default_params(C.byref(p))
-    return p
+    return defaults(None, hip.TrackParams, hip.lib.gh_track_default_params)
 
 
 def track_group_lanes():
@@ -303,29 +275,34 @@ def triangulate_tracks(ctx: hip.Context, cam_pose, obs_cam, obs_point, obs_xy, n
     place (the points that are not selected keep their values) or None for a zeroed one.  -> dict of device tensors:
     point_xyz n_points x 3, status n_points int32 (TRACK_*), n_good n_points int32, obs_good n_obs uint8; nothing is
     synchronised."""
-    import torch
-    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() % 7 == 0
-    assert obs_xy.is_cuda and obs_xy.dtype == torch.float64 and obs_xy.is_contiguous()
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (obs_cam, obs_point))
-    n_cams, n_obs, n_points = cam_pose.numel() // 7, obs_cam.numel(), int(n_points)
-    assert obs_point.numel() == n_obs and obs_xy.numel() == 2 * n_obs and n_points >= 0
-    assert obs_use is None or (obs_use.is_cuda and obs_use.dtype == torch.uint8 and obs_use.is_contiguous() and obs_use.numel() == n_obs)
-    assert point_select is None or (point_select.is_cuda and point_select.dtype == torch.uint8 and point_select.is_contiguous() and
-                                    point_select.numel() == n_points)
-    dev = cam_pose.device
-    if point_xyz is None:
-        point_xyz = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
-    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
-    prm = params if params is not None else track_default_params()
-    out = {"point_xyz": point_xyz,
-           "status": torch.empty(n_points, dtype=torch.int32, device=dev),
-           "n_good": torch.empty(n_points, dtype=torch.int32, device=dev),
-           "obs_good": torch.empty(n_obs, dtype=torch.uint8, device=dev)}
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_triangulate_tracks_dev(ctx.h, p(cam_pose), n_cams, p(obs_cam), p(obs_point), p(obs_xy), n_obs, n_points,
-                                                _p(obs_use), _p(point_select), C.byref(prm), *(p(out[k]) for k in out)))
+    n_cams = dev("cam_pose", cam_pose, "float64", multiple_of=7).numel() // 7
+    n_obs, n_points = dev("obs_cam", obs_cam, "int32").numel(), int(n_points)
+    require(n_points >= 0, "n_points: %d" % n_points)
+    dev("obs_point", obs_point, "int32", n_obs)
+    dev("obs_xy", obs_xy, "float64", 2 * n_obs)
+    dev("obs_use", obs_use, "uint8", n_obs, optional=True)
+    dev("point_select", point_select, "uint8", n_points, optional=True)
+    dev("point_xyz", point_xyz, "float64", 3 * n_points, optional=True)
+    prm = defaults(params, hip.TrackParams, hip.lib.gh_track_default_params)
+    out = alloc(cam_pose.device, {"point_xyz": ((n_points, 3), "float64", True) if point_xyz is None else point_xyz,
+                                  "status": (n_points, "int32"), "n_good": (n_points, "int32"),
+                                  "obs_good": (n_obs, "uint8")})
+    ctx.check(hip.lib.gh_triangulate_tracks_dev(ctx.h, ptr_array(cam_pose), n_cams, ptr_array(obs_cam), ptr_array(obs_point),
+                                                ptr_array(obs_xy), n_obs, n_points, ptr(obs_use), ptr(point_select), C.byref(prm),
+                                                *map(ptr_array, out.values())))
     return out
+
+
+def _pair_args(counts, F, cap, pair_q, pair_t, P, idx1, mask):
+    """The C arguments counts .. keep / inlier of the map entries: the arrays are wanted even when they hold nothing, the mask
+    is NULL when it is not given."""
+    return ptr_array(counts), F, cap, ptr_array(pair_q), ptr_array(pair_t), P, ptr_array(idx1), ptr(mask)
+
+
+def _obs_outputs(N):
+    """The node labels and the observation list that link_tracks and extend_tracks write, in the order of the C arguments."""
+    return {"node_point": (N, "int32"), "obs_cam": (N, "int32"), "obs_point": (N, "int32"),
+            "obs_xy": ((N, 2), "float64"), "obs_node": (N, "int32")}
 
 
 def link_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, intrinsics, min_views=2):
@@ -337,49 +314,26 @@ def link_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, int
     int32, totals 4 int32 (n_obs, n_points, CONFLICT components, SHORT components of two nodes or more); nothing is
     synchronised and nothing is read back: obs_cam, obs_point, obs_xy go to triangulate_tracks as they are, with
     n_points = N // 2."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
-    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
-    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap
-    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    N, dev = F * cap, kps.device
-    out = {"node_point": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_cam": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_point": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
-           "obs_node": torch.empty(N, dtype=torch.int32, device=dev),
-           "point_len": torch.empty(N // 2, dtype=torch.int32, device=dev),
-           "totals": torch.empty(4, dtype=torch.int32, device=dev)}
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_link_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
-                                         C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), int(min_views),
-                                         *(p(out[k]) for k in out)))
+    F, cap = keypoints(kps)
+    P = pair_arrays(counts, F, cap, pair_q, pair_t, idx1, inlier, "inlier")
+    N = F * cap
+    out = alloc(kps.device, {**_obs_outputs(N), "point_len": (N // 2, "int32"), "totals": (4, "int32")})
+    ctx.check(hip.lib.gh_link_tracks_dev(ctx.h, ptr_array(kps), *_pair_args(counts, F, cap, pair_q, pair_t, P, idx1, inlier),
+                                         *pinhole(intrinsics), int(min_views), *map(ptr_array, out.values())))
     return out
 
 
 def _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status):
     """The inputs of the two map entries, checked, and the gather's output tensors in the order of the C arguments
     -> (F, cap, P, n_points, out)."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1, node_point))
-    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
-    N, dev = F * cap, kps.device
-    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap and node_point.numel() == N
-    assert keep is None or (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.numel() == P * cap)
-    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() % 3 == 0
-    n_points = point_xyz.numel() // 3
-    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
-                                    point_status.numel() == n_points)
-    out = {"row_point": torch.empty(N, dtype=torch.int32, device=dev),
-           "offsets": torch.empty(F + 1, dtype=torch.int32, device=dev),
-           "xyz": torch.empty((N, 3), dtype=torch.float64, device=dev),
-           "xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
-           "corr_node": torch.empty(N, dtype=torch.int32, device=dev),
-           "totals": torch.empty(4, dtype=torch.int32, device=dev)}
+    F, cap = keypoints(kps)
+    P = pair_arrays(counts, F, cap, pair_q, pair_t, idx1, keep)
+    N = F * cap
+    dev("node_point", node_point, "int32", N)
+    n_points = dev("point_xyz", point_xyz, "float64", multiple_of=3).numel() // 3
+    dev("point_status", point_status, "int32", n_points, optional=True)
+    out = alloc(kps.device, {"row_point": (N, "int32"), "offsets": (F + 1, "int32"), "xyz": ((N, 3), "float64"),
+                             "xy": ((N, 2), "float64"), "corr_node": (N, "int32"), "totals": (4, "int32")})
     return F, cap, P, n_points, out
 
 
@@ -393,12 +347,9 @@ def gather_map_matches(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep
     totals 4 int32 (n_corr, AMBIGUOUS nodes, SHARED nodes, frames with a correspondence); nothing is synchronised and nothing is
     read back: xyz, xy, offsets go to pnp_batch as they are."""
     F, cap, P, n_points, out = _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_pnp_gather_pairs_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(keep),
-                                              p(node_point), n_points, p(point_xyz), _p(point_status), C.c_double(fx),
-                                              C.c_double(fy), C.c_double(cx), C.c_double(cy), *(p(out[k]) for k in out)))
+    ctx.check(hip.lib.gh_pnp_gather_pairs_dev(ctx.h, ptr_array(kps), *_pair_args(counts, F, cap, pair_q, pair_t, P, idx1, keep),
+                                              ptr_array(node_point), n_points, ptr_array(point_xyz), ptr(point_status),
+                                              *pinhole(intrinsics), *map(ptr_array, out.values())))
     return out
 
 
@@ -410,22 +361,15 @@ def localize_pairs(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, keep, no
     totals), then models F x 12, ransac_inliers F, poses F x 7, info F x 36 or None, summaries F x 2 x 32 uint8 (view the host
     copy as SUMMARY_DTYPE), row_inlier F * cap uint8 (1 where the row's correspondence is an inlier of the last round); nothing
     is synchronised.  row_point and row_inlier are what extends the tracks with the new observations."""
-    import torch
     F, cap, P, n_points, out = _gather_io(kps, counts, pair_q, pair_t, idx1, keep, node_point, point_xyz, point_status)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    dev = kps.device
-    out.update({"models": torch.empty((F, 12), dtype=torch.float64, device=dev),
-                "ransac_inliers": torch.empty(F, dtype=torch.int32, device=dev),
-                "poses": torch.empty((F, 7), dtype=torch.float64, device=dev),
-                "info": torch.empty((F, 36), dtype=torch.float64, device=dev) if want_information else None,
-                "summaries": torch.empty((F, 2, C.sizeof(hip.PnpBatchSummary)), dtype=torch.uint8, device=dev),
-                "row_inlier": torch.empty(F * cap, dtype=torch.uint8, device=dev)})
-    opt = _ba_options(options)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_localize_pairs_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(keep),
-                                            p(node_point), n_points, p(point_xyz), _p(point_status), C.c_double(fx), C.c_double(fy),
-                                            C.c_double(cx), C.c_double(cy), C.c_double(ransac_threshold), C.c_uint64(seed), int(dof),
-                                            C.byref(opt), int(min_rows), C.c_double(inlier_threshold), *(p(out[k]) for k in out)))
+    out.update(alloc(kps.device, {**_pnp_outputs(F, want_information, chain=True), "row_inlier": (F * cap, "uint8")}))
+    opt = defaults(options, hip.BaOptions, hip.lib.gh_ba_default_options)
+    # (ptr_opt on the outputs: info is None when it was not asked for)
+    ctx.check(hip.lib.gh_localize_pairs_dev(ctx.h, ptr_array(kps), *_pair_args(counts, F, cap, pair_q, pair_t, P, idx1, keep),
+                                            ptr_array(node_point), n_points, ptr_array(point_xyz), ptr(point_status),
+                                            *pinhole(intrinsics), C.c_double(ransac_threshold), C.c_uint64(seed), int(dof),
+                                            C.byref(opt), int(min_rows), C.c_double(inlier_threshold),
+                                            *map(ptr_opt, out.values())))
     return out
 
 
@@ -441,36 +385,21 @@ def extend_tracks(ctx: hip.Context, kps, counts, pair_q, pair_t, idx1, inlier, n
     n_points_total, ADOPTED nodes, REJECTED nodes, CONFLICT components, SHORT components of two nodes or more); nothing is
     synchronised and nothing is read back: obs_cam, obs_point, obs_xy go to triangulate_tracks as they are, with n_points = PC
     and point_select = point_new (keep the map's status array apart: that call marks every old point TRACK_SKIPPED)."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1))
-    F, cap, P = kps.shape[0], kps.shape[1], pair_q.shape[0]
-    N, dev, n_points = F * cap, kps.device, int(n_points)
-    assert counts.numel() == F and pair_t.shape[0] == P and idx1.numel() == P * cap and n_points >= 0
-    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
-    assert node_point is None or (node_point.is_cuda and node_point.dtype == torch.int32 and node_point.is_contiguous() and
-                                  node_point.numel() == N)
-    assert (row_point is None) == (row_inlier is None)
-    assert row_point is None or (row_point.is_cuda and row_point.dtype == torch.int32 and row_point.is_contiguous() and
-                                 row_point.numel() == N and row_inlier.is_cuda and row_inlier.dtype == torch.uint8 and
-                                 row_inlier.is_contiguous() and row_inlier.numel() == N)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    F, cap = keypoints(kps)
+    P = pair_arrays(counts, F, cap, pair_q, pair_t, idx1, inlier, "inlier")
+    N, n_points = F * cap, int(n_points)
+    require(n_points >= 0, "n_points: %d" % n_points)
+    dev("node_point", node_point, "int32", N, optional=True)
+    require((row_point is None) == (row_inlier is None), "row_point and row_inlier: both or neither")
+    dev("row_point", row_point, "int32", N, optional=True)
+    dev("row_inlier", row_inlier, "uint8", N, optional=True)
     PC = n_points + N // 2
-    out = {"node_point": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_cam": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_point": torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_xy": torch.empty((N, 2), dtype=torch.float64, device=dev),
-           "obs_node": torch.empty(N, dtype=torch.int32, device=dev),
-           "point_len": torch.empty(PC, dtype=torch.int32, device=dev),
-           "point_new": torch.empty(PC, dtype=torch.uint8, device=dev),
-           "point_grew": torch.empty(PC, dtype=torch.uint8, device=dev),
-           "totals": torch.empty(6, dtype=torch.int32, device=dev)}
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    q = lambda t: None if t is None else p(t)  # (NULL means "not given" for these three, also when N == 0)
-    ctx.check(hip.lib.gh_extend_tracks_dev(ctx.h, p(kps), p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier),
-                                           q(node_point), n_points, q(row_point), q(row_inlier), C.c_double(fx), C.c_double(fy),
-                                           C.c_double(cx), C.c_double(cy), int(min_views), *(p(out[k]) for k in out)))
+    out = alloc(kps.device, {**_obs_outputs(N), "point_len": (PC, "int32"), "point_new": (PC, "uint8"),
+                             "point_grew": (PC, "uint8"), "totals": (6, "int32")})
+    # (ptr_opt: NULL means "not given" for these three, also when N == 0)
+    ctx.check(hip.lib.gh_extend_tracks_dev(ctx.h, ptr_array(kps), *_pair_args(counts, F, cap, pair_q, pair_t, P, idx1, inlier),
+                                           ptr_opt(node_point), n_points, ptr_opt(row_point), ptr_opt(row_inlier),
+                                           *pinhole(intrinsics), int(min_views), *map(ptr_array, out.values())))
     return out
 
 
@@ -489,42 +418,47 @@ def merge_points(ctx: hip.Context, counts, cap, pair_q, pair_t, idx1, inlier, no
     in CONFLICT or FAR groups); nothing is synchronised and nothing is read back: obs_cam / obs_xy of extend_tracks stay valid,
     and triangulate_tracks with point_select = point_select gives the survivors their coordinates from all of their
     observations."""
-    import torch
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, pair_q, pair_t, idx1, node_point))
-    F, cap, P = counts.numel(), int(cap), pair_q.shape[0]
-    N, dev, n_points = F * cap, counts.device, int(n_points)
-    assert pair_t.shape[0] == P and idx1.numel() == P * cap and node_point.numel() == N and n_points >= 0
-    assert inlier is None or (inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == P * cap)
-    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
-                                    point_status.numel() == n_points)
-    assert point_xyz is None or (point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and
-                                 point_xyz.numel() == 3 * n_points)
-    assert obs_point is None or (obs_point.is_cuda and obs_point.dtype == torch.int32 and obs_point.is_contiguous() and
-                                 obs_point.numel() == N)
-    out = {"point_remap": torch.empty(n_points, dtype=torch.int32, device=dev),
-           "point_state": torch.empty(n_points, dtype=torch.uint8, device=dev),
-           "point_select": torch.empty(n_points, dtype=torch.uint8, device=dev),
-           "node_point": node_point if in_place else torch.empty(N, dtype=torch.int32, device=dev),
-           "obs_point": None if obs_point is None else (obs_point if in_place else torch.empty(N, dtype=torch.int32, device=dev)),
-           "point_len": torch.empty(n_points, dtype=torch.int32, device=dev),
-           "totals": torch.empty(6, dtype=torch.int32, device=dev)}
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    q = lambda t: None if t is None else p(t)  # (NULL means "not given", also when the array holds nothing)
-    ctx.check(hip.lib.gh_merge_points_dev(ctx.h, p(counts), F, cap, p(pair_q), p(pair_t), P, p(idx1), _p(inlier), p(node_point),
-                                          n_points, q(point_status), q(point_xyz), C.c_double(float(max_dist)), 1 if bridge else 0,
-                                          q(obs_point), *(q(out[k]) for k in out)))
+    F, cap = dev("counts", counts, "int32").numel(), int(cap)
+    P = pair_arrays(counts, F, cap, pair_q, pair_t, idx1, inlier, "inlier")
+    N, n_points = F * cap, int(n_points)
+    require(n_points >= 0, "n_points: %d" % n_points)
+    dev("node_point", node_point, "int32", N)
+    dev("point_status", point_status, "int32", n_points, optional=True)
+    dev("point_xyz", point_xyz, "float64", 3 * n_points, optional=True)
+    dev("obs_point", obs_point, "int32", N, optional=True)
+    out = alloc(counts.device, {"point_remap": (n_points, "int32"), "point_state": (n_points, "uint8"),
+                                "point_select": (n_points, "uint8"),
+                                "node_point": node_point if in_place else (N, "int32"),
+                                "obs_point": obs_point if in_place or obs_point is None else (N, "int32"),
+                                "point_len": (n_points, "int32"), "totals": (6, "int32")})
+    # (ptr_opt: NULL means "not given", also when the array holds nothing; obs_point of the outputs is None with its input)
+    ctx.check(hip.lib.gh_merge_points_dev(ctx.h, *_pair_args(counts, F, cap, pair_q, pair_t, P, idx1, inlier),
+                                          ptr_array(node_point), n_points, ptr_opt(point_status), ptr_opt(point_xyz),
+                                          C.c_double(float(max_dist)), 1 if bridge else 0, ptr_opt(obs_point),
+                                          *map(ptr_opt, out.values())))
     return out
 
 
 def point_desc_default_params():
     """gh_point_desc_default_params -> hip.PointDescParams (scale_factor, n_levels, max_views)."""
-    p = hip.PointDescParams()
-    hip.lib.gh_point_desc_default_params(C.byref(p))
-    return p
+    return defaults(None, hip.PointDescParams, hip.lib.gh_point_desc_default_params)
 
 
 DESCRIBE_OUTPUTS = ("point_state", "point_desc", "point_obs", "point_views", "point_normal", "point_dist", "totals")
+
+
+def _frame_io(kps, desc, counts, cam_pose, n_points, point_xyz, point_status, point_select):
+    """The frame and point arrays describe_points and search_projection share, checked -> (F, cap, n_points)."""
+    F, cap = keypoints(kps)
+    n_points = int(n_points)
+    require(n_points >= 0, "n_points: %d" % n_points)
+    dev("desc", desc, "uint8", 32 * F * cap)
+    dev("counts", counts, "int32", F)
+    dev("cam_pose", cam_pose, "float64", 7 * F)
+    dev("point_xyz", point_xyz, "float64", 3 * n_points)
+    dev("point_status", point_status, "int32", n_points, optional=True)
+    dev("point_select", point_select, "uint8", n_points, optional=True)
+    return F, cap, n_points
 
 
 def describe_points(ctx: hip.Context, kps, desc, counts, cam_pose, obs_cam, obs_point, obs_node, n_points, point_xyz, obs_use=None,
@@ -542,45 +476,33 @@ def describe_points(ctx: hip.Context, kps, desc, counts, cam_pose, obs_cam, obs_
     observation, the reference observation), point_views n_points int32, point_normal n_points x 3 and point_dist n_points x 2
     float64 (min, max), totals 4 int32 (OK, EMPTY, NOT_OK points, OK points with more than max_views observations); nothing is
     synchronised and nothing is read back."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    F, cap = kps.shape[0], kps.shape[1]
-    N, dev, n_points = F * cap, kps.device, int(n_points)
-    assert desc.is_cuda and desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() == 32 * N
-    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (counts, obs_cam, obs_point, obs_node))
-    n_obs = obs_cam.numel()
-    assert counts.numel() == F and obs_point.numel() == n_obs and obs_node.numel() == n_obs and n_points >= 0
-    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() == 7 * F
-    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
-    assert obs_use is None or (obs_use.is_cuda and obs_use.dtype == torch.uint8 and obs_use.is_contiguous() and obs_use.numel() == n_obs)
-    assert point_status is None or (point_status.is_cuda and point_status.dtype == torch.int32 and point_status.is_contiguous() and
-                                    point_status.numel() == n_points)
-    assert point_select is None or (point_select.is_cuda and point_select.dtype == torch.uint8 and point_select.is_contiguous() and
-                                    point_select.numel() == n_points)
-    shapes = {"point_state": ((n_points,), torch.uint8), "point_desc": ((n_points, 32), torch.uint8),
-              "point_obs": ((n_points, 2), torch.int32), "point_views": ((n_points,), torch.int32),
-              "point_normal": ((n_points, 3), torch.float64), "point_dist": ((n_points, 2), torch.float64),
-              "totals": ((4,), torch.int32)}
+    F, cap, n_points = _frame_io(kps, desc, counts, cam_pose, n_points, point_xyz, point_status, point_select)
+    n_obs = dev("obs_cam", obs_cam, "int32").numel()
+    dev("obs_point", obs_point, "int32", n_obs)
+    dev("obs_node", obs_node, "int32", n_obs)
+    dev("obs_use", obs_use, "uint8", n_obs, optional=True)
+    spec = dict(zip(DESCRIBE_OUTPUTS, (((n_points,), "uint8", True), ((n_points, 32), "uint8", True),
+                                       ((n_points, 2), "int32", True), ((n_points,), "int32", True),
+                                       ((n_points, 3), "float64", True), ((n_points, 2), "float64", True),
+                                       ((4,), "int32", True))))
     if out is None:
-        out = {k: torch.zeros(shape, dtype=dtype, device=dev) for k, (shape, dtype) in shapes.items()}
+        out = alloc(kps.device, spec)
     else:
-        assert list(out) == list(DESCRIBE_OUTPUTS)
-        assert all(out[k].is_cuda and out[k].dtype == dtype and out[k].is_contiguous() and tuple(out[k].shape) == shape
-                   for k, (shape, dtype) in shapes.items())
-    prm = params if params is not None else point_desc_default_params()
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    ctx.check(hip.lib.gh_describe_points_dev(ctx.h, p(kps), p(desc), p(counts), F, cap, p(cam_pose), p(obs_cam), p(obs_point),
-                                             p(obs_node), _p(obs_use), n_obs, n_points, p(point_xyz), _p(point_status),
-                                             _p(point_select), C.byref(prm), *(p(out[k]) for k in DESCRIBE_OUTPUTS)))
+        require(list(out) == list(DESCRIBE_OUTPUTS), "out: keys %s, expected %s" % (list(out), list(DESCRIBE_OUTPUTS)))
+        for k, (shape, dtype, _) in spec.items():
+            have = tuple(dev("out[%r]" % k, out[k], dtype).shape)
+            require(have == shape, "out[%r]: shape %s, expected %s" % (k, have, shape))
+    prm = defaults(params, hip.PointDescParams, hip.lib.gh_point_desc_default_params)
+    ctx.check(hip.lib.gh_describe_points_dev(ctx.h, ptr_array(kps), ptr_array(desc), ptr_array(counts), F, cap, ptr_array(cam_pose),
+                                             ptr_array(obs_cam), ptr_array(obs_point), ptr_array(obs_node), ptr(obs_use), n_obs,
+                                             n_points, ptr_array(point_xyz), ptr(point_status), ptr(point_select), C.byref(prm),
+                                             *map(ptr_array, out.values())))
     return out
 
 
 def search_default_params():
     """gh_search_default_params -> hip.SearchParams."""
-    p = hip.SearchParams()
-    hip.lib.gh_search_default_params(C.byref(p))
-    return p
+    return defaults(None, hip.SearchParams, hip.lib.gh_search_default_params)
 
 
 SEARCH_OUTPUTS = ("row_point", "row_inlier", "row_dist", "frame_totals", "totals")
@@ -601,38 +523,28 @@ def search_projection(ctx: hip.Context, kps, desc, counts, cam_pose, frame_searc
     uint16 (the Hamming distance of a winner, 0xFFFF elsewhere), frame_totals F x 10 int32 (the pairs per verdict,
     SEARCH_VERDICTS), totals 12 int32 (the column sums, the searched frames, the searchable points); nothing is synchronised and
     nothing is read back."""
-    import torch
-    assert kps.is_cuda and kps.dtype == torch.float32 and kps.is_contiguous() and kps.dim() == 3 and kps.shape[2] == 7
-    F, cap = kps.shape[0], kps.shape[1]
-    N, dev, n_points = F * cap, kps.device, int(n_points)
-    assert desc.is_cuda and desc.dtype == torch.uint8 and desc.is_contiguous() and desc.numel() == 32 * N
-    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == F
-    assert cam_pose.is_cuda and cam_pose.dtype == torch.float64 and cam_pose.is_contiguous() and cam_pose.numel() == 7 * F
-    assert frame_search.is_cuda and frame_search.dtype == torch.uint8 and frame_search.is_contiguous() and frame_search.numel() == F
-    assert point_xyz.is_cuda and point_xyz.dtype == torch.float64 and point_xyz.is_contiguous() and point_xyz.numel() == 3 * n_points
-    want = {"point_views": (torch.int32, n_points), "point_desc": (torch.uint8, 32 * n_points),
-            "point_normal": (torch.float64, 3 * n_points), "point_dist": (torch.float64, 2 * n_points)}
-    assert all(summaries[k].is_cuda and summaries[k].dtype == dt and summaries[k].is_contiguous() and summaries[k].numel() == n
-               for k, (dt, n) in want.items())
-    for t, dt, n in ((node_point, torch.int32, N), (row_point, torch.int32, N), (row_inlier, torch.uint8, N),
-                     (point_status, torch.int32, n_points), (point_select, torch.uint8, n_points)):
-        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n)
-    assert (row_point is None) == (row_inlier is None) and not (in_place and row_point is None)
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    out = {"row_point": row_point if in_place else torch.empty(N, dtype=torch.int32, device=dev),
-           "row_inlier": row_inlier if in_place else torch.empty(N, dtype=torch.uint8, device=dev),
-           "row_dist": torch.empty(N, dtype=torch.uint16, device=dev),
-           "frame_totals": torch.empty((F, 10), dtype=torch.int32, device=dev),
-           "totals": torch.empty(12, dtype=torch.int32, device=dev)}
-    prm = params if params is not None else search_default_params()
-    # (an empty tensor has no storage: its pointer is 0, and the entry wants its arrays even when they hold nothing)
-    p = lambda t: C.c_void_p(t.data_ptr() or 256)
-    q = lambda t: None if t is None else p(t)  # (NULL means "not given", also when the array holds nothing)
-    ctx.check(hip.lib.gh_search_projection_dev(ctx.h, p(kps), p(desc), p(counts), F, cap, p(cam_pose), p(frame_search), q(node_point),
-                                               q(row_point), q(row_inlier), n_points, p(point_xyz), q(point_status), q(point_select),
-                                               *(p(summaries[k]) for k in want), C.c_double(fx), C.c_double(fy), C.c_double(cx),
-                                               C.c_double(cy), int(size[0]), int(size[1]), C.byref(prm),
-                                               *(p(out[k]) for k in SEARCH_OUTPUTS)))
+    F, cap, n_points = _frame_io(kps, desc, counts, cam_pose, n_points, point_xyz, point_status, point_select)
+    N = F * cap
+    dev("frame_search", frame_search, "uint8", F)
+    want = {"point_views": ("int32", n_points), "point_desc": ("uint8", 32 * n_points),
+            "point_normal": ("float64", 3 * n_points), "point_dist": ("float64", 2 * n_points)}
+    for k, (dtype, n) in want.items():
+        dev("summaries[%r]" % k, summaries[k], dtype, n)
+    dev("node_point", node_point, "int32", N, optional=True)
+    dev("row_point", row_point, "int32", N, optional=True)
+    dev("row_inlier", row_inlier, "uint8", N, optional=True)
+    require((row_point is None) == (row_inlier is None), "row_point and row_inlier: both or neither")
+    require(not (in_place and row_point is None), "in_place: there are no claims to update")
+    out = alloc(kps.device, dict(zip(SEARCH_OUTPUTS, (row_point if in_place else (N, "int32"),
+                                                      row_inlier if in_place else (N, "uint8"), (N, "uint16"),
+                                                      ((F, 10), "int32"), (12, "int32")))))
+    prm = defaults(params, hip.SearchParams, hip.lib.gh_search_default_params)
+    # (ptr_opt: NULL means "not given", also when the array holds nothing)
+    ctx.check(hip.lib.gh_search_projection_dev(ctx.h, ptr_array(kps), ptr_array(desc), ptr_array(counts), F, cap, ptr_array(cam_pose),
+                                               ptr_array(frame_search), ptr_opt(node_point), ptr_opt(row_point), ptr_opt(row_inlier),
+                                               n_points, ptr_array(point_xyz), ptr_opt(point_status), ptr_opt(point_select),
+                                               *(ptr_array(summaries[k]) for k in want), *pinhole(intrinsics), int(size[0]),
+                                               int(size[1]), C.byref(prm), *map(ptr_array, out.values())))
     return out
 
 

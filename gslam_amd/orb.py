@@ -11,13 +11,10 @@ import numpy as np
 import torch
 
 from . import hip
+from .devargs import ptr, require
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4"), ("class_id", "<i4")])
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def synth_frames(ctx, n_frames, width, height, base_seed=0x5EED0000, first_frame=0, row_stride=None,
@@ -25,7 +22,7 @@ def synth_frames(ctx, n_frames, width, height, base_seed=0x5EED0000, first_frame
     """n_frames deterministic gray frames generated in HBM (bit-identical to oracle/synth.c)."""
     row_stride = row_stride or width
     out = torch.empty((n_frames, height, row_stride), dtype=torch.uint8, device=device)
-    ctx.check(hip.lib.gh_synth_frames_dev(ctx.h, _p(out), width, height, row_stride,
+    ctx.check(hip.lib.gh_synth_frames_dev(ctx.h, ptr(out), width, height, row_stride,
                                           C.c_size_t(height * row_stride), int(first_frame), int(n_frames),
                                           C.c_uint32(base_seed & 0xFFFFFFFF)))
     return out
@@ -98,14 +95,16 @@ class OrbExtractor:
         """frames: B x H x stride u8 (cuda).  Returns (kps B x K x 7 f32-view of KeyPoint, desc B x K x 32, counts).
         Small calls (up to two 1080p frames) replay a captured launch graph when the SAME frames / out buffers come back
         (pass out= and reuse it); with fresh buffers every call the plan stops capturing after a few misses."""
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
+        # (not dev(): the frames of a batch may lie apart, frames.stride(0) goes to the entry; only the rows must be dense)
+        require(frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3, "frames: expected a cuda uint8 B x H x stride tensor")
         B, H, stride = frames.shape
-        assert H == self.h and stride >= self.w and frames.stride(2) == 1 and frames.stride(1) == stride
+        require(H == self.h and stride >= self.w and frames.stride(2) == 1 and frames.stride(1) == stride,
+                "frames: expected the plan's number of dense rows, each at least the plan's width")
         if out is None:
             out = self.alloc_outputs(B, frames.device)
         kps, desc, counts = out
-        self.ctx.check(hip.lib.gh_orb_extract_dev(self.plan, _p(frames), B, C.c_size_t(frames.stride(0)), stride,
-                                                  _p(kps), _p(desc), _p(counts)))
+        self.ctx.check(hip.lib.gh_orb_extract_dev(self.plan, ptr(frames), B, C.c_size_t(frames.stride(0)), stride,
+                                                  ptr(kps), ptr(desc), ptr(counts)))
         return kps, desc, counts
 
     def extract_host(self, gray: np.ndarray):

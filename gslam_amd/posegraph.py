@@ -9,12 +9,12 @@ from . import hip
 from .ba import default_options
 
 
-def _p(a):
+def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def _fill_pose_part(pr, S, d, problem, keep):
-    pr.n_frames, pr.frame_sim3, pr.frame_dof = len(S), _p(S), _p(d)
+    pr.n_frames, pr.frame_sim3, pr.frame_dof = len(S), _ptr(S), _ptr(d)
     for key in ("se3", "sim3"):
         if problem.get(key) is not None:
             f, s, m, inf = problem[key]
@@ -23,14 +23,14 @@ def _fill_pose_part(pr, S, d, problem, keep):
             inf = np.ascontiguousarray(inf, dtype=np.float64) if inf is not None else None
             keep += [f, s, m, inf]
             setattr(pr, "n_" + key, len(f))
-            setattr(pr, key + "_first", _p(f)); setattr(pr, key + "_second", _p(s))
-            setattr(pr, key + "_meas", _p(m)); setattr(pr, key + "_info", _p(inf))
+            setattr(pr, key + "_first", _ptr(f)); setattr(pr, key + "_second", _ptr(s))
+            setattr(pr, key + "_meas", _ptr(m)); setattr(pr, key + "_info", _ptr(inf))
     if problem.get("gps") is not None:
         f, m, inf = problem["gps"]
         f, m = np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(m, dtype=np.float64)
         inf = np.ascontiguousarray(inf, dtype=np.float64) if inf is not None else None
         keep += [f, m, inf]
-        pr.n_gps, pr.gps_frame, pr.gps_meas, pr.gps_info = len(f), _p(f), _p(m), _p(inf)
+        pr.n_gps, pr.gps_frame, pr.gps_meas, pr.gps_info = len(f), _ptr(f), _ptr(m), _ptr(inf)
 
 
 def solve(ctx: hip.Context, frames, dof, problem: dict, options=None):
@@ -73,16 +73,16 @@ def solve_graph(ctx: hip.Context, frames, dof, problem: dict, options=None):
     xfree, ifree, host, anchor = u8(xfree), u8(ifree), i32(host), f64(anchor)
     kind, point, frame, xy, oinfo = i32(kind), i32(point), i32(frame), f64(xy), f64(oinfo)
     keep += [xyz, rho, xfree, ifree, host, anchor, kind, point, frame, xy, oinfo]
-    gp.n_xyz, gp.xyz, gp.xyz_free = len(xyz), _p(xyz), _p(xfree)
-    gp.n_idp, gp.idp_host, gp.idp_anchor, gp.idp_rho, gp.idp_free = len(rho), _p(host), _p(anchor), _p(rho), _p(ifree)
+    gp.n_xyz, gp.xyz, gp.xyz_free = len(xyz), _ptr(xyz), _ptr(xfree)
+    gp.n_idp, gp.idp_host, gp.idp_anchor, gp.idp_rho, gp.idp_free = len(rho), _ptr(host), _ptr(anchor), _ptr(rho), _ptr(ifree)
     sphere = problem.get("projection") == "sphere"  # then `xy` is n x 3 unit bearings
-    gp.n_obs, gp.obs_kind, gp.obs_point, gp.obs_frame, gp.obs_info = len(kind), _p(kind), _p(point), _p(frame), _p(oinfo)
-    gp.projection, gp.obs_xy, gp.obs_bearing = (1, None, _p(xy)) if sphere else (0, _p(xy), None)
+    gp.n_obs, gp.obs_kind, gp.obs_point, gp.obs_frame, gp.obs_info = len(kind), _ptr(kind), _ptr(point), _ptr(frame), _ptr(oinfo)
+    gp.projection, gp.obs_xy, gp.obs_bearing = (1, None, _ptr(xy)) if sphere else (0, _ptr(xy), None)
     cam = None
     if problem.get("intrinsics") is not None:
         cam = np.ascontiguousarray(problem["intrinsics"][0], dtype=np.float64).copy()
         keep.append(cam)
-        gp.intrinsics, gp.intrinsics_free = _p(cam), int(problem["intrinsics"][1])
+        gp.intrinsics, gp.intrinsics_free = _ptr(cam), int(problem["intrinsics"][1])
     sm = hip.BaSummary()
     st = hip.lib.gh_graph_solve(ctx.h, C.byref(gp), C.byref(options), C.byref(sm))
     if st not in (0, 4):
@@ -95,7 +95,7 @@ def align_sim3(ctx: hip.Context, src, dst, dof=127):
     a = np.ascontiguousarray(src, dtype=np.float64)
     b = np.ascontiguousarray(dst, dtype=np.float64)
     out, info, ssq, ok = np.zeros(8), np.zeros(49), C.c_double(), C.c_int()
-    ctx.check(hip.lib.gh_align_sim3(ctx.h, _p(a), _p(b), len(a), int(dof), _p(out), _p(info), C.byref(ssq), C.byref(ok)))
+    ctx.check(hip.lib.gh_align_sim3(ctx.h, _ptr(a), _ptr(b), len(a), int(dof), _ptr(out), _ptr(info), C.byref(ssq), C.byref(ok)))
     return bool(ok.value), out, info.reshape(7, 7), ssq.value
 
 
@@ -106,7 +106,7 @@ def bs_symbolic(n_frames, prow, pcol, root_min=128, max_rounds=64):
     pcol = np.ascontiguousarray(pcol, dtype=np.int32)
     counts = np.zeros(5, np.int64)
     pos = np.zeros(n_frames, np.int32)
-    st = hip.lib.gh_bs_symbolic(n_frames, len(prow), _p(prow), _p(pcol), root_min, max_rounds, _p(pos), _p(counts), None, 0, None,
+    st = hip.lib.gh_bs_symbolic(n_frames, len(prow), _ptr(prow), _ptr(pcol), root_min, max_rounds, _ptr(pos), _ptr(counts), None, 0, None,
                                 None, 0)
     if st:
         raise RuntimeError("gh_bs_symbolic failed: %d" % st)
@@ -114,8 +114,8 @@ def bs_symbolic(n_frames, prow, pcol, root_min=128, max_rounds=64):
     round_ptr = np.zeros(n_rounds + 1, np.int32)
     colptr = np.zeros(ns + 1, np.int32)
     rows = np.zeros(max(n_slots, 1), np.int32)
-    st = hip.lib.gh_bs_symbolic(n_frames, len(prow), _p(prow), _p(pcol), root_min, max_rounds, _p(pos), _p(counts), _p(round_ptr),
-                                len(round_ptr), _p(colptr), _p(rows), len(rows))
+    st = hip.lib.gh_bs_symbolic(n_frames, len(prow), _ptr(prow), _ptr(pcol), root_min, max_rounds, _ptr(pos), _ptr(counts), _ptr(round_ptr),
+                                len(round_ptr), _ptr(colptr), _ptr(rows), len(rows))
     if st:
         raise RuntimeError("gh_bs_symbolic failed: %d" % st)
     return dict(pos=pos, ns=ns, nr=nr, round_ptr=round_ptr, colptr=colptr, rows=rows[:n_slots], pair_products=int(counts[4]))
@@ -131,6 +131,6 @@ def bs_solve(ctx: hip.Context, prow, pcol, diag, off, g, radius=1e30, root_min=1
     nf = len(diag)
     x = np.zeros(7 * nf)
     info = C.c_int(0)
-    ctx.check(hip.lib.gh_bs_solve_host(ctx.h, nf, len(prow), _p(prow), _p(pcol), _p(diag), _p(off), _p(g), float(radius), root_min,
-                                       max_rounds, _p(x), C.byref(info)))
+    ctx.check(hip.lib.gh_bs_solve_host(ctx.h, nf, len(prow), _ptr(prow), _ptr(pcol), _ptr(diag), _ptr(off), _ptr(g), float(radius), root_min,
+                                       max_rounds, _ptr(x), C.byref(info)))
     return x, info.value

@@ -105,6 +105,7 @@ def exchange_matches(idx1: torch.Tensor, g_idx1: torch.Tensor, frames_per_rank: 
 import ctypes as _C
 
 from . import hip as _hip
+from .devargs import ptr as _ptr
 
 
 class _DeviceView:
@@ -165,17 +166,16 @@ class Comm:
 
     def allgather_features(self, desc, counts, g_desc, g_counts, kps=None, g_kps=None):
         F, K = desc.shape[0], desc.shape[1]
-        p = lambda t: _C.c_void_p(t.data_ptr()) if t is not None else None
-        self.ctx.check(_hip.lib.gh_allgather_features(self.h, F, K, p(kps), p(desc), p(counts), p(g_kps), p(g_desc), p(g_counts)))
+        self.ctx.check(_hip.lib.gh_allgather_features(self.h, F, K, _ptr(kps), _ptr(desc), _ptr(counts), _ptr(g_kps), _ptr(g_desc),
+                                                      _ptr(g_counts)))
 
     def allgather_matches(self, idx1, g_idx1, d1=None, g_d1=None, d2=None, g_d2=None):
         R, K = idx1.shape
-        p = lambda t: _C.c_void_p(t.data_ptr()) if t is not None else None
-        self.ctx.check(_hip.lib.gh_allgather_matches(self.h, R, K, p(idx1), p(d1), p(d2), p(g_idx1), p(g_d1), p(g_d2)))
+        self.ctx.check(_hip.lib.gh_allgather_matches(self.h, R, K, _ptr(idx1), _ptr(d1), _ptr(d2), _ptr(g_idx1), _ptr(g_d1),
+                                                     _ptr(g_d2)))
 
     def allgather(self, send, gathered):
-        self.ctx.check(_hip.lib.gh_allgather(self.h, _C.c_void_p(send.data_ptr()), _C.c_void_p(gathered.data_ptr()),
-                                             send.numel() * send.element_size()))
+        self.ctx.check(_hip.lib.gh_allgather(self.h, _ptr(send), _ptr(gathered), send.numel() * send.element_size()))
 
     def wait(self):
         """Orders the context's stream after the gather in flight; the host does not wait (both transports)."""

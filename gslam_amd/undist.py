@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .devargs import dev, ptr
 
 
 class Undistorter:
@@ -33,13 +34,11 @@ class Undistorter:
 
     def undistort(self, imgs: torch.Tensor, fast=False, out=None):
         """imgs: B x H_in x W_in [x C] u8 (cuda, dense) -> B x H_out x W_out [x C]."""
-        assert imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.is_contiguous()
-        B = imgs.shape[0]
+        B = dev("imgs", imgs, "uint8").shape[0]
         ch = 1 if imgs.dim() == 3 else imgs.shape[3]
         shape = (B, self.h_out, self.w_out) if ch == 1 else (B, self.h_out, self.w_out, ch)
         out = out if out is not None else torch.empty(shape, dtype=torch.uint8, device=imgs.device)
-        self.ctx.check(hip.lib.gh_undistort_dev(self.h, C.c_void_p(imgs.data_ptr()), ch, B,
-                                                C.c_size_t(self.h_in * self.w_in * ch), C.c_void_p(out.data_ptr()),
+        self.ctx.check(hip.lib.gh_undistort_dev(self.h, ptr(imgs), ch, B, C.c_size_t(self.h_in * self.w_in * ch), ptr(out),
                                                 C.c_size_t(self.h_out * self.w_out * ch), 1 if fast else 0))
         return out
 

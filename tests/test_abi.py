@@ -26,6 +26,60 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert hip.lib.gh_abi_version() == 2  # (bumped in round 5: gh_graph_problem grew two fields in round 4, new entry points)
 
 
+_C_KINDS = {"int": "int", "int32_t": "int", "gh_status": "int", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64",
+            "size_t": "u64", "double": "double", "float": "float", "void": "void"}
+
+
+def _c_kind(text):
+    """The kind of one C parameter or return type: every pointer and array is 'ptr', the scalars by width and sign."""
+    if "*" in text or "[" in text:
+        return "ptr"
+    words = [w for w in text.split() if w not in ("const", "extern", "GH_API")]
+    hits = [w for w in words if w in _C_KINDS]
+    assert len(hits) == 1 and words[0] == hits[0] and len(words) <= 2, "cannot classify %r" % text  # type [name]
+    return _C_KINDS[hits[0]]
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, (C._Pointer, C.Array)):
+        return "ptr"
+    if t in (C.c_double, C.c_float):
+        return "double" if t is C.c_double else "float"
+    assert issubclass(t, C._SimpleCData) and t._type_ in "iIlLqQ", "cannot classify %r" % t
+    signed, size = t._type_ in "ilq", C.sizeof(t)
+    return {(True, 4): "int", (False, 4): "u32", (True, 8): "i64", (False, 8): "u64"}[(signed, size)]
+
+
+def _header_prototypes():
+    src = open(os.path.join(ROOT, "include", "gslam_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", "", src, flags=re.M)  # preprocessor lines, continued ones included
+    protos = {}
+    for ret, name, params in re.findall(r"(?:^|(?<=[;{}]))\s*([A-Za-z_][\w\s\*]*?)\b(gh_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [p.strip() for p in params.split(",")]
+        kinds = [] if params in ([""], ["void"]) else [_c_kind(p) for p in params]
+        assert name not in protos, name
+        protos[name] = (_c_kind(ret), kinds)
+    return protos
+
+
+def test_every_bound_signature_has_the_argument_kinds_of_its_prototype():
+    """Count and kind (pointer, int, u32, i64, u64, double, float) of every argument, and the return: a pointer listed where an
+    int goes, or an argument too few, binds and loads without complaint and is caught only here."""
+    from gslam_amd import hip
+    protos = _header_prototypes()
+    assert sorted(protos) == _header_functions()  # (every declared function was parsed as a prototype)
+    bad = {}
+    for name, (restype, argtypes) in hip.SIGNATURES.items():
+        have = (_ctypes_kind(restype), [_ctypes_kind(t) for t in argtypes])
+        if have != protos[name]:
+            bad[name] = {"table": have, "header": protos[name]}
+    assert not bad, bad
+
+
 def test_record_layouts():
     from gslam_amd import hip
     from gslam_amd.orb import KP_DTYPE

@@ -273,6 +273,38 @@ def test_degenerate_sizes(ctx):
     assert got["totals"].tolist()[2:4] == [0, 0] and got["totals"][1] >= 1
 
 
+def test_the_wrapper_refuses_a_tensor_a_kernel_could_not_read_before_any_launch(ctx):
+    """estimator.extend_tracks with a float32 idx1, or with a transposed (non-contiguous) kps, raises ValueError naming the
+    argument; nothing was launched, so every tensor that went in holds what it held.  F = 3, cap = 8, P = 2."""
+    import torch
+    from gslam_amd import estimator
+    F, cap, P, n_points = 3, 8, 2, 5
+    g = torch.Generator().manual_seed(7)
+    good = dict(kps=torch.rand((F, cap, 7), generator=g).cuda(), counts=torch.full((F,), cap, dtype=torch.int32).cuda(),
+                pair_q=torch.tensor([1, 2], dtype=torch.int32).cuda(), pair_t=torch.tensor([0, 1], dtype=torch.int32).cuda(),
+                idx1=torch.randint(0, cap, (P, cap), generator=g, dtype=torch.int32).cuda(),
+                inlier=torch.ones((P, cap), dtype=torch.uint8).cuda(),
+                node_point=torch.randint(-1, n_points, (F * cap,), generator=g, dtype=torch.int32).cuda(),
+                row_point=torch.randint(-1, n_points, (F * cap,), generator=g, dtype=torch.int32).cuda(),
+                row_inlier=torch.ones(F * cap, dtype=torch.uint8).cuda())
+    bad_idx1 = good["idx1"].to(torch.float32)
+    bad_kps = torch.rand((F, 7, cap), generator=g).cuda().transpose(1, 2)
+    assert tuple(bad_kps.shape) == (F, cap, 7) and not bad_kps.is_contiguous()
+    for name, bad in (("idx1", bad_idx1), ("kps", bad_kps)):
+        d = dict(good, **{name: bad})
+        before = {k: t.clone() for k, t in d.items()}
+        with pytest.raises(ValueError, match="^%s: " % name):
+            estimator.extend_tracks(ctx, d["kps"], d["counts"], d["pair_q"], d["pair_t"], d["idx1"], d["inlier"], d["node_point"],
+                                    n_points, d["row_point"], d["row_inlier"], ec.INTRINSICS)
+        torch.cuda.synchronize()
+        for k, t in d.items():
+            assert t.dtype == before[k].dtype and t.stride() == before[k].stride() and torch.equal(t, before[k]), (name, k)
+    out = estimator.extend_tracks(ctx, *(good[k] for k in ("kps", "counts", "pair_q", "pair_t", "idx1", "inlier", "node_point")),
+                                  n_points, good["row_point"], good["row_inlier"], ec.INTRINSICS)  # (the same call, valid, goes through)
+    torch.cuda.synchronize()
+    assert out["totals"].numel() == 6
+
+
 @pytest.mark.parametrize("late_points", [False, True])
 def test_the_map_grows_by_three_frames_without_a_read_back(ctx, late_points):
     """localize_cases.scene(): link_tracks on the map pairs -> triangulate_tracks at the true poses -> localize_pairs for the 3 new
